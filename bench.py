@@ -10,7 +10,12 @@ whole HBM-resident corpus through the C-ABI (rxgpu_search_knn_device), results l
 holds its own 10M-row shard (weak scaling = BASELINE configs[3]: 80M rows on 8 GPUs); each step then also does the
 per-shard top-k all-gather over RCCL and the k-way merge.  Rank 0 prints ONE JSON line.
 
-Extra legs (rank 0, N = 1 only, outside the timed region; each leg is skipped â€” and says so â€” once --time-budget is used up):
+A plain run sets up, warms up, times --steps steps and prints that line (metric, value, unit, higher_is_better, dtype, ms_per_step, plus the
+scan roofline from the events of the timed steps).  --dump-outputs DIR also writes what the last timed step returned (distances and rows,
+.npy) for output-for-output comparison of two builds; the inputs are seeded, so equal arguments give equal inputs.  Every other measurement
+and check runs only with --full:
+
+Extra legs (--full; rank 0, N = 1 only, outside the timed region; each leg is skipped â€” and says so â€” once --time-budget is used up):
   roofline      HIP events recorded by the library around every scan-kernel launch on the launch stream
   batched / pruned_scan / prefilter   the other brute-force kernels at the same 10M x 768 shape
   cpu_baseline  the reference's own BruteforceSearch (oracle/_ref, AVX-512 path) built over the FULL corpus on the host: measured,
@@ -18,7 +23,8 @@ Extra legs (rank 0, N = 1 only, outside the timed region; each leg is skipped â€
   parity        GPU result vs that CPU result on the same FULL corpus (ids must be identical, distance bits too): every query through
                 the timed batch-1 kernel, then in one batched call; ip / l2 / cosine each against a reference index of that metric
   hnsw          BASELINE configs[2] (scaled to --hnsw-rows): graph built here by the product's concurrent builder, searched on the GPU and by
-                the reference's own engine on the same graph (tools/bench_hnsw.py)
+                the reference's own engine on the same graph (tools/bench_hnsw.py); --time-budget 1350 leaves room for the 10M-row graph
+--full at N > 1 also times one GPU scanning the whole corpus (speedup_vs_one_gpu); --full --in-process re-checks the merged list shard by shard.
   hybrid        BASELINE configs[4]: BM25 merge + KNN + RRF fusion on the GPU vs the reference's merger / brute force / rank merger
                 (tools/bench_hybrid.py)
   ft_packed     index-commit side of the ft half: a dictionary's PackedIdRelVec posting streams decoded on the device vs the per-word host path
@@ -97,8 +103,13 @@ def parse_args():
     ap.add_argument("--hybrid-docs", type=int, default=5_000_000, help="hybrid leg: documents = vectors (0 = skip)")
     ap.add_argument("--ft-packed-words", type=int, default=100_000, help="ft_packed leg: dictionary words whose PackedIdRelVec streams are decoded "
                                                                          "on the device (0 = skip)")
-    ap.add_argument("--time-budget", type=float, default=1350.0, help="seconds of wall clock after which remaining extra legs are skipped "
-                                                                      "(the 10M-row HNSW host build alone takes 6 - 9 minutes; without it the run takes ~3)")
+    ap.add_argument("--full", action="store_true", help="also run every extra leg and check (roofline legs, CPU baseline, parity, HNSW, hybrid, "
+                                                        "ft_packed, one-GPU denominator); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy "
+                                                                         "(float32 distances, float64 rows)")
+    ap.add_argument("--time-budget", type=float, default=480.0, help="seconds of wall clock after which remaining extra legs are skipped; the "
+                                                                     "default keeps --full under 10 minutes (HNSW leg at --hnsw-fallback-rows); "
+                                                                     "1350 leaves room for the 10M-row HNSW host build (6 - 9 minutes)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / parity leg")
     ap.add_argument("--batch", type=int, default=256, help="extra leg (N=1, untimed region): batched queries on the MFMA path; 0 = skip")
     ap.add_argument("--batch-iters", type=int, default=3)
@@ -108,7 +119,20 @@ def parse_args():
     ap.add_argument("--shards-per-gpu", type=int, default=1, help="--in-process: shards per listed device (a 1-GPU box can run the N-shard path)")
     ap.add_argument("--full-json", default=str(ROOT / "gpurun_out" / "bench_full.json"),
                     help="every leg in full goes to this file (and to stderr); stdout carries ONE compact line (< 8 KB)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: the arrays the timed path handed its caller in the last timed step, one DIR/<name>.npy each; float32 stays float32,
+    everything else (row ids) is written as float64, exact for any row number below 2**53."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(d / f"{name}.npy", a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 _DROP_KEYS = {"note", "against", "host", "kernels", "builder", "params", "value_definition", "traffic_source", "ms_fusion_note",
@@ -559,13 +583,18 @@ def main_in_process(args, t_start: float) -> None:
     per_shard = [v.profile_read("scan") for v in views]
     for v in views:
         v.profile_enable(False)
-    # parity of the last query against every shard searched on its own (single-device entry point) and merged here under (dist, global row)
-    cand = []
-    for s, v in enumerate(views):
-        d1, r1, _ = v.search_knn(queries[total_q - 1:total_q], kk)
-        cand += [(float(d), int(r) + s * rows) for d, r in zip(d1[0], r1[0])]
-    cand.sort()
-    merged_ok = [c[1] for c in cand[:kk]] == [int(r) for r in row[0]] and [np.float32(c[0]).view(np.uint32) for c in cand[:kk]] == list(dist[0].view(np.uint32))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"knn_dist": dist, "knn_row": row, "knn_count": cnt})
+    merged_ok = None
+    if args.full:
+        # parity of the last query against every shard searched on its own (single-device entry point) and merged here under (dist, global row)
+        cand = []
+        for s, v in enumerate(views):
+            d1, r1, _ = v.search_knn(queries[total_q - 1:total_q], kk)
+            cand += [(float(d), int(r) + s * rows) for d, r in zip(d1[0], r1[0])]
+        cand.sort()
+        merged_ok = bool([c[1] for c in cand[:kk]] == [int(r) for r in row[0]]
+                         and [np.float32(c[0]).view(np.uint32) for c in cand[:kk]] == list(dist[0].view(np.uint32)))
     qps = args.steps / elapsed
     algo_bytes = rows * args.dim * 4
     launches = sum(n for n, _ in per_shard)
@@ -581,7 +610,7 @@ def main_in_process(args, t_start: float) -> None:
             "rows_per_shard": rows, "total_rows": rows * nshards, "dim": args.dim, "k": args.k, "batch": 1,
             "sharding": "rxgpu_index_create_sharded: per-shard scans, ncclAllGather of kk x 8 B per shard inside librxgpu.so, merge kernel on device 0",
             "merge_mode": sx.merge_mode, "rccl_ranks": sx.ranks, "collectives_in_timed_region": collectives,
-            "merged_equals_per_shard_lists": bool(merged_ok), "qps_over_full_corpus": qps, "shard_scans_per_sec": qps * nshards,
+            "merged_equals_per_shard_lists": merged_ok, "qps_over_full_corpus": qps, "shard_scans_per_sec": qps * nshards,
             "arch": capi.device_arch(0),
             "host_boundary": "queries enter as host pointers (3 KB H2D per step) and the merged list leaves by one D2H copy (88 B): both inside the timed region",
         },
@@ -719,13 +748,16 @@ def main():
         elapsed = float(t.item())
     launches, scan_ms = ix.profile_read("scan")
     ix.profile_enable(False)
+    if args.dump_outputs and rank == 0:   # N > 1: out_row holds global rows, the same merged list on every rank
+        last = total_q - 1
+        dump_outputs(args.dump_outputs, {"knn_dist": out_dist[last:last + 1], "knn_row": out_row[last:last + 1]})
 
     qps_global = args.steps / elapsed            # queries/s over the whole (N x rows) corpus
     # N > 1: value = queries/s over the WHOLE corpus (every query scans every shard) in either mode â€” the metric's unit; the aggregate of
     # shard scans (rows_per_gpu-row scans/s, what "weak" used to report as value) is a side field.  N = 1: the two coincide.
     value = qps_global
     one_gpu = None
-    if world > 1:
+    if world > 1 and args.full:
         # The same bytes on ONE GPU, measured here: rank 0 scans its shard `world` times back to back per query (what a single GPU holding the
         # whole corpus does: HBM-bound, rows x world x dim x 4 bytes; the shard is 100x the caches, nothing is reused) -> queries/s of one GPU
         # over a corpus of the full size, the denominator of the speedup.
@@ -790,7 +822,7 @@ def main():
                 out.setdefault("leg_seconds", time.perf_counter() - t0)
             return out
 
-        extra = world == 1 and not strong
+        extra = args.full and world == 1 and not strong
         if extra:
             result["sharded_in_process"] = leg("sharded_in_process", 5, lambda: sharded_in_process_leg(args, ix, corpus, d_inv, queries, device, kk))
         if extra and args.batch > 1:

@@ -33,9 +33,18 @@ def build_oracle(force: bool = False) -> Path:
     return ORACLE_SO
 
 
+def reference_tree_available() -> bool:
+    """The reference tree is there and this user may read it.  A stat below a directory the user cannot enter raises instead of
+    answering False, so a checkout built by an ordinary user next to a private copy of the tree must not ask Path.exists()."""
+    try:
+        return REFERENCE_TREE.is_dir() and os.access(REFERENCE_TREE, os.R_OK | os.X_OK)
+    except OSError:
+        return False
+
+
 def build_ref() -> Path | None:
     """Builds oracle/_ref from the reference tree when it is present (this container only)."""
-    if REFERENCE_TREE.exists():
+    if reference_tree_available():
         subprocess.run(["make", "-C", str(HERE), "-j8", "ref"], check=True, capture_output=True)
     return REF_SO if REF_SO.exists() else None
 

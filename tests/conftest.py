@@ -36,7 +36,7 @@ def oracle():
 def ref():
     """The real reference engines (oracle/_ref). Built on demand where /root/reference exists; else skipped."""
     from oracle import pyoracle
-    if not pyoracle.REF_SO.exists() and pyoracle.REFERENCE_TREE.exists():
+    if not pyoracle.REF_SO.exists() and pyoracle.reference_tree_available():
         pyoracle.build_ref()
     r = pyoracle.ref_or_none()
     if r is None:

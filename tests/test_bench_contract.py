@@ -60,3 +60,28 @@ def test_printed_line_is_small_and_complete(path, tmp_path):
     # the full record went to the side file and to stderr
     assert json.loads(open(args.full_json).read()) == full
     assert json.loads(err.getvalue().strip().splitlines()[-1]) == full
+
+
+def test_plain_run_options(monkeypatch):
+    """--full is off by default (a plain run times the headline steps only); --steps must name at least one timed step."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.warmup == 3 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with redirect_stderr(io.StringIO()), pytest.raises(SystemExit):
+        bench.parse_args()
+
+
+def test_dump_outputs_as_float_arrays(tmp_path):
+    """--dump-outputs: float32 stays float32, row ids become float64 (exact beyond float32's 2**24)."""
+    import numpy as np
+    import bench
+    rows = np.array([[3, (1 << 24) + 1, 9_999_999]], np.int32)
+    bench.dump_outputs(str(tmp_path / "d"), {"knn_dist": np.array([[0.5, 1.25, -2.0]], np.float32), "knn_row": rows})
+    d, r = np.load(tmp_path / "d" / "knn_dist.npy"), np.load(tmp_path / "d" / "knn_row.npy")
+    assert d.dtype == np.float32 and d.tolist() == [[0.5, 1.25, -2.0]]
+    assert r.dtype == np.float64 and np.array_equal(r.astype(np.int64), rows.astype(np.int64))

@@ -24,8 +24,8 @@ def main():
         w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs", "StdDev"])
         for r in stats:
             w.writerow([r["Name"][:96], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"], r["StdDev"]])
-    summary = {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --steps 30 --warmup 5 --no-cpu ; "
-                          "rocprofv3 --pmc FETCH_SIZE -- python bench.py --steps 10 --warmup 2 --no-cpu ; "
+    summary = {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 30 --warmup 5 --no-cpu ; "
+                          "rocprofv3 --pmc FETCH_SIZE -- python bench.py --full --steps 10 --warmup 2 --no-cpu ; "
                           "rocprofv3 --pmc WRITE_SIZE -- (same)", "kernels": {}}
     for r in stats:
         if "rxgpu" in r["Name"]:
