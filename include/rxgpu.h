@@ -151,9 +151,19 @@ int rxgpu_search_knn_resident(rxgpu_index* h, const float* query, uint32_t kk, v
 /* Diagnostics: how many threads hold a resident context (stream + result buffers) on the index right now.  A thread that ends gives its
  * context back to the index's pool, so the number follows the LIVE searching threads, not every thread that ever searched. */
 uint32_t rxgpu_index_resident_contexts(rxgpu_index* h);
-/* Same, device-resident in/out on `stream` (hipStream_t); d_out_count may be NULL.  No synchronisation. */
+/* Same, device-resident in/out on `stream` (hipStream_t); d_out_count may be NULL.  No synchronisation.
+ * A single query (nq == 1) on an index of at least 1 GiB of f32 rows is served by default from a bf16 shadow of the rows (2 bytes per
+ * element read instead of 4; the survivors of a rigorous rounding bound are re-scored by the exact f32 kernels: the same rows and distance
+ * bits).  The shadow costs +2 bytes per element of HBM and is built by the first such call on the index (about one pass over the rows, as
+ * the first call with two or more queries always did), then kept up to date by upload_rows / move_row / truncate; when it does not fit, or
+ * a row has a NaN / infinite norm, the f32 scan serves the query as before.  RXGPU_SCAN_BF16 (environment, read per call): unset =
+ * automatic, 0 = always the f32 paths, 1 = the pruned scan for up to 8 queries at any size; RXGPU_SCAN_BF16_MIN_BYTES moves the 1 GiB. */
 int rxgpu_search_knn_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, void* d_out_dist, void* d_out_row,
 							void* d_out_count, void* stream);
+/* The decision above as a pure function (no device is touched): 1 when a call with nq queries on an index of rows x dim f32 rows takes the
+ * bf16-pruned scan under the current environment.  shadow_available: the bf16 shadow fits in HBM; stats_finite: no row has a NaN or
+ * infinite norm (both are facts the index learns on the device). */
+int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite);
 
 /* ---- Pre-filtered brute force: the caller side of `WHERE cond AND KNN(...)` -------------------
  * The reference evaluates such a query by taking the KNN result and filtering it on the host (selectLoop,

@@ -63,6 +63,7 @@ _SIGNATURES = {
     "rxgpu_search_knn_resident": (_i, [_vp, _vp, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u32)]),
     "rxgpu_index_resident_contexts": (_u32, [_vp]),
     "rxgpu_search_knn_device": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "rxgpu_scan_policy": (_i, [_u64, _u32, _u32, _i, _i]),
     "rxgpu_search_knn_subset": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "rxgpu_search_knn_bitmap": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_index_set_lists": (_i, [_vp, _u32, _vp, _vp]),
@@ -187,6 +188,11 @@ def device_arch(device: int = 0) -> str:
     buf = C.create_string_buffer(256)
     _check(lib().rxgpu_device_arch(device, buf, 256))
     return buf.value.decode()
+
+
+def scan_policy(rows: int, dim: int, nq: int = 1, shadow_available: bool = True, stats_finite: bool = True) -> bool:
+    """rxgpu_scan_policy: does such a call take the bf16-pruned scan under the current environment?  Touches no device."""
+    return bool(lib().rxgpu_scan_policy(rows, dim, nq, int(shadow_available), int(stats_finite)))
 
 
 def _f32c(a) -> np.ndarray:

@@ -194,7 +194,8 @@ __global__ __launch_bounds__(kGemmThreads * QS) void knn_gemm(GemmParams p) {
 }
 
 // ---- per-row statistics: |x|^2 (L2 needs it per row) and the maxima entering the rounding bound ----
-// stats[0] = max |x|^2, stats[1] = max (|x| * inv_norm)^2 (cosine)
+// stats[0] = max |x|^2, stats[1] = max (|x| * inv_norm)^2 (cosine), stats[2] = 1 once a row with a NaN or infinite |x|^2 (or cosine factor) was
+// seen: fmaxf drops a NaN, so the maxima alone do not show it.  The bound is void for such an index (rxgpu_index::stats_finite).
 __global__ __launch_bounds__(256) void knn_row_stats(const float* rows, const float* inv_norms, uint64_t n, uint32_t stride, uint32_t dim,
 													  float* row_sq, unsigned int* stats) {
 	const int lane = threadIdx.x & 63, m = lane & 15;
@@ -202,6 +203,7 @@ __global__ __launch_bounds__(256) void knn_row_stats(const float* rows, const fl
 	const uint64_t gid = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 4;
 	const uint64_t rounds = (n + ngroups - 1) / ngroups;
 	float mx = 0.f, mxc = 0.f;
+	bool bad = false;
 	for (uint64_t it = 0; it < rounds; ++it) {   // uniform trip count: every lane takes part in the shuffles
 		const uint64_t row = it * ngroups + gid;
 		const bool ok = row < n;
@@ -215,12 +217,15 @@ __global__ __launch_bounds__(256) void knn_row_stats(const float* rows, const fl
 		if (ok) {
 			if (row_sq && m == 0) row_sq[row] = s;
 			mx = fmaxf(mx, s);
+			bad |= !(s < __builtin_inff());
 			if (inv_norms) {
 				const float inv = inv_norms[row];
 				mxc = fmaxf(mxc, s * inv * inv);
+				bad |= !(s * inv * inv < __builtin_inff());
 			}
 		}
 	}
+	const bool any_bad = __ballot(bad) != 0;
 	for (int o = 32; o; o >>= 1) {
 		mx = fmaxf(mx, __shfl_xor(mx, o));
 		mxc = fmaxf(mxc, __shfl_xor(mxc, o));
@@ -228,11 +233,36 @@ __global__ __launch_bounds__(256) void knn_row_stats(const float* rows, const fl
 	if (lane == 0) {   // non-negative floats order like their bit patterns
 		atomicMax(&stats[0], __float_as_uint(mx));
 		atomicMax(&stats[1], __float_as_uint(mxc));
+		if (any_bad) atomicMax(&stats[2], 1u);
 	}
 }
 
-// |q|^2 and the per-query margin 2*eps_q (see file header); one 64-lane wave per query
+// the per-query margin 2*eps_q from |q|^2 = s (see file header)
 // kBf16: the nomination runs on bf16-rounded operands (knn_batched_bf16.hip): + (2^-8 + 2^-18)|q||x| for the two roundings
+template <int kMetric, bool kBf16>
+__device__ __forceinline__ float query_margin(float s, uint32_t dim, const unsigned int* stats) {
+	const float u = 5.9604645e-08f;   // 2^-24
+	// f32 accumulation: covers both summation trees (D-chain vs 64-chain + fold), 10% slack.  The bf16 MFMA adds 16 products per instruction in an
+	// adder tree whose internal rounding mode is not documented: allow 2 ulp-halves per addition and the tree depth on top of the chain (4x)
+	const float gamma = (kBf16 ? 4.4f : 1.1f) * float(dim + 64) * u;
+	// rne_bf16 on q and x: |q~.x~ - q.x| <= ((1+2^-9)^2 - 1) sum|q_i x_i| <= 2^-8 (1 + 2^-10) |q||x|   (only the inner product is affected:
+	// |q|^2 and |x|^2 of the L2 form come from the f32 data)
+	const float gb = kBf16 ? 1.01f * 0.00390625f : 0.0f;
+	const float xmax2 = __uint_as_float(stats[0]);
+	float eps;
+	if constexpr (kMetric == kL2) {
+		// d = (qq + xx) - 2 ip: 2*gamma*|q||x| <= gamma*(qq+xx), plus the roundings of qq, xx and of the reference's own sum; bf16 adds 2*gb*|q||x|
+		eps = 2.0f * gamma * (s + xmax2) + 2.0f * gb * sqrtf(s) * sqrtf(xmax2);
+	} else if constexpr (kMetric == kIP) {
+		eps = (gamma + gb) * sqrtf(s) * sqrtf(xmax2);
+	} else {
+		eps = (gamma + gb + 4.0f * u) * sqrtf(s) * sqrtf(__uint_as_float(stats[1]));
+	}
+	// bf16 MFMA may flush subnormal inputs: at most dim * 2^-126 * (|q| + max|x|), far below the 1e-30 floor added here
+	return 2.0f * eps * 1.01f + (kBf16 ? 1e-30f : 1e-37f);
+}
+
+// |q|^2 and the per-query margin; one 64-lane wave per query
 template <int kMetric, bool kBf16>
 __global__ __launch_bounds__(64) void knn_query_stats(const float* queries, uint32_t nq, uint32_t q_stride, uint32_t dim,
 													   const unsigned int* stats, float* q_sq, float* margin) {
@@ -246,25 +276,32 @@ __global__ __launch_bounds__(64) void knn_query_stats(const float* queries, uint
 	for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o);
 	if (lane == 0) {
 		q_sq[qi] = s;
-		const float u = 5.9604645e-08f;   // 2^-24
-		// f32 accumulation: covers both summation trees (D-chain vs 64-chain + fold), 10% slack.  The bf16 MFMA adds 16 products per instruction in an
-		// adder tree whose internal rounding mode is not documented: allow 2 ulp-halves per addition and the tree depth on top of the chain (4x)
-		const float gamma = (kBf16 ? 4.4f : 1.1f) * float(dim + 64) * u;
-		// rne_bf16 on q and x: |q~.x~ - q.x| <= ((1+2^-9)^2 - 1) sum|q_i x_i| <= 2^-8 (1 + 2^-10) |q||x|   (only the inner product is affected:
-		// |q|^2 and |x|^2 of the L2 form come from the f32 data)
-		const float gb = kBf16 ? 1.01f * 0.00390625f : 0.0f;
-		const float xmax2 = __uint_as_float(stats[0]);
-		float eps;
-		if constexpr (kMetric == kL2) {
-			// d = (qq + xx) - 2 ip: 2*gamma*|q||x| <= gamma*(qq+xx), plus the roundings of qq, xx and of the reference's own sum; bf16 adds 2*gb*|q||x|
-			eps = 2.0f * gamma * (s + xmax2) + 2.0f * gb * sqrtf(s) * sqrtf(xmax2);
-		} else if constexpr (kMetric == kIP) {
-			eps = (gamma + gb) * sqrtf(s) * sqrtf(xmax2);
-		} else {
-			eps = (gamma + gb + 4.0f * u) * sqrtf(s) * sqrtf(__uint_as_float(stats[1]));
-		}
-		// bf16 MFMA may flush subnormal inputs: at most dim * 2^-126 * (|q| + max|x|), far below the 1e-30 floor added here
-		margin[qi] = 2.0f * eps * 1.01f + (kBf16 ? 1e-30f : 1e-37f);
+		margin[qi] = query_margin<kMetric, kBf16>(s, dim, stats);
+	}
+}
+
+// Everything the bf16-pruned scan needs in front of it, in one launch: the caller's unpadded query -> the padded copy (zero tail), |q|^2, the
+// bf16 margin, and the candidate counter of the query — 0, or cap + 1 when |q|^2 or the margin is not finite (a NaN / infinite query, an
+// overflow): the bound says nothing then, knn_filter_approx nominates nothing and the exact scan behind the gate answers the query.
+template <int kMetric>
+__global__ __launch_bounds__(64) void knn_query_prep(const float* src, uint32_t dim, float* qpad, uint32_t ld, const unsigned int* stats, float* q_sq,
+													  float* margin, uint32_t* cand_cnt, uint32_t cap) {
+	const uint32_t qi = blockIdx.x;
+	const int lane = threadIdx.x;
+	const float* q = src + size_t(qi) * dim;
+	float* o = qpad + size_t(qi) * ld;
+	float s = 0.f;
+	for (uint32_t i = lane; i < ld; i += 64) {
+		const float v = i < dim ? q[i] : 0.f;
+		o[i] = v;
+		if (i < dim) s = __builtin_fmaf(v, v, s);
+	}
+	for (int off = 32; off; off >>= 1) s += __shfl_xor(s, off);
+	if (lane == 0) {
+		const float mg = query_margin<kMetric, true>(s, dim, stats);
+		q_sq[qi] = s;
+		margin[qi] = mg;
+		cand_cnt[qi] = (s < __builtin_inff() && mg < __builtin_inff()) ? 0u : cap + 1u;
 	}
 }
 
@@ -319,7 +356,8 @@ __global__ __launch_bounds__(256) void knn_rescore(const float* rows, const floa
 													float* cand_dist) {
 	const int lane = threadIdx.x & 63, m = lane & 15;
 	const uint32_t qi = blockIdx.y;
-	const uint32_t cnt = min(cand_cnt[qi], cap);
+	const uint32_t have = cand_cnt[qi];
+	const uint32_t cnt = have > cap ? 0u : have;   // overflow: the gated exact scan answers the query; the slots may hold nothing (knn_query_prep)
 	const uint32_t slot = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
 	if (slot >= cap) return;
 	const size_t o = size_t(qi) * cap + slot;
@@ -401,6 +439,15 @@ void launch_query_stats(int metric, const float* queries, uint32_t nq, uint32_t 
 		}
 	}
 #undef RX_QS
+}
+
+void launch_query_prep(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, uint32_t ld, const unsigned int* stats, float* q_sq,
+					   float* margin, uint32_t* cand_cnt, uint32_t cap, hipStream_t s) {
+	switch (metric) {
+		case kL2: hipLaunchKernelGGL((knn_query_prep<kL2>), dim3(nq), dim3(64), 0, s, src, dim, qpad, ld, stats, q_sq, margin, cand_cnt, cap); break;
+		case kIP: hipLaunchKernelGGL((knn_query_prep<kIP>), dim3(nq), dim3(64), 0, s, src, dim, qpad, ld, stats, q_sq, margin, cand_cnt, cap); break;
+		default: hipLaunchKernelGGL((knn_query_prep<kCos>), dim3(nq), dim3(64), 0, s, src, dim, qpad, ld, stats, q_sq, margin, cand_cnt, cap); break;
+	}
 }
 
 void launch_sample_threshold(const float* dense, uint64_t ns, uint32_t nq, uint32_t mt, uint32_t kk, const float* margin, float* thr,

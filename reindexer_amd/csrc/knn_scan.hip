@@ -289,10 +289,13 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_subset_generic(ScanPara
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// bf16-pruned scan (opt-in, RXGPU_SCAN_BF16=1): half the HBM bytes per query, the SAME result bits.
+// bf16-pruned scan (the default for a single query on a large index, see scan_policy_pruned in rxgpu_capi.hip; RXGPU_SCAN_BF16=1 / 0 force it
+// on / off): half the HBM bytes per query, the SAME result bits.
+//   0. knn_query_prep     (knn_batched.hip) padded copy of the query, |q|^2, the margin 2 eps, cand_cnt = 0 — or cap + 1 for a query without a
+//                         finite bound, which steps 3-4 then leave to the gated exact scan
 //   1. knn_scan_bf16      approximate distance d~ of every row from the bf16 shadow (2 bytes per element), stored ([n] floats) and folded
 //                         into the per-wave top-kk exactly like the f32 scan
-//   2. knn_merge          -> d~_(kk), the kk-th best approximate distance
+//   2. knn_merge_lists    -> d~_(kk), the kk-th best approximate distance (the scan leaves sorted per-workgroup lists)
 //   3. knn_filter_approx  rows with d~ <= d~_(kk) + 2 eps  (eps = the rigorous bf16 bound of knn_query_stats<.., true>)
 //   4. knn_rescore + knn_merge   EXACT distances of those few dozen rows, exact top-kk by (dist, row)
 // Soundness: a row r of the true top-kk has d~_r <= d_r + eps <= D_kk + eps, and D_kk <= kk-th smallest of (d~ + eps) = d~_(kk) + eps.
@@ -498,6 +501,7 @@ __global__ __launch_bounds__(256) void knn_filter_approx(const float* approx, ui
 														 const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap) {
 	const uint32_t qi = blockIdx.y;
 	const int lane = threadIdx.x & 63;
+	if (!(margin[qi] < __builtin_inff())) return;   // no bound for this query (knn_query_prep has set cand_cnt = cap + 1): the exact scan answers it
 	const float thr = (top_count[qi] >= kk ? top_dist[size_t(qi) * kk + kk - 1] : __builtin_inff()) + margin[qi];
 	const float* a = approx + size_t(qi) * n;
 	const uint64_t span = uint64_t(gridDim.x) * blockDim.x;
@@ -679,10 +683,12 @@ __device__ void merge_by_insertion(const float* part_dist, const uint32_t* part_
 
 template <typename TK>
 __global__ __launch_bounds__(kMergeThreads) void knn_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
-																  float* out_dist, uint32_t* out_row, uint32_t* out_count) {
+																  float* out_dist, uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt,
+																  uint32_t gate_cap) {
 	__shared__ unsigned long long s_key[kMergeHeadsMax];
 	__shared__ float s_val[kMergeHeadsMax];
 	__shared__ uint32_t s_n;
+	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;   // workgroup-uniform (knn_merge's gate)
 	const uint32_t tid = threadIdx.x, total = nlists * kk;
 	const size_t base = size_t(blockIdx.x) * total;
 	bool serial = nlists < kk || nlists > kMergeHeadsMax;
@@ -965,6 +971,7 @@ struct ScanTuning {
 		if (wg_per_cu < 1) wg_per_cu = 1;
 	}
 };
+constexpr int kScanBf16WgPerCu = 2;   // 2 / 3 / 4 measured at 10M x 768: 2.393 / 2.402 / 2.461 ms per query (profiles/scan_bf16_grid_ab.json)
 static const ScanTuning& tuning() {
 	static ScanTuning t;
 	static const bool dynamic = getenv("RXGPU_TUNE_DYNAMIC") != nullptr;   // tools/tune_scan.py: re-read on every launch
@@ -1024,6 +1031,18 @@ uint32_t scan_grid_x(uint64_t n, int cus) {
 	const uint64_t nquads = (n + kRowsPerWave - 1) / kRowsPerWave;
 	const uint64_t want = (nquads + kScanWaves - 1) / kScanWaves;
 	const uint64_t cap = uint64_t(cus) * tuning().wg_per_cu;
+	return uint32_t(want < cap ? (want ? want : 1) : cap);
+}
+
+// The bf16 scans keep half the bytes in flight per workgroup (two 6 KB load buffers per wavefront at 768 dims, against 12 KB): their grid has
+// its own workgroups-per-CU figure.  RXGPU_SCAN_BF16_WG_PER_CU overrides it (read per call: A/B runs inside one process).
+uint32_t scan_bf16_grid_x(uint64_t n, int cus) {
+	int wg = kScanBf16WgPerCu;
+	if (const char* e = getenv("RXGPU_SCAN_BF16_WG_PER_CU")) wg = atoi(e);
+	wg = wg < 1 ? 1 : wg > 8 ? 8 : wg;
+	const uint64_t nquads = (n + kRowsPerWave - 1) / kRowsPerWave;   // small corpora: scan_grid_x's rule
+	const uint64_t want = (nquads + kScanWaves - 1) / kScanWaves;
+	const uint64_t cap = uint64_t(cus) * wg;
 	return uint32_t(want < cap ? (want ? want : 1) : cap);
 }
 
@@ -1143,11 +1162,13 @@ void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t tot
 
 // the partial results are SORTED lists of kk entries (nlists per query): knn_merge_lists
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
-						uint32_t* out_count, hipStream_t s) {
+						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt, uint32_t gate_cap) {
 	if (kk > uint32_t(kMaxFusedK)) {
-		hipLaunchKernelGGL((knn_merge_lists<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count);
+		hipLaunchKernelGGL((knn_merge_lists<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
+						   gate_cnt, gate_cap);
 	} else {
-		hipLaunchKernelGGL((knn_merge_lists<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count);
+		hipLaunchKernelGGL((knn_merge_lists<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
+						   gate_cnt, gate_cap);
 	}
 }
 

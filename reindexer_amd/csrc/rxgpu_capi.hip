@@ -3,6 +3,7 @@
 #include <unistd.h>   // environ
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -317,11 +318,24 @@ static int batch_min_queries() {
 	return v;
 }
 
+// The three statistics words back on the host (h->mtx held): are the maxima finite and has no NaN row been seen?  Only then does the rounding
+// bound of the bf16-pruned scan mean anything; the automatic scan policy (enqueue_knn) keeps such an index on the f32 scan.
+int read_stats_finite(rxgpu_index* h, hipStream_t s) {
+	unsigned int w[3] = {0, 0, 0};
+	RX_HIP(hipMemcpyAsync(w, h->d_stats, sizeof(w), hipMemcpyDeviceToHost, s));
+	RX_HIP(hipStreamSynchronize(s));
+	float a, b;
+	std::memcpy(&a, &w[0], sizeof(a));
+	std::memcpy(&b, &w[1], sizeof(b));
+	h->stats_finite = std::isfinite(a) && std::isfinite(b) && w[2] == 0;
+	return RXGPU_OK;
+}
+
 // Per-row statistics are cached on the index; recomputed (synchronously, under the index mutex) after any mutation.
 int ensure_row_stats(rxgpu_index* h, hipStream_t s) {
 	std::lock_guard<std::mutex> lk(h->mtx);
 	if (h->stats_valid) return RXGPU_OK;
-	if (!h->d_stats) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats), 2 * sizeof(unsigned int)));
+	if (!h->d_stats) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats), 3 * sizeof(unsigned int)));
 	if (h->metric == RXGPU_METRIC_L2 && h->row_sq_capacity < h->count) {
 		if (h->d_row_sq) (void)hipFree(h->d_row_sq);
 		h->d_row_sq = nullptr;
@@ -329,11 +343,11 @@ int ensure_row_stats(rxgpu_index* h, hipStream_t s) {
 		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_row_sq), std::max<uint64_t>(h->capacity, h->count) * sizeof(float)));
 		h->row_sq_capacity = std::max<uint64_t>(h->capacity, h->count);
 	}
-	RX_HIP(hipMemsetAsync(h->d_stats, 0, 2 * sizeof(unsigned int), s));
+	RX_HIP(hipMemsetAsync(h->d_stats, 0, 3 * sizeof(unsigned int), s));
 	rxgpu::launch_row_stats(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->metric == RXGPU_METRIC_L2 ? h->d_row_sq : nullptr,
 							h->d_stats, h->cus, s);
 	RX_HIP(hipGetLastError());
-	RX_HIP(hipStreamSynchronize(s));
+	if (int rc = read_stats_finite(h, s); rc) return rc;   // synchronises the stream
 	h->stats_valid = true;
 	return RXGPU_OK;
 }
@@ -571,12 +585,31 @@ int enqueue_knn_batched(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_quer
 	return RXGPU_OK;
 }
 
-// bf16-pruned scan for one .. a few queries (opt-in: RXGPU_SCAN_BF16=1): 2 bytes per element from HBM instead of 4, exact result (knn_scan.hip).
-static bool scan_bf16_enabled() {   // read per call: a process can switch it for A/B runs
+// bf16-pruned scan for one .. a few queries: 2 bytes per element from HBM instead of 4, exact result (knn_scan.hip).
+// RXGPU_SCAN_BF16, read per call (a process can switch it for A/B runs): 1 = forced on (up to kPrunedMaxQueries queries, any size), 0 = forced
+// off (the f32 paths, always), unset = automatic: single queries on indexes of at least kPrunedAutoMinBytes of f32 rows.
+enum ScanBf16Mode { kScanBf16Off = 0, kScanBf16On = 1, kScanBf16Auto = 2 };
+static ScanBf16Mode scan_bf16_mode() {
 	const char* e = getenv("RXGPU_SCAN_BF16");
-	return e && atoi(e) != 0;
+	if (!e || !*e) return kScanBf16Auto;
+	return atoi(e) != 0 ? kScanBf16On : kScanBf16Off;
 }
 constexpr uint32_t kPrunedMaxQueries = 8;
+// Automatic mode: the pruned path pays a fixed tail per query (filter, re-score, two merges, the gated scan) and saves half the streaming; it
+// also costs +2 bytes per element of HBM.  Never below 1 GiB (small indexes keep the f32 kernel and their footprint); measured crossover in
+// profiles/scan_policy_crossover.json.  RXGPU_SCAN_BF16_MIN_BYTES overrides it (tests exercise the decision on small corpora).
+constexpr uint64_t kPrunedAutoMinBytes = 1ull << 30;
+static uint64_t pruned_auto_min_bytes() {
+	const char* e = getenv("RXGPU_SCAN_BF16_MIN_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : kPrunedAutoMinBytes;
+}
+// The whole decision, without a device: does a call with nq queries on rows x dim f32 rows take the bf16-pruned scan?
+static bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite) {
+	const ScanBf16Mode mode = scan_bf16_mode();
+	if (mode == kScanBf16Off || !shadow_available || !rxgpu::scan_bf16_supported((dim + 63u) & ~63u)) return false;
+	if (mode == kScanBf16On) return nq <= kPrunedMaxQueries;
+	return nq == 1 && stats_finite && rows * dim * sizeof(float) >= pruned_auto_min_bytes();
+}
 constexpr uint32_t kPrunedCap = 4096;
 
 int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
@@ -584,13 +617,15 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 	if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
 	if (int rc = ensure_bf16_shadow(h, c->stream); rc) return rc;
 	const uint32_t ld = (h->dim + 63u) & ~63u;
-	const uint32_t gridx = rxgpu::scan_grid_x(h->count, h->cus);
+	const uint32_t gridx = rxgpu::scan_bf16_grid_x(h->count, h->cus);   // the bf16 scan's grid
+	const uint32_t gridx_exact = rxgpu::scan_grid_x(h->count, h->cus);   // the gated f32 scan's
+	const uint32_t grid_max = std::max(gridx, gridx_exact);
 	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (h->count + 63) & ~63ull)));
 	if (int rc = c->d_qpad.ensure(size_t(nq) * ld * sizeof(float)); rc) return rc;
 	if (int rc = c->d_qstats.ensure(size_t(2) * nq * sizeof(float)); rc) return rc;
 	if (int rc = c->d_dense.ensure(size_t(nq) * h->count * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_dist.ensure(size_t(nq) * gridx * kk * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(size_t(nq) * gridx * kk * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
+	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
@@ -602,10 +637,8 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
 	uint32_t* top_cnt = top_row + size_t(nq) * kk;
 	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
-	RX_HIP(hipMemsetAsync(qpad, 0, size_t(nq) * ld * sizeof(float), c->stream));
-	RX_HIP(hipMemcpy2DAsync(qpad, ld * sizeof(float), d_queries, h->dim * sizeof(float), h->dim * sizeof(float), nq, hipMemcpyDeviceToDevice, c->stream));
-	RX_HIP(hipMemsetAsync(cand_cnt, 0, size_t(nq) * sizeof(uint32_t), c->stream));
-	rxgpu::launch_query_stats(h->metric, qpad, nq, nq, ld, h->dim, h->d_stats, q_sq, margin, true, c->stream);
+	// one launch: padded copy of the query, |q|^2, margin, cand_cnt = 0 (cap + 1 for a query without a finite bound: the gated exact scan answers it)
+	rxgpu::launch_query_prep(h->metric, d_queries, nq, h->dim, qpad, ld, h->d_stats, q_sq, margin, cand_cnt, cap, c->stream);
 	rxgpu::ScanBf16Params p{};
 	p.sp.inv_norms = h->d_inv_norms;
 	p.sp.n = h->count;
@@ -623,7 +656,8 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 		ProfileScope ps(h, "scan_bf16", c->stream);
 		rxgpu::launch_scan_bf16(h->metric, p, nq, gridx, c->stream);
 	}
-	rxgpu::launch_merge(p.sp.part_dist, p.sp.part_row, gridx * kk, kk, nq, top_dist, top_row, top_cnt, nullptr, 0, c->stream);
+	// (the scan leaves sorted lists like the f32 scan: the list merge, 4 us against 28 for the insertion merge in the kernel trace of the headline)
+	rxgpu::launch_merge_lists(p.sp.part_dist, p.sp.part_row, gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
 	{
 		ProfileScope ps(h, "filter_approx", c->stream);
 		rxgpu::launch_filter_approx(p.approx, h->count, top_dist, top_cnt, kk, margin, static_cast<uint32_t*>(c->d_cand_row.ptr), cand_cnt, cap, nq,
@@ -636,7 +670,7 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 	}
 	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
 						d_out_count, nullptr, 0, c->stream);
-	{   // more rows inside the bound than the list holds (massive ties): exact scan, gated on device
+	{   // more rows inside the bound than the list holds (massive ties), or no finite bound: the f32 path's own scan + merge, gated on device
 		rxgpu::ScanParams e{};
 		e.rows = h->d_rows;
 		e.inv_norms = h->d_inv_norms;
@@ -650,8 +684,8 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 		e.gate_cnt = cand_cnt;
 		e.gate_cap = cap;
 		ProfileScope ps(h, "fallback_scan", c->stream);
-		rxgpu::launch_scan(h->metric, e, nq, gridx, c->stream);
-		rxgpu::launch_merge(e.part_dist, e.part_row, gridx * kk, kk, nq, d_out_dist, d_out_row, d_out_count, cand_cnt, cap, c->stream);
+		rxgpu::launch_scan(h->metric, e, nq, gridx_exact, c->stream);
+		rxgpu::launch_merge_lists(e.part_dist, e.part_row, gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, cand_cnt, cap);
 	}
 	RX_HIP(hipGetLastError());
 	return RXGPU_OK;
@@ -746,7 +780,11 @@ int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries
 
 int enqueue_knn(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
 				uint32_t* d_out_row, uint32_t* d_out_count) {
-	if (scan_bf16_enabled() && nq <= kPrunedMaxQueries && !h->bf16_unavailable && rxgpu::scan_bf16_supported((h->dim + 63u) & ~63u)) {
+	// (automatic mode asks whether the row statistics are finite: compute them first where everything else already says yes)
+	if (scan_bf16_mode() == kScanBf16Auto && scan_policy_pruned(h->count, h->dim, nq, !h->bf16_unavailable, true)) {
+		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
+	}
+	if (scan_policy_pruned(h->count, h->dim, nq, !h->bf16_unavailable, h->stats_finite)) {
 		const int rc = enqueue_knn_pruned(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
 		if (!(rc == RXGPU_ERR_NOMEM && h->bf16_unavailable)) return rc;
 	}
@@ -760,6 +798,10 @@ extern "C" {
 
 const char* rxgpu_last_error(void) { return rxgpu::g_err.c_str(); }
 int rxgpu_abi_version(void) { return RXGPU_ABI_VERSION; }
+
+int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
+	return scan_policy_pruned(rows, dim, nq, shadow_available != 0, stats_finite != 0) ? 1 : 0;
+}
 
 int rxgpu_device_count(void) {
 	int n = 0;
@@ -924,6 +966,7 @@ int rxgpu_index_upload_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, cons
 		} else {
 			rxgpu::launch_row_stats(dst, h->d_inv_norms ? h->d_inv_norms + first_row : nullptr, n, h->stride, h->dim,
 									h->metric == RXGPU_METRIC_L2 ? h->d_row_sq + first_row : nullptr, h->d_stats, h->cus, nullptr);
+			if (int rc = read_stats_finite(h, nullptr); rc) return rc;   // maxima never shrink: an index that has held a non-finite row stays on the f32 scan
 		}
 	}
 	if (h->bf16_valid) {

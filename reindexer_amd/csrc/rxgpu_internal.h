@@ -20,13 +20,15 @@ uint32_t scan_grid_x(uint64_t n, int cus);
 void launch_scan(int metric, const ScanParams& p, uint32_t nq, uint32_t gridx, hipStream_t s);
 struct ScanBf16Params;
 bool scan_bf16_supported(uint32_t ld);
+uint32_t scan_bf16_grid_x(uint64_t n, int cus);
 void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
 						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s);
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s);
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
-						uint32_t* out_count, hipStream_t s);   // the partial results are sorted lists of kk entries: no serial insertions
+						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt = nullptr,
+						uint32_t gate_cap = 0);   // the partial results are sorted lists of kk entries: no serial insertions; gated like launch_merge
 void launch_merge_shards(const uint32_t* gathered, uint32_t world, uint32_t nq, uint32_t kk, uint32_t shard_rows, float* out_dist,
 						 uint32_t* out_row, uint32_t* out_count, hipStream_t s, const uint32_t* slot_base = nullptr, bool sorted = true);
 // one shard's HNSW result (unordered, counts <= k) into its [nq][kk] | [nq][kk] slot of the exchange's send buffer, padded with invalid entries
@@ -68,6 +70,8 @@ void launch_row_stats(const float* rows, const float* inv_norms, uint64_t n, uin
 					  unsigned int* stats, int cus, hipStream_t s);
 void launch_query_stats(int metric, const float* queries, uint32_t nq, uint32_t mt, uint32_t q_stride, uint32_t dim, const unsigned int* stats,
 						float* q_sq, float* margin, bool bf16, hipStream_t s);
+void launch_query_prep(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, uint32_t ld, const unsigned int* stats, float* q_sq,
+					   float* margin, uint32_t* cand_cnt, uint32_t cap, hipStream_t s);   // the pruned scan's query side in one launch
 struct GemmBf16Params;
 hipError_t launch_gemm_bf16(int metric, int mode, int qt, const GemmBf16Params& p, uint32_t grid, hipStream_t s);
 void launch_to_bf16(const float* src, uint64_t n, uint32_t stride, uint32_t dim, uint16_t* dst, uint32_t ld, int cus, hipStream_t s, uint64_t first_row = 0,
@@ -509,6 +513,7 @@ struct rxgpu_index {
 	uint64_t row_sq_capacity = 0;
 	unsigned int* d_stats = nullptr;
 	bool stats_valid = false;
+	std::atomic<bool> stats_finite{true};   // valid with stats_valid: no row has a NaN / infinite |x|^2 — what the pruning bound of the bf16 scan needs
 	uint16_t* d_rows_bf16 = nullptr;   // bf16 shadow of the rows for the nomination GEMM (built lazily with the row statistics)
 	uint64_t bf16_capacity = 0;
 	bool bf16_blocked = true;   // layout of the shadow (knn_kernels.hip.h); RXGPU_SHADOW_BLOCKED=0 when the shadow is first built: row-major (A/B)

@@ -3,6 +3,7 @@
 
     python tools/summarize_prof.py gpurun_out/prof r1
 
+An optional third argument names the profiled command in the summary when it is not the default --full triple.
 Kernel names are truncated (torch's template names run to kilobytes).  PMC correction per
 /opt/skills/guides/MI355X_MICROARCH.md §HBM: on gfx950 FETCH_SIZE (KiB) counts 128-B requests as 64 B for wide
 coalesced streaming reads, so read bytes = 2 * FETCH_SIZE * 1024; WRITE_SIZE is taken as reported (KiB).
@@ -24,7 +25,8 @@ def main():
         w.writerow(["Name", "Calls", "TotalDurationNs", "AverageNs", "Percentage", "MinNs", "MaxNs", "StdDev"])
         for r in stats:
             w.writerow([r["Name"][:96], r["Calls"], r["TotalDurationNs"], r["AverageNs"], r["Percentage"], r["MinNs"], r["MaxNs"], r["StdDev"]])
-    summary = {"command": "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 30 --warmup 5 --no-cpu ; "
+    summary = {"command": sys.argv[3] if len(sys.argv) > 3 else
+                          "rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 30 --warmup 5 --no-cpu ; "
                           "rocprofv3 --pmc FETCH_SIZE -- python bench.py --full --steps 10 --warmup 2 --no-cpu ; "
                           "rocprofv3 --pmc WRITE_SIZE -- (same)", "kernels": {}}
     for r in stats:

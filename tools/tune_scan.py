@@ -16,6 +16,7 @@ import sys
 from pathlib import Path
 
 os.environ["RXGPU_TUNE_DYNAMIC"] = "1"
+os.environ["RXGPU_SCAN_BF16"] = "0"   # this tool reads the profile slot "scan": the f32 kernel, which large indexes no longer take by default
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 
 import torch  # noqa: E402
