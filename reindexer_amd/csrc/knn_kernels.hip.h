@@ -20,6 +20,8 @@
 
 #include <atomic>
 
+#include "hnsw_launch_plan.h"   // kHnswMaxEf, kHnswLdsCandEf, kHnswCandLds, kHnswSortedMaxEf, kHnswSortedMaxEfDel: the constants the host-side policy reads too
+
 namespace rxgpu {
 
 // hipFuncSetAttribute acts on the CURRENT device, and launch helpers are entered from several host threads (sharded indexes run one worker
@@ -116,9 +118,6 @@ struct GemmBf16Params {
 	uint32_t cap;
 };
 
-constexpr int kHnswMaxEf = 4096;        // result-heap capacity in LDS (above kHnswLdsCandEf the candidate heap lives in global scratch)
-constexpr int kHnswLdsCandEf = 1024;    // largest ef whose candidate heap is tried in LDS first
-constexpr int kHnswCandLds = 2048;      // candidate-heap capacity in LDS
 constexpr int kHnswMaxNeighbors = 128;  // 2*M <= 128
 constexpr uint32_t kHnswOverflow = 0xFFFFFFFFu;
 constexpr uint32_t kHnswSpecLog2 = 11;   // speculative team search: 2048-entry direct-mapped table of distances computed ahead of time
@@ -126,8 +125,6 @@ constexpr uint32_t kHnswSpecBytes = (2u << kHnswSpecLog2) * 4 + (128 + 3 * 64) *
 constexpr int kHnswNblRows = 32;             // team searches: link blocks fetched along with a hop's rows (one 64-word slot each)
 constexpr uint32_t kHnswNblBytes = kHnswNblRows * 64 * 4;
 constexpr uint32_t kHnswTie = 0xFFFFFFFEu;        // sorted-list search met equal keys: re-run on the heap kernel
-constexpr int kHnswSortedMaxEf = 256;            // largest ef the sorted-list search holds in registers (4 entries a lane)
-constexpr int kHnswSortedMaxEfDel = 224;         // ... for a graph with deleted nodes: 32 entries of room for the deleted candidates in reach
 
 struct HnswParams {
 	const float* rows;

@@ -1,8 +1,6 @@
 // C-ABI implementation (include/rxgpu.h): index storage in HBM, search entry points, instrumentation.
 // Host-side plumbing only — all arithmetic is in the kernels.
-#include <unistd.h>   // environ
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -75,23 +73,6 @@ hipError_t device_wait_all(int device) {
 	return e;
 }
 }  // namespace rxgpu
-
-#define RX_HIP(expr)                                                                                      \
-	do {                                                                                                  \
-		hipError_t e__ = (expr);                                                                          \
-		if (e__ != hipSuccess) {                                                                          \
-			set_error(std::string(#expr) + ": " + hipGetErrorString(e__));                                \
-			return e__ == hipErrorOutOfMemory ? RXGPU_ERR_NOMEM : RXGPU_ERR_DEVICE;                       \
-		}                                                                                                 \
-	} while (0)
-
-#define RX_CHECK(cond, code, msg) \
-	do {                          \
-		if (!(cond)) {            \
-			set_error(msg);       \
-			return code;          \
-		}                         \
-	} while (0)
 
 int rxgpu_devbuf::ensure(size_t need) {
 	if (need <= bytes) return RXGPU_OK;
@@ -171,20 +152,7 @@ void rxgpu_search_ctx::release() {
 	stream = nullptr;
 }
 
-namespace {
-
-struct DeviceGuard {
-	int prev = -1;
-	bool ok = true;
-	explicit DeviceGuard(int dev) {
-		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
-	}
-	~DeviceGuard() {
-		if (prev >= 0) (void)hipSetDevice(prev);
-	}
-};
-
+namespace rxgpu {
 // Check out a scratch context with its own stream (host-synchronous searches).
 rxgpu_search_ctx* acquire_ctx(rxgpu_index* h) {
 	{
@@ -208,6 +176,30 @@ void release_ctx(rxgpu_index* h, rxgpu_search_ctx* c) {
 	std::lock_guard<std::mutex> lk(h->mtx);
 	h->free_ctx.push_back(c);
 }
+ProfileScope::ProfileScope(rxgpu_index* h_, const char* n, hipStream_t s_) : h(h_), name(n), s(s_) {
+	if (!h->profiling) return;
+	if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
+		a = b = nullptr;
+		return;
+	}
+	(void)hipEventRecord(a, s);
+}
+ProfileScope::~ProfileScope() {
+	if (!a) return;
+	(void)hipEventRecord(b, s);
+	std::lock_guard<std::mutex> lk(h->mtx);
+	h->profile[name].events.emplace_back(a, b);
+}
+}  // namespace rxgpu
+
+using rxgpu::acquire_ctx;
+using rxgpu::CtxLease;
+using rxgpu::DeviceGuard;
+using rxgpu::ProfileScope;
+using rxgpu::release_ctx;
+
+namespace {
+
 // Resident contexts are per calling thread (rxgpu_search_knn_resident).  Planner threads come and go: a thread that ends hands the contexts it
 // held back to the pools of the indexes that still exist — looked up by serial number, never through a pointer the thread kept — so short-lived
 // threads neither pile up streams + device buffers until rxgpu_index_destroy nor leave their context to a later thread that got the same id.
@@ -255,27 +247,6 @@ rxgpu_search_ctx* stream_ctx(rxgpu_index* h, void* stream) {
 	h->stream_ctx[stream] = c;
 	return c;
 }
-
-struct ProfileScope {
-	rxgpu_index* h;
-	const char* name;
-	hipStream_t s;
-	hipEvent_t a = nullptr, b = nullptr;
-	ProfileScope(rxgpu_index* h_, const char* n, hipStream_t s_) : h(h_), name(n), s(s_) {
-		if (!h->profiling) return;
-		if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) {
-			a = b = nullptr;
-			return;
-		}
-		(void)hipEventRecord(a, s);
-	}
-	~ProfileScope() {
-		if (!a) return;
-		(void)hipEventRecord(b, s);
-		std::lock_guard<std::mutex> lk(h->mtx);
-		h->profile[name].events.emplace_back(a, b);
-	}
-};
 
 // Enqueue scan + merge for nq device-resident queries; results land in d_out_* (device).
 int enqueue_knn_fused(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
@@ -984,10 +955,7 @@ int rxgpu_index_upload_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, cons
 
 int rxgpu_index_adopt_device_rows(rxgpu_index* h, const void* d_rows, uint64_t n, uint32_t row_stride, const void* d_inv_norms) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_index_adopt_device_rows: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_index_adopt_device_rows: not available on a sharded index");
 	RX_CHECK(d_rows || n == 0, RXGPU_ERR_PARAMS, "rxgpu_index_adopt_device_rows: d_rows is null");
 	RX_CHECK(row_stride >= h->dim && row_stride % 4 == 0, RXGPU_ERR_PARAMS, "row_stride must be >= dim and a multiple of 4 floats");
 	RX_CHECK((reinterpret_cast<uintptr_t>(d_rows) & 15) == 0, RXGPU_ERR_PARAMS, "d_rows must be 16-byte aligned");
@@ -1075,10 +1043,7 @@ uint64_t rxgpu_index_device_bytes(const rxgpu_index* h) {
 int rxgpu_search_knn_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, void* d_out_dist, void* d_out_row,
 							void* d_out_count, void* stream) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_search_knn_device: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_device: not available on a sharded index");
 	RX_CHECK(nq > 0 && d_queries && d_out_dist && d_out_row, RXGPU_ERR_PARAMS, "rxgpu_search_knn_device: null argument");
 	RX_CHECK(kk > 0 && kk <= uint32_t(rxgpu::kMaxFusedK), RXGPU_ERR_PARAMS, "rxgpu_search_knn_device: kk must be in [1, 64]");
 	RX_CHECK(h->count > 0, RXGPU_ERR_PARAMS, "rxgpu_search_knn_device: index is empty");
@@ -1091,10 +1056,7 @@ int rxgpu_search_knn_device(rxgpu_index* h, const void* d_queries, uint32_t nq, 
 // internal row -> row id table for consumers on the device (the hybrid fusion maps the scan's rows to the planner's row ids there)
 int rxgpu_index_upload_row_ids(rxgpu_index* h, uint64_t first_row, uint64_t n, const int32_t* row_ids) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_index_upload_row_ids: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_index_upload_row_ids: not available on a sharded index");
 	if (n == 0) return RXGPU_OK;
 	RX_CHECK(row_ids && first_row + n <= h->capacity, RXGPU_ERR_PARAMS, "rxgpu_index_upload_row_ids: rows out of range");
 	DeviceGuard dg(h->device);
@@ -1120,10 +1082,7 @@ int rxgpu_search_knn_resident(rxgpu_index* h, const float* query, uint32_t kk, v
 							  uint32_t* entries) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
 	RX_CHECK(query && d_dist && d_row && d_count && stream && entries, RXGPU_ERR_PARAMS, "rxgpu_search_knn_resident: null argument");
-	if (h->shard_set) {
-		set_error("rxgpu_search_knn_resident: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_resident: not available on a sharded index");
 	RX_CHECK(kk >= 1 && kk <= uint32_t(rxgpu::kMaxFusedK2), RXGPU_ERR_PARAMS, "rxgpu_search_knn_resident: kk must be in [1, 128]");
 	RX_CHECK(h->count > 0, RXGPU_ERR_PARAMS, "rxgpu_search_knn_resident: index is empty");
 	DeviceGuard dg(h->device);
@@ -1187,11 +1146,7 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	const uint32_t eff = uint32_t(std::min<uint64_t>(kk, h->count));
 	const size_t qbytes = size_t(nq) * h->dim * sizeof(float);
 	if (int rc = c->d_queries.ensure(qbytes); rc) return rc;
@@ -1282,11 +1237,7 @@ int rxgpu_search_knn_subset(rxgpu_index* h, const float* queries, uint32_t nq, u
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	if (int rc = c->d_subset.ensure(n_ids * sizeof(uint32_t)); rc) return rc;
 	RX_HIP(hipMemcpyAsync(c->d_subset.ptr, row_ids, n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 	return search_subset_host(h, c, queries, nq, kk, static_cast<const uint32_t*>(c->d_subset.ptr), n_ids, out_dist, out_row, out_count);
@@ -1295,10 +1246,7 @@ int rxgpu_search_knn_subset(rxgpu_index* h, const float* queries, uint32_t nq, u
 int rxgpu_search_knn_bitmap(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* allowed_words, uint64_t n_words,
 							float* out_dist, uint32_t* out_row, uint32_t* out_count, uint64_t* out_allowed) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_search_knn_bitmap: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_bitmap: not available on a sharded index");
 	RX_CHECK(queries && out_dist && out_row && out_count && allowed_words, RXGPU_ERR_PARAMS, "rxgpu_search_knn_bitmap: null argument");
 	const uint64_t need_words = (h->count + 31) / 32;
 	RX_CHECK(n_words >= need_words, RXGPU_ERR_PARAMS, "rxgpu_search_knn_bitmap: the bitmap must cover every row (ceil(count / 32) words)");
@@ -1311,11 +1259,7 @@ int rxgpu_search_knn_bitmap(rxgpu_index* h, const float* queries, uint32_t nq, u
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	const uint32_t tiles = rxgpu::bitmap_tiles(h->count);
 	if (int rc = c->d_bitmap.ensure(need_words * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_tiles.ensure(size_t(2) * tiles * sizeof(uint32_t) + sizeof(unsigned long long)); rc) return rc;
@@ -1347,10 +1291,7 @@ int rxgpu_search_knn_bitmap(rxgpu_index* h, const float* queries, uint32_t nq, u
 
 int rxgpu_index_set_lists(rxgpu_index* h, uint32_t nlist, const uint64_t* list_off, const uint32_t* list_rows) {
 	RX_CHECK(h && list_off && nlist > 0, RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: null argument");
-	if (h->shard_set) {
-		set_error("rxgpu_index_set_lists: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_index_set_lists: not available on a sharded index");
 	RX_CHECK(list_off[0] == 0, RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: offsets start at 0");
 	for (uint32_t l = 0; l < nlist; ++l) RX_CHECK(list_off[l] <= list_off[l + 1], RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: offsets must not decrease");
 	const uint64_t total = list_off[nlist];
@@ -1453,11 +1394,7 @@ int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* que
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	unsigned long long total = 0;
 	if (int rc = ivf_probe_rows(h, coarse, c, query, nprobe, &total, "rxgpu_search_knn_lists"); rc) return rc;
 	if (out_scanned) *out_scanned = total;
@@ -1516,11 +1453,7 @@ int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* q
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	unsigned long long total = 0;
 	if (int rc = ivf_probe_rows(h, coarse, c, query, nprobe, &total, "rxgpu_search_range_lists"); rc) return rc;
 	if (out_scanned) *out_scanned = total;
@@ -1531,10 +1464,7 @@ int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* q
 int rxgpu_search_knn_subset_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, const void* d_row_ids, uint64_t n_ids,
 								   void* d_out_dist, void* d_out_row, void* d_out_count, void* stream) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_search_knn_subset_device: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_subset_device: not available on a sharded index");
 	RX_CHECK(nq > 0 && d_queries && d_row_ids && d_out_dist && d_out_row, RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset_device: null argument");
 	RX_CHECK(kk > 0 && kk <= uint32_t(rxgpu::kMaxFusedK2), RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset_device: kk must be in [1, 128]");
 	RX_CHECK(n_ids > 0 && n_ids <= h->count, RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset_device: the row list must hold 1..count entries");
@@ -1585,11 +1515,7 @@ int rxgpu_search_range(rxgpu_index* h, const float* query, float radius, int inc
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	const uint64_t dcap = std::min<uint64_t>(cap, h->count);
 	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
 	if (int rc = c->d_out_dist.ensure(std::max<uint64_t>(dcap, 1) * sizeof(float)); rc) return rc;
@@ -1645,11 +1571,7 @@ int rxgpu_search_range_subset(rxgpu_index* h, const float* query, float radius, 
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
 	if (int rc = c->d_subset.ensure(n_ids * sizeof(uint32_t)); rc) return rc;
 	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, h->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -1666,11 +1588,7 @@ int rxgpu_distances(rxgpu_index* h, const float* query, const uint32_t* rows, ui
 	DeviceGuard dg(h->device);
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
+	CtxLease lease{h, c};
 	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
 	if (int rc = c->d_out_row.ensure(size_t(n) * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_out_dist.ensure(size_t(n) * sizeof(float)); rc) return rc;
@@ -1687,1293 +1605,9 @@ int rxgpu_distances(rxgpu_index* h, const float* query, const uint32_t* rows, ui
 	return RXGPU_OK;
 }
 
-/* ------------------------------------------------------------------------------------------------ HNSW */
-
-int rxgpu_hnsw_attach_graph(rxgpu_index* h, const uint32_t* links0, const uint64_t* upper_off, const uint32_t* upper, uint64_t upper_blocks,
-							const uint8_t* deleted, uint32_t M, uint32_t max_m0, int32_t maxlevel, uint32_t entry, uint64_t num_deleted) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_hnsw_attach_graph: a sharded index holds one graph per shard — attach to the rxgpu_index_shard(h, s) handles");
-		return RXGPU_ERR_LOGIC;
-	}
-	const uint64_t n = h->count;
-	RX_CHECK(n == 0 || (links0 && upper_off && deleted), RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_graph: null argument");
-	RX_CHECK(upper_blocks == 0 || upper, RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_graph: upper is null");
-	RX_CHECK(M >= 1 && max_m0 <= uint32_t(rxgpu::kHnswMaxNeighbors) && M <= max_m0, RXGPU_ERR_PARAMS,
-			 "rxgpu_hnsw_attach_graph: the GPU engine supports M <= 64 (2*M <= 128)");
-	RX_CHECK(n == 0 || entry < n, RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_graph: entry point out of range");
-	DeviceGuard dg(h->device);
-	RX_HIP(rxgpu::device_wait_all(h->device));
-	// allocated for the index CAPACITY (and with headroom for upper-level blocks), so that rxgpu_hnsw_patch_graph can grow the graph in place
-	auto replace = [&](auto*& dst, const void* src, size_t bytes, size_t cap_bytes) -> int {
-		if (dst) (void)hipFree(dst);
-		dst = nullptr;
-		if (cap_bytes == 0) return RXGPU_OK;
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&dst), cap_bytes));
-		if (bytes) RX_HIP(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-		return RXGPU_OK;
-	};
-	h->graph_attached = false;
-	const uint64_t rows_cap = std::max<uint64_t>(std::max<uint64_t>(h->capacity, n), 1);
-	// expected upper blocks of a full index: sum over levels of cap / M^level = cap / (M - 1); twice that (and at least what is there) as headroom
-	const uint64_t upper_cap = std::max<uint64_t>(2 * upper_blocks + 64, 2 * rows_cap / std::max<uint32_t>(M - 1, 1) + 64);
-	const size_t row_bytes = (1 + size_t(max_m0)) * sizeof(uint32_t), blk_bytes = (1 + size_t(M)) * sizeof(uint32_t);
-	if (int rc = replace(h->d_links0, links0, n * row_bytes, rows_cap * row_bytes); rc) return rc;
-	if (int rc = replace(h->d_upper_off, upper_off, n ? (n + 1) * sizeof(uint64_t) : 0, (rows_cap + 1) * sizeof(uint64_t)); rc) return rc;
-	if (int rc = replace(h->d_upper, upper, upper_blocks * blk_bytes, upper_cap * blk_bytes); rc) return rc;
-	if (int rc = replace(h->d_deleted, deleted, n, rows_cap); rc) return rc;
-	h->graph_rows_cap = rows_cap;
-	h->graph_upper_cap = upper_cap;
-	h->graph_upper_used = upper_blocks;
-	if (!h->d_hnsw_stats) {
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_hnsw_stats), 8 * sizeof(unsigned long long)));   // evals, hops, in-kernel restarts, spare, [4..7] phase cycles (RXGPU_HNSW_PHASES builds)
-		RX_HIP(hipMemset(h->d_hnsw_stats, 0, 8 * sizeof(unsigned long long)));
-	}
-	h->graph_n = n;
-	h->graph_M = M;
-	h->graph_maxM0 = max_m0;
-	h->graph_maxlevel = maxlevel;
-	h->graph_entry = entry;
-	h->graph_deleted = num_deleted;
-	h->graph_attached = true;
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_patch_graph(rxgpu_index* h, uint32_t n_dirty, const uint32_t* dirty_ids, const uint32_t* links0_rows, const uint8_t* deleted_flags,
-						   const int32_t* levels, const uint32_t* upper_rows, int32_t maxlevel, uint32_t entry, uint64_t num_deleted) {
-	RX_CHECK(h && h->graph_attached, RXGPU_ERR_LOGIC, "rxgpu_hnsw_patch_graph: no graph attached");
-	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel reads what changes here
-	RX_CHECK(n_dirty == 0 || (dirty_ids && links0_rows && deleted_flags && levels), RXGPU_ERR_PARAMS, "rxgpu_hnsw_patch_graph: null argument");
-	const uint64_t n_new = h->count;   // the rows were uploaded first (rxgpu_index_upload_rows)
-	RX_CHECK(n_new >= h->graph_n, RXGPU_ERR_LOGIC, "rxgpu_hnsw_patch_graph: the index shrank under the graph");
-	RX_CHECK(n_new == 0 || entry < n_new, RXGPU_ERR_PARAMS, "rxgpu_hnsw_patch_graph: entry point out of range");
-	if (n_new > h->graph_rows_cap) {
-		set_error("rxgpu_hnsw_patch_graph: the graph arrays were allocated for fewer rows (re-attach the graph)");
-		return RXGPU_ERR_OVERFLOW;
-	}
-	// staging: ids, per-node upper placement, lists — one buffer, one upload, one scatter launch
-	const uint32_t M = h->graph_M, max_m0 = h->graph_maxM0;
-	const size_t stride0 = 1 + size_t(max_m0), stride = 1 + size_t(M);
-	std::vector<uint64_t> upper_at(n_dirty);
-	std::vector<uint32_t> upper_src(n_dirty);
-	uint64_t used = h->graph_upper_used, staged_blocks = 0, next_new = h->graph_n;
-	for (uint32_t j = 0; j < n_dirty; ++j) {
-		RX_CHECK(dirty_ids[j] < n_new && levels[j] >= 0, RXGPU_ERR_PARAMS, "rxgpu_hnsw_patch_graph: node id / level out of range");
-		upper_src[j] = uint32_t(staged_blocks);
-		staged_blocks += uint64_t(levels[j]);
-		if (dirty_ids[j] >= h->graph_n) {   // a new node: ids ascending, every one of them listed (its blocks are appended in id order)
-			RX_CHECK(dirty_ids[j] == next_new, RXGPU_ERR_PARAMS, "rxgpu_hnsw_patch_graph: new nodes must be listed in ascending id order, none skipped");
-			++next_new;
-			upper_at[j] = used;
-			used += uint64_t(levels[j]);
-		} else {
-			upper_at[j] = ~uint64_t(0);
-		}
-	}
-	RX_CHECK(next_new == n_new, RXGPU_ERR_PARAMS, "rxgpu_hnsw_patch_graph: every new node must be listed");
-	RX_CHECK(staged_blocks == 0 || upper_rows, RXGPU_ERR_PARAMS, "rxgpu_hnsw_patch_graph: upper_rows is null");
-	if (used > h->graph_upper_cap) {
-		set_error("rxgpu_hnsw_patch_graph: upper-level storage exhausted (re-attach the graph)");
-		return RXGPU_ERR_OVERFLOW;
-	}
-	DeviceGuard dg(h->device);
-	rxgpu_search_ctx* c = acquire_ctx(h);
-	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
-	RX_HIP(rxgpu::device_wait_all(h->device));   // no search may be reading the lists while they change (the Map calls this under its writer lock)
-	auto al = [](size_t v) { return (v + 255) & ~size_t(255); };
-	const size_t o_ids = 0, o_at = al(o_ids + size_t(n_dirty) * 4), o_src = al(o_at + size_t(n_dirty) * 8), o_lv = al(o_src + size_t(n_dirty) * 4),
-				 o_l0 = al(o_lv + size_t(n_dirty) * 4), o_up = al(o_l0 + size_t(n_dirty) * stride0 * 4), o_del = al(o_up + staged_blocks * stride * 4),
-				 total = al(o_del + n_dirty);
-	if (n_dirty) {
-		if (int rc = c->d_misc.ensure(total); rc) return rc;
-		if (int rc = c->ensure_pinned(total); rc) return rc;
-		char* hp = static_cast<char*>(c->h_pinned);
-		std::memcpy(hp + o_ids, dirty_ids, size_t(n_dirty) * 4);
-		std::memcpy(hp + o_at, upper_at.data(), size_t(n_dirty) * 8);
-		std::memcpy(hp + o_src, upper_src.data(), size_t(n_dirty) * 4);
-		std::memcpy(hp + o_lv, levels, size_t(n_dirty) * 4);
-		std::memcpy(hp + o_l0, links0_rows, size_t(n_dirty) * stride0 * 4);
-		if (staged_blocks) std::memcpy(hp + o_up, upper_rows, staged_blocks * stride * 4);
-		std::memcpy(hp + o_del, deleted_flags, n_dirty);
-		char* db = static_cast<char*>(c->d_misc.ptr);
-		RX_HIP(hipMemcpyAsync(db, hp, total, hipMemcpyHostToDevice, c->stream));
-		rxgpu::HnswPatch p{};
-		p.ids = reinterpret_cast<const uint32_t*>(db + o_ids);
-		p.upper_at = reinterpret_cast<const uint64_t*>(db + o_at);
-		p.upper_src = reinterpret_cast<const uint32_t*>(db + o_src);
-		p.levels = reinterpret_cast<const int32_t*>(db + o_lv);
-		p.src_links0 = reinterpret_cast<const uint32_t*>(db + o_l0);
-		p.src_upper = reinterpret_cast<const uint32_t*>(db + o_up);
-		p.src_deleted = reinterpret_cast<const uint8_t*>(db + o_del);
-		p.links0 = h->d_links0;
-		p.upper_off = h->d_upper_off;
-		p.upper = h->d_upper;
-		p.deleted = h->d_deleted;
-		p.M = M;
-		p.maxM0 = max_m0;
-		rxgpu::launch_hnsw_patch(p, n_dirty, c->stream);
-		RX_HIP(hipGetLastError());
-		RX_HIP(hipStreamSynchronize(c->stream));
-	}
-	h->graph_upper_used = used;
-	h->graph_n = n_new;
-	h->graph_maxlevel = maxlevel;
-	h->graph_entry = entry;
-	h->graph_deleted = num_deleted;
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_update_deleted(rxgpu_index* h, const uint8_t* deleted, uint64_t num_deleted) {
-	RX_CHECK(h && h->graph_attached, RXGPU_ERR_LOGIC, "rxgpu_hnsw_update_deleted: no graph attached");
-	RX_CHECK(deleted || h->graph_n == 0, RXGPU_ERR_PARAMS, "rxgpu_hnsw_update_deleted: null argument");
-	DeviceGuard dg(h->device);
-	RX_HIP(rxgpu::device_wait_all(h->device));
-	if (h->graph_n) RX_HIP(hipMemcpy(h->d_deleted, deleted, h->graph_n, hipMemcpyHostToDevice));
-	h->graph_deleted = num_deleted;
-	return RXGPU_OK;
-}
-
-// Rows [first_row, first_row + n) of the code table: the device side of a point added to / updated in a quantised graph (addPoint with a
-// quantizer, hnswalg.h:1480-1495).  The table is allocated for the index CAPACITY (like the rows), so an upsert is a copy of its own D + 4
-// bytes, not a re-upload of the table.
-int rxgpu_hnsw_upload_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, const uint8_t* codes, const float* corr, float alpha_2) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_hnsw_upload_sq8_rows: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
-	if (n == 0) return RXGPU_OK;
-	RX_CHECK(codes && corr, RXGPU_ERR_PARAMS, "rxgpu_hnsw_upload_sq8_rows: null argument");
-	RX_CHECK(first_row <= h->sq8_n && first_row + n <= h->count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_upload_sq8_rows: rows follow the table without a hole and stay below count");
-	DeviceGuard dg(h->device);
-	const uint64_t cap = std::max<uint64_t>(h->capacity, h->count);
-	if (h->sq8_cap < first_row + n) {   // first rows, or the index was reserved larger since: a new table, the old rows copied over
-		RX_HIP(rxgpu::device_wait_all(h->device));
-		uint8_t* nc = nullptr;
-		float* nr = nullptr;
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&nc), size_t(cap) * h->dim + 4));
-		if (hipMalloc(reinterpret_cast<void**>(&nr), size_t(cap) * sizeof(float)) != hipSuccess) {
-			(void)hipFree(nc);
-			set_error("rxgpu_hnsw_upload_sq8_rows: not enough memory for the corrective offsets");
-			return RXGPU_ERR_NOMEM;
-		}
-		if (h->sq8_n) {
-			RX_HIP(hipMemcpy(nc, h->d_codes, size_t(h->sq8_n) * h->dim, hipMemcpyDeviceToDevice));
-			RX_HIP(hipMemcpy(nr, h->d_corr, size_t(h->sq8_n) * sizeof(float), hipMemcpyDeviceToDevice));
-		}
-		if (h->d_codes) (void)hipFree(h->d_codes);
-		if (h->d_corr) (void)hipFree(h->d_corr);
-		h->d_codes = nc;
-		h->d_corr = nr;
-		h->sq8_cap = cap;
-	}
-	RX_HIP(hipMemcpy(h->d_codes + size_t(first_row) * h->dim, codes, size_t(n) * h->dim, hipMemcpyHostToDevice));
-	RX_HIP(hipMemcpy(h->d_corr + first_row, corr, size_t(n) * sizeof(float), hipMemcpyHostToDevice));
-	h->sq8_alpha2 = alpha_2;
-	h->sq8_n = std::max<uint64_t>(h->sq8_n, first_row + n);
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_attach_sq8(rxgpu_index* h, const uint8_t* codes, const float* corr, uint64_t count, float alpha_2) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_hnsw_attach_sq8: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
-	RX_CHECK(count == h->count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_sq8: one code row per index row");
-	RX_CHECK(count == 0 || (codes && corr), RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_sq8: null argument");
-	DeviceGuard dg(h->device);
-	RX_HIP(rxgpu::device_wait_all(h->device));
-	if (h->d_codes) (void)hipFree(h->d_codes);
-	if (h->d_corr) (void)hipFree(h->d_corr);
-	h->d_codes = nullptr;
-	h->d_corr = nullptr;
-	h->sq8_n = 0;
-	h->sq8_cap = 0;
-	if (count) {
-		// sized by the index capacity: rows added later are patched in (rxgpu_hnsw_upload_sq8_rows)
-		// + 4 bytes: the word loads of the last row's last block stay inside the allocation whatever dim % 4 is
-		const uint64_t cap = std::max<uint64_t>(h->capacity, count);
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_codes), size_t(cap) * h->dim + 4));
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_corr), size_t(cap) * sizeof(float)));
-		h->sq8_cap = cap;
-		RX_HIP(hipMemcpy(h->d_codes, codes, size_t(count) * h->dim, hipMemcpyHostToDevice));
-		RX_HIP(hipMemcpy(h->d_corr, corr, size_t(count) * sizeof(float), hipMemcpyHostToDevice));
-	}
-	h->sq8_alpha2 = alpha_2;
-	h->sq8_n = count;
-	return RXGPU_OK;
-}
-
-// One body for both row formats: `queries` are float rows (qcorr == nullptr) or SQ8 codes with their corrective offsets and normCoefs.
-// sink (sharded HNSW, rxgpu_sharded.hip): the result lists stay in HBM — packed into the shard's slot of the exchange's send buffer
-// ([nq][kk] distances | [nq][kk] local rows, invalid entries past a query's count) instead of travelling to the host; only the counts
-// come back (the re-run tiers are driven by them).  The stream is drained before the call returns.
-static int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef,
-							float* out_dist, uint32_t* out_row, uint32_t* out_count, const rxgpu::HnswSink* sink = nullptr, bool try_server = true);
-
-extern "C++" {
-// The A/B and test hooks of the HNSW search (RXGPU_HNSW_*), read in ONE pass over the environment per call — a dozen getenv() lookups each
-// walked the whole environment, on the path of every single-query SearchKnn.  (Still the process environment: tests flip the hooks between
-// calls.  Not safe against a concurrent setenv, like getenv itself.)
-struct HnswKnobs {
-	const char* visited = nullptr;       // RXGPU_HNSW_VISITED = bitset | hash
-	int visited_log2 = -1;               // RXGPU_HNSW_VISITED_LOG2
-	int visited_lds = -1;                // RXGPU_HNSW_VISITED_LDS
-	int split_upload = -1;               // RXGPU_HNSW_SPLIT_UPLOAD
-	int prefetch = -1;                   // RXGPU_HNSW_PREFETCH
-	int lds_cand_cap = -1;               // RXGPU_HNSW_LDS_CAND_CAP
-	int helper = -1;                     // RXGPU_HNSW_HELPER
-	int restart_cand = -1;               // RXGPU_HNSW_RESTART_CAND
-	int sorted = -1;                     // RXGPU_HNSW_SORTED
-	int gcand_cap = -1;                  // RXGPU_HNSW_GCAND_CAP
-	int team = -1;                       // RXGPU_HNSW_TEAM: wavefronts per search of a small launch (1 = off)
-	int team_max = -1;                   // RXGPU_HNSW_TEAM_MAX: searches per launch up to which the team form is used
-	int zero_copy = -1;                  // RXGPU_HNSW_ZERO_COPY = 0: small calls copy their queries / results like large ones
-	int nbl = -1;                        // RXGPU_HNSW_NBL = 1: team searches fetch the link blocks of a hop's rows along with the rows (an experiment, off by default)
-	int spec = -1;                       // RXGPU_HNSW_SPEC = 1: team searches also evaluate the next candidate's neighbours in the hop's distance trip (an experiment, off by default)
-	int server = -1;                     // RXGPU_HNSW_SERVER = 0: single queries take a launch each (no resident kernel)
-	int server_slots = -1, server_idle_us = -1, server_life_ms = -1;   // RXGPU_HNSW_SERVER_SLOTS / _IDLE_US / _LIFE_MS
-	bool names_a_kernel = false;         // a hook that picks a kernel form is set: the resident kernel (one form) stands aside
-};
-static HnswKnobs read_hnsw_knobs() {
-	HnswKnobs k;
-	static const char kPrefix[] = "RXGPU_HNSW_";
-	for (char** e = environ; e && *e; ++e) {
-		const char* s = *e;
-		if (s[0] != 'R' || std::strncmp(s, kPrefix, sizeof(kPrefix) - 1) != 0) continue;
-		const char* name = s + sizeof(kPrefix) - 1;
-		const char* eq = std::strchr(name, '=');
-		if (!eq) continue;
-		const size_t n = size_t(eq - name);
-		const char* val = eq + 1;
-		auto is = [&](const char* want) { return std::strlen(want) == n && std::strncmp(name, want, n) == 0; };
-		if (is("VISITED")) k.visited = val;
-		else if (is("VISITED_LOG2")) k.visited_log2 = atoi(val);
-		else if (is("VISITED_LDS")) k.visited_lds = atoi(val);
-		else if (is("SPLIT_UPLOAD")) k.split_upload = atoi(val);
-		else if (is("PREFETCH")) k.prefetch = atoi(val);
-		else if (is("LDS_CAND_CAP")) k.lds_cand_cap = atoi(val);
-		else if (is("HELPER")) k.helper = atoi(val);
-		else if (is("RESTART_CAND")) k.restart_cand = atoi(val);
-		else if (is("SORTED")) k.sorted = atoi(val);
-		else if (is("GCAND_CAP")) k.gcand_cap = atoi(val);
-		else if (is("TEAM")) k.team = atoi(val);
-		else if (is("TEAM_MAX")) k.team_max = atoi(val);
-		else if (is("ZERO_COPY")) k.zero_copy = atoi(val);
-		else if (is("SPEC")) k.spec = atoi(val);
-		else if (is("NBL")) k.nbl = atoi(val);
-		else if (is("SERVER")) k.server = atoi(val);
-		else if (is("SERVER_SLOTS")) k.server_slots = atoi(val);
-		else if (is("SERVER_IDLE_US")) k.server_idle_us = atoi(val);
-		else if (is("SERVER_LIFE_MS")) k.server_life_ms = atoi(val);
-		else continue;
-		if (!is("SERVER") && !is("SERVER_SLOTS") && !is("SERVER_IDLE_US") && !is("SERVER_LIFE_MS") && !is("SPLIT_UPLOAD") && !is("HELPER") && !is("SPEC") && !is("NBL")) k.names_a_kernel = true;
-	}
-	return k;
-}
-}  // extern "C++"
-
-// 1: the index's resident kernel answered; 0: it does not take this query (the caller launches); otherwise an error code
-static int hnsw_try_server(rxgpu_index* h, const HnswKnobs& knobs, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
-						   uint32_t* out_count) {
-	if (knobs.server == 0 || knobs.names_a_kernel) return 0;
-	rxgpu::HnswServerConfig cfg;
-	if (knobs.server_slots > 0) cfg.slots = uint32_t(knobs.server_slots);
-	if (knobs.server_idle_us > 0) cfg.idle_us = uint32_t(knobs.server_idle_us);
-	if (knobs.server_life_ms > 0) cfg.life_ms = uint32_t(knobs.server_life_ms);
-	cfg.spec = knobs.spec > 0;
-	cfg.nbl = knobs.nbl > 0;
-	return rxgpu::hnsw_server_search(h, cfg, query, k, ef, out_dist, out_row, out_count);
-}
-
-int rxgpu_hnsw_search_knn_posted(rxgpu_index* h, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-								 int32_t* served) {
-	RX_CHECK(h && query && out_dist && out_row && out_count && served, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_posted: null argument");
-	*served = 0;
-	if (h->shard_set || h->count == 0 || k == 0 || !h->graph_attached || h->graph_n != h->count) return RXGPU_OK;   // the launching call says what is wrong
-	k = uint32_t(std::min<uint64_t>(k, h->count));
-	if (!ef) ef = k * 3 / 2;
-	if (!ef) ef = 1;
-	const int rc = hnsw_try_server(h, read_hnsw_knobs(), query, k, ef, out_dist, out_row, out_count);
-	if (rc == 1) {
-		*served = 1;
-		return RXGPU_OK;
-	}
-	if (rc == 2) {   // the mailbox took it and the search needs the re-run tiers: answered here by the launches, not offered to the mailbox again
-		const int r2 = hnsw_search_impl(h, query, nullptr, nullptr, 1, k, ef, out_dist, out_row, out_count, nullptr, false);
-		if (r2 == RXGPU_OK) *served = 1;
-		return r2;
-	}
-	return rc;
-}
-
-int rxgpu_hnsw_server_times(rxgpu_index* h, uint64_t* device_us, uint64_t* caller_us) {
-	RX_CHECK(h && device_us && caller_us, RXGPU_ERR_PARAMS, "rxgpu_hnsw_server_times: null argument");
-	rxgpu::hnsw_server_times(h, device_us, caller_us);
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_server_stats(rxgpu_index* h, uint64_t* served, uint64_t* generations) {
-	RX_CHECK(h && served && generations, RXGPU_ERR_PARAMS, "rxgpu_hnsw_server_stats: null argument");
-	rxgpu::hnsw_server_counters(h, served, generations);
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
-						  uint32_t* out_count) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	RX_CHECK(queries, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn: null argument");
-	if (h->shard_set) {   // SURVEY 8(e) "HNSW": a graph per shard, the per-shard results meet in the same all-gather + merge as brute force
-		RX_CHECK(out_dist && out_row && out_count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn: null argument");
-		return rxgpu::sharded_hnsw_search_knn(h, queries, nullptr, nullptr, nq, k, ef, out_dist, out_row, out_count);
-	}
-	return hnsw_search_impl(h, queries, nullptr, nullptr, nq, k, ef, out_dist, out_row, out_count);
-}
-
-extern "C++" {
-namespace rxgpu {
-int hnsw_search_to_sink(rxgpu_index* shard, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef, const HnswSink& sink) {
-	std::vector<uint32_t> counts(nq);
-	if (qcorr && !(shard->d_codes && shard->sq8_n == shard->count)) {
-		set_error("rxgpu_hnsw_search_knn_sq8: SQ8 codes are not attached / out of date on a shard");
-		return RXGPU_ERR_LOGIC;
-	}
-	return hnsw_search_impl(shard, queries, qcorr, qnorm, nq, k, ef, nullptr, nullptr, counts.data(), &sink);
-}
-}  // namespace rxgpu
-}  // extern "C++"
-
-int rxgpu_hnsw_search_knn_sq8(rxgpu_index* h, const uint8_t* query_codes, const float* query_corr, const float* query_norm_coef, uint32_t nq,
-							  uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	RX_CHECK(query_codes && query_corr && query_norm_coef, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_sq8: null argument");
-	if (h->shard_set) {   // every shard searches the code table attached to ITS handle (rxgpu_hnsw_attach_sq8 on rxgpu_index_shard(h, s)); same exchange
-		RX_CHECK(out_dist && out_row && out_count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_sq8: null argument");
-		for (uint32_t s = 0; s < rxgpu_index_shard_count(h); ++s) {
-			const rxgpu_index* sh = rxgpu_index_shard(h, s);
-			RX_CHECK(sh->count == 0 || (sh->d_codes && sh->sq8_n == sh->count), RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_knn_sq8: SQ8 codes are not attached / out of date on a shard");
-		}
-		return rxgpu::sharded_hnsw_search_knn(h, query_codes, query_corr, query_norm_coef, nq, k, ef, out_dist, out_row, out_count);
-	}
-	RX_CHECK(h->count == 0 || (h->d_codes && h->sq8_n == h->count), RXGPU_ERR_LOGIC,
-			 "rxgpu_hnsw_search_knn_sq8: SQ8 codes are not attached / out of date");
-	return hnsw_search_impl(h, query_codes, query_corr, query_norm_coef, nq, k, ef, out_dist, out_row, out_count);
-}
-
-static int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef,
-							float* out_dist, uint32_t* out_row, uint32_t* out_count, const rxgpu::HnswSink* sink, bool try_server) {
-	const bool sq8 = qcorr != nullptr;
-	const bool to_host = sink == nullptr;
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_hnsw_search_knn_sq8: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
-	RX_CHECK(queries && out_count && (sink || (out_dist && out_row)), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn: null argument");
-	if (nq == 0) return RXGPU_OK;
-	if (h->count == 0 || k == 0) {   // hnswalg.h:1989-1991
-		RX_CHECK(to_host, RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_knn: an empty shard has no list to send");
-		std::fill(out_count, out_count + nq, 0u);
-		return RXGPU_OK;
-	}
-	RX_CHECK(h->graph_attached && h->graph_n == h->count, RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_knn: graph is not attached / out of date");
-	k = uint32_t(std::min<uint64_t>(k, h->count));
-	if (!ef) ef = k * 3 / 2;                                        // hnswalg.h:1995
-	if (!ef) ef = 1;
-	RX_CHECK(ef <= uint32_t(rxgpu::kHnswMaxEf), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn: ef must be <= 4096 on the GPU engine");
-	// ef > 1024: the result heap alone takes the LDS budget of a search — the candidate heap goes to global scratch from the start
-	const bool big_ef = ef > uint32_t(rxgpu::kHnswLdsCandEf);
-	const HnswKnobs knobs = read_hnsw_knobs();
-	// ONE query, the planner's call: through the mailbox of the index's resident kernel (rxgpu_hnsw_server.hip) — no launch on the path
-	if (nq == 1 && to_host && !sq8 && try_server) {
-		const int served = hnsw_try_server(h, knobs, static_cast<const float*>(queries), k, ef, out_dist, out_row, out_count);
-		if (served == 1) return RXGPU_OK;
-		if (served != 0 && served != 2) return served;   // (2: the search ran there and came back flagged — the tiers below answer it)
-	}
-	DeviceGuard dg(h->device);
-	rxgpu_search_ctx* c = acquire_ctx(h);
-	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
-	const uint64_t words = (h->count + 31) / 32;
-	// visited bitsets are the memory hog (N / 8 bytes per resident search): a launch gets an eighth of the free HBM for them, between 2 and
-	// 16 GiB.  (A fixed 2 GiB held a 10M-node index to 1717 searches per launch — fewer than the chip keeps resident.)
-	// (a handful of searches never comes near the budget: no driver call on the path of a single-query SearchKnn)
-	size_t free_b = 0, total_b = 0;
-	if (nq > 256 && hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-	const uint64_t visited_budget = std::min<uint64_t>(16ull << 30, std::max<uint64_t>(2ull << 30, (uint64_t(free_b) + c->d_visited.bytes) / 8));
-	const uint64_t max_slots = std::max<uint64_t>(1, std::min<uint64_t>(32768, visited_budget / (words * 4)));
-	// The visited set of the first pass (and of the tie re-runs) is a HASH SET sized by ef, zeroed by the search itself — not a bitset over
-	// the nodes zeroed by a memset: 2^k words >= 64 ef (8192 words = 32 KB at ef = 128; a search may fill half: 4096 nodes, against the
-	// 850 - 2300 it tests at 1M - 10M rows) instead of N / 8 bytes (1.25 MB per search at 10M rows: 20 GB of memset in front of a 16 384-query
-	// launch).  Searches that would outgrow it come back as kHnswOverflow and take the global-heap re-run, which keeps the bitset.
-	// Graphs so small that the bitset is the smaller of the two keep it.  RXGPU_HNSW_VISITED=bitset: the former path (A/B, tests).
-	uint32_t vis_hash_log2 = 12;
-	while ((1ull << vis_hash_log2) < 64ull * ef && vis_hash_log2 < 18) ++vis_hash_log2;
-	if (knobs.visited_log2 >= 0) vis_hash_log2 = uint32_t(std::min(20, std::max(6, knobs.visited_log2)));   // test hook: force overflows
-	// a handful of searches (the latency form of the kernel, at most two workgroups per CU): the same hash set in LDS, whatever the rule
-	// below picks for batches — the launcher decides (launch_hnsw_nb).  RXGPU_HNSW_VISITED_LDS=0: off (A/B)
-	uint32_t vis_lds_log2 = vis_hash_log2;
-	if (knobs.visited_lds == 0) vis_lds_log2 = 0;
-	if (knobs.visited) vis_lds_log2 = 0;   // an explicit choice of the global form (A/B, tests) stands for every launch
-	{
-		const char* e = knobs.visited;   // "bitset" / "hash": force one of the two (A/B, tests on small graphs)
-		const bool force_hash = e && std::strcmp(e, "hash") == 0;
-		// Which one by default: the hash set costs a second dependent trip on the hops where a lane's first slot is taken (measured at 1M x 768,
-		// ef = 128, same box and graph: 1.28 - 1.33 M q/s against 1.43 - 1.46 M on the bitset, profiles/rd4f_hnsw_visited_ab.txt); the bitset
-		// costs its memset (N / 8 bytes per query) and, once the bitsets of the searches in flight outgrow the Infinity Cache, an HBM round trip per
-		// test.  The hash set takes over where one search's bitset is 16 x its hash set or more (4.2 M nodes at ef = 128).
-		if ((e && std::strcmp(e, "bitset") == 0) || (!force_hash && (16ull << vis_hash_log2) > words)) vis_hash_log2 = 0;
-		// in HBM the set gets twice the words (a quarter full at most): fewer second probes — 10M x 768, one graph and box, 16 384 queries:
-		// 2^13 words 469 k q/s kernels only, 2^14 498 k, 2^15 497 k, 2^16 483 k, bitset 472 k (profiles/rd4j_hnsw_10m_*.json)
-		if (vis_hash_log2 && knobs.visited_log2 < 0 && vis_hash_log2 < 18) vis_hash_log2 += 1;
-	}
-	const uint64_t vis_words = vis_hash_log2 ? (1ull << vis_hash_log2) : words;   // per search of the first pass
-	const uint64_t vis_slots = vis_hash_log2 ? std::max<uint64_t>(1, std::min<uint64_t>(32768, visited_budget / (vis_words * 4))) : max_slots;
-	// SQ8 queries: [codes, padded to 4 bytes][corr][normCoef] in the one query buffer
-	const size_t qelem = sq8 ? sizeof(uint8_t) : sizeof(float);
-	const size_t qbytes = size_t(nq) * h->dim * qelem;
-	const size_t o_qcorr = (qbytes + 255) & ~size_t(255), o_qnorm = o_qcorr + ((size_t(nq) * 4 + 255) & ~size_t(255));
-	if (int rc = c->d_queries.ensure(sq8 ? o_qnorm + size_t(nq) * 4 : qbytes); rc) return rc;
-	if (int rc = c->d_out_dist.ensure(size_t(nq) * k * sizeof(float)); rc) return rc;
-	if (int rc = c->d_out_row.ensure(size_t(nq) * k * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
-	// the bitsets of the first launch (N / 8 bytes per search: 2 GB for 16 384 searches over 1M nodes) are zeroed on a second stream and
-	// enqueued BEFORE the upload of the query block (a copy from pageable memory keeps this thread until it is staged): the two overlap,
-	// the launch waits for both
-	bool first_zeroed = false;
-	if (!big_ef && !vis_hash_log2) {
-		const uint32_t cq = uint32_t(std::min<uint64_t>(vis_slots, nq));
-		const size_t zero_bytes = size_t(cq) * words * 4;
-		if (zero_bytes >= (size_t(8) << 20)) {
-			if (int rc = c->d_visited.ensure(zero_bytes); rc) return rc;
-			if (int rc = c->ensure_aux(); rc) return rc;
-			RX_HIP(hipMemsetAsync(c->d_visited.ptr, 0, zero_bytes, c->aux_stream));
-			RX_HIP(hipEventRecord(c->aux_done, c->aux_stream));
-			first_zeroed = true;
-		}
-	}
-	// A large batch in ONE launch is searched in two halves on two streams: the upload of the second half of the query block (a copy from
-	// pageable memory keeps this thread until it is staged) runs while the first half's searches have started; the halves overlap on the
-	// device like the workgroups of one launch.  RXGPU_HNSW_SPLIT_UPLOAD=0: one upload, one launch.
-	// Round 6: four parts from 2048 queries on (the first launch waits for a quarter of the block, three quarters of the upload run under
-	// searches), the parts alternating between the two streams; RXGPU_HNSW_SPLIT_UPLOAD = n: that many parts (0 / 1: one upload, one launch).
-	bool split_upload = !big_ef && nq >= 2048 && uint64_t(nq) <= vis_slots;
-	uint32_t split_parts = 4;
-	if (knobs.split_upload >= 0) {
-		split_upload = split_upload && knobs.split_upload > 1;
-		split_parts = uint32_t(std::min(16, std::max(2, knobs.split_upload)));
-	}
-	const uint32_t part_q = split_upload ? (nq + split_parts - 1) / split_parts : nq;
-	const uint32_t first_half = part_q;   // queries uploaded in front of the first launch
-	if (split_upload) {
-		if (int rc = c->ensure_aux(); rc) return rc;
-	}
-	// Small calls — the Map's single queries and its coalesced batches — move their queries and results through the context's PINNED buffer.
-	// A copy between pageable memory and the device goes through the runtime's own staging, one call after the other whatever their
-	// streams: T planner threads then queue up in the copies on both sides of a 0.5 ms kernel.  (Large batches keep the direct copies:
-	// they are the bandwidth case, and the two-halves upload overlaps them with the searches.)
-	const size_t up_bytes = (size_t(nq) * h->dim * qelem + 15) & ~size_t(15);
-	const size_t st_corr = up_bytes, st_norm = st_corr + size_t(nq) * 4, st_count = st_norm + size_t(nq) * 4, st_dist = st_count + size_t(nq) * 4,
-				 st_row = st_dist + size_t(nq) * k * 4, st_end = st_row + size_t(nq) * k * 4;
-	const bool staged = !split_upload && st_end <= (size_t(1) << 20);
-	const void* up_queries = queries;
-	const float *up_qcorr = qcorr, *up_qnorm = qnorm;
-	uint32_t* dl_count = out_count;
-	float* dl_dist = out_dist;
-	uint32_t* dl_row = out_row;
-	// The Map's single queries and its small coalesced batches do not copy at all: the kernel reads the queries from the pinned buffer (once,
-	// into LDS or registers) and writes counts and lists there — a call is ONE launch and one wait instead of a launch between four copies
-	// (each an enqueue of its own on the path of a 0.5 ms search).  RXGPU_HNSW_ZERO_COPY=0: the copies (A/B).
-	const bool zero_copy = staged && to_host && !sq8 && nq <= 64 && knobs.zero_copy != 0;
-	char* zc_dev = nullptr;   // the pinned buffer as the device sees it
-	if (staged) {
-		if (int rc = c->ensure_pinned(st_end); rc) return rc;
-		char* hp = static_cast<char*>(c->h_pinned);
-		if (zero_copy) {
-			void* dv = nullptr;
-			RX_HIP(hipHostGetDevicePointer(&dv, hp, 0));
-			zc_dev = static_cast<char*>(dv);
-		}
-		std::memcpy(hp, queries, size_t(nq) * h->dim * qelem);
-		up_queries = hp;
-		if (sq8) {
-			std::memcpy(hp + st_corr, qcorr, size_t(nq) * 4);
-			std::memcpy(hp + st_norm, qnorm, size_t(nq) * 4);
-			up_qcorr = reinterpret_cast<const float*>(hp + st_corr);
-			up_qnorm = reinterpret_cast<const float*>(hp + st_norm);
-		}
-		dl_count = reinterpret_cast<uint32_t*>(hp + st_count);
-		dl_dist = reinterpret_cast<float*>(hp + st_dist);
-		dl_row = reinterpret_cast<uint32_t*>(hp + st_row);
-	}
-	auto done_host = [&]() -> int {   // (behind the last hipStreamSynchronize) what was staged goes to the caller's arrays
-		if (staged) {
-			std::memcpy(out_count, dl_count, size_t(nq) * 4);
-			if (to_host) {
-				std::memcpy(out_dist, dl_dist, size_t(nq) * k * 4);
-				std::memcpy(out_row, dl_row, size_t(nq) * k * 4);
-			}
-		}
-		return RXGPU_OK;
-	};
-	void* const d_q = zero_copy ? static_cast<void*>(zc_dev) : c->d_queries.ptr;   // where the kernels read the queries
-	if (!zero_copy) RX_HIP(hipMemcpyAsync(c->d_queries.ptr, up_queries, size_t(first_half) * h->dim * qelem, hipMemcpyHostToDevice, c->stream));
-	// counts / lists back to the host (nothing to do when the kernels wrote them there), and the wait behind a small launch: polled — the
-	// wake-up out of hipStreamSynchronize alone is tens of microseconds
-	auto fetch_counts = [&]() -> int {
-		if (!zero_copy) RX_HIP(hipMemcpyAsync(dl_count, c->d_out_count.ptr, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-		return RXGPU_OK;
-	};
-	auto fetch_lists = [&]() -> int {
-		if (!zero_copy) {
-			RX_HIP(hipMemcpyAsync(dl_dist, c->d_out_dist.ptr, size_t(nq) * k * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-			RX_HIP(hipMemcpyAsync(dl_row, c->d_out_row.ptr, size_t(nq) * k * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-		}
-		return RXGPU_OK;
-	};
-	auto wait_stream = [&]() -> int {
-		if (nq <= 256) {
-			const auto t0 = std::chrono::steady_clock::now();
-			hipError_t q = hipStreamQuery(c->stream);
-			while (q == hipErrorNotReady && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() < 4000.0) q = hipStreamQuery(c->stream);
-			if (q != hipErrorNotReady) {
-				RX_HIP(q);
-				return RXGPU_OK;
-			}
-		}
-		RX_HIP(hipStreamSynchronize(c->stream));
-		return RXGPU_OK;
-	};
-	rxgpu::HnswParams p{};
-	if (sq8) {
-		char* qb = static_cast<char*>(c->d_queries.ptr);
-		RX_HIP(hipMemcpyAsync(qb + o_qcorr, up_qcorr, size_t(nq) * 4, hipMemcpyHostToDevice, c->stream));
-		RX_HIP(hipMemcpyAsync(qb + o_qnorm, up_qnorm, size_t(nq) * 4, hipMemcpyHostToDevice, c->stream));
-		p.codes = h->d_codes;
-		p.corr = h->d_corr;
-		p.alpha2 = h->sq8_alpha2;
-		p.qcodes = reinterpret_cast<const uint8_t*>(qb);
-		p.qcorr = reinterpret_cast<const float*>(qb + o_qcorr);
-		p.qnorm = reinterpret_cast<const float*>(qb + o_qnorm);
-	}
-	p.rows = h->d_rows;
-	p.inv_norms = h->d_inv_norms;
-	p.links0 = h->d_links0;
-	p.upper_off = h->d_upper_off;
-	p.upper = h->d_upper;
-	p.deleted = h->d_deleted;
-	p.n = h->count;
-	p.stride = h->stride;
-	p.dim = h->dim;
-	p.M = h->graph_M;
-	p.maxM0 = h->graph_maxM0;
-	p.maxlevel = h->graph_maxlevel;
-	p.entry = h->graph_entry;
-	p.bare = h->graph_deleted == 0;
-	p.nq = nq;
-	p.k = k;
-	p.ef = ef;
-	p.visited_words = words;
-	p.vis_lds_log2 = vis_lds_log2;
-	p.prefetch_links = 1;
-	if (knobs.prefetch >= 0) p.prefetch_links = knobs.prefetch ? 1u : 0u;   // A/B hook
-	// a handful of searches on the chip: four wavefronts share a search's distance batches (RXGPU_HNSW_TEAM=1: off, RXGPU_HNSW_TEAM_MAX: up to
-	// how many searches per launch)
-	p.team = knobs.team >= 0 ? uint32_t(knobs.team) : 4u;
-	p.team_max = knobs.team_max >= 0 ? uint32_t(knobs.team_max) : 256u;
-	p.nbl = knobs.nbl > 0 ? 1u : 0u;
-	p.spec = knobs.spec > 0 ? 1u : 0u;   // off by default: measured slower at 1M x 768 (profiles/rd6sp_single.json), see hnsw_search_core.hip.h
-	p.out_dist = zero_copy ? reinterpret_cast<float*>(zc_dev + st_dist) : static_cast<float*>(c->d_out_dist.ptr);
-	p.out_row = zero_copy ? reinterpret_cast<uint32_t*>(zc_dev + st_row) : static_cast<uint32_t*>(c->d_out_row.ptr);
-	p.out_count = zero_copy ? reinterpret_cast<uint32_t*>(zc_dev + st_count) : static_cast<uint32_t*>(c->d_out_count.ptr);
-	p.stats = h->d_hnsw_stats;
-	p.ef_cap = (ef + 63u) & ~63u;
-	auto to_sink = [&]() -> int {   // the finished lists into the exchange's send buffer (sharded HNSW), on this search's stream, drained
-		rxgpu::launch_pack_lists(p.out_dist, p.out_row, p.out_count, nq, k, sink->kk, sink->d_dist, sink->d_row, c->stream);
-		RX_HIP(hipGetLastError());
-		RX_HIP(hipStreamSynchronize(c->stream));
-		return done_host();   // (the counts)
-	};
-	// typical candidate heaps stay within a few x ef.  Measured at 1M x 768, ef = 128: 512 entries overflow for a handful of queries and the
-	// global-heap re-run costs more than the extra occupancy brings (1.07 M q/s at 1024 against 0.43 M at 512 and 0.86 M at 768)
-	p.lds_cand_cap = ef <= 256 ? 1024u : uint32_t(rxgpu::kHnswCandLds);
-	if (knobs.lds_cand_cap >= 0) {   // test hook: force the global-heap re-run
-		p.lds_cand_cap = std::min<uint32_t>(uint32_t(rxgpu::kHnswCandLds), uint32_t(std::max(1, knobs.lds_cand_cap)));
-	}
-	// Graphs without deleted nodes, ef <= 256: both queues as one sorted list in registers (hnsw_search.hip).  A query that meets equal
-	// distances there comes back as kHnswTie and takes the heap kernel, whose sift order is the reference's.
-	bool use_sorted = ef <= uint32_t(p.bare ? rxgpu::kHnswSortedMaxEf : rxgpu::kHnswSortedMaxEfDel);
-	uint32_t sorted_mode = 1;
-	// candidate-heap entries a restarted search gets in LDS.  Measured at 1M x 768, ef = 128, 16 384 queries, ~90 restarts (profiles/
-	// rd3p_restart_caps.txt, one graph, one box): 384 entries (8 KB per workgroup, 19 per CU) -> one restart overflows and the global-heap
-	// launch it needs costs 2.9 ms; 600 (10 KB, 16 per CU) 11.96 ms in all; 780 12.10; 1024 12.25; no in-kernel restart (0: the tie queries
-	// come back to this function and get a launch of their own) 9.92 + 2.53 = 12.46 ms.
-	uint32_t sorted_restart_cap = 600;
-	// Round 4: with helper workgroups beside the batch (below) an overflowing restart is no longer a launch behind the batch, and the area
-	// can shrink to what lets a CU hold 20 searches instead of 15 (LDS per workgroup 10.3 -> 7.6 KB): first pass of 16 384 queries at
-	// 1M x 768 11.9 -> 10.5 ms (profiles/rd4k_hnsw_1m_restart_caps.txt; without the helpers the one restart that overflows costs 2.5 ms).
-	const bool helper_wanted = nq >= 2048 && !big_ef && knobs.helper != 0;
-	// ... where a batch lasts long against one heap search: the overflowing searches now run beside the batch, but one that is queued late
-	// still sticks out by its own length (2.5 ms at 1M x 768, where the whole batch takes 10: 1.29 M q/s with the copies at 600 entries
-	// against 1.16 - 1.22 M at 256 although the first pass alone runs at 1.57 - 1.70 M; at 10M x 768: 495 k -> 586 k q/s,
-	// profiles/rd4l_hnsw_*.json).  Same size rule as the hash set.
-	if (helper_wanted && ef <= 128 && (16ull << 13) <= words) sorted_restart_cap = 256;
-	if (knobs.restart_cand >= 0) sorted_restart_cap = std::min<uint32_t>(uint32_t(rxgpu::kHnswCandLds), uint32_t(knobs.restart_cand));
-	if (knobs.sorted >= 0) {   // A/B and test hook: 0 = heaps only, 2 = list shifts through ds_bpermute instead of DPP
-		sorted_mode = uint32_t(knobs.sorted);
-		use_sorted = use_sorted && sorted_mode != 0;
-	}
-	std::vector<uint32_t> redo;
-	if (big_ef) {
-		redo.resize(nq);
-		for (uint32_t q = 0; q < nq; ++q) redo[q] = q;
-	} else {
-		// Helper workgroups beside a large batch (hnsw_helper_kernel, second stream): a search that overflows its LDS heap area is queued and
-		// runs with the largest LDS heap while the batch is still going, instead of as a launch of its own behind it.  RXGPU_HNSW_HELPER=0: off.
-		constexpr uint32_t kHelperGroups = 64, kHelperCap = 4096;
-		// ONE batch at a time has helpers, and only a batch that is one chunk.  A helper polls until ITS batch is over; HIP streams share a
-		// few hardware queues, so with two callers at it helper A can sit in front of batch B's kernels while helper B sits in front of
-		// batch A's — each waits for a batch that cannot start, until the helpers' wall-clock bail-out (seconds: four threads with 2300-query
-		// batches measured 3 s calls, tests/test_gpu_hnsw_visited.py).  With a single set of helpers in flight nothing that spins ever waits
-		// for work queued behind another spinner; the callers that come second run their overflowing searches behind their batch, as batches
-		// below 2048 queries always do.  (The same inside one call: the kernels of a second chunk would queue up behind its own helpers.)
-		static std::atomic<bool> helpers_in_flight{false};
-		struct HelperLease {
-			bool held = false;
-			~HelperLease() {
-				if (held) helpers_in_flight.store(false, std::memory_order_release);
-			}
-		} helper_lease;
-		if (helper_wanted && uint64_t(nq) <= vis_slots) {
-			bool expected = false;
-			helper_lease.held = helpers_in_flight.compare_exchange_strong(expected, true, std::memory_order_acq_rel);
-		}
-		const bool use_helper = helper_lease.held;
-		uint32_t* hq_words = nullptr;   // [0] entries appended, [1] stop, [2] searches of the batch that have ended, [16 ..] ids
-		uint32_t helper_n = 0;
-		if (use_helper) {
-			const uint64_t words4 = (words + 3) & ~uint64_t(3);
-			const size_t hq_bytes = (size_t(kHelperCap) + 16) * 4;
-			if (int rc = c->ensure_aux(); rc) return rc;
-			if (int rc = c->d_helper.ensure(hq_bytes); rc) return rc;
-			if (int rc = c->d_helper_bits.ensure(size_t(kHelperGroups) * words4 * 4); rc) return rc;
-			hq_words = static_cast<uint32_t*>(c->d_helper.ptr);
-			RX_HIP(hipMemsetAsync(hq_words, 0, hq_bytes, c->aux_stream));
-			RX_HIP(hipEventRecord(c->main_done, c->aux_stream));      // the queue is empty before the first search of the batch can append to it
-			RX_HIP(hipStreamWaitEvent(c->stream, c->main_done, 0));
-		}
-		// The helpers spin until the batch says stop, so they are enqueued BEHIND the batch's launches: HIP streams share a few
-		// hardware queues, and a helper that reached a queue in front of the batch kernel it waits for would hold that queue until its
-		// wall-clock bail-out.  Launched last, the worst case is the serial one — helpers behind the batch on one queue find the stop flag and
-		// only drain what was queued; on separate queues they run beside the batch as intended.
-		auto launch_helpers = [&]() -> int {
-			const uint64_t words4 = (words + 3) & ~uint64_t(3);
-			rxgpu::HnswParams ph = p;
-			ph.queries = static_cast<const float*>(d_q);
-			ph.visited = static_cast<uint32_t*>(c->d_helper_bits.ptr);
-			ph.visited_words = words4;
-			ph.vis_hash_log2 = 0;
-			ph.vis_lds_log2 = 0;
-			ph.lds_cand_cap = uint32_t(rxgpu::kHnswCandLds);
-			ph.sorted = 0;
-			rxgpu::HnswHelper hq{hq_words, hq_words + 16, hq_words + 1, hq_words + 2, nq, kHelperCap, 100000000ull};   // (last resort: gives up after 1 s)
-			rxgpu::launch_hnsw_helper(h->metric, ph, hq, kHelperGroups, c->aux_stream);
-			RX_HIP(hipGetLastError());
-			return RXGPU_OK;
-		};
-		bool helpers_launched = false;
-		for (uint32_t q0 = 0; q0 < nq; q0 += uint32_t(vis_slots)) {
-			const uint32_t cq = uint32_t(std::min<uint64_t>(vis_slots, nq - q0));
-			if (int rc = c->d_visited.ensure(size_t(cq) * vis_words * 4); rc) return rc;
-			if (!vis_hash_log2) {
-				const size_t zero_bytes = size_t(cq) * words * 4;
-				if (q0 == 0 && first_zeroed) {
-					RX_HIP(hipStreamWaitEvent(c->stream, c->aux_done, 0));
-				} else {   // (a later chunk of the same call reuses the buffer behind the chunk before it)
-					RX_HIP(hipMemsetAsync(c->d_visited.ptr, 0, zero_bytes, c->stream));
-				}
-			}
-			// searches [qa, qa + cnt) of the batch on stream st (slot = index inside this launch's visited block)
-			auto launch_part = [&](uint32_t qa, uint32_t cnt, uint32_t slot0, hipStream_t st) {
-				rxgpu::HnswParams pc = p;
-				pc.vis_hash_log2 = vis_hash_log2;
-				pc.visited_words = vis_words;
-				pc.queries = reinterpret_cast<const float*>(static_cast<const char*>(d_q) + size_t(qa) * h->dim * qelem);
-				if (sq8) {
-					pc.qcodes = p.qcodes + size_t(qa) * h->dim;
-					pc.qcorr = p.qcorr + qa;
-					pc.qnorm = p.qnorm + qa;
-				}
-				pc.visited = static_cast<uint32_t*>(c->d_visited.ptr) + size_t(slot0) * vis_words;
-				pc.out_dist = p.out_dist + size_t(qa) * k;
-				pc.out_row = p.out_row + size_t(qa) * k;
-				pc.out_count = p.out_count + qa;
-				if (use_helper) {
-					pc.helper_n = hq_words;
-					pc.helper_ids = hq_words + 16;
-					pc.helper_cap = kHelperCap;
-					pc.q_base = qa;
-				}
-				if (use_sorted) {   // the list lives in registers; LDS holds only the heap area of a search that starts over (equal keys that matter)
-					pc.sorted = sorted_mode;
-					pc.lds_cand_cap = sorted_restart_cap;
-					if (sorted_restart_cap == 0) pc.ef_cap = 0;
-				}
-				rxgpu::launch_hnsw_search(h->metric, pc, cnt, false, st);
-			};
-			ProfileScope ps(h, "hnsw", c->stream);   // (with two halves: until the main stream has waited for the second one)
-			if (split_upload) {
-				hipStream_t sb = c->aux2_stream;
-				// whatever the first half waits for — zeroed bitsets, the empty overflow queue, the SQ8 query terms — the second half waits for too
-				RX_HIP(hipEventRecord(c->split_done, c->stream));
-				RX_HIP(hipStreamWaitEvent(sb, c->split_done, 0));
-				launch_part(0, first_half, 0, c->stream);
-				for (uint32_t qa = first_half, part = 1; qa < nq; qa += part_q, ++part) {
-					const uint32_t cnt = std::min(part_q, nq - qa);
-					hipStream_t st = (part & 1u) ? sb : c->stream;
-					const size_t off = size_t(qa) * h->dim * qelem;
-					RX_HIP(hipMemcpyAsync(static_cast<char*>(c->d_queries.ptr) + off, static_cast<const char*>(queries) + off, size_t(cnt) * h->dim * qelem, hipMemcpyHostToDevice, st));
-					launch_part(qa, cnt, qa, st);
-				}
-				RX_HIP(hipEventRecord(c->split_done, sb));
-				RX_HIP(hipStreamWaitEvent(c->stream, c->split_done, 0));
-			} else {
-				launch_part(q0, cq, 0, c->stream);
-			}
-			if (use_helper && !helpers_launched) {   // behind the first chunk's launches (all of them, for a batch that fits one chunk)
-				if (int rc = launch_helpers(); rc) return rc;
-				helpers_launched = true;
-			}
-		}
-		RX_HIP(hipGetLastError());
-		if (use_helper) {   // the batch is over: tell the helpers, take their results with the batch's
-			RX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(hq_words + 1), 1, 1, c->stream));
-			RX_HIP(hipEventRecord(c->aux_done, c->aux_stream));
-			RX_HIP(hipStreamWaitEvent(c->stream, c->aux_done, 0));
-			RX_HIP(hipMemcpyAsync(&helper_n, hq_words, sizeof(helper_n), hipMemcpyDeviceToHost, c->stream));
-		}
-		// counts and results travel together: a batch without re-runs (the common case for a handful of queries) is done after ONE wait
-		if (int rc = fetch_counts(); rc) return rc;
-		if (to_host) {
-			if (int rc = fetch_lists(); rc) return rc;
-		}
-		if (int rc = wait_stream(); rc) return rc;
-		const uint32_t helper_queued = std::min<uint32_t>(helper_n, kHelperCap);
-		h->hnsw_lds_reruns += helper_queued;
-		std::vector<uint32_t> ties;
-		bool clean = true;
-		for (uint32_t q = 0; q < nq; ++q) {
-			if (dl_count[q] == rxgpu::kHnswTie) ties.push_back(q);
-			clean = clean && dl_count[q] != rxgpu::kHnswTie && dl_count[q] != rxgpu::kHnswOverflow;
-		}
-		if (clean) return to_host ? done_host() : to_sink();
-		if (!ties.empty()) {   // equal keys met in the sorted list: the same queries through the reference's heaps (candidate heap in LDS)
-			h->hnsw_tie_reruns += ties.size();
-			if (int rc = c->d_redo.ensure(ties.size() * sizeof(uint32_t)); rc) return rc;
-			RX_HIP(hipMemcpyAsync(c->d_redo.ptr, ties.data(), ties.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-			for (size_t r0 = 0; r0 < ties.size(); r0 += vis_slots) {
-				const uint32_t cq = uint32_t(std::min<uint64_t>(vis_slots, ties.size() - r0));
-				if (int rc = c->d_visited.ensure(size_t(cq) * vis_words * 4); rc) return rc;
-				if (!vis_hash_log2) RX_HIP(hipMemsetAsync(c->d_visited.ptr, 0, size_t(cq) * words * 4, c->stream));
-				rxgpu::HnswParams pc = p;
-				pc.vis_hash_log2 = vis_hash_log2;
-				pc.visited_words = vis_words;
-				pc.queries = static_cast<const float*>(d_q);
-				pc.visited = static_cast<uint32_t*>(c->d_visited.ptr);
-				pc.only = static_cast<const uint32_t*>(c->d_redo.ptr) + r0;
-				ProfileScope ps(h, "hnsw_ties", c->stream);
-				rxgpu::launch_hnsw_search(h->metric, pc, cq, false, c->stream);
-			}
-			RX_HIP(hipGetLastError());
-			if (int rc = fetch_counts(); rc) return rc;
-			RX_HIP(hipStreamSynchronize(c->stream));
-		}
-		// Queries whose candidate heap outgrew its LDS area — 600 entries for a search that started over inside the sorted-list kernel, 1024 for
-		// the heap kernel's first pass: once more on the heap kernel with the largest LDS heap there is and a bitset (a search that filled
-		// its hash set lands here too), before the global-heap tiers.  A search with its heap in global scratch takes 5 - 7 ms at 10M x 768
-		// (profiles/rd4i_hnsw_10m_*.json: ONE such query was a fifth of a 16 384-query batch), one in LDS about 1 ms.
-		std::vector<uint32_t> over;
-		for (uint32_t q = 0; q < nq; ++q) {
-			if (dl_count[q] == rxgpu::kHnswOverflow) over.push_back(q);
-		}
-		const uint32_t first_cap = use_sorted ? sorted_restart_cap : p.lds_cand_cap;
-		if (!over.empty() && first_cap < uint32_t(rxgpu::kHnswCandLds) && knobs.lds_cand_cap < 0) {   // (the hook forces the global tiers)
-			if (int rc = c->d_redo.ensure(over.size() * sizeof(uint32_t)); rc) return rc;
-			RX_HIP(hipMemcpyAsync(c->d_redo.ptr, over.data(), over.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-			for (size_t r0 = 0; r0 < over.size(); r0 += max_slots) {
-				const uint32_t cq = uint32_t(std::min<uint64_t>(max_slots, over.size() - r0));
-				if (int rc = c->d_visited.ensure(size_t(cq) * words * 4); rc) return rc;
-				RX_HIP(hipMemsetAsync(c->d_visited.ptr, 0, size_t(cq) * words * 4, c->stream));
-				rxgpu::HnswParams pc = p;
-				pc.lds_cand_cap = uint32_t(rxgpu::kHnswCandLds);
-				pc.vis_lds_log2 = 0;   // (a search that filled its hash set is among these)
-				pc.queries = static_cast<const float*>(d_q);
-				pc.visited = static_cast<uint32_t*>(c->d_visited.ptr);
-				pc.only = static_cast<const uint32_t*>(c->d_redo.ptr) + r0;
-				ProfileScope ps(h, "hnsw_redo", c->stream);
-				rxgpu::launch_hnsw_search(h->metric, pc, cq, false, c->stream);
-			}
-			RX_HIP(hipGetLastError());
-			if (int rc = fetch_counts(); rc) return rc;
-			RX_HIP(hipStreamSynchronize(c->stream));
-			// searches the helpers had queued but not finished are in `over` again: counted once
-			h->hnsw_lds_reruns += over.size() > helper_queued ? over.size() - helper_queued : 0;
-		}
-		// ... and what still does not fit: re-run with the heap in global scratch (bounded by one entry per node)
-		for (const uint32_t q : over) {
-			if (dl_count[q] == rxgpu::kHnswOverflow) redo.push_back(q);
-		}
-	}
-	// Re-runs with the candidate heap in global scratch, in two tiers: 64 K entries first (0.5 MB per search: hundreds of re-runs share one
-	// launch), one entry per node — the bound that cannot overflow — only for what outgrows that.  (With the full bound from the start a
-	// 10M-node index allows 13 searches per launch: 39 overflowing queries out of 16 384 cost a quarter of the whole batch.)
-	uint64_t tier_cap[2] = {std::min<uint64_t>(h->count + 1, 65536), h->count + 1};
-	if (knobs.gcand_cap >= 0) tier_cap[0] = std::min<uint64_t>(h->count + 1, uint64_t(std::max(1, knobs.gcand_cap)));   // test hook
-	for (int tier = 0; tier < 2 && !redo.empty(); ++tier) {
-		if (tier == 1 && tier_cap[1] == tier_cap[0]) break;
-		const uint64_t gcap = tier_cap[tier];
-		const uint64_t redo_slots = std::max<uint64_t>(1, std::min<uint64_t>(max_slots, (1ull << 30) / (gcap * 8)));
-		if (int rc = c->d_redo.ensure(redo.size() * sizeof(uint32_t)); rc) return rc;
-		RX_HIP(hipMemcpyAsync(c->d_redo.ptr, redo.data(), redo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-		for (size_t r0 = 0; r0 < redo.size(); r0 += redo_slots) {
-			const uint32_t cq = uint32_t(std::min<uint64_t>(redo_slots, redo.size() - r0));
-			if (int rc = c->d_visited.ensure(size_t(cq) * words * 4); rc) return rc;
-			if (int rc = c->d_gcand_d.ensure(size_t(cq) * gcap * sizeof(uint2)); rc) return rc;
-			RX_HIP(hipMemsetAsync(c->d_visited.ptr, 0, size_t(cq) * words * 4, c->stream));
-			rxgpu::HnswParams pc = p;
-			pc.queries = static_cast<const float*>(d_q);
-			pc.visited = static_cast<uint32_t*>(c->d_visited.ptr);
-			pc.only = static_cast<const uint32_t*>(c->d_redo.ptr) + r0;
-			pc.gcand = static_cast<uint2*>(c->d_gcand_d.ptr);
-			pc.gcand_cap = gcap;
-			ProfileScope ps(h, "hnsw_redo", c->stream);
-			rxgpu::launch_hnsw_search(h->metric, pc, cq, true, c->stream);
-		}
-		RX_HIP(hipGetLastError());
-		if (int rc = fetch_counts(); rc) return rc;
-		RX_HIP(hipStreamSynchronize(c->stream));
-		std::vector<uint32_t> again;
-		for (const uint32_t q : redo) {
-			if (dl_count[q] == rxgpu::kHnswOverflow) again.push_back(q);
-		}
-		redo.swap(again);
-	}
-	RX_CHECK(redo.empty(), RXGPU_ERR_DEVICE, "rxgpu_hnsw_search_knn: a candidate heap of one entry per node overflowed");
-	if (!to_host) return to_sink();
-	if (int rc = fetch_lists(); rc) return rc;
-	RX_HIP(hipStreamSynchronize(c->stream));
-	return done_host();
-}
-
-// ---------------------------------------------------------------------------------------------- SearchRange, expansion on the device
-// hnswalg.h:2015-2070: ef-search (the kernels above), then the closure over level-0 links while dist < radius — hnsw_range_kernel, one
-// launch whatever the depth of the expansion.  cap too small: RXGPU_ERR_OVERFLOW with *out_total = hits counted so far (a lower bound: the
-// expansion stops growing where it cannot store) — the caller retries with more room.
-static int hnsw_range_impl(rxgpu_index* h, const void* query, const float* qcorr, const float* qnorm, float radius, uint32_t ef, float* out_dist,
-						   uint32_t* out_row, uint64_t cap, uint64_t* out_total) {
-	const bool sq8 = qcorr != nullptr;
-	RX_CHECK(h && query && out_total, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_range: null argument");
-	*out_total = 0;
-	RX_CHECK(cap == 0 || (out_dist && out_row), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_range: null argument");
-	if (h->count == 0) return RXGPU_OK;
-	const uint32_t ef_eff = ef ? ef : 1;
-	const uint32_t kk = uint32_t(std::min<uint64_t>(ef_eff, h->count));
-	std::vector<float> sd(kk);
-	std::vector<uint32_t> sr(kk);
-	uint32_t sc = 0;
-	if (int rc = hnsw_search_impl(h, query, qcorr, qnorm, 1, kk, ef_eff, sd.data(), sr.data(), &sc); rc) return rc;
-	DeviceGuard dg(h->device);
-	rxgpu_search_ctx* c = acquire_ctx(h);
-	if (!c) return RXGPU_ERR_DEVICE;
-	struct Rel {
-		rxgpu_index* h;
-		rxgpu_search_ctx* c;
-		~Rel() { release_ctx(h, c); }
-	} rel{h, c};
-	const uint64_t words = (h->count + 31) / 32;
-	const uint64_t room = std::max<uint64_t>(cap, 1);
-	const size_t qelem = sq8 ? 1 : 4;
-	size_t carve = 0;
-	auto take = [&carve](size_t bytes) {
-		const size_t at = carve;
-		carve = (carve + bytes + 255) & ~size_t(255);
-		return at;
-	};
-	const size_t o_q = take(size_t(h->dim) * qelem + 16), o_qc = take(8), o_sd = take(size_t(kk) * 4), o_sr = take(size_t(kk) * 4),
-				 o_front = take(size_t(2) * room * 4), o_total = take(8);
-	if (int rc = c->d_misc.ensure(carve); rc) return rc;
-	if (int rc = c->d_visited.ensure(words * 4); rc) return rc;
-	if (int rc = c->d_out_dist.ensure(room * 4); rc) return rc;
-	if (int rc = c->d_out_row.ensure(room * 4); rc) return rc;
-	char* mb = static_cast<char*>(c->d_misc.ptr);
-	RX_HIP(hipMemcpyAsync(mb + o_q, query, size_t(h->dim) * qelem, hipMemcpyHostToDevice, c->stream));
-	if (sq8) {
-		const float qc[2] = {*qcorr, *qnorm};
-		RX_HIP(hipMemcpyAsync(mb + o_qc, qc, 8, hipMemcpyHostToDevice, c->stream));
-	}
-	if (sc) {
-		RX_HIP(hipMemcpyAsync(mb + o_sd, sd.data(), size_t(sc) * 4, hipMemcpyHostToDevice, c->stream));
-		RX_HIP(hipMemcpyAsync(mb + o_sr, sr.data(), size_t(sc) * 4, hipMemcpyHostToDevice, c->stream));
-	}
-	RX_HIP(hipMemsetAsync(mb + o_total, 0, 8, c->stream));
-	RX_HIP(hipMemsetAsync(c->d_visited.ptr, 0, words * 4, c->stream));
-	rxgpu::HnswParams p{};
-	p.rows = h->d_rows;
-	p.inv_norms = h->d_inv_norms;
-	p.links0 = h->d_links0;
-	p.deleted = h->d_deleted;
-	p.n = h->count;
-	p.stride = h->stride;
-	p.dim = h->dim;
-	p.M = h->graph_M;
-	p.maxM0 = h->graph_maxM0;
-	p.bare = h->graph_deleted == 0;
-	p.queries = reinterpret_cast<const float*>(mb + o_q);
-	if (sq8) {
-		p.codes = h->d_codes;
-		p.corr = h->d_corr;
-		p.alpha2 = h->sq8_alpha2;
-		p.qcodes = reinterpret_cast<const uint8_t*>(mb + o_q);
-		p.qcorr = reinterpret_cast<const float*>(mb + o_qc);
-		p.qnorm = reinterpret_cast<const float*>(mb + o_qc) + 1;
-	}
-	rxgpu::HnswRange r{};
-	r.seed_dist = reinterpret_cast<const float*>(mb + o_sd);
-	r.seed_row = reinterpret_cast<const uint32_t*>(mb + o_sr);
-	r.seed_n = sc;
-	r.radius = radius;
-	r.visited = static_cast<uint32_t*>(c->d_visited.ptr);
-	r.frontier = reinterpret_cast<uint32_t*>(mb + o_front);
-	r.out_dist = static_cast<float*>(c->d_out_dist.ptr);
-	r.out_row = static_cast<uint32_t*>(c->d_out_row.ptr);
-	r.total = reinterpret_cast<unsigned long long*>(mb + o_total);
-	r.cap = cap;
-	{
-		ProfileScope ps(h, "hnsw_range", c->stream);
-		rxgpu::launch_hnsw_range(h->metric, p, r, c->stream);
-	}
-	RX_HIP(hipGetLastError());
-	unsigned long long total = 0;
-	RX_HIP(hipMemcpyAsync(&total, mb + o_total, 8, hipMemcpyDeviceToHost, c->stream));
-	RX_HIP(hipStreamSynchronize(c->stream));
-	*out_total = total;
-	const uint64_t have = std::min<uint64_t>(total, cap);
-	if (have) {
-		RX_HIP(hipMemcpyAsync(out_dist, c->d_out_dist.ptr, have * 4, hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipMemcpyAsync(out_row, c->d_out_row.ptr, have * 4, hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipStreamSynchronize(c->stream));
-	}
-	if (total > cap) {
-		set_error("rxgpu_hnsw_search_range: more hits than the output buffer holds");
-		return RXGPU_ERR_OVERFLOW;
-	}
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_search_range(rxgpu_index* h, const float* query, float radius, uint32_t ef, float* out_dist, uint32_t* out_row, uint64_t cap,
-							uint64_t* out_total) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) return rxgpu::sharded_hnsw_search_range(h, query, radius, ef, out_dist, out_row, cap, out_total);
-	RX_CHECK(h->count == 0 || (h->graph_attached && h->graph_n == h->count), RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_range: graph is not attached / out of date");
-	return hnsw_range_impl(h, query, nullptr, nullptr, radius, ef, out_dist, out_row, cap, out_total);
-}
-
-int rxgpu_hnsw_search_range_sq8(rxgpu_index* h, const uint8_t* query_codes, float query_corr, float query_norm_coef, float radius, uint32_t ef,
-								float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total) {
-	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_range_sq8: not available on a sharded index");
-	RX_CHECK(h->count == 0 || (h->graph_attached && h->graph_n == h->count), RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_range_sq8: graph is not attached / out of date");
-	RX_CHECK(h->count == 0 || (h->d_codes && h->sq8_n == h->count), RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_range_sq8: SQ8 codes are not attached / out of date");
-	return hnsw_range_impl(h, query_codes, &query_corr, &query_norm_coef, radius, ef, out_dist, out_row, cap, out_total);
-}
-
-// ---------------------------------------------------------------------------------------------- streaming KNN sessions
-struct rxgpu_hnsw_stream {
-	rxgpu_index* owner = nullptr;
-	uint64_t graph_n = 0;
-	uint32_t ef = 0;
-	hipStream_t stream = nullptr;
-	rxgpu_devbuf d_query, d_visited, d_cand, d_top, d_ext, d_state, d_out;
-	uint32_t out_cap = 0;
-	rxgpu::HnswStreamState host_state{};
-	bool empty_graph = false;
-	bool sq8 = false;          // the session runs over the SQ8 codes: d_query holds the query's codes
-	float qcorr = 0.f, qnorm = 1.f;
-};
-
-static void fill_hnsw_params(const rxgpu_index* h, rxgpu::HnswParams& p) {
-	p.rows = h->d_rows;
-	p.inv_norms = h->d_inv_norms;
-	p.links0 = h->d_links0;
-	p.upper_off = h->d_upper_off;
-	p.upper = h->d_upper;
-	p.deleted = h->d_deleted;
-	p.n = h->count;
-	p.stride = h->stride;
-	p.dim = h->dim;
-	p.M = h->graph_M;
-	p.maxM0 = h->graph_maxM0;
-	p.maxlevel = h->graph_maxlevel;
-	p.entry = h->graph_entry;
-	p.bare = h->graph_deleted == 0;
-}
-
-static void fill_sq8_params(const rxgpu_index* h, const rxgpu_hnsw_stream* s, rxgpu::HnswParams& p) {
-	if (!s->sq8) return;
-	p.codes = h->d_codes;
-	p.corr = h->d_corr;
-	p.alpha2 = h->sq8_alpha2;
-}
-
-static void fill_stream(const rxgpu_hnsw_stream* s, rxgpu::HnswStream& d) {
-	const uint64_t cap = s->graph_n;
-	d.query = static_cast<const float*>(s->d_query.ptr);
-	d.qcodes = s->sq8 ? static_cast<const uint8_t*>(s->d_query.ptr) : nullptr;
-	d.qcorr = s->qcorr;
-	d.qnorm = s->qnorm;
-	d.visited = static_cast<uint32_t*>(s->d_visited.ptr);
-	d.cand_d = static_cast<float*>(s->d_cand.ptr);
-	d.cand_i = reinterpret_cast<uint32_t*>(d.cand_d + cap);
-	d.top_d = static_cast<float*>(s->d_top.ptr);
-	d.top_i = reinterpret_cast<uint32_t*>(d.top_d + 2 * cap);
-	d.ext_d = static_cast<float*>(s->d_ext.ptr);
-	d.ext_i = reinterpret_cast<uint32_t*>(d.ext_d + 2 * cap);
-	d.cap = uint32_t(cap);
-	d.ef = s->ef;
-	d.state = static_cast<rxgpu::HnswStreamState*>(s->d_state.ptr);
-	d.out_dist = static_cast<float*>(s->d_out.ptr);
-	d.out_row = reinterpret_cast<uint32_t*>(d.out_dist + s->out_cap);
-}
-
-void rxgpu_hnsw_stream_end(rxgpu_hnsw_stream* s) {
-	if (!s) return;
-	DeviceGuard dg(s->owner->device);
-	if (s->stream) {
-		(void)hipStreamSynchronize(s->stream);
-		(void)hipStreamDestroy(s->stream);
-	}
-	for (rxgpu_devbuf* b : {&s->d_query, &s->d_visited, &s->d_cand, &s->d_top, &s->d_ext, &s->d_state, &s->d_out}) b->release();
-	delete s;
-}
-
-static int hnsw_stream_begin_impl(rxgpu_index* h, const void* query, bool sq8, float qcorr, float qnorm, uint32_t ef, rxgpu_hnsw_stream** out) {
-	RX_CHECK(h && query && out, RXGPU_ERR_PARAMS, "rxgpu_hnsw_stream_begin: null argument");
-	*out = nullptr;
-	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_hnsw_stream_begin: streaming sessions are per graph — not available on a sharded index");
-	RX_CHECK(!sq8 || h->count == 0 || (h->d_codes && h->sq8_n == h->count), RXGPU_ERR_LOGIC,
-			 "rxgpu_hnsw_stream_begin_sq8: SQ8 codes are not attached / out of date");
-	DeviceGuard dg(h->device);
-	auto* s = new rxgpu_hnsw_stream();
-	s->owner = h;
-	s->ef = ef ? ef : 100;   // kDefaultStreamingEf (hnswalg.h:1867)
-	s->sq8 = sq8;
-	s->qcorr = qcorr;
-	s->qnorm = qnorm;
-	s->graph_n = h->count;
-	if (h->count == 0) {     // hnswalg.h:1880-1882: an empty graph yields a session that is exhausted at once
-		s->empty_graph = true;
-		*out = s;
-		return RXGPU_OK;
-	}
-	struct Guard {
-		rxgpu_hnsw_stream* s;
-		~Guard() {
-			if (s) rxgpu_hnsw_stream_end(s);
-		}
-	} guard{s};
-	RX_CHECK(h->graph_attached && h->graph_n == h->count, RXGPU_ERR_LOGIC, "rxgpu_hnsw_stream_begin: graph is not attached / out of date");
-	RX_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-	const uint64_t cap = h->count, words = (h->count + 31) / 32;
-	const size_t qbytes = size_t(h->dim) * (sq8 ? 1 : 4);
-	if (int rc = s->d_query.ensure(size_t(h->dim) * 4); rc) return rc;
-	if (int rc = s->d_visited.ensure(words * 4); rc) return rc;
-	if (int rc = s->d_cand.ensure(cap * 8); rc) return rc;
-	if (int rc = s->d_top.ensure(cap * 16); rc) return rc;
-	if (int rc = s->d_ext.ensure(cap * 16); rc) return rc;
-	if (int rc = s->d_state.ensure(sizeof(rxgpu::HnswStreamState)); rc) return rc;
-	RX_HIP(hipMemcpyAsync(s->d_query.ptr, query, qbytes, hipMemcpyHostToDevice, s->stream));
-	RX_HIP(hipMemsetAsync(s->d_visited.ptr, 0, words * 4, s->stream));
-	rxgpu::HnswParams p{};
-	fill_hnsw_params(h, p);
-	fill_sq8_params(h, s, p);
-	rxgpu::HnswStream d{};
-	fill_stream(s, d);
-	rxgpu::launch_hnsw_stream(h->metric, p, d, 0, rxgpu::kStreamBegin, false, s->stream);
-	RX_HIP(hipGetLastError());
-	RX_HIP(hipMemcpyAsync(&s->host_state, s->d_state.ptr, sizeof(s->host_state), hipMemcpyDeviceToHost, s->stream));
-	RX_HIP(hipStreamSynchronize(s->stream));
-	guard.s = nullptr;
-	*out = s;
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_stream_begin(rxgpu_index* h, const float* query, uint32_t ef, rxgpu_hnsw_stream** out) {
-	return hnsw_stream_begin_impl(h, query, false, 0.f, 1.f, ef, out);
-}
-
-// The same session over a quantised graph (HierarchicalNSWImpl<uint8_t>): the query as prepareData leaves it (codes + corrective offset),
-// every distance scaled by its normCoef — BeginStreamingSearch / ContinueStreamingSearch (hnswalg.h:1865-1975) instantiated for uint8_t.
-int rxgpu_hnsw_stream_begin_sq8(rxgpu_index* h, const uint8_t* query_codes, float query_corr, float query_norm_coef, uint32_t ef, rxgpu_hnsw_stream** out) {
-	return hnsw_stream_begin_impl(h, query_codes, true, query_corr, query_norm_coef, ef, out);
-}
-
-int rxgpu_hnsw_stream_continue(rxgpu_hnsw_stream* s, uint32_t batch, float* out_dist, uint32_t* out_row, uint32_t* out_count, int32_t* exhausted) {
-	RX_CHECK(s && out_count && exhausted, RXGPU_ERR_PARAMS, "rxgpu_hnsw_stream_continue: null argument");
-	*out_count = 0;
-	*exhausted = 0;
-	if (batch == 0) return RXGPU_OK;   // hnswalg.h:1956-1958
-	if (s->empty_graph) {
-		*exhausted = 1;
-		return RXGPU_OK;
-	}
-	RX_CHECK(out_dist && out_row, RXGPU_ERR_PARAMS, "rxgpu_hnsw_stream_continue: null argument");
-	rxgpu_index* h = s->owner;
-	// the whole session must run under the caller's read lock (hnsw_interface.h:99): a mutated graph invalidates it
-	RX_CHECK(h->graph_attached && h->graph_n == s->graph_n && h->count == s->graph_n, RXGPU_ERR_LOGIC,
-			 "rxgpu_hnsw_stream_continue: the graph changed under the session");
-	DeviceGuard dg(h->device);
-	const uint32_t out_need = uint32_t(std::min<uint64_t>(batch, s->graph_n));
-	if (out_need > s->out_cap) {
-		if (int rc = s->d_out.ensure(size_t(out_need) * 8); rc) return rc;
-		s->out_cap = out_need;
-	}
-	rxgpu::HnswParams p{};
-	fill_hnsw_params(h, p);
-	fill_sq8_params(h, s, p);
-	rxgpu::HnswStream d{};
-	fill_stream(s, d);
-	const rxgpu::HnswStreamState& hs = s->host_state;
-	const uint32_t ef_eff = std::max(s->ef, batch);
-	bool lds = ef_eff <= uint32_t(rxgpu::kStreamLdsTop) && uint32_t(hs.top_n) <= uint32_t(rxgpu::kStreamLdsTop) &&
-			   uint32_t(hs.ext_n) <= uint32_t(rxgpu::kStreamLdsExt) && uint32_t(hs.cand_n) + h->graph_maxM0 <= uint32_t(rxgpu::kStreamLdsCand);
-	if (getenv("RXGPU_HNSW_STREAM_GLOBAL")) lds = false;   // test hook: run every call with the heaps in HBM
-	int mode = rxgpu::kStreamContinue;
-	for (int attempt = 0; attempt < 2; ++attempt) {
-		ProfileScope ps(h, lds ? "hnsw_stream" : "hnsw_stream_global", s->stream);
-		rxgpu::launch_hnsw_stream(h->metric, p, d, batch, mode, lds, s->stream);
-		RX_HIP(hipGetLastError());
-		RX_HIP(hipMemcpyAsync(&s->host_state, s->d_state.ptr, sizeof(s->host_state), hipMemcpyDeviceToHost, s->stream));
-		RX_HIP(hipStreamSynchronize(s->stream));
-		if (s->host_state.status != rxgpu::kStreamNeedGlobal) break;
-		RX_CHECK(lds, RXGPU_ERR_DEVICE, "rxgpu_hnsw_stream_continue: global-heap pass asked for more room");
-		lds = false;                       // outgrew LDS at a step boundary: same call, heaps in HBM, no second mergeExtras
-		mode = rxgpu::kStreamResume;
-	}
-	RX_CHECK(s->host_state.status == rxgpu::kStreamOk, RXGPU_ERR_DEVICE, "rxgpu_hnsw_stream_continue: device-side session error");
-	const uint32_t n = s->host_state.out_count;
-	if (n) {
-		RX_HIP(hipMemcpyAsync(out_dist, d.out_dist, size_t(n) * 4, hipMemcpyDeviceToHost, s->stream));
-		RX_HIP(hipMemcpyAsync(out_row, d.out_row, size_t(n) * 4, hipMemcpyDeviceToHost, s->stream));
-		RX_HIP(hipStreamSynchronize(s->stream));
-	}
-	*out_count = n;
-	*exhausted = s->host_state.exhausted ? 1 : 0;
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_read_stats(rxgpu_index* h, uint64_t* distance_evals, uint64_t* hops) {
-	RX_CHECK(h && distance_evals && hops, RXGPU_ERR_PARAMS, "rxgpu_hnsw_read_stats: null argument");
-	*distance_evals = 0;
-	*hops = 0;
-	if (h->shard_set) {   // the sum over the shards' graphs
-		for (uint32_t s = 0; s < rxgpu_index_shard_count(h); ++s) {
-			uint64_t e = 0, hp = 0;
-			if (int rc = rxgpu_hnsw_read_stats(rxgpu_index_shard(h, s), &e, &hp); rc) return rc;
-			*distance_evals += e;
-			*hops += hp;
-		}
-		return RXGPU_OK;
-	}
-	if (!h->d_hnsw_stats) return RXGPU_OK;
-	DeviceGuard dg(h->device);
-	unsigned long long v[4] = {0, 0, 0, 0};   // evals, hops, in-kernel restarts, distance trips of the speculative team searches
-	RX_HIP(rxgpu::device_wait_all(h->device));
-	RX_HIP(hipMemcpy(v, h->d_hnsw_stats, sizeof(v), hipMemcpyDeviceToHost));
-	RX_HIP(hipMemset(h->d_hnsw_stats, 0, sizeof(v)));
-	*distance_evals = v[0];
-	*hops = v[1];
-	if (std::getenv("RXGPU_HNSW_TRIPS")) std::fprintf(stderr, "[rxgpu hnsw] hops %llu evals %llu restarts %llu speculative-search distance trips %llu\n", v[1], v[0], v[2], v[3]);
-	if (std::getenv("RXGPU_HNSW_PHASES")) {   // a library built with -DRXGPU_HNSW_PHASES: shader cycles of the sorted-list search by phase
-		unsigned long long ph[4] = {0, 0, 0, 0};
-		RX_HIP(hipMemcpy(ph, h->d_hnsw_stats + 4, sizeof(ph), hipMemcpyDeviceToHost));
-		RX_HIP(hipMemset(h->d_hnsw_stats + 4, 0, sizeof(ph)));
-		std::fprintf(stderr, "[rxgpu hnsw phases] hops %llu evals %llu | cycles: pop+links+visited %llu  distances %llu  inserts %llu  layer0 total %llu\n", v[1], v[0], ph[0],
-					 ph[1], ph[2], ph[3]);
-	}
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_read_stats4(rxgpu_index* h, uint64_t* out4) {
-	RX_CHECK(h && out4, RXGPU_ERR_PARAMS, "rxgpu_hnsw_read_stats4: null argument");
-	out4[0] = out4[1] = out4[2] = out4[3] = 0;
-	if (h->shard_set || !h->d_hnsw_stats) return RXGPU_OK;
-	DeviceGuard dg(h->device);
-	unsigned long long v[4] = {0, 0, 0, 0};
-	RX_HIP(rxgpu::device_wait_all(h->device));
-	RX_HIP(hipMemcpy(v, h->d_hnsw_stats, sizeof(v), hipMemcpyDeviceToHost));
-	RX_HIP(hipMemset(h->d_hnsw_stats, 0, sizeof(v)));
-	for (int i = 0; i < 4; ++i) out4[i] = v[i];
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_read_lds_reruns(rxgpu_index* h, uint64_t* reruns) {
-	RX_CHECK(h && reruns, RXGPU_ERR_PARAMS, "rxgpu_hnsw_read_lds_reruns: null argument");
-	if (h->shard_set) {
-		*reruns = 0;
-		for (uint32_t s = 0; s < rxgpu_index_shard_count(h); ++s) {
-			uint64_t v = 0;
-			if (int rc = rxgpu_hnsw_read_lds_reruns(rxgpu_index_shard(h, s), &v); rc) return rc;
-			*reruns += v;
-		}
-		return RXGPU_OK;
-	}
-	*reruns = h->hnsw_lds_reruns.exchange(0);
-	return RXGPU_OK;
-}
-
-int rxgpu_hnsw_read_tie_reruns(rxgpu_index* h, uint64_t* reruns) {
-	RX_CHECK(h && reruns, RXGPU_ERR_PARAMS, "rxgpu_hnsw_read_tie_reruns: null argument");
-	if (h->shard_set) {
-		*reruns = 0;
-		for (uint32_t s = 0; s < rxgpu_index_shard_count(h); ++s) {
-			uint64_t v = 0;
-			if (int rc = rxgpu_hnsw_read_tie_reruns(rxgpu_index_shard(h, s), &v); rc) return rc;
-			*reruns += v;
-		}
-		return RXGPU_OK;
-	}
-	*reruns = h->hnsw_tie_reruns.exchange(0);   // queries this library re-ran in a launch of their own ...
-	if (h->d_hnsw_stats) {                      // ... and searches that started over on the heaps inside the sorted-list kernel
-		DeviceGuard dg(h->device);
-		unsigned long long v = 0;
-		RX_HIP(rxgpu::device_wait_all(h->device));
-		RX_HIP(hipMemcpy(&v, h->d_hnsw_stats + 2, sizeof(v), hipMemcpyDeviceToHost));
-		RX_HIP(hipMemset(h->d_hnsw_stats + 2, 0, sizeof(v)));
-		*reruns += v;
-	}
-	return RXGPU_OK;
-}
-
 int rxgpu_profile_enable(rxgpu_index* h, int on) {
 	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
-	if (h->shard_set) {
-		set_error("rxgpu_profile_enable: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
-	if (h->shard_set) {
-		set_error("rxgpu_hnsw_stream_begin: not available on a sharded index");
-		return RXGPU_ERR_LOGIC;
-	}
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_profile_enable: not available on a sharded index");
 	std::lock_guard<std::mutex> lk(h->mtx);
 	for (auto& kv : h->profile) {
 		for (auto& ev : kv.second.events) {

@@ -24,22 +24,6 @@
 
 using rxgpu::set_error;
 
-#define RX_HIP(expr)                                                                \
-	do {                                                                            \
-		hipError_t e__ = (expr);                                                    \
-		if (e__ != hipSuccess) {                                                    \
-			set_error(std::string(#expr) + ": " + hipGetErrorString(e__));          \
-			return e__ == hipErrorOutOfMemory ? RXGPU_ERR_NOMEM : RXGPU_ERR_DEVICE; \
-		}                                                                           \
-	} while (0)
-#define RX_CHECK(cond, code, msg) \
-	do {                          \
-		if (!(cond)) {            \
-			set_error(msg);       \
-			return code;          \
-		}                         \
-	} while (0)
-
 struct rxgpu_ft_word {
 	uint64_t n = 0, nent = 0;
 	uint32_t* doc = nullptr;
@@ -200,16 +184,6 @@ struct rxgpu_ft_shard_set {
 
 
 namespace {
-struct DevGuard {
-	int prev = -1;
-	explicit DevGuard(int dev) {
-		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != dev) (void)hipSetDevice(dev);
-	}
-	~DevGuard() {
-		if (prev >= 0) (void)hipSetDevice(prev);
-	}
-};
 // HIP event pair that cannot leak on an early error return
 struct EventPair {
 	hipEvent_t a = nullptr, b = nullptr;
@@ -248,7 +222,7 @@ int rxgpu_ft_create(uint32_t num_fields, int device, rxgpu_ft_index** out) {
 	int ndev = 0;
 	RX_HIP(hipGetDeviceCount(&ndev));
 	RX_CHECK(device >= 0 && device < ndev, RXGPU_ERR_PARAMS, "rxgpu_ft_create: no such device");
-	DevGuard dg(device);
+	rxgpu::DeviceGuard dg(device);
 	auto* h = new rxgpu_ft_index();
 	h->device = device;
 	h->num_fields = num_fields;
@@ -441,7 +415,7 @@ int checkout_lane(rxgpu_ft_index* h, LaneLock& out) {
 		lane->device = h->device;
 		lane->num_fields = h->num_fields;
 		lane->root = h;
-		DevGuard dg(h->device);
+		rxgpu::DeviceGuard dg(h->device);
 		if (hipStreamCreateWithFlags(&lane->stream, hipStreamNonBlocking) != hipSuccess) {
 			set_error("hipStreamCreateWithFlags failed");
 			return RXGPU_ERR_DEVICE;
@@ -533,11 +507,11 @@ static int ft_shards_set_word(rxgpu_ft_index* h, uint32_t word_id, uint64_t n, c
 void rxgpu_ft_destroy(rxgpu_ft_index* h) {
 	if (!h) return;
 	if (h->shard_set) {
-		DevGuard dgs(h->device);
+		rxgpu::DeviceGuard dgs(h->device);
 		ft_shards_destroy(h->shard_set);
 		h->shard_set = nullptr;
 	}
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	(void)rxgpu::device_wait_all(h->device);
 	for (auto& kv : h->words) kv.second.release();
 	for (void* p : {static_cast<void*>(h->d_words), static_cast<void*>(h->d_avg), static_cast<void*>(h->d_removed), static_cast<void*>(h->d_removed_bits)}) {
@@ -560,7 +534,7 @@ int rxgpu_ft_set_docs(rxgpu_ft_index* h, uint64_t total_docs, const float* words
 	if (h->shard_set) return ft_shards_set_docs(h, total_docs, words_in_field, avg_words, removed);
 	std::lock_guard<std::mutex> lk(h->mtx);
 	std::unique_lock<std::shared_mutex> dict_lk(h->dict_mtx);   // no merge on any lane reads the dictionary meanwhile
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	RX_HIP(hipStreamSynchronize(h->stream));
 	if (int rc = upload(h->d_words, words_in_field, total_docs * h->num_fields); rc) return rc;
 	if (int rc = upload(h->d_avg, avg_words, h->num_fields); rc) return rc;
@@ -597,7 +571,7 @@ int rxgpu_ft_set_word(rxgpu_ft_index* h, uint32_t word_id, uint64_t n, const uin
 	if (h->shard_set) return ft_shards_set_word(h, word_id, n, doc, ent_off, ent_field, ent_tf, ent_first_pos, nullptr, nullptr);
 	std::lock_guard<std::mutex> lk(h->mtx);
 	std::unique_lock<std::shared_mutex> dict_lk(h->dict_mtx);   // no merge on any lane reads the dictionary meanwhile
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	RX_HIP(hipStreamSynchronize(h->stream));
 	rxgpu_ft_word& w = h->words[word_id];
 	w.release();
@@ -2143,7 +2117,7 @@ int rxgpu_ft_merge_simple_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, con
 	RX_CHECK(word_ids && procs && opts->field_boost && opts->need_sum_rank, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_raw: null argument");
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	std::vector<QueryTermIn> terms{QueryTermIn{1, opts, 0, nsub}};
 	return run_merge(ll.lane, cfg, true, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, nullptr, cap, out_n, nullptr,
 					 "rxgpu_ft_merge_simple_raw");
@@ -2175,7 +2149,7 @@ int rxgpu_ft_set_word_positions(rxgpu_ft_index* h, uint32_t word_id, uint64_t n,
 	if (n == 0) return RXGPU_OK;
 	std::lock_guard<std::mutex> lk(h->mtx);
 	std::unique_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	rxgpu_ft_word& w = h->words[word_id];
 	if (int rc = upload(w.pos_off, pos_off, n + 1); rc) return rc;
 	if (int rc = upload(w.fpos, fpos, size_t(pos_off[n])); rc) return rc;
@@ -2220,7 +2194,7 @@ int rxgpu_ft_set_words_packed_ptrs(rxgpu_ft_index* h, uint32_t nwords, const uin
 	std::lock_guard<std::mutex> lk(h->mtx);
 	WallClock wall{h, t_call};
 	std::unique_lock<std::shared_mutex> dict_lk(h->dict_mtx);   // no merge on any lane reads the dictionary meanwhile
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	RX_HIP(hipStreamSynchronize(h->stream));
 	// wavefronts of similar work: the words are launched longest first (a wavefront lasts as long as its longest stream).  A bucket sort by
 	// the length's power of two is enough for that — O(n); a comparison sort of a 100 000-word dictionary cost 8 ms of this call.
@@ -2438,7 +2412,7 @@ int rxgpu_ft_set_words_packed_ptrs(rxgpu_ft_index* h, uint32_t nwords, const uin
 		RX_HIP(hipMalloc(&raw, cv.off));
 		const int device = h->device;
 		pool = std::shared_ptr<void>(raw, [device](void* q) {
-			DevGuard g(device);
+			rxgpu::DeviceGuard g(device);
 			(void)hipFree(q);
 		});
 		base = static_cast<char*>(raw);
@@ -2539,7 +2513,7 @@ int rxgpu_ft_get_word(rxgpu_ft_index* h, uint32_t word_id, uint64_t* n, uint64_t
 	RX_CHECK(h && n && npos && nent && n_ranges, RXGPU_ERR_PARAMS, "rxgpu_ft_get_word: null argument");
 	std::lock_guard<std::mutex> lk(h->mtx);
 	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	RX_HIP(hipStreamSynchronize(h->stream));
 	const auto it = h->words.find(word_id);
 	RX_CHECK(it != h->words.end(), RXGPU_ERR_PARAMS, "rxgpu_ft_get_word: unknown word");
@@ -2587,7 +2561,7 @@ int rxgpu_ft_merge_terms_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	RX_CHECK(sub_off[nterms] == 0 || (word_ids && procs), RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_raw: null argument");
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	std::vector<QueryTermIn> terms(nterms);
 	for (uint32_t t = 0; t < nterms; ++t) terms[t] = QueryTermIn{ops[t], &opts[t], sub_off[t], sub_off[t + 1]};
 	return run_merge(ll.lane, cfg, false, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected,
@@ -2633,7 +2607,7 @@ int rxgpu_ft_merge_query_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	if (empty) return RXGPU_OK;
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	return run_merge(ll.lane, cfg, simple, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected, who);
 }
 
@@ -2668,7 +2642,7 @@ int rxgpu_ft_merge_query2_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, con
 	}
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	return run_merge(ll.lane, cfg, simple, terms, q->word_ids, q->procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected, who,
 					 false, q->nsyn ? &syn : nullptr);
 }
@@ -2692,7 +2666,7 @@ int rxgpu_ft_merge_query_areas_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg
 	if (empty) return RXGPU_OK;
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	AreasOut ao;
 	ao.max_areas = max_areas_in_doc;
 	ao.cnt = out_area_cnt;
@@ -2733,7 +2707,7 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	if (batched.empty()) return RXGPU_OK;
 	std::lock_guard<std::mutex> batch_lk(h->batch_mtx);
 	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	if (!h->batch_stream) RX_HIP(hipStreamCreateWithFlags(&h->batch_stream, hipStreamNonBlocking));
 	if (!h->ev_ba) {
 		RX_HIP(hipEventCreate(&h->ev_ba));
@@ -2870,7 +2844,7 @@ int rxgpu_ft_merge_query_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg,
 	std::unique_lock<std::mutex> lk(h->mtx);
 	open_resident_session(h, lk);
 	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	h->res_cap = 0;
 	h->prep_done = false;
 	if (empty) return finish_pending(h, who);   // nothing is merged: the fusion sees an empty FT side
@@ -2911,7 +2885,7 @@ int rxgpu_ft_merge_query2_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg
 	std::unique_lock<std::mutex> lk(h->mtx);
 	open_resident_session(h, lk);
 	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	h->res_cap = 0;
 	h->prep_done = false;
 	if (empty) return finish_pending(h, who);   // nothing is merged: the fusion sees an empty FT side
@@ -2933,7 +2907,7 @@ int rxgpu_ft_merge_simple_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg
 	std::unique_lock<std::mutex> lk(h->mtx);
 	open_resident_session(h, lk);
 	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	std::vector<QueryTermIn> terms{QueryTermIn{1, opts, 0, nsub}};
 	uint64_t n = 0;
 	h->res_cap = 0;
@@ -2952,7 +2926,7 @@ int rxgpu_ft_merge_terms_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg,
 	std::unique_lock<std::mutex> lk(h->mtx);
 	open_resident_session(h, lk);
 	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	std::vector<QueryTermIn> terms(nterms);
 	for (uint32_t t = 0; t < nterms; ++t) terms[t] = QueryTermIn{ops[t], &opts[t], sub_off[t], sub_off[t + 1]};
 	uint64_t n = 0;
@@ -3030,7 +3004,7 @@ int rxgpu_hybrid_prepare_resident(rxgpu_ft_index* h, int32_t min_rank, const rxg
 	if (int rc = check_hybrid_params(params, "rxgpu_hybrid_prepare_resident"); rc) return rc;
 	std::unique_lock<std::mutex> lk(h->mtx);
 	if (int rc = check_resident_session(h, lk, "rxgpu_hybrid_prepare_resident"); rc) return rc;
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	return enqueue_prepare(h, min_rank, params, metric, d_row_of_doc);
 }
 
@@ -3049,7 +3023,7 @@ int rxgpu_hybrid_fuse_resident(rxgpu_ft_index* h, int32_t min_rank, const rxgpu_
 		rxgpu_ft_index* h;
 		~SessionEnd() { close_resident_session(h); }
 	} session_end{h};
-	DevGuard dg(h->device);
+	rxgpu::DeviceGuard dg(h->device);
 	const uint32_t M = h->res_pending ? h->res_cap : 0;   // no resident merge: an empty FT side (the merge found nothing to do)
 	const size_t out_cap = size_t(M) + k;
 	RX_CHECK(cap >= out_cap && (out_cap == 0 || (out_ids && out_ranks)), RXGPU_ERR_OVERFLOW, "rxgpu_hybrid_fuse_resident: output buffers too small");
@@ -3172,7 +3146,7 @@ int rxgpu_hybrid_fuse(int device, const rxgpu_hybrid_params* params, int metric,
 	int ndev = 0;
 	RX_HIP(hipGetDeviceCount(&ndev));
 	RX_CHECK(device >= 0 && device < ndev, RXGPU_ERR_PARAMS, "rxgpu_hybrid_fuse: no such device");
-	DevGuard dg(device);
+	rxgpu::DeviceGuard dg(device);
 	const size_t nf = std::max<uint32_t>(n_ft, 1), nk = std::max<uint32_t>(n_knn, 1), no = size_t(n_ft) + n_knn + 1;
 	Carver cv;
 	const size_t o_fid = cv.take(nf * 4), o_fr = cv.take(nf), o_kid = cv.take(nk * 4), o_kr = cv.take(nk * 4), o_key = cv.take(2 * nf * 4),
@@ -3180,10 +3154,10 @@ int rxgpu_hybrid_fuse(int device, const rxgpu_hybrid_params* params, int metric,
 				 o_state = cv.take(sizeof(rxgpu::HybridFuseState));
 	rxgpu_devbuf buf;
 	if (int rc = buf.ensure(cv.off); rc) return rc;
-	struct Rel {
+	struct BufRelease {
 		rxgpu_devbuf& b;
-		~Rel() { b.release(); }
-	} rel{buf};
+		~BufRelease() { b.release(); }
+	} buf_release{buf};
 	char* d = static_cast<char*>(buf.ptr);
 	if (n_ft) {
 		RX_HIP(hipMemcpy(d + o_fid, ft_ids, size_t(n_ft) * 4, hipMemcpyHostToDevice));

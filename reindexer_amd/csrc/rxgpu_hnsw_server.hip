@@ -210,7 +210,7 @@ static void server_quiesce_state(HnswServerState* st) {
 	if (!st->maybe_alive.load(std::memory_order_acquire)) return;   // (mutators call this per row: no lock, no driver call when nothing ran)
 	std::lock_guard<std::mutex> lk(st->mtx);
 	if (!st->maybe_alive.load(std::memory_order_acquire)) return;
-	DeviceGuardLite dg(st->device);
+	DeviceGuard dg(st->device);
 	store_rel(st->stop(), 1u);
 	(void)hipStreamSynchronize(st->stream);
 	store_rel(st->leaving(), st->launched.load());   // (a generation that ended on its wall-clock fallback never wrote it)
@@ -347,7 +347,7 @@ int hnsw_server_search(rxgpu_index* h, const HnswServerConfig& cfg, const float*
 	auto ensure_alive = [&]() -> int {
 		if (load_acq(st->leaving()) == st->launched.load(std::memory_order_acquire) && !load_acq(st->stop())) {   // no generation alive or queued
 			std::lock_guard<std::mutex> lk(st->mtx);
-			DeviceGuardLite dg(st->device);
+			DeviceGuard dg(st->device);
 			return server_launch(h, st);
 		}
 		return RXGPU_OK;

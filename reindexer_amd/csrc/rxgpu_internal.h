@@ -397,6 +397,24 @@ void set_error(const std::string& msg);
 
 }  // namespace rxgpu
 
+// The early returns of the C-ABI functions (include/rxgpu.h for the codes): a failed HIP call, a failed precondition
+#define RX_HIP(expr)                                                                                      \
+	do {                                                                                                  \
+		hipError_t e__ = (expr);                                                                          \
+		if (e__ != hipSuccess) {                                                                          \
+			::rxgpu::set_error(std::string(#expr) + ": " + hipGetErrorString(e__));                                \
+			return e__ == hipErrorOutOfMemory ? RXGPU_ERR_NOMEM : RXGPU_ERR_DEVICE;                       \
+		}                                                                                                 \
+	} while (0)
+
+#define RX_CHECK(cond, code, msg) \
+	do {                          \
+		if (!(cond)) {            \
+			::rxgpu::set_error(msg);       \
+			return code;          \
+		}                         \
+	} while (0)
+
 // A growable device buffer.
 struct rxgpu_devbuf {
 	void* ptr = nullptr;
@@ -470,7 +488,8 @@ struct HnswServerConfig {
 	bool spec = false;         // RXGPU_HNSW_SPEC=1: look-ahead distance batches (read when the index's mailbox is made; off by default)
 	uint32_t life_ms = 50;     // RXGPU_HNSW_SERVER_LIFE_MS: ... and after so long in any case (the next caller launches the next one)
 };
-// 1: served, 0: not served (the caller takes the launches), < 0: -(RXGPU error code is returned as is by the caller) — see the .hip
+// 1: served; 0: not served (the caller takes the launches); 2: the search ran there and came back flagged (the launching tiers answer it);
+// otherwise a (positive) RXGPU error code, which the caller returns as it is — see the .hip
 int hnsw_server_search(struct ::rxgpu_index* h, const HnswServerConfig& cfg, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
 					   uint32_t* out_count);
 void hnsw_server_quiesce(struct ::rxgpu_index* h);      // before the index changes: the resident kernel leaves, none is queued
@@ -482,13 +501,15 @@ void drain_retired();
 hipError_t device_wait_all(int device);                 // hipDeviceSynchronize behind hnsw_servers_pause_device
 void hnsw_server_times(const struct ::rxgpu_index* h, uint64_t* device_us, uint64_t* caller_us);
 void hnsw_server_counters(const struct ::rxgpu_index* h, uint64_t* served, uint64_t* generations);
-struct DeviceGuardLite {
+// The calling thread's device for a scope; what was current before comes back behind it.  ok: the switch worked (rxgpu_index_create asks).
+struct DeviceGuard {
 	int prev = -1;
-	explicit DeviceGuardLite(int dev) {
+	bool ok = true;
+	explicit DeviceGuard(int dev) {
 		if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-		if (prev != dev) (void)hipSetDevice(dev);
+		if (prev != dev) ok = hipSetDevice(dev) == hipSuccess;
 	}
-	~DeviceGuardLite() {
+	~DeviceGuard() {
 		if (prev >= 0) (void)hipSetDevice(prev);
 	}
 };
@@ -562,3 +583,24 @@ struct rxgpu_index {
 	bool profiling = false;
 	std::map<std::string, rxgpu_profile_slot> profile;
 };
+
+namespace rxgpu {
+// Check out a scratch context with its own stream (host-synchronous searches), and hand it back (rxgpu_capi.hip).
+rxgpu_search_ctx* acquire_ctx(rxgpu_index* h);
+void release_ctx(rxgpu_index* h, rxgpu_search_ctx* c);
+// ... handed back when the scope ends
+struct CtxLease {
+	rxgpu_index* h;
+	rxgpu_search_ctx* c;
+	~CtxLease() { release_ctx(h, c); }
+};
+// While the index is profiling (rxgpu_profile_enable): an event pair around what the scope enqueues on s, filed under `name`.
+struct ProfileScope {
+	rxgpu_index* h;
+	const char* name;
+	hipStream_t s;
+	hipEvent_t a = nullptr, b = nullptr;
+	ProfileScope(rxgpu_index* h_, const char* n, hipStream_t s_);
+	~ProfileScope();
+};
+}  // namespace rxgpu
