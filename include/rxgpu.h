@@ -308,6 +308,16 @@ int rxgpu_hnsw_upload_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, c
  * rxgpu_hnsw_search_knn. */
 int rxgpu_hnsw_search_knn_sq8(rxgpu_index* h, const uint8_t* query_codes, const float* query_corr, const float* query_norm_coef, uint32_t nq,
 							  uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count);
+/* ONE quantised query through the index's RESIDENT search kernel over the SQ8 codes — rxgpu_hnsw_search_knn_posted for a quantised graph: the
+ * same mailbox protocol, the same lifetime rules (idle / lifetime / every mutating entry point, the uploads of the code table among them, make
+ * the kernel leave), one wavefront per slot.  The query travels as for rxgpu_hnsw_search_knn_sq8 with nq == 1: query_codes [dim], its
+ * corrective offset and its normCoef.  *served = 1: out_* hold what rxgpu_hnsw_search_knn_sq8 returns for this query (the same device code
+ * runs the search; a search that comes back flagged is answered by the launches' re-run tiers inside this call).  *served = 0: this query is
+ * not taken — every slot is busy, ef > 256 (224 on a graph with deleted nodes), a dimension other than 128 / 384 / 512 / 768 / 1024 / 1536
+ * (with deleted nodes: other than 128 / 768), no code table attached, a profiled or sharded index, RXGPU_HNSW_SERVER=0 or
+ * RXGPU_HNSW_SERVER_SQ8=0 — and the caller uses rxgpu_hnsw_search_knn_sq8, which tries the mailbox itself for nq == 1 and launches otherwise. */
+int rxgpu_hnsw_search_knn_sq8_posted(rxgpu_index* h, const uint8_t* query_codes, float query_corr, float query_norm_coef, uint32_t k, uint32_t ef,
+									 float* out_dist, uint32_t* out_row, uint32_t* out_count, int32_t* served);
 /* Counters accumulated since the last call (for the roofline accounting: bytes = evals*dim*4 + hops*(1+2M)*4). */
 int rxgpu_hnsw_read_stats(rxgpu_index* h, uint64_t* distance_evals, uint64_t* hops);
 /* Searches with ef <= 256 (<= 224 when the graph has deleted nodes) keep top_candidates + candidate_set (hnswalg.h:741-777) as one sorted

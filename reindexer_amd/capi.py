@@ -86,6 +86,7 @@ _SIGNATURES = {
     "rxgpu_hnsw_attach_sq8": (_i, [_vp, _vp, _vp, _u64, _f]),
     "rxgpu_hnsw_upload_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp, _f]),
     "rxgpu_hnsw_search_knn_sq8": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "rxgpu_hnsw_search_knn_sq8_posted": (_i, [_vp, _vp, _f, _f, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "rxgpu_hnsw_read_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rxgpu_hnsw_read_tie_reruns": (_i, [_vp, C.POINTER(_u64)]),
     "rxgpu_hnsw_read_lds_reruns": (_i, [_vp, C.POINTER(_u64)]),
@@ -471,6 +472,18 @@ class VectorIndex:
         _check(lib().rxgpu_hnsw_search_knn_sq8(self._h, qc.ctypes.data, qcorr.ctypes.data, qnorm.ctypes.data, nq, k, ef, dist.ctypes.data,
                                                row.ctypes.data, cnt.ctypes.data))
         return dist[:, :k], row[:, :k], cnt
+
+    def hnsw_search_knn_sq8_posted(self, qcodes, qcorr: float, qnorm: float, k: int, ef: int = 0):
+        """One quantised query through the index's resident search kernel over the SQ8 codes (rxgpu_hnsw_search_knn_sq8_posted):
+        (dist, row, count, served)."""
+        qc = np.ascontiguousarray(qcodes, np.uint8).reshape(self.dim)
+        dist = np.full(max(k, 1), np.inf, np.float32)
+        row = np.full(max(k, 1), 0xFFFFFFFF, np.uint32)
+        cnt = _u32(0)
+        served = C.c_int32(0)
+        _check(lib().rxgpu_hnsw_search_knn_sq8_posted(self._h, qc.ctypes.data, float(qcorr), float(qnorm), k, ef, dist.ctypes.data, row.ctypes.data,
+                                                      C.addressof(cnt), C.byref(served)))
+        return dist[:k], row[:k], int(cnt.value), bool(served.value)
 
     def hnsw_read_stats(self):
         a, b = _u64(0), _u64(0)

@@ -39,6 +39,7 @@ struct HnswKnobs {
 	int nbl = -1;                        // RXGPU_HNSW_NBL = 1: team searches fetch the link blocks of a hop's rows along with the rows (an experiment, off by default)
 	int spec = -1;                       // RXGPU_HNSW_SPEC = 1: team searches also evaluate the next candidate's neighbours in the hop's distance trip (an experiment, off by default)
 	int server = -1;                     // RXGPU_HNSW_SERVER = 0: single queries take a launch each (no resident kernel)
+	int server_sq8 = -1;                 // RXGPU_HNSW_SERVER_SQ8 = 0: single queries over SQ8 codes take a launch each (the float mailbox stays; A/B)
 	int server_slots = -1, server_idle_us = -1, server_life_ms = -1;   // RXGPU_HNSW_SERVER_SLOTS / _IDLE_US / _LIFE_MS
 	bool names_a_kernel = false;         // a hook that picks a kernel form is set: the resident kernel (one form) stands aside
 };
@@ -70,11 +71,12 @@ inline HnswKnobs read_hnsw_knobs() {
 		else if (is("SPEC")) k.spec = atoi(val);
 		else if (is("NBL")) k.nbl = atoi(val);
 		else if (is("SERVER")) k.server = atoi(val);
+		else if (is("SERVER_SQ8")) k.server_sq8 = atoi(val);
 		else if (is("SERVER_SLOTS")) k.server_slots = atoi(val);
 		else if (is("SERVER_IDLE_US")) k.server_idle_us = atoi(val);
 		else if (is("SERVER_LIFE_MS")) k.server_life_ms = atoi(val);
 		else continue;
-		if (!is("SERVER") && !is("SERVER_SLOTS") && !is("SERVER_IDLE_US") && !is("SERVER_LIFE_MS") && !is("SPLIT_UPLOAD") && !is("HELPER") && !is("SPEC") && !is("NBL")) k.names_a_kernel = true;
+		if (!is("SERVER") && !is("SERVER_SQ8") && !is("SERVER_SLOTS") && !is("SERVER_IDLE_US") && !is("SERVER_LIFE_MS") && !is("SPLIT_UPLOAD") && !is("HELPER") && !is("SPEC") && !is("NBL")) k.names_a_kernel = true;
 	}
 	return k;
 }

@@ -739,6 +739,13 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 			}
 		}
 	}
+	// the query's corrective offset and normCoef, read ONCE: in the resident form they sit in the mailbox (pinned host memory) like the codes,
+	// and a read per distance batch would be a trip across PCIe per hop
+	float sq_qcorr = 0.f, sq_qnorm = 1.f;
+	if constexpr (kSq8) {
+		sq_qcorr = p.qcorr[qi];
+		sq_qnorm = p.qnorm[qi];
+	}
 	if constexpr (NB > 0 && !kSq8) {
 		const float4* qp = reinterpret_cast<const float4*>(q);
 		for (int i = lane; i < NB * 16; i += 64) q_s[i] = qp[i];
@@ -747,9 +754,9 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 	int team_links = 0;   // (team searches) 1 while the batches are a hop's fresh neighbours, see HnswTeamBox::links
 	auto distances = [&](const uint32_t* ids, int cnt, float* dists) {
 		if constexpr (kSq8 && NB > 0) {
-			batch_distances_sq8_fixed<kMetric, NB>(p, sq_q, sq_qq, p.qcorr[qi], p.qnorm[qi], ids, cnt, dists, lane);
+			batch_distances_sq8_fixed<kMetric, NB>(p, sq_q, sq_qq, sq_qcorr, sq_qnorm, ids, cnt, dists, lane);
 		} else if constexpr (kSq8) {
-			batch_distances_sq8<kMetric>(p, p.qcodes + size_t(qi) * p.dim, p.qcorr[qi], p.qnorm[qi], ids, cnt, dists, lane);
+			batch_distances_sq8<kMetric>(p, p.qcodes + size_t(qi) * p.dim, sq_qcorr, sq_qnorm, ids, cnt, dists, lane);
 		} else if constexpr (NB > 0 && kTeam > 1) {
 			box->ids = ids;
 			box->dists = dists;

@@ -15,10 +15,70 @@ namespace rxgpu {
 //     poll in device memory.  No wait in here depends on another kernel or on the host making progress;
 //   * the next generation is an ordinary launch on the SAME stream: it starts when this one is gone, so a slot has one server at a time and
 //     a request posted while a generation leaves is simply the next one's first.
+// Two kernels speak this protocol: hnsw_server_kernel (float rows, a team of four wavefronts a slot) and hnsw_server_sq8_kernel (SQ8 codes,
+// one wavefront a slot).
+
+// Lane 0 of a slot waits for the slot's next request or for the kernel's end and leaves the verdict in s_cmd: [0] 1 = a request, 2 = leave;
+// [1] its sequence number; [2] k; [3] ef.  Shared by the two resident kernels below: the protocol is one.
+__device__ __forceinline__ void server_await(const HnswServer& sv, uint32_t slot, uint32_t last, unsigned long long t_start, uint32_t* s_cmd) {
+	uint32_t cmd = 0u, seq = last, quiet = 0u;
+	while (!cmd) {
+		seq = __hip_atomic_load(&sv.post[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		if (seq != last) {
+			cmd = 1u;
+			break;
+		}
+		const unsigned long long now = wall_clock64();
+		if (slot == 0u) {
+			const unsigned long long seen = __hip_atomic_load(&sv.dev[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			const unsigned long long since = seen > t_start ? seen : t_start;
+			if (__hip_atomic_load(sv.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u || now - t_start > sv.life_ticks ||
+				(now > since && now - since > sv.idle_ticks)) {
+				__hip_atomic_store(sv.leaving, sv.generation, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+				__hip_atomic_store(&sv.dev[0], 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+				cmd = 2u;
+			}
+		} else if (__hip_atomic_load(&sv.dev[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull || now - t_start > 2ull * sv.life_ticks) {
+			cmd = 2u;   // (twice the lifetime: workgroup 0 never came to decide — e.g. it was not resident yet; the kernel ends anyway)
+		}
+		// every look is a read across PCIe: close together while requests keep coming, ~7 us apart once the slot has been quiet for a while
+		if (!cmd) {
+			if (++quiet < 64u) {
+				__builtin_amdgcn_s_sleep(24);
+			} else {
+				__builtin_amdgcn_s_sleep(127);
+				__builtin_amdgcn_s_sleep(127);
+			}
+		}
+	}
+	if (cmd == 1u) {
+		s_cmd[2] = __hip_atomic_load(&sv.req[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		s_cmd[3] = __hip_atomic_load(&sv.req[2 * slot + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+		(void)__hip_atomic_fetch_max(&sv.dev[1], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	s_cmd[1] = seq;
+	s_cmd[0] = cmd;
+}
+// the parameters of the search a slot runs for the request in s_cmd: k, ef, the slot's result arrays (its query: the caller)
+__device__ __forceinline__ HnswParams server_slot_params(const HnswParams& p, const HnswServer& sv, uint32_t slot, const uint32_t* s_cmd) {
+	HnswParams pl = p;
+	pl.k = s_cmd[2];
+	pl.ef = s_cmd[3];
+	pl.out_dist = p.out_dist + size_t(slot) * sv.kcap;
+	pl.out_row = p.out_row + size_t(slot) * sv.kcap;
+	pl.out_count = p.out_count + slot;
+	return pl;
+}
+// lane 0, behind the release fence over the slot's result stores: the answer
+__device__ __forceinline__ void server_answer(const HnswServer& sv, uint32_t slot, uint32_t seq, unsigned long long t_search) {
+	__hip_atomic_store(&sv.took[slot], uint32_t(wall_clock64() - t_search), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	__hip_atomic_store(&sv.done[slot], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 template <int kMetric, int NB, int kSorted, bool kDel, int kTeam>
 __global__ __launch_bounds__(64 * kTeam) void hnsw_server_kernel(HnswParams p, HnswServer sv) {
 	__shared__ HnswTeamBox box;
-	__shared__ uint32_t s_cmd[4];   // [0] 1 = a request, 2 = leave; [1] its sequence number; [2] k; [3] ef
+	__shared__ uint32_t s_cmd[4];
 	const uint32_t slot = blockIdx.x;
 	if (threadIdx.x >= 64) {   // the other wavefronts of the team: distance batches of every search until the workgroup leaves
 		for (;;) {
@@ -31,66 +91,53 @@ __global__ __launch_bounds__(64 * kTeam) void hnsw_server_kernel(HnswParams p, H
 	const unsigned long long t_start = wall_clock64();
 	uint32_t last = __hip_atomic_load(&sv.done[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // the host keeps it across generations
 	for (;;) {
-		if (lane == 0) {
-			uint32_t cmd = 0u, seq = last, quiet = 0u;
-			while (!cmd) {
-				seq = __hip_atomic_load(&sv.post[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-				if (seq != last) {
-					cmd = 1u;
-					break;
-				}
-				const unsigned long long now = wall_clock64();
-				if (slot == 0u) {
-					const unsigned long long seen = __hip_atomic_load(&sv.dev[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-					const unsigned long long since = seen > t_start ? seen : t_start;
-					if (__hip_atomic_load(sv.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u || now - t_start > sv.life_ticks ||
-						(now > since && now - since > sv.idle_ticks)) {
-						__hip_atomic_store(sv.leaving, sv.generation, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-						__hip_atomic_store(&sv.dev[0], 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-						cmd = 2u;
-					}
-				} else if (__hip_atomic_load(&sv.dev[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0ull || now - t_start > 2ull * sv.life_ticks) {
-					cmd = 2u;   // (twice the lifetime: workgroup 0 never came to decide — e.g. it was not resident yet; the kernel ends anyway)
-				}
-				// every look is a read across PCIe: close together while requests keep coming, ~7 us apart once the slot has been quiet for a while
-				if (!cmd) {
-					if (++quiet < 64u) {
-						__builtin_amdgcn_s_sleep(24);
-					} else {
-						__builtin_amdgcn_s_sleep(127);
-						__builtin_amdgcn_s_sleep(127);
-					}
-				}
-			}
-			if (cmd == 1u) {
-				s_cmd[2] = __hip_atomic_load(&sv.req[2 * slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-				s_cmd[3] = __hip_atomic_load(&sv.req[2 * slot + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-				(void)__hip_atomic_fetch_max(&sv.dev[1], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
-			s_cmd[1] = seq;
-			s_cmd[0] = cmd;
-		}
+		if (lane == 0) server_await(sv, slot, last, t_start, s_cmd);
 		__syncthreads();
 		if (s_cmd[0] == 2u) return;
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // the query the host wrote in front of the sequence number, not a cached line of the slot's last one
 		const uint32_t seq = s_cmd[1];
 		const unsigned long long t_search = wall_clock64();
-		HnswParams pl = p;
-		pl.k = s_cmd[2];
-		pl.ef = s_cmd[3];
+		HnswParams pl = server_slot_params(p, sv, slot, s_cmd);
 		pl.queries = p.queries + size_t(slot) * p.dim;
-		pl.out_dist = p.out_dist + size_t(slot) * sv.kcap;
-		pl.out_row = p.out_row + size_t(slot) * sv.kcap;
-		pl.out_count = p.out_count + slot;
 		hnsw_search_one<kMetric, false, NB, true, false, kSorted, kDel, kTeam>(pl, slot, 0u, &box);
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "");   // this wavefront's result stores are out before the sequence number
 		if (lane == 0) {
-			__hip_atomic_store(&sv.took[slot], uint32_t(wall_clock64() - t_search), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-			__hip_atomic_store(&sv.done[slot], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+			server_answer(sv, slot, seq, t_search);
 			box.cnt = -1;
 		}
 		last = seq;
 		__syncthreads();   // the team leaves hnsw_team_serve
+	}
+}
+
+// The same mailbox over the SQ8 codes of a quantised graph.  A slot is ONE wavefront (the team form serves float rows only: a 768-byte code row
+// is a quarter of a float row's gather, and nobody has measured four wavefronts over it).  The slot's query is dim code bytes (padded to 16), one
+// corrective offset and one normCoef; hnsw_search_one pulls all three into registers in its prologue and never looks at the mailbox again.
+// Class 0 keeps the visited set in LDS (kLatency: the hash set behind the heaps, 2^14 words — what a launch of that ef gets in HBM).
+template <int kMetric, int NB, int kSorted, bool kDel>
+__global__ __launch_bounds__(64) void hnsw_server_sq8_kernel(HnswParams p, HnswServer sv) {
+	static_assert(NB > 0, "the generic SQ8 form re-reads the query codes at every distance batch: not over a mailbox");
+	__shared__ uint32_t s_cmd[4];
+	const uint32_t slot = blockIdx.x;
+	const int lane = threadIdx.x;
+	const unsigned long long t_start = wall_clock64();
+	uint32_t last = __hip_atomic_load(&sv.done[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+	for (;;) {
+		if (lane == 0) server_await(sv, slot, last, t_start, s_cmd);
+		__syncthreads();
+		if (s_cmd[0] == 2u) return;
+		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+		const uint32_t seq = s_cmd[1];
+		const unsigned long long t_search = wall_clock64();
+		HnswParams pl = server_slot_params(p, sv, slot, s_cmd);
+		pl.qcodes = p.qcodes + size_t(slot) * hnsw_server_sq8_record(p.dim);
+		pl.qcorr = p.qcorr + slot;
+		pl.qnorm = p.qnorm + slot;
+		hnsw_search_one<kMetric, false, NB, true, true, kSorted, kDel, 1>(pl, slot, 0u);
+		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+		if (lane == 0) server_answer(sv, slot, seq, t_search);
+		last = seq;
+		__syncthreads();   // s_cmd is read by every lane before lane 0 writes the next verdict
 	}
 }
 
@@ -141,12 +188,57 @@ static void launch_hnsw_server_dim(int metric, const HnswParams& p, const HnswSe
 		wide ? launch_hnsw_server_nb<NB, 4, true>(metric, p, sv, slots, s) : launch_hnsw_server_nb<NB, 2, true>(metric, p, sv, slots, s);
 	}
 }
-// Two classes of resident kernel (an index may have one of each, serving a mailbox of its own): ef <= 128 (96 with deleted nodes) — lists of
-// two entries a lane, the visited set in LDS — and ef <= 256 (224) — four entries a lane, the visited hash set of a slot in HBM
-// (p.visited: [slots][visited_words], zeroed by the search itself).  p.ef_cap says which: 128 or 256.
+// The mailbox over codes: one wavefront a slot, heaps (a search that starts over) and — class 0 — the visited set in dynamic LDS.
+template <int NB, int kSorted, bool kDel>
+static void launch_hnsw_server_sq8_nb(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
+	const size_t lds = (size_t(p.ef_cap) + p.lds_cand_cap) * 8 + (p.vis_lds_log2 ? (size_t(4) << p.vis_lds_log2) : 0);
+#define RX_SERVER(M)                                                                                                                       \
+	do {                                                                                                                                   \
+		static std::atomic<uint64_t> raised{0};                                                                                            \
+		if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_sq8_kernel<M, NB, kSorted, kDel>), kServerLdsLimit); \
+		hipLaunchKernelGGL((hnsw_server_sq8_kernel<M, NB, kSorted, kDel>), dim3(slots), dim3(64), lds, s, p, sv);                           \
+	} while (0)
+	switch (metric) {
+		case kL2: RX_SERVER(kL2); break;
+		case kIP: RX_SERVER(kIP); break;
+		default: RX_SERVER(kCos); break;
+	}
+#undef RX_SERVER
+}
+template <int NB, bool kDel>
+static void launch_hnsw_server_sq8_dim(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
+	p.ef_cap > 128u ? launch_hnsw_server_sq8_nb<NB, 4, kDel>(metric, p, sv, slots, s) : launch_hnsw_server_sq8_nb<NB, 2, kDel>(metric, p, sv, slots, s);
+}
+// the embedding sizes with a fixed-dimension SQ8 distance batch (launch_hnsw_sq8_sorted, hnsw_search.hip): six for a bare graph, two with deleted nodes
+bool hnsw_server_sq8_serves(uint32_t dim, bool bare) {
+	return dim == 128u || dim == 768u || (bare && (dim == 384u || dim == 512u || dim == 1024u || dim == 1536u));
+}
+static bool launch_hnsw_server_sq8(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
+	if (!hnsw_server_sq8_serves(p.dim, p.bare != 0) || !p.corr || !p.qcodes || !p.qcorr || !p.qnorm) return false;
+	if (p.bare) {
+		switch (p.dim) {
+			case 128: launch_hnsw_server_sq8_dim<2, false>(metric, p, sv, slots, s); return true;
+			case 384: launch_hnsw_server_sq8_dim<6, false>(metric, p, sv, slots, s); return true;
+			case 512: launch_hnsw_server_sq8_dim<8, false>(metric, p, sv, slots, s); return true;
+			case 768: launch_hnsw_server_sq8_dim<12, false>(metric, p, sv, slots, s); return true;
+			case 1024: launch_hnsw_server_sq8_dim<16, false>(metric, p, sv, slots, s); return true;
+			default: launch_hnsw_server_sq8_dim<24, false>(metric, p, sv, slots, s); return true;
+		}
+	}
+	if (p.dim == 128u) {
+		launch_hnsw_server_sq8_dim<2, true>(metric, p, sv, slots, s);
+	} else {
+		launch_hnsw_server_sq8_dim<12, true>(metric, p, sv, slots, s);
+	}
+	return true;
+}
+// Two classes of resident kernel (an index may have one of each per row format, serving a mailbox of its own): ef <= 128 (96 with deleted
+// nodes) — lists of two entries a lane, the visited set in LDS — and ef <= 256 (224) — four entries a lane, the visited hash set of a slot in
+// HBM (p.visited: [slots][visited_words], zeroed by the search itself).  p.ef_cap says which: 128 or 256.  p.codes: the mailbox over SQ8 codes.
 bool launch_hnsw_server(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	if (p.codes || !p.sorted || hnsw_server_lds_bytes(p) > kServerLdsLimit) return false;
+	if (!p.sorted || hnsw_server_lds_bytes(p) > kServerLdsLimit) return false;
 	if (p.ef_cap <= 128u ? (!p.vis_lds || p.vis_lds_log2 > 14) : (p.vis_lds || p.vis_lds_log2 || !p.visited || p.vis_hash_log2 < 14)) return false;
+	if (p.codes) return launch_hnsw_server_sq8(metric, p, sv, slots, s);
 	switch (p.dim) {
 		case 128: launch_hnsw_server_dim<2>(metric, p, sv, slots, s); return true;
 		case 512: launch_hnsw_server_dim<8>(metric, p, sv, slots, s); return true;

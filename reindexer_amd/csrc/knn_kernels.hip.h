@@ -209,6 +209,9 @@ struct HnswServer {
 	uint32_t kcap;             // result entries per slot
 	unsigned long long idle_ticks, life_ticks;   // wall_clock64 ticks (100 MHz): leave after so long without a request / so long after the start
 };
+// the mailbox over SQ8 codes (hnsw_server_sq8_kernel): bytes of a slot's query record — the codes, padded so that every record starts on a
+// 16-byte boundary (the search reads them with 16-byte loads); the corrective offsets and normCoefs are [slots] arrays of their own
+__host__ __device__ inline uint32_t hnsw_server_sq8_record(uint32_t dim) { return (dim + 15u) & ~15u; }
 
 // In-place graph update (rxgpu_hnsw_patch_graph): one workgroup per touched node scatters its staged lists into the resident arrays
 struct HnswPatch {

@@ -67,17 +67,20 @@ void fill_sq8_params(const rxgpu_index* h, rxgpu::HnswParams& p) {
 	p.alpha2 = h->sq8_alpha2;
 }
 
-// 1: the index's resident kernel answered; 0: it does not take this query (the caller launches); otherwise an error code
-int hnsw_try_server(rxgpu_index* h, const HnswKnobs& knobs, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
-					uint32_t* out_count) {
+// 1: the index's resident kernel answered; 0: it does not take this query (the caller launches); 2: it ran the search and the search came back
+// flagged (the launches' re-run tiers answer it); otherwise an error code.  qcorr != nullptr: `query` are SQ8 codes, through the mailbox over codes.
+int hnsw_try_server(rxgpu_index* h, const HnswKnobs& knobs, const void* query, const float* qcorr, const float* qnorm, uint32_t k, uint32_t ef,
+					float* out_dist, uint32_t* out_row, uint32_t* out_count) {
 	if (knobs.server == 0 || knobs.names_a_kernel) return 0;
+	if (qcorr && knobs.server_sq8 == 0) return 0;
 	rxgpu::HnswServerConfig cfg;
 	if (knobs.server_slots > 0) cfg.slots = uint32_t(knobs.server_slots);
 	if (knobs.server_idle_us > 0) cfg.idle_us = uint32_t(knobs.server_idle_us);
 	if (knobs.server_life_ms > 0) cfg.life_ms = uint32_t(knobs.server_life_ms);
 	cfg.spec = knobs.spec > 0;
 	cfg.nbl = knobs.nbl > 0;
-	return rxgpu::hnsw_server_search(h, cfg, query, k, ef, out_dist, out_row, out_count);
+	if (qcorr) return rxgpu::hnsw_server_search_sq8(h, cfg, static_cast<const uint8_t*>(query), *qcorr, *qnorm, k, ef, out_dist, out_row, out_count);
+	return rxgpu::hnsw_server_search(h, cfg, static_cast<const float*>(query), k, ef, out_dist, out_row, out_count);
 }
 
 // Helper workgroups beside a large batch (hnsw_helper_kernel, second stream): a search that overflows its LDS heap area is queued and
@@ -413,8 +416,8 @@ int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, co
 	RX_CHECK(ef <= uint32_t(rxgpu::kHnswMaxEf), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn: ef must be <= 4096 on the GPU engine");
 	const HnswKnobs knobs = rxgpu::read_hnsw_knobs();
 	// 2. ONE query, the planner's call: through the mailbox of the index's resident kernel (rxgpu_hnsw_server.hip) — no launch on the path
-	if (nq == 1 && to_host && !sq8 && try_server) {
-		const int served = hnsw_try_server(h, knobs, static_cast<const float*>(queries), k, ef, out_dist, out_row, out_count);
+	if (nq == 1 && to_host && try_server) {
+		const int served = hnsw_try_server(h, knobs, queries, qcorr, qnorm, k, ef, out_dist, out_row, out_count);
 		if (served == 1) return RXGPU_OK;
 		if (served != 0 && served != 2) return served;   // (2: the search ran there and came back flagged — the tiers below answer it)
 	}
@@ -838,6 +841,7 @@ int rxgpu_hnsw_upload_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, c
 	if (n == 0) return RXGPU_OK;
 	RX_CHECK(codes && corr, RXGPU_ERR_PARAMS, "rxgpu_hnsw_upload_sq8_rows: null argument");
 	RX_CHECK(first_row <= h->sq8_n && first_row + n <= h->count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_upload_sq8_rows: rows follow the table without a hole and stay below count");
+	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel over the codes reads what changes (or moves) here
 	DeviceGuard dg(h->device);
 	const uint64_t cap = std::max<uint64_t>(h->capacity, h->count);
 	if (h->sq8_cap < first_row + n) {   // first rows, or the index was reserved larger since: a new table, the old rows copied over
@@ -872,6 +876,7 @@ int rxgpu_hnsw_attach_sq8(rxgpu_index* h, const uint8_t* codes, const float* cor
 	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_hnsw_attach_sq8: not available on a sharded index");
 	RX_CHECK(count == h->count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_sq8: one code row per index row");
 	RX_CHECK(count == 0 || (codes && corr), RXGPU_ERR_PARAMS, "rxgpu_hnsw_attach_sq8: null argument");
+	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel over the codes reads the tables freed below
 	DeviceGuard dg(h->device);
 	RX_HIP(rxgpu::device_wait_all(h->device));
 	if (h->d_codes) (void)hipFree(h->d_codes);
@@ -897,23 +902,38 @@ int rxgpu_hnsw_attach_sq8(rxgpu_index* h, const uint8_t* codes, const float* cor
 
 /* ------------------------------------------------------------------------------------------------ SearchKnn */
 
-int rxgpu_hnsw_search_knn_posted(rxgpu_index* h, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-								 int32_t* served) {
-	RX_CHECK(h && query && out_dist && out_row && out_count && served, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_posted: null argument");
+namespace {
+// one body for both row formats (qcorr == nullptr: float rows), behind the callers' argument checks
+int hnsw_posted_impl(rxgpu_index* h, const void* query, const float* qcorr, const float* qnorm, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
+					 uint32_t* out_count, int32_t* served) {
 	*served = 0;
 	if (h->shard_set || h->count == 0 || k == 0 || !h->graph_attached || h->graph_n != h->count) return RXGPU_OK;   // the launching call says what is wrong
+	if (qcorr && (!h->d_codes || h->sq8_n != h->count)) return RXGPU_OK;
 	default_k_ef(h, k, ef);
-	const int rc = hnsw_try_server(h, rxgpu::read_hnsw_knobs(), query, k, ef, out_dist, out_row, out_count);
+	const int rc = hnsw_try_server(h, rxgpu::read_hnsw_knobs(), query, qcorr, qnorm, k, ef, out_dist, out_row, out_count);
 	if (rc == 1) {
 		*served = 1;
 		return RXGPU_OK;
 	}
 	if (rc == 2) {   // the mailbox took it and the search needs the re-run tiers: answered here by the launches, not offered to the mailbox again
-		const int r2 = hnsw_search_impl(h, query, nullptr, nullptr, 1, k, ef, out_dist, out_row, out_count, nullptr, false);
+		const int r2 = hnsw_search_impl(h, query, qcorr, qnorm, 1, k, ef, out_dist, out_row, out_count, nullptr, false);
 		if (r2 == RXGPU_OK) *served = 1;
 		return r2;
 	}
 	return rc;
+}
+}  // namespace
+
+int rxgpu_hnsw_search_knn_posted(rxgpu_index* h, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count,
+								 int32_t* served) {
+	RX_CHECK(h && query && out_dist && out_row && out_count && served, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_posted: null argument");
+	return hnsw_posted_impl(h, query, nullptr, nullptr, k, ef, out_dist, out_row, out_count, served);
+}
+
+int rxgpu_hnsw_search_knn_sq8_posted(rxgpu_index* h, const uint8_t* query_codes, float query_corr, float query_norm_coef, uint32_t k, uint32_t ef,
+									 float* out_dist, uint32_t* out_row, uint32_t* out_count, int32_t* served) {
+	RX_CHECK(h && query_codes && out_dist && out_row && out_count && served, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_sq8_posted: null argument");
+	return hnsw_posted_impl(h, query_codes, &query_corr, &query_norm_coef, k, ef, out_dist, out_row, out_count, served);
 }
 
 int rxgpu_hnsw_server_times(rxgpu_index* h, uint64_t* device_us, uint64_t* caller_us) {

@@ -8,10 +8,14 @@
 // Measured at the end of round 6 (profiles/rd6zz_bench_full.json): T = 16 / 64 / 256 -> 21.9 k / 82.4 k / 175 k q/s over 10M x 768, every search
 // 0.67 - 0.69 ms on the device whatever T; the reference's 16 cores 19.1 k q/s.
 //
-// What is NOT served here (the caller takes the ordinary launches): batches, SQ8 graphs, ef above 256 (224 with deleted nodes; an index has a
-// mailbox per list size: ef <= 128 / 96 and above), embedding sizes without a fixed-dimension distance batch, a profiled index, every RXGPU_HNSW_* A/B hook that names a
-// kernel form.  A search that comes back flagged (equal keys that the in-kernel restart could not settle, a visited set half full) is
-// answered by the launches' re-run tiers inside the same call.
+// A quantised (SQ8) graph has mailboxes of its own, over the codes (hnsw_server_sq8_kernel: one wavefront a slot; a slot's query is dim code
+// bytes, a corrective offset and a normCoef): hnsw_server_search_sq8.  Slot claim, wait and accounting are the float path's.
+//
+// What is NOT served here (the caller takes the ordinary launches): batches, ef above 256 (224 with deleted nodes; an index has a mailbox per
+// row format and list size: ef <= 128 / 96 and above), embedding sizes without a fixed-dimension distance batch (floats: 128, 512, 768; codes:
+// 128, 384, 512, 768, 1024, 1536, with deleted nodes 128 and 768), a profiled index, the Map over a device list, every RXGPU_HNSW_* A/B hook
+// that names a kernel form; codes also with RXGPU_HNSW_SERVER_SQ8=0.  A search that comes back flagged (equal keys that the in-kernel restart
+// could not settle, a visited set half full) is answered by the launches' re-run tiers inside the same call.
 #include <immintrin.h>
 #include <sched.h>
 #include <sys/prctl.h>
@@ -51,8 +55,10 @@ struct HnswServerState {
 	char* dev_view = nullptr;           // ... as the device addresses it
 	unsigned long long* d_words = nullptr;
 	uint32_t slots = 0, dim = 0, cls = 0, kcap = 128;
+	bool sq8 = false;                   // the mailbox over SQ8 codes
+	uint32_t qrec = 0;                  // bytes of a slot's query record: dim floats, or dim codes padded to 16
 	uint32_t* d_visited = nullptr;      // class 1: [slots][2^kServerWideVisLog2] words
-	size_t o_took = 0, o_post = 0, o_done = 0, o_req = 0, o_stop = 0, o_leaving = 0, o_count = 0, o_query = 0, o_dist = 0, o_row = 0, bytes = 0;
+	size_t o_took = 0, o_post = 0, o_done = 0, o_req = 0, o_stop = 0, o_leaving = 0, o_count = 0, o_query = 0, o_qcorr = 0, o_qnorm = 0, o_dist = 0, o_row = 0, bytes = 0;
 	std::atomic<uint64_t> free_mask[4];
 	std::vector<uint32_t> seq;          // per slot; touched by the slot's holder only
 	std::atomic<uint32_t> launched{0};  // generation number of the newest launch
@@ -82,9 +88,11 @@ static void server_free(HnswServerState* st) {
 }
 
 // (under h->mtx) the index's mailbox, made at the first single query
-static HnswServerState* server_create(rxgpu_index* h, uint32_t cls, uint32_t slots, uint32_t idle_us, uint32_t life_ms, bool spec, bool nbl) {
+static HnswServerState* server_create(rxgpu_index* h, uint32_t cls, bool sq8, uint32_t slots, uint32_t idle_us, uint32_t life_ms, bool spec, bool nbl) {
 	auto* st = new HnswServerState();
 	st->cls = cls;
+	st->sq8 = sq8;
+	st->qrec = sq8 ? hnsw_server_sq8_record(h->dim) : h->dim * 4u;
 	st->kcap = kServerEfCapOf[cls];
 	st->spec = spec;
 	st->nbl = nbl;
@@ -105,7 +113,11 @@ static HnswServerState* server_create(rxgpu_index* h, uint32_t cls, uint32_t slo
 	st->o_stop = take(4);
 	st->o_leaving = take(4);
 	st->o_count = take(size_t(slots) * 4);
-	st->o_query = take(size_t(slots) * h->dim * 4);
+	st->o_query = take(size_t(slots) * st->qrec);
+	if (sq8) {
+		st->o_qcorr = take(size_t(slots) * 4);
+		st->o_qnorm = take(size_t(slots) * 4);
+	}
 	st->o_dist = take(size_t(slots) * st->kcap * 4);
 	st->o_row = take(size_t(slots) * st->kcap * 4);
 	int least = 0, greatest = 0;
@@ -174,6 +186,15 @@ static int server_launch(rxgpu_index* h, HnswServerState* st) {
 	p.spec = st->spec ? 1u : 0u;
 	p.nbl = st->nbl ? 1u : 0u;
 	p.queries = reinterpret_cast<const float*>(st->dev_view + st->o_query);
+	if (st->sq8) {   // (as fill_sq8_params, rxgpu_hnsw_capi.hip; the uploads of the code table make this kernel leave first)
+		p.codes = h->d_codes;
+		p.corr = h->d_corr;
+		p.alpha2 = h->sq8_alpha2;
+		p.qcodes = reinterpret_cast<const uint8_t*>(st->dev_view + st->o_query);
+		p.qcorr = reinterpret_cast<const float*>(st->dev_view + st->o_qcorr);
+		p.qnorm = reinterpret_cast<const float*>(st->dev_view + st->o_qnorm);
+		p.team = 1;
+	}
 	p.out_dist = reinterpret_cast<float*>(st->dev_view + st->o_dist);
 	p.out_row = reinterpret_cast<uint32_t*>(st->dev_view + st->o_row);
 	p.out_count = reinterpret_cast<uint32_t*>(st->dev_view + st->o_count);
@@ -221,8 +242,8 @@ static void server_quiesce_state(HnswServerState* st) {
 
 void hnsw_server_quiesce(rxgpu_index* h) {
 	if (!h) return;
-	for (HnswServerState* st : h->hnsw_server) {
-		if (st) server_quiesce_state(st);
+	for (const auto& slot : h->hnsw_server) {
+		if (HnswServerState* st = slot.load(std::memory_order_acquire)) server_quiesce_state(st);
 	}
 }
 
@@ -235,15 +256,15 @@ void hnsw_servers_pause_device(int device) {
 
 void hnsw_server_destroy(rxgpu_index* h) {
 	if (!h) return;
-	for (HnswServerState*& slot : h->hnsw_server) {
-		HnswServerState* st = slot;
+	for (auto& slot : h->hnsw_server) {
+		HnswServerState* st = slot.load(std::memory_order_acquire);
 		if (!st) continue;
 		server_quiesce_state(st);
 		{
 			std::lock_guard<std::mutex> lk(g_servers_mtx);
 			g_servers.erase(st);
 		}
-		slot = nullptr;
+		slot.store(nullptr, std::memory_order_release);
 		server_free(st);
 	}
 }
@@ -251,8 +272,8 @@ void hnsw_server_destroy(rxgpu_index* h) {
 void hnsw_server_times(const rxgpu_index* h, uint64_t* device_us, uint64_t* caller_us) {
 	*device_us = *caller_us = 0;
 	if (!h) return;
-	for (const HnswServerState* st : h->hnsw_server) {
-		if (st) {
+	for (const auto& slot : h->hnsw_server) {
+		if (const HnswServerState* st = slot.load(std::memory_order_acquire)) {
 			*device_us += st->device_ticks.load() / 100u;
 			*caller_us += st->caller_us.load();
 		}
@@ -262,36 +283,39 @@ void hnsw_server_times(const rxgpu_index* h, uint64_t* device_us, uint64_t* call
 void hnsw_server_counters(const rxgpu_index* h, uint64_t* served, uint64_t* generations) {
 	*served = *generations = 0;
 	if (!h) return;
-	for (const HnswServerState* st : h->hnsw_server) {
-		if (st) {
+	for (const auto& slot : h->hnsw_server) {
+		if (const HnswServerState* st = slot.load(std::memory_order_acquire)) {
 			*served += st->served.load();
 			*generations += st->generations.load();
 		}
 	}
 }
 
+// One request through a mailbox of the index — the float one or the one over codes: the slot claim, the wait and the accounting are the same.
+// query: the slot's query record (st->qrec bytes at most: dim floats or dim codes); qcorr / qnorm: codes only.
 // 1: served (out_* hold the result), 0: not taken — the caller takes the launches, 2: taken, but the search came back flagged (equal keys the
 // in-kernel restart could not settle, a visited set half full): the launches' re-run tiers answer it; any other value: an RXGPU error code
-int hnsw_server_search(rxgpu_index* h, const HnswServerConfig& cfg, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
-					   uint32_t* out_count) {
+static int server_search(rxgpu_index* h, const HnswServerConfig& cfg, bool sq8, const void* query, size_t query_bytes, float qcorr, float qnorm, uint32_t k,
+						 uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count) {
 	if (h->profiling) return 0;
-	if (h->dim != 128 && h->dim != 512 && h->dim != 768) return 0;
 	const bool bare = h->graph_deleted == 0;
 	if (ef > (bare ? 256u : 224u) || k > ef) return 0;
 	const uint32_t cls = ef > (bare ? 128u : 96u) ? 1u : 0u;
 	if (k > kServerEfCapOf[cls]) return 0;
-	HnswServerState* st = h->hnsw_server[cls];
+	const uint32_t box = cls + (sq8 ? 2u : 0u);
+	HnswServerState* st = h->hnsw_server[box].load(std::memory_order_acquire);
 	if (!st) {
 		std::lock_guard<std::mutex> lk(h->mtx);
-		if (!h->hnsw_server[cls]) {
-			if (h->hnsw_server_failed[cls]) return 0;
-			h->hnsw_server[cls] = server_create(h, cls, std::min<uint32_t>(256u, std::max<uint32_t>(1u, cfg.slots)), cfg.idle_us, cfg.life_ms, cfg.spec, cfg.nbl);
-			if (!h->hnsw_server[cls]) {
-				h->hnsw_server_failed[cls] = true;
+		st = h->hnsw_server[box].load(std::memory_order_acquire);
+		if (!st) {
+			if (h->hnsw_server_failed[box]) return 0;
+			st = server_create(h, cls, sq8, std::min<uint32_t>(256u, std::max<uint32_t>(1u, cfg.slots)), cfg.idle_us, cfg.life_ms, cfg.spec, cfg.nbl);
+			if (!st) {
+				h->hnsw_server_failed[box] = true;
 				return 0;
 			}
+			h->hnsw_server[box].store(st, std::memory_order_release);
 		}
-		st = h->hnsw_server[cls];
 	}
 	if (st->broken.load(std::memory_order_relaxed)) return 0;
 	// a free slot (none: every workgroup is busy — this query takes a launch of its own)
@@ -314,7 +338,11 @@ int hnsw_server_search(rxgpu_index* h, const HnswServerConfig& cfg, const float*
 		int slot;
 		~Release() { st->free_mask[slot >> 6].fetch_or(1ull << (slot & 63), std::memory_order_release); }
 	} release{st, slot};
-	std::memcpy(st->host + st->o_query + size_t(slot) * st->dim * 4, query, size_t(st->dim) * 4);
+	std::memcpy(st->host + st->o_query + size_t(slot) * st->qrec, query, query_bytes);
+	if (sq8) {
+		reinterpret_cast<float*>(st->host + st->o_qcorr)[slot] = qcorr;
+		reinterpret_cast<float*>(st->host + st->o_qnorm)[slot] = qnorm;
+	}
 	st->req()[2 * slot] = k;
 	st->req()[2 * slot + 1] = ef;
 	const uint32_t seq = ++st->seq[slot];
@@ -400,6 +428,19 @@ int hnsw_server_search(rxgpu_index* h, const HnswServerConfig& cfg, const float*
 	*out_count = count;
 	st->served.fetch_add(1, std::memory_order_relaxed);
 	return 1;
+}
+
+int hnsw_server_search(rxgpu_index* h, const HnswServerConfig& cfg, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
+					   uint32_t* out_count) {
+	if (h->dim != 128 && h->dim != 512 && h->dim != 768) return 0;
+	return server_search(h, cfg, false, query, size_t(h->dim) * 4, 0.f, 1.f, k, ef, out_dist, out_row, out_count);
+}
+
+// (the generic SQ8 form re-reads the query codes at every distance batch — in a mailbox a PCIe read per hop: those embedding sizes keep the launches)
+int hnsw_server_search_sq8(rxgpu_index* h, const HnswServerConfig& cfg, const uint8_t* codes, float qcorr, float qnorm, uint32_t k, uint32_t ef, float* out_dist,
+						   uint32_t* out_row, uint32_t* out_count) {
+	if (!hnsw_server_sq8_serves(h->dim, h->graph_deleted == 0) || !h->d_codes || h->sq8_n != h->count) return 0;
+	return server_search(h, cfg, true, codes, size_t(h->dim), qcorr, qnorm, k, ef, out_dist, out_row, out_count);
 }
 
 }  // namespace rxgpu

@@ -91,6 +91,7 @@ struct HnswServer;
 // the resident search kernel (one workgroup per mailbox slot); false: this (metric, dim, list size, deleted nodes) has no resident form
 bool launch_hnsw_server(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s);
 size_t hnsw_server_lds_bytes(const HnswParams& p);
+bool hnsw_server_sq8_serves(uint32_t dim, bool bare);   // the resident kernel over SQ8 codes exists for this embedding size
 struct HnswPatch;
 void launch_hnsw_patch(const HnswPatch& p, uint32_t n_dirty, hipStream_t s);
 struct HnswStream;
@@ -489,9 +490,12 @@ struct HnswServerConfig {
 	uint32_t life_ms = 50;     // RXGPU_HNSW_SERVER_LIFE_MS: ... and after so long in any case (the next caller launches the next one)
 };
 // 1: served; 0: not served (the caller takes the launches); 2: the search ran there and came back flagged (the launching tiers answer it);
-// otherwise a (positive) RXGPU error code, which the caller returns as it is — see the .hip
+// any other value: an RXGPU error code (negative, as everywhere in the ABI), which the caller returns as it is
 int hnsw_server_search(struct ::rxgpu_index* h, const HnswServerConfig& cfg, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
 					   uint32_t* out_count);
+// the same through the index's mailbox over SQ8 codes: the query as prepareData leaves it (dim codes, corrective offset) and its normCoef
+int hnsw_server_search_sq8(struct ::rxgpu_index* h, const HnswServerConfig& cfg, const uint8_t* codes, float qcorr, float qnorm, uint32_t k, uint32_t ef,
+						   float* out_dist, uint32_t* out_row, uint32_t* out_count);
 void hnsw_server_quiesce(struct ::rxgpu_index* h);      // before the index changes: the resident kernel leaves, none is queued
 void hnsw_server_destroy(struct ::rxgpu_index* h);
 void hnsw_servers_pause_device(int device);             // before a device-wide wait: every index's resident kernel on that device leaves
@@ -563,8 +567,10 @@ struct rxgpu_index {
 	uint32_t graph_entry = 0;
 	bool graph_attached = false;
 	unsigned long long* d_hnsw_stats = nullptr;
-	rxgpu::HnswServerState* hnsw_server[2] = {nullptr, nullptr};   // the resident search kernels' mailboxes: [0] ef <= 128, [1] ef <= 256 (made at the first single query of the class)
-	bool hnsw_server_failed[2] = {false, false};
+	// the resident search kernels' mailboxes, made at the first single query of the class: [0] floats, ef <= 128; [1] floats, ef <= 256;
+	// [2] / [3] the same two over the SQ8 codes.  Written once under mtx (release), read without it (acquire).
+	std::atomic<rxgpu::HnswServerState*> hnsw_server[4] = {{nullptr}, {nullptr}, {nullptr}, {nullptr}};
+	bool hnsw_server_failed[4] = {false, false, false, false};
 	std::atomic<uint64_t> hnsw_lds_reruns{0};   // searches whose candidate heap outgrew its first LDS area and were re-run with the largest one
 	std::atomic<uint64_t> hnsw_tie_reruns{0};   // queries the sorted-list search handed to the heap kernel (equal distances met)
 

@@ -701,8 +701,14 @@ SearchResultQueue GpuHnswMap::SearchKnn(const float* queryDataRaw, std::optional
 		float normCoef = 1.f;
 		std::vector<uint8_t> qcodes;
 		const float qcorr = quantizeQuery(queryDataRaw, queryDataNorm, qcodes, normCoef);
-		if (rxgpu_hnsw_search_knn_sq8(dev_, qcodes.data(), &qcorr, &normCoef, 1, uint32_t(k), uint32_t(ef), dist.data(), row.data(), &count) !=
-			RXGPU_OK) {
+		// the index's resident search kernel over the codes first (rxgpu_hnsw_search_knn_sq8_posted), as fetchKnn does for float rows
+		int32_t served = 0;
+		if (rxgpu_hnsw_search_knn_sq8_posted(dev_, qcodes.data(), qcorr, normCoef, uint32_t(k), uint32_t(ef), dist.data(), row.data(), &count, &served) != RXGPU_OK) {
+			throwDevice("SearchKnn");
+		}
+		if (served) {
+			coPosted_.fetch_add(1, std::memory_order_relaxed);
+		} else if (rxgpu_hnsw_search_knn_sq8(dev_, qcodes.data(), &qcorr, &normCoef, 1, uint32_t(k), uint32_t(ef), dist.data(), row.data(), &count) != RXGPU_OK) {
 			throwDevice("SearchKnn");
 		}
 	} else {

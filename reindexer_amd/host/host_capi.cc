@@ -539,8 +539,9 @@ long rxhost_hnsw_search_knn(void* h, const float* q, size_t k, size_t ef, float*
 // The reference's concurrency model on the GPU Map (SURVEY 8b "Threading", 8d): T planner threads, each running its own SearchKnn with ONE
 // query over the shared Map (cf. runMultithreadQueries, gtests/tests/unit/float_vector_index.cc:258-294) — native threads, started outside the
 // timed region; a thread stops STARTING searches once deadlineS has passed.  Thread t searches queries[(t * perThread + j) % nq].
-int rxhost_hnsw_search_knn_mt(void* h, const float* queries, size_t nq, size_t dim, size_t k, size_t ef, unsigned threads, size_t perThread,
-							  double deadlineS, double* outSeconds, size_t* outDone, size_t* outBatches) {
+// norms: null, or [nq] — what SearchKnn gets as query_data_norm (a quantised cosine Map needs it)
+static int searchKnnThreads(void* h, const float* queries, const float* norms, size_t nq, size_t dim, size_t k, size_t ef, unsigned threads, size_t perThread,
+							double deadlineS, double* outSeconds, size_t* outDone, size_t* outBatches) {
 	return guarded([&] {
 		const auto* m = static_cast<const GpuHnswMap*>(h);
 		std::atomic<int> gate{0};
@@ -554,7 +555,8 @@ int rxhost_hnsw_search_knn_mt(void* h, const float* queries, size_t nq, size_t d
 			try {
 				for (size_t j = 0; j < perThread; ++j) {
 					if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > deadlineS) break;
-					auto res = m->SearchKnn(queries + ((size_t(t) * perThread + j) % nq) * dim, std::nullopt, k, ef);
+					const size_t qi = (size_t(t) * perThread + j) % nq;
+					auto res = m->SearchKnn(queries + qi * dim, norms ? std::optional<float>(norms[qi]) : std::nullopt, k, ef);
 					if (res.empty()) throw std::logic_error("empty SearchKnn result");
 					done.fetch_add(1, std::memory_order_relaxed);
 				}
@@ -575,6 +577,19 @@ int rxhost_hnsw_search_knn_mt(void* h, const float* queries, size_t nq, size_t d
 		if (outBatches) *outBatches = m->CoalescedBatches() - b0;
 		if (!error.empty()) throw std::logic_error(error);
 	});
+}
+int rxhost_hnsw_search_knn_mt(void* h, const float* queries, size_t nq, size_t dim, size_t k, size_t ef, unsigned threads, size_t perThread,
+							  double deadlineS, double* outSeconds, size_t* outDone, size_t* outBatches) {
+	return searchKnnThreads(h, queries, nullptr, nq, dim, k, ef, threads, perThread, deadlineS, outSeconds, outDone, outBatches);
+}
+// the same runner with a norm per query (hnsw_index.cc:168): the one a quantised cosine Map can be driven with
+int rxhost_hnsw_search_knn_norm_mt(void* h, const float* queries, const float* norms, size_t nq, size_t dim, size_t k, size_t ef, unsigned threads,
+								   size_t perThread, double deadlineS, double* outSeconds, size_t* outDone, size_t* outBatches) {
+	if (!norms) {
+		g_err = "rxhost_hnsw_search_knn_norm_mt: norms is null";
+		return -4;
+	}
+	return searchKnnThreads(h, queries, norms, nq, dim, k, ef, threads, perThread, deadlineS, outSeconds, outDone, outBatches);
 }
 // the quantised Map: Quantize(minQ, maxQ), SearchKnn with query_data_norm (hnsw_index.cc:168: normL2 = 1.f / NormalizeCopyVector(...))
 int rxhost_hnsw_quantize(void* h, float minQ, float maxQ) {
