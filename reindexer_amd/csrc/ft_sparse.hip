@@ -1,5 +1,5 @@
 // ft_fast merge on gfx950, the train for SPARSELY hit document ranges (Merger::Merge, cpp_src/core/ft/ft_fast/mergerimpl.h:466-566, for the
-// queries ft_sparse_eligible() in rxgpu_ft_capi.hip admits: plain terms whose every field has the same positive boost, at most kFtSparseSubs
+// queries ft_sparse_eligible() in ft_merge_plan.h admits: plain terms whose every field has the same positive boost, at most kFtSparseSubs
 // sub-terms, postings on a fraction of the documents).
 //
 // The dense train (ft_merge.hip) gives every document range of 8192 documents a 256-thread workgroup and keeps per-DOCUMENT arrays in HBM

@@ -371,6 +371,30 @@ struct LaneLock {
 	std::unique_lock<std::mutex> lk;
 	std::shared_lock<std::shared_mutex> dict;
 };
+int make_lane(rxgpu_ft_index* h, bool stream, std::unique_ptr<rxgpu_ft_index>& out) {
+	auto lane = std::make_unique<rxgpu_ft_index>();
+	lane->device = h->device;
+	lane->num_fields = h->num_fields;
+	lane->root = h;
+	if (stream) {
+		rxgpu::DeviceGuard dg(h->device);
+		if (hipStreamCreateWithFlags(&lane->stream, hipStreamNonBlocking) != hipSuccess) {
+			set_error("hipStreamCreateWithFlags failed");
+			return RXGPU_ERR_DEVICE;
+		}
+	}
+	out = std::move(lane);
+	return RXGPU_OK;
+}
+void lane_adopt_docs(rxgpu_ft_index* l, const rxgpu_ft_index* h) {
+	l->total_docs = h->total_docs;
+	l->d_words = h->d_words;
+	l->d_avg = h->d_avg;
+	l->d_removed = h->d_removed;
+	l->d_removed_bits = h->d_removed_bits;
+	l->h_avg = h->h_avg;
+}
+
 int checkout_lane(rxgpu_ft_index* h, LaneLock& out) {
 	if (h->shard_set) {   // a sharded index runs one merge at a time: every shard's handle is busy with it
 		out.lane = h;
@@ -382,14 +406,7 @@ int checkout_lane(rxgpu_ft_index* h, LaneLock& out) {
 		out.lane = l;
 		out.lk = std::move(lk);
 		out.dict = std::shared_lock<std::shared_mutex>(h->dict_mtx);
-		if (l != h) {   // what a merge reads of the statistics
-			l->total_docs = h->total_docs;
-			l->d_words = h->d_words;
-			l->d_avg = h->d_avg;
-			l->d_removed = h->d_removed;
-			l->d_removed_bits = h->d_removed_bits;
-			l->h_avg = h->h_avg;
-		}
+		if (l != h) lane_adopt_docs(l, h);
 	};
 	{
 		std::unique_lock<std::mutex> lk(h->mtx, std::try_to_lock);
@@ -411,15 +428,8 @@ int checkout_lane(rxgpu_ft_index* h, LaneLock& out) {
 		}
 	}
 	if (have.size() + 1 < std::max<uint32_t>(ft_lane_limit(), 2)) {   // (at least one lane besides the handle: a parked resident merge keeps the handle busy)
-		auto lane = std::make_unique<rxgpu_ft_index>();
-		lane->device = h->device;
-		lane->num_fields = h->num_fields;
-		lane->root = h;
-		rxgpu::DeviceGuard dg(h->device);
-		if (hipStreamCreateWithFlags(&lane->stream, hipStreamNonBlocking) != hipSuccess) {
-			set_error("hipStreamCreateWithFlags failed");
-			return RXGPU_ERR_DEVICE;
-		}
+		std::unique_ptr<rxgpu_ft_index> lane;
+		if (int rc = make_lane(h, true, lane); rc) return rc;
 		rxgpu_ft_index* l = lane.get();
 		std::unique_lock<std::mutex> lk(l->mtx);
 		{
@@ -608,26 +618,9 @@ int rxgpu_ft_set_word(rxgpu_ft_index* h, uint32_t word_id, uint64_t n, const uin
 // ---------------------------------------------------------------------------------------------------- one merge = one launch train
 namespace {
 
-struct QueryTermIn {
-	int32_t op;
-	const rxgpu_ft_term_opts* opts;
-	uint32_t sub_begin, sub_end;
-	int32_t phrase_num = -1;   // FtDslOpts::phraseNum: consecutive terms with the same number >= 0 are one phrase (selecterimpl.h:482-572)
-	int32_t distance = 1;      // FtDslOpts::distance (the phrase's terms)
-};
-// multi-word synonyms of a query (rxgpu_ft_query): their terms are terms[first_term ..] of run_merge's list
-struct SynonymsIn {
-	uint32_t nsyn = 0, first_term = 0;
-	const uint32_t* syn_term_off = nullptr;   // [nsyn + 1], relative to first_term
-	const uint32_t* part_syn_off = nullptr;   // [nparts + 1]
-	const uint32_t* part_syn = nullptr;
-	const uint8_t* suppressed = nullptr;      // per sub-term
-};
-// a query part (PhraseOrTerm, querymergedata.h:145-176): one plain term or the terms [t_begin, t_end) of one phrase
-struct QueryPartIn {
-	bool phrase;
-	uint32_t t_begin, t_end;
-};
+using rxgpu::QueryPartIn;   // the inputs of a merge: ft_merge_plan.h
+using rxgpu::QueryTermIn;
+using rxgpu::SynonymsIn;
 
 // the calculator's IDF per sub-term (bm25.h): totalDocCount = totalNumDocs - 1 ("first doc is always empty"), matchedDocCount = |postings|
 double subterm_idf(int bm25_type, uint64_t total_docs, uint64_t n) {
@@ -639,32 +632,10 @@ double subterm_idf(int bm25_type, uint64_t total_docs, uint64_t n) {
 	return f;
 }
 
-size_t align256(size_t v) { return (v + 255) & ~size_t(255); }
-
-// Carves `bytes` out of one growable device buffer; every region starts on a 256-byte boundary
-struct Carver {
-	size_t off = 0;
-	size_t take(size_t bytes) {
-		const size_t at = off;
-		off = align256(off + bytes);
-		return at;
-	}
-};
-
-// FtDslOpts of a term as the kernels want it
-int check_term_opts(const QueryTermIn& qt, uint32_t nf, const char* who, bool& same, bool& all_pos) {
-	RX_CHECK(qt.opts->field_boost && qt.opts->need_sum_rank, RXGPU_ERR_PARAMS, std::string(who) + ": null term options");
-	uint32_t nsum = 0;
-	same = true;
-	all_pos = true;
-	for (uint32_t f = 0; f < nf; ++f) {
-		nsum += qt.opts->need_sum_rank[f] ? 1 : 0;
-		same = same && qt.opts->field_boost[f] == qt.opts->field_boost[0];
-		all_pos = all_pos && qt.opts->field_boost[f] != 0.0f;
-	}
-	RX_CHECK(nsum <= 8, RXGPU_ERR_PARAMS, std::string(who) + ": more than 8 fields with needSumRank (GPU engine limit)");
-	RX_CHECK(qt.sub_end - qt.sub_begin <= 4096, RXGPU_ERR_PARAMS, std::string(who) + ": more than 4096 sub-terms in one term (GPU engine limit)");
-	return RXGPU_OK;
+// a refusal of the plan (ft_merge_plan.h) as the C-ABI reports it
+int plan_error(const rxgpu::FtPlanError& e) {
+	set_error(e.msg);
+	return e.code;
 }
 void fill_term_cfg(rxgpu::FtTermCfg& tc, const rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const QueryTermIn& qt, bool same, bool all_pos) {
 	tc.num_fields = h->num_fields;
@@ -766,7 +737,7 @@ int run_phrase(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const std::vector<
 	for (uint32_t k = 0; k < T; ++k) {
 		const QueryTermIn& qt = terms[part.t_begin + k];
 		bool same, all_pos;
-		if (int rc = check_term_opts(qt, nf, who, same, all_pos); rc) return rc;
+		if (rxgpu::FtPlanError e = rxgpu::ft_check_term_opts(qt, nf, who, same, all_pos); e) return plan_error(e);
 		fill_term_cfg(tcfg[k], h, cfg, qt, same, all_pos);
 		distance[k] = qt.distance;
 		tcfg[k].sub_begin = uint32_t(subs.size());
@@ -815,7 +786,7 @@ int run_phrase(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const std::vector<
 		h->d_phrase_a.resize(phrase_index + 1);
 		h->d_phrase_b.resize(phrase_index + 1);
 	}
-	Carver ca;
+	rxgpu::FtCarver ca;
 	const size_t o_subs = ca.take(subs.size() * sizeof(rxgpu::FtPosSubterm));
 	const size_t o_terms = ca.take(size_t(T) * sizeof(rxgpu::FtTermCfg));
 	const size_t o_dist = ca.take(size_t(T) * 4);
@@ -950,7 +921,7 @@ int finish_phrase(rxgpu_ft_index* h, const float* procs, PhraseCtx& c, PhraseRow
 	// ---- workspace + packed rows, sized by what the admission found
 	const size_t pad = rxgpu::kFtPhraseRowPad;
 	const size_t cap_entries = size_t(admitted) + (size_t(n_rows0) + 1) * pad;
-	Carver cb;
+	rxgpu::FtCarver cb;
 	const size_t o_ws = cb.take(std::max<uint64_t>(1, 2 * sum_caps) * 8);
 	const size_t o_rcnt = cb.take(size_t(n_rows0) * 4), o_rbase = cb.take(size_t(n_rows0) * 4);
 	const size_t o_odoc = cb.take(cap_entries * 4), o_orank = cb.take(cap_entries * 4), o_ofield = cb.take(cap_entries), o_opoff = cb.take(cap_entries * 4);
@@ -1064,18 +1035,45 @@ void close_resident_session(rxgpu_ft_index* h) {
 	if (tl_res_handle == h) tl_res_generation = 0;
 }
 
-// A resident merge was enqueued and nobody looked at its header yet: wait for it, check the look-back word, settle the kept-clean state.
-int finish_pending(rxgpu_ft_index* h, const char* who) {
-	if (!h->res_pending) return RXGPU_OK;
-	h->res_pending = false;
-	RX_HIP(hipStreamSynchronize(h->stream));
+// The header of a packed result (FtOutLayout): the look-back word and the count
+int check_result_header(const uint32_t* hdr, uint64_t max_merged, const char* who) {
+	RX_CHECK(hdr[1] == 0, RXGPU_ERR_DEVICE, std::string(who) + ": ordered look-back timed out on the device");
+	RX_CHECK(hdr[0] <= max_merged, RXGPU_ERR_DEVICE, std::string(who) + ": corrupt result header");
+	return RXGPU_OK;
+}
+
+// A merge is ~0.1 ms of device time: poll for its end instead of sleeping in hipStreamSynchronize (the wake-up alone is tens of
+// microseconds); anything that takes longer than a few milliseconds falls back to the blocking wait
+int wait_stream_polled(hipStream_t st) {
+	using clk = std::chrono::steady_clock;
+	const auto t_poll = clk::now();
+	hipError_t q = hipStreamQuery(st);
+	while (q == hipErrorNotReady && std::chrono::duration<double, std::micro>(clk::now() - t_poll).count() < 3000.0) q = hipStreamQuery(st);
+	if (q == hipErrorNotReady) {
+		RX_HIP(hipStreamSynchronize(st));
+	} else {
+		RX_HIP(q);
+	}
+	return RXGPU_OK;
+}
+
+// The header of a resident merge that has ended: the look-back word, the kernel time, the kept-clean state.  (Its capacity may be gone by
+// now — a later resident call resets res_cap — so the count is not checked here.)
+int settle_resident_merge(rxgpu_ft_index* h, const char* who) {
 	uint32_t hdr[4] = {0, 0, 0, 0};
 	RX_HIP(hipMemcpy(hdr, h->d_out.ptr, sizeof(hdr), hipMemcpyDeviceToHost));
 	float ms = 0.f;
 	if (h->ev_a && hipEventElapsedTime(&ms, h->ev_a, h->ev_b) == hipSuccess) h->stat_ms += ms;
-	RX_CHECK(hdr[1] == 0, RXGPU_ERR_DEVICE, std::string(who) + ": ordered look-back timed out on the device");
+	if (int rc = check_result_header(hdr, UINT64_MAX, who); rc) return rc;
 	h->clean_dirty = false;
 	return RXGPU_OK;
+}
+// A resident merge was enqueued and nobody looked at its header yet: wait for it and settle it.
+int finish_pending(rxgpu_ft_index* h, const char* who) {
+	if (!h->res_pending) return RXGPU_OK;
+	h->res_pending = false;
+	RX_HIP(hipStreamSynchronize(h->stream));
+	return settle_resident_merge(h, who);
 }
 
 // MergeDataAreas<Area>: what the caller wants back besides the merged documents (rxgpu_ft_merge_query_areas_raw)
@@ -1111,571 +1109,437 @@ std::atomic<int>* ft_train_mode() {
 	return &mode;
 }
 
-// The sparse train (ft_sparse.hip) derives every per-document fact from one bitmap per sub-term and ranks a document only once its merge slot
-// is known.  That is the reference's merge exactly when
-//   * the query is made of plain terms (no phrase rows, no multi-word synonyms, no areas) with at most kFtSparseSubs sub-terms,
-//   * every field of every merged term has the same positive boost — calcTermBitmask / calcTermScores then never look at an occurrence's
-//     fields (mergerimpl.h:252-324: allFieldsHaveSameBoost; checkFieldsRelevance is true for every occurrence),
-//   * calcTermRank cannot return 0 for any posting, so that "added by its first posting with a non-zero rank" (merger.h:161-180) is "added
-//     by its first posting": Bm25Rx / TermCount (positive, finite for avg_words > 0), every weight below 1 and every boost >= 0, which
-//     bounds each factor of phrasemergerimpl.h:51-63 from below by (1 - weight) > 0; the product's lower bound must stay a normal float.
-bool ft_sparse_eligible(const rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const std::vector<QueryTermIn>& terms, const float* procs, size_t n_subs,
-						size_t n_phrases, uint32_t nsyn, uint32_t max_areas) {
-	if (h->sh_total > 1 || n_phrases || nsyn || max_areas) return false;
-	if (n_subs == 0 || n_subs > rxgpu::kFtSparseSubs || terms.size() > 32) return false;
-	if (cfg->bm25_type == rxgpu::kFtBm25Classic) return false;   // TF = count / wordsInDoc: a field without words makes the rank NaN, which is never admitted
-	if (!(cfg->bm25_k1 >= 0.0) || !(cfg->bm25_b >= 0.0 && cfg->bm25_b <= 1.0) || !(cfg->summation_ranks_by_fields_ratio >= 0.0)) return false;
-	const uint32_t nf = h->num_fields;
-	if (h->h_avg.size() != nf) return false;
-	double floor_fields = 1.0;   // lower bound of norm * termLenBoost * positionRank over the fields
-	for (uint32_t f = 0; f < nf; ++f) {
-		if (!(h->h_avg[f] > 0.0f) || !std::isfinite(h->h_avg[f])) return false;
-		const double w[3] = {cfg->bm25_weight[f], cfg->term_len_weight[f], cfg->position_weight[f]};
-		const double b[3] = {cfg->bm25_boost[f], cfg->term_len_boost[f], cfg->position_boost[f]};
-		double fl = 1.0;
-		for (int k = 0; k < 3; ++k) {
-			if (!(w[k] >= 0.0 && w[k] <= 0.999) || !(b[k] >= 0.0) || !std::isfinite(b[k])) return false;
-			fl *= 1.0 - w[k];
-		}
-		floor_fields = std::min(floor_fields, fl);
-	}
-	for (const QueryTermIn& qt : terms) {
-		if (qt.phrase_num >= 0) return false;
-		if (qt.op == 3) continue;   // a NOT term only clears mask bits, whatever its options (excludeTermFromBitmask, mergerimpl.h:276-287)
-		const float fb = qt.opts->field_boost[0];
-		if (!(fb > 0.0f) || !std::isfinite(fb)) return false;
-		for (uint32_t f = 1; f < nf; ++f) {
-			if (qt.opts->field_boost[f] != fb) return false;
-		}
-		if (!(qt.opts->boost > 0.0f) || !std::isfinite(qt.opts->boost) || !(qt.opts->term_len_boost >= 0.0f) || !std::isfinite(qt.opts->term_len_boost)) return false;
-		for (uint32_t si = qt.sub_begin; si < qt.sub_end; ++si) {
-			if (!(procs[si] > 0.0f) || !std::isfinite(procs[si])) return false;
-			if (double(fb) * floor_fields * double(qt.opts->boost) * double(procs[si]) < 1e-30) return false;
-		}
-	}
-	return true;
-}
+// Where a merge's documents go: the caller's lists (terms_counter may be null for a Simple() query; all null: a resident merge)
+struct MergeOut {
+	uint32_t* doc = nullptr;
+	float* proc = nullptr;
+	uint8_t* field = nullptr;
+	uint16_t* terms_counter = nullptr;
+	uint64_t cap = 0;
+	uint64_t* n = nullptr;
+	int32_t* preselected = nullptr;   // may be null
+	bool complete(bool simple) const { return doc && proc && field && (simple || terms_counter); }
+};
+// One query as the merge functions take it
+struct MergeQuery {
+	const rxgpu_ft_config* cfg = nullptr;
+	bool simple = false;
+	const std::vector<QueryTermIn>* terms = nullptr;
+	const uint32_t* word_ids = nullptr;
+	const float* procs = nullptr;
+	const uint8_t* excluded = nullptr;
+	const SynonymsIn* synonyms = nullptr;
+	const AreasOut* areas = nullptr;
+	const char* who = "";
+	uint32_t max_areas() const { return areas ? areas->max_areas : 0u; }
+};
 
-// First half of a merge: the plan (sub-terms, per-part configuration, posting-side grid), the lane's scratch, the plan staged in the lane's
-// pinned buffer — FtPlan included, behind the tables it points into — and (import_now) the copy kernel that takes it to HBM.  Everything is
-// enqueued on `st`: the lane's own stream for a single merge, the batch stream when Q lanes' merges go into one train.
-int prepare_merge(rxgpu_ft_index* h, hipStream_t st, const rxgpu_ft_config* cfg, bool simple, const std::vector<QueryTermIn>& terms, const uint32_t* word_ids,
-				  const float* procs, const uint8_t* excluded, bool have_outs, uint64_t cap, const char* who, bool resident, const SynonymsIn* synonyms,
-				  MergeJob& job, bool import_now, uint32_t max_areas = 0, std::vector<PhraseRows>* shard_phrases = nullptr, int phrase_mode = 0) {
-	// shard_phrases / phrase_mode (document-range shards): 1 = run the query's phrases only and hand their rows out (nothing else is prepared);
-	// 2 = the rows come in, `admitted` holding the sum over the shards (the 2-phase estimate is a fact of the whole index).
-	using clk = std::chrono::steady_clock;
-	const auto t_begin = clk::now();
-	auto since = [](clk::time_point a) { return std::chrono::duration<double, std::micro>(clk::now() - a).count(); };
-	const uint32_t nf = h->num_fields;
-	const uint64_t N = h->total_docs;
-	const uint32_t nterms = uint32_t(terms.size());   // the query parts' terms, then the synonyms' terms
-	const uint32_t nsyn = synonyms ? synonyms->nsyn : 0;
-	const uint32_t npart_terms = nsyn ? synonyms->first_term : nterms;
-	const uint32_t nsyn_terms = nterms - npart_terms;
-	const int bm25_type = cfg->bm25_type;
-	RX_CHECK(bm25_type >= 0 && bm25_type <= 2, RXGPU_ERR_PARAMS, std::string(who) + ": bm25_type must be 0 (rx), 1 (classic) or 2 (wordCount)");
+// ---------------------------------------------------------------------------------------------------- the first half of a merge
+// Three steps: gather the facts (the one look at the dictionary), let ft_merge_plan.h decide, execute — scratch, the plan staged in the lane's
+// pinned buffer (FtPlan included, behind the tables it points into) and the copy kernel that takes it to HBM.  Everything is enqueued on one
+// stream: the lane's own for a single merge, the batch stream when Q lanes' merges go into one train.
+static_assert(rxgpu::kFtPlanBm25Classic == rxgpu::kFtBm25Classic, "ft_merge_plan.h and ft_rank.hip.h name the same calculator");
 
-	// ---- the query parts (selecterimpl.h:482-572): consecutive terms with the same phraseNum >= 0 are one phrase
-	std::vector<QueryPartIn> parts;
-	for (uint32_t t = 0; t < npart_terms;) {
-		if (terms[t].phrase_num < 0) {
-			parts.push_back({false, t, t + 1});
-			++t;
-			continue;
-		}
-		uint32_t e = t + 1;
-		while (e < npart_terms && terms[e].phrase_num == terms[t].phrase_num) ++e;
-		parts.push_back({true, t, e});
-		t = e;
-	}
-	const uint32_t nparts = uint32_t(parts.size());
-	RX_CHECK(nparts < 0x7FFF, RXGPU_ERR_PARAMS, std::string(who) + ": too many query parts");
-	RX_CHECK(!simple || (nparts == 1 && !parts[0].phrase && !nsyn), RXGPU_ERR_LOGIC, std::string(who) + ": a phrase is not a Simple() query");
-	if (nsyn) {
-		RX_CHECK(synonyms->syn_term_off && synonyms->part_syn_off && synonyms->syn_term_off[0] == 0 && synonyms->syn_term_off[nsyn] == nsyn_terms &&
-					 synonyms->part_syn_off[0] == 0,
-				 RXGPU_ERR_PARAMS, std::string(who) + ": inconsistent synonym tables");
-		for (uint32_t k = 0; k < synonyms->part_syn_off[nparts]; ++k) {
-			RX_CHECK(synonyms->part_syn && synonyms->part_syn[k] < nsyn, RXGPU_ERR_PARAMS, std::string(who) + ": synonym id out of range");
-		}
-	}
+constexpr rxgpu::FtStructSizes kStructSizes{sizeof(rxgpu::FtPosSubterm), sizeof(rxgpu::FtTermCfg), sizeof(rxgpu::FtSynMaskJob), sizeof(rxgpu::FtPlan), sizeof(uint4)};
 
-	// ---- the plan: sub-terms, per-part configuration, the posting-side grid
-	std::vector<rxgpu::FtPosSubterm> subs;
-	std::vector<rxgpu::FtTermCfg> tcfg(nparts + nsyn_terms);
-	std::vector<rxgpu::FtGridEntry> merge_grid;
-	std::vector<uint64_t> term_postings(nterms, 0);
-	uint64_t total_vids = 0, merged_postings = 0, merge_blocks = 0;
-	for (uint32_t t = 0; t < nterms; ++t) {
-		const QueryTermIn& qt = terms[t];
-		for (uint32_t si = qt.sub_begin; si < qt.sub_end; ++si) {
-			auto it = h->dict().find(word_ids[si]);
-			RX_CHECK(it != h->dict().end(), RXGPU_ERR_NOTFOUND, std::string(who) + ": unknown word id");
-			// the kernels index words_in_field[doc * fields + f] and an (N + 31) / 32-word mask by document: a list reaching past the
-			// documents rxgpu_ft_set_docs described would read and write out of bounds (set_docs may follow the words, so it is checked here)
-			RX_CHECK(it->second.n == 0 || it->second.last_doc < N, RXGPU_ERR_PARAMS,
-					 std::string(who) + ": a posting list holds a document id >= total_docs (rxgpu_ft_set_docs)");
-			term_postings[t] += word_df(it->second);   // (a document-range shard: the whole index's count — limits and gates are global facts)
-		}
-		total_vids += term_postings[t];   // totalORVids: MaxVDocs of every term, whatever its operator and inside phrases too (selecterimpl.h:546)
-	}
-	RX_CHECK(total_vids < 0xFFFFFFFFull, RXGPU_ERR_PARAMS, std::string(who) + ": more than 2^32 postings in one merge");
-	const uint64_t max_merged = std::min<uint64_t>(cfg->merge_limit, total_vids);   // Merge(): min(mergeLimit, totalORVids)
-	if (max_merged == 0) {
-		job.empty = true;
-		return RXGPU_OK;
-	}
-	RX_CHECK(resident || (cap >= max_merged && have_outs), RXGPU_ERR_OVERFLOW, std::string(who) + ": output buffers too small");
-
-	bool any_phrase = false;
-	for (const QueryPartIn& part : parts) any_phrase = any_phrase || part.phrase;
-	// the launch train: the sparse one for eligible queries whose postings lie on a fraction of the documents (or on request)
-	bool sparse = false;
-	{
-		const int mode = ft_train_mode()->load(std::memory_order_relaxed);
-		size_t n_subs_all = 0;
-		uint64_t local_postings = 0;
-		for (uint32_t t = 0; t < nterms; ++t) {
-			for (uint32_t si = terms[t].sub_begin; si < terms[t].sub_end; ++si) {
-				const rxgpu_ft_word& w = h->dict().find(word_ids[si])->second;
-				if (!word_df(w)) continue;
-				++n_subs_all;
-				local_postings += w.n;
-			}
-		}
-		if (mode != 0 && ft_sparse_eligible(h, cfg, terms, procs, n_subs_all, any_phrase ? 1 : 0, nsyn, max_areas)) {
-			sparse = mode == 1 || local_postings * 10 <= N * 3;   // dense queries keep the dense train (posting-parallel ranking, per-range workgroups)
-		}
-	}
+// room in the caller's lists, as the plan's overflow check wants it
+struct OutRoom {
+	bool have_outs;
+	uint64_t cap;
+};
+// One merge between its query and its MergeJob
+struct MergePrep {
+	std::vector<rxgpu::FtSubFact> subs;
+	rxgpu::FtMergeFacts facts;
+	rxgpu::FtMergePlan plan;
+	std::vector<PhraseRows> phrase_rows;   // per part; filled for the phrase parts
+	size_t n_phrases = 0;
 	const uint8_t* d_excluded = nullptr;
 	const uint32_t* d_excluded_bits = nullptr;
-	if (excluded && sparse) {   // the sparse train reads docsExcluded as one bit per document
+};
+struct PhraseView {   // what ft_plan_rows reads of the phrases
+	const std::vector<PhraseRows>& pr;
+	uint64_t admitted(uint32_t pi) const { return pr[pi].admitted; }
+	uint32_t n_rows(uint32_t pi) const { return uint32_t(pr[pi].rows.size()); }
+	uint64_t row_n(uint32_t pi, uint32_t r) const { return pr[pi].rows[r].n; }
+};
+
+// Step 1: the facts.  The dictionary is looked up once per sub-term; an unknown word is a fact too (the plan reports it in its turn).
+void gather_facts(const rxgpu_ft_index* h, const MergeQuery& q, bool resident, OutRoom room, MergePrep& mp) {
+	const std::vector<QueryTermIn>& terms = *q.terms;
+	const auto& dict = h->dict();
+	uint32_t n_subs = 0;   // (sized by the largest range, whatever the order of the caller's offsets)
+	for (const QueryTermIn& qt : terms) n_subs = std::max(n_subs, qt.sub_end);
+	mp.subs.assign(n_subs, rxgpu::FtSubFact{});
+	for (const QueryTermIn& qt : terms) {
+		for (uint32_t si = qt.sub_begin; si < qt.sub_end; ++si) {
+			const auto it = dict.find(q.word_ids[si]);
+			if (it == dict.end()) continue;
+			const rxgpu_ft_word& w = it->second;
+			mp.subs[si] = rxgpu::FtSubFact{w.n, word_df(w), w.last_doc, true, w.fpos != nullptr, &w};
+		}
+	}
+	rxgpu::FtMergeFacts& f = mp.facts;
+	f.terms = terms.data();
+	f.nterms = uint32_t(terms.size());
+	f.synonyms = q.synonyms;
+	f.subs = mp.subs.data();
+	f.procs = q.procs;
+	f.cfg = q.cfg;
+	f.num_fields = h->num_fields;
+	f.h_avg = h->h_avg.data();
+	f.n_avg = uint32_t(h->h_avg.size());
+	f.total_docs = h->total_docs;
+	f.sh_total = h->sh_total;
+	f.train_mode = ft_train_mode()->load(std::memory_order_relaxed);
+	f.simple = q.simple;
+	f.resident = resident;
+	f.max_areas = q.max_areas();
+	f.have_outs = room.have_outs;
+	f.cap = room.cap;
+	f.who = q.who;
+}
+
+// docsExcluded of the merge: one byte per document, or (the sparse train) one bit
+int upload_excluded(rxgpu_ft_index* h, hipStream_t st, const uint8_t* excluded, MergePrep& mp) {
+	const uint64_t N = h->total_docs;
+	if (excluded && mp.plan.sparse) {
 		std::vector<uint32_t> bits((N + 31) / 32, 0u);
 		for (uint64_t d = 0; d < N; ++d) bits[d >> 5] |= (excluded[d] ? 1u : 0u) << (d & 31);
 		if (int rc = h->d_excl.ensure(bits.size() * 4); rc) return rc;
 		RX_HIP(hipMemcpyAsync(h->d_excl.ptr, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, st));   // (pageable source: the copy is staged before the call returns)
-		d_excluded_bits = static_cast<const uint32_t*>(h->d_excl.ptr);
+		mp.d_excluded_bits = static_cast<const uint32_t*>(h->d_excl.ptr);
 	} else if (excluded) {
 		if (int rc = h->d_excl.ensure(N); rc) return rc;
 		RX_HIP(hipMemcpyAsync(h->d_excl.ptr, excluded, N, hipMemcpyHostToDevice, st));
-		d_excluded = static_cast<const uint8_t*>(h->d_excl.ptr);
+		mp.d_excluded = static_cast<const uint8_t*>(h->d_excl.ptr);
 	}
-	// ---- phrases first (Merger::init, merger.h:73-81): every PhraseMerger runs before the query parts are looked at
-	std::vector<PhraseRows> phrase_rows(nparts);
-	size_t n_phrases = 0;
-	if (phrase_mode == 2) {
-		RX_CHECK(shard_phrases && shard_phrases->size() == nparts, RXGPU_ERR_LOGIC, std::string(who) + ": phrase rows of another query");
-		phrase_rows = *shard_phrases;
-		for (uint32_t pi = 0; pi < nparts; ++pi) n_phrases += parts[pi].phrase ? 1 : 0;
-	} else {
-		for (uint32_t pi = 0; pi < nparts; ++pi) {
-			if (!parts[pi].phrase) continue;
-			if (int rc = run_phrase(h, cfg, terms, parts[pi], word_ids, procs, d_excluded, n_phrases++, phrase_rows[pi], who, phrase_mode == 1); rc) return rc;
-		}
-		if (phrase_mode == 1) {
-			*shard_phrases = std::move(phrase_rows);
-			return RXGPU_OK;
-		}
-	}
+	return RXGPU_OK;
+}
 
-	// 2-phase gate, host half (estimateNumDocsInMerge, merger.h:239-267; mergerimpl.h:486-490)
-	uint64_t est_or = 0, est_and = UINT64_MAX;
-	uint32_t query_len = 0;
-	for (uint32_t pi = 0; pi < nparts; ++pi) {
-		const QueryPartIn& part = parts[pi];
-		query_len += part.t_end - part.t_begin;
-		const int32_t op = terms[part.t_begin].op;   // PhraseResults::Op(): its first term's
-		if (op == 3) continue;
-		uint64_t num_docs = part.phrase ? phrase_rows[pi].admitted : term_postings[part.t_begin];
-		if (nsyn) {   // + the first term of every synonym of the part (merger.h:251-255)
-			for (uint32_t k = synonyms->part_syn_off[pi]; k < synonyms->part_syn_off[pi + 1]; ++k) {
-				const uint32_t sy = synonyms->part_syn[k];
-				if (synonyms->syn_term_off[sy + 1] > synonyms->syn_term_off[sy]) num_docs += term_postings[npart_terms + synonyms->syn_term_off[sy]];
-			}
-		}
-		if (op == 2) {
-			est_and = std::min(est_and, num_docs);
-		} else {
-			est_or += num_docs;
-		}
-	}
-	const bool prescore = !simple && std::min(std::min(est_or, est_and), N) > cfg->merge_limit && N > cfg->merge_limit;
+// Facts, the plan's first half, docsExcluded: what every kind of preparation starts with.  mp.plan.empty: nothing is merged.
+int begin_merge(rxgpu_ft_index* h, hipStream_t st, const MergeQuery& q, bool resident, OutRoom room, MergePrep& mp) {
+	gather_facts(h, q, resident, room, mp);
+	if (rxgpu::FtPlanError e = rxgpu::ft_plan_volume(mp.facts, mp.plan); e) return plan_error(e);
+	if (mp.plan.empty) return RXGPU_OK;
+	return upload_excluded(h, st, q.excluded, mp);
+}
 
-	uint16_t qp = 0, last_term_qp = 0;
-	for (uint32_t pi = 0; pi < nparts; ++pi) {
-		const QueryPartIn& part = parts[pi];
-		const QueryTermIn& qt = terms[part.t_begin];
-		rxgpu::FtTermCfg& tc = tcfg[pi];
-		if (part.phrase) {
-			// the phrase as one part: its rows carry rank and field, every document counts for the masks, the pre-score adds CalcProc16
-			fill_term_cfg(tc, h, cfg, qt, true, true);
+// Phrases first (Merger::init, merger.h:73-81): every PhraseMerger runs before the query parts are looked at
+int run_query_phrases(rxgpu_ft_index* h, const MergeQuery& q, MergePrep& mp, bool first_half_only) {
+	mp.n_phrases = 0;
+	if (!mp.plan.any_phrase) return RXGPU_OK;   // (phrase_rows is read for phrase parts only)
+	mp.phrase_rows.assign(mp.plan.nparts, PhraseRows{});
+	for (uint32_t pi = 0; pi < mp.plan.nparts; ++pi) {
+		if (!mp.plan.parts[pi].phrase) continue;
+		if (int rc = run_phrase(h, q.cfg, *q.terms, mp.plan.parts[pi], q.word_ids, q.procs, mp.d_excluded, mp.n_phrases++, mp.phrase_rows[pi], q.who, first_half_only); rc) return rc;
+	}
+	return RXGPU_OK;
+}
+
+// The tables of the plan region, staged in pinned memory `hp`; device addresses are those of `base` (the lane's state buffer)
+void stage_plan_tables(rxgpu_ft_index* h, const MergeQuery& q, const MergePrep& mp, char* hp, char* base) {
+	const rxgpu::FtMergePlan& pl = mp.plan;
+	const rxgpu::FtStateLayout& L = pl.state;
+	const rxgpu_ft_config* cfg = q.cfg;
+	const std::vector<QueryTermIn>& terms = *q.terms;
+	const uint32_t nf = h->num_fields, nparts = pl.nparts;
+	std::memset(hp, 0, L.plan_bytes);
+	auto* subs = reinterpret_cast<rxgpu::FtPosSubterm*>(hp + L.plan_subs.off);
+	for (size_t i = 0; i < pl.rows.size(); ++i) {
+		const rxgpu::FtRow& r = pl.rows[i];
+		rxgpu::FtPosSubterm ft = r.phrase ? mp.phrase_rows[r.term].rows[r.src]
+										  : word_subterm(*static_cast<const rxgpu_ft_word*>(mp.subs[r.src].source), cfg->bm25_type, h->total_docs, q.procs[r.src]);
+		ft.term = r.term;
+		ft.qp = r.qp;
+		ft.prev_term_qp = r.prev_term_qp;
+		ft.ord_in_term = r.ord_in_term;
+		ft.row = r.row;
+		ft.suppressed = r.suppressed;
+		subs[i] = ft;
+	}
+	float* fc = reinterpret_cast<float*>(hp + L.plan_fc.off);
+	uint8_t* need_sum = reinterpret_cast<uint8_t*>(fc + L.cfg_floats);
+	const float* d_fc = reinterpret_cast<const float*>(base + L.plan_fc.off);
+	const uint8_t* d_need_sum = reinterpret_cast<const uint8_t*>(d_fc + L.cfg_floats);
+	stage_field_cfg(fc, cfg, nf);
+	auto* tcfg = reinterpret_cast<rxgpu::FtTermCfg*>(hp + L.plan_terms.off);
+	for (uint32_t ti = 0; ti < uint32_t(pl.terms.size()); ++ti) {   // the query parts (a phrase is one part: its first term's), then the synonyms' terms
+		const rxgpu::FtPlanTerm& pt = pl.terms[ti];
+		const QueryTermIn& qt = ti < nparts ? terms[pl.parts[ti].t_begin] : terms[pl.npart_terms + (ti - nparts)];
+		rxgpu::FtTermCfg& tc = tcfg[ti];
+		fill_term_cfg(tc, h, cfg, qt, pt.same_boost, pt.all_pos_boost);
+		tc.op = pt.op;
+		tc.sub_begin = pt.sub_begin;
+		tc.sub_end = pt.sub_end;
+		if (pt.phrase) {   // its rows carry rank and field, every document counts for the masks, the pre-score adds CalcProc16
 			tc.opts_boost = 1.0f;
 			tc.phrase = 1;
-			tc.phrase_proc16 = phrase_rows[pi].proc16;
-			tc.sub_begin = uint32_t(subs.size());
-			if (qt.op != 3) ++qp;
-			for (rxgpu::FtPosSubterm ft : phrase_rows[pi].rows) {
-				ft.term = pi;
-				ft.qp = qt.op == 3 ? 0 : qp;
-				ft.prev_term_qp = last_term_qp;
-				ft.ord_in_term = uint16_t(subs.size() - tc.sub_begin);
-				const uint32_t sub_index = uint32_t(subs.size());
-				if (qt.op != 3) {
-					ft.row = uint32_t(merge_grid.size());
-					merge_grid.push_back({uint32_t(merge_blocks), sub_index});
-					merge_blocks += rxgpu::ft_pass_blocks(ft.n);
-					merged_postings += ft.n;
-				}
-				subs.push_back(ft);
-			}
-			tc.sub_end = uint32_t(subs.size());
-			h->stat_postings += phrase_rows[pi].postings;
-			continue;
+			tc.phrase_proc16 = mp.phrase_rows[ti].proc16;
 		}
-		bool same, all_pos;
-		if (int rc = check_term_opts(qt, nf, who, same, all_pos); rc) return rc;
-		fill_term_cfg(tc, h, cfg, qt, same, all_pos);
-		tc.sub_begin = uint32_t(subs.size());
-		if (qt.op != 3) last_term_qp = ++qp;
-		for (uint32_t si = qt.sub_begin; si < qt.sub_end; ++si) {
-			const rxgpu_ft_word& w = h->dict().find(word_ids[si])->second;
-			RX_CHECK(simple || w.n == 0 || w.fpos, RXGPU_ERR_LOGIC, std::string(who) + ": the word was uploaded without positions (rxgpu_ft_set_word_positions)");
-			RX_CHECK(si == qt.sub_begin || procs[si] <= procs[si - 1], RXGPU_ERR_PARAMS,
-					 std::string(who) + ": sub-terms must be sorted by proc, descending (SortSubterms)");
-			if (!word_df(w)) continue;   // (a shard keeps the row of a word it holds no posting of: rows are numbered alike on every shard)
-			rxgpu::FtPosSubterm ft = word_subterm(w, bm25_type, N, procs[si]);
-			ft.term = pi;
-			ft.qp = qt.op == 3 ? 0 : qp;
-			ft.ord_in_term = uint16_t(si - qt.sub_begin);
-			ft.row = 0;
-			const uint32_t blocks = rxgpu::ft_pass_blocks(w.n);
-			const uint32_t sub_index = uint32_t(subs.size());
-			if (qt.op != 3) {
-				ft.row = uint32_t(merge_grid.size());
-				merge_grid.push_back({uint32_t(merge_blocks), sub_index});
-				merge_blocks += blocks;
-				merged_postings += w.n;
-			}
-			subs.push_back(ft);
-		}
-		tc.sub_end = uint32_t(subs.size());
-	}
-	// ---- the multi-word synonyms' terms behind the parts (mergerimpl.h:509-514): plain mergeTerm calls, every term takes a qp
-	const uint32_t n_part_qp = qp;
-	std::vector<rxgpu::FtSynonym> syns(nsyn);
-	for (uint32_t sy = 0; sy < nsyn; ++sy) {
-		syns[sy].term_begin = nparts + synonyms->syn_term_off[sy];
-		syns[sy].term_end = nparts + synonyms->syn_term_off[sy + 1];
-		syns[sy].nterms = synonyms->syn_term_off[sy + 1] - synonyms->syn_term_off[sy];
-		for (uint32_t k = synonyms->syn_term_off[sy]; k < synonyms->syn_term_off[sy + 1]; ++k) {
-			const QueryTermIn& qt = terms[npart_terms + k];
-			rxgpu::FtTermCfg& tc = tcfg[nparts + k];
-			bool same, all_pos;
-			if (int rc = check_term_opts(qt, nf, who, same, all_pos); rc) return rc;
-			fill_term_cfg(tc, h, cfg, qt, same, all_pos);
-			tc.op = 1;   // for ft_ranges: scored like any term (calcTermScores, mergerimpl.h:393-397), never a restriction of its own
-			tc.sub_begin = uint32_t(subs.size());
-			RX_CHECK(qp < 0x7FFE, RXGPU_ERR_PARAMS, std::string(who) + ": too many query terms");
-			++qp;
-			for (uint32_t si = qt.sub_begin; si < qt.sub_end; ++si) {
-				const rxgpu_ft_word& w = h->dict().find(word_ids[si])->second;
-				RX_CHECK(w.n == 0 || w.fpos, RXGPU_ERR_LOGIC, std::string(who) + ": the word was uploaded without positions (rxgpu_ft_set_word_positions)");
-				RX_CHECK(si == qt.sub_begin || procs[si] <= procs[si - 1], RXGPU_ERR_PARAMS,
-						 std::string(who) + ": sub-terms must be sorted by proc, descending (SortSubterms)");
-				if (!word_df(w)) continue;
-				rxgpu::FtPosSubterm ft = word_subterm(w, bm25_type, N, procs[si]);
-				ft.term = nparts + k;
-				ft.qp = qt.op == 3 ? 0 : qp;
-				ft.ord_in_term = uint16_t(si - qt.sub_begin);
-				ft.suppressed = synonyms->suppressed && synonyms->suppressed[si] ? 1 : 0;
-				const uint32_t sub_index = uint32_t(subs.size());
-				if (qt.op != 3) {   // mergeTerm returns at once for a NOT term (mergerimpl.h:110-112)
-					ft.row = uint32_t(merge_grid.size());
-					merge_grid.push_back({uint32_t(merge_blocks), sub_index});
-					merge_blocks += rxgpu::ft_pass_blocks(w.n);
-					merged_postings += w.n;
-				}
-				subs.push_back(ft);
-			}
-			tc.sub_end = uint32_t(subs.size());
-		}
-		syns[sy].end_qp = qp;
-	}
-	// the AND parts whose term mask takes their synonyms' masks in (ft_syn_masks)
-	std::vector<rxgpu::FtSynMaskJob> syn_jobs;
-	std::vector<uint32_t> job_syns, job_part;
-	for (uint32_t pi = 0; pi < nparts && nsyn; ++pi) {
-		if (terms[parts[pi].t_begin].op != 2 || synonyms->part_syn_off[pi + 1] == synonyms->part_syn_off[pi]) continue;
-		rxgpu::FtSynMaskJob job{};
-		job.syn_begin = uint32_t(job_syns.size());
-		for (uint32_t k = synonyms->part_syn_off[pi]; k < synonyms->part_syn_off[pi + 1]; ++k) job_syns.push_back(synonyms->part_syn[k]);
-		job.syn_end = uint32_t(job_syns.size());
-		syn_jobs.push_back(job);
-		job_part.push_back(pi);
-	}
-	RX_CHECK(merge_blocks * rxgpu::kFtBlockPostings < 0xFFFFFFFFull, RXGPU_ERR_PARAMS,
-			 std::string(who) + ": more than 2^32 (padded) postings in one merge");
-	const uint32_t n_rows = uint32_t(merge_grid.size());
-	RX_CHECK(n_rows < 0xFFFFu, RXGPU_ERR_PARAMS, std::string(who) + ": more than 65534 merged sub-terms in one query (GPU engine limit)");
-	const uint64_t nwords = (N + 31) / 32;
-	const size_t M = size_t(max_merged);
-
-	if (max_areas) {   // MergeDataAreas<Area>: plain terms only (a phrase's areas come out of the PhraseMerger's position chains, phrasemerger.h:147-181)
-		RX_CHECK(!resident && !nsyn, RXGPU_ERR_LOGIC, std::string(who) + ": areas are built for queries of plain terms (no multi-word synonyms, no resident form)");
-		for (const QueryPartIn& part : parts) RX_CHECK(!part.phrase, RXGPU_ERR_LOGIC, std::string(who) + ": a phrase's areas stay on the CPU merger");
-		for (const rxgpu::FtPosSubterm& ft : subs) {
-			RX_CHECK(ft.n == 0 || ft.fpos, RXGPU_ERR_LOGIC, std::string(who) + ": areas need the words' positions (rxgpu_ft_set_word_positions)");
-		}
-	}
-	h->trace_us[0] += since(t_begin);
-	const auto t_stage = clk::now();
-	// ---- device scratch (one buffer each for the state and for the packed result)
-	Carver cv;
-	const size_t o_plan_subs = cv.take(std::max<size_t>(1, subs.size()) * sizeof(rxgpu::FtPosSubterm));
-	const uint32_t nplan_terms = nparts + nsyn_terms;
-	const size_t o_plan_terms = cv.take(size_t(nplan_terms) * sizeof(rxgpu::FtTermCfg));
-	const size_t o_plan_mgrid = cv.take(std::max<size_t>(1, merge_grid.size()) * sizeof(rxgpu::FtGridEntry));
-	const size_t cfg_floats = size_t(6) * nf + size_t(nplan_terms) * nf;
-	const size_t o_plan_fc = cv.take(cfg_floats * sizeof(float) + size_t(nplan_terms) * nf);
-	const size_t o_plan_syns = cv.take(std::max<size_t>(1, syns.size()) * sizeof(rxgpu::FtSynonym));
-	const size_t o_plan_jobs = cv.take(std::max<size_t>(1, syn_jobs.size()) * sizeof(rxgpu::FtSynMaskJob));
-	const size_t o_plan_jsyn = cv.take(std::max<size_t>(1, job_syns.size()) * 4);
-	const size_t o_plan_self = cv.take(sizeof(rxgpu::FtPlan));   // the FtPlan itself: the kernels read it from HBM (a batch of one)
-	const size_t plan_bytes = cv.off;   // everything above is uploaded in one copy
-	// (a sparse merge keeps nothing per document or per posting in HBM: ft_sparse.hip)
-	const size_t o_mask = cv.take(sparse ? 0 : nwords * 4);
-	const size_t o_synmask = cv.take(syn_jobs.size() * nwords * 4);
-	const size_t o_score = cv.take(prescore && !sparse ? nwords * 32 * 2 : 0);   // padded to whole mask words (ft_preselect_apply reads 32 scores at a time)
-	const uint32_t n_ranges = uint32_t((N + rxgpu::kFtRangeDocs - 1) / rxgpu::kFtRangeDocs);
-	const size_t o_brec = cv.take(sparse ? 0 : size_t(merged_postings) * sizeof(uint4));
-	const size_t o_boff = cv.take(size_t(n_ranges) * 4);
-	const size_t o_adders = cv.take(std::max<size_t>(1, size_t(n_rows) * n_ranges) * 4);
-	const size_t o_eidx = cv.take(sparse ? 0 : size_t(n_rows) * M * 4);
-	const size_t o_efield = cv.take(sparse ? 0 : size_t(n_rows) * M);
-	const size_t o_tdoc = cv.take(sparse ? M * 4 : 0);
-	const size_t o_tpos = cv.take(sparse ? M * 4 : 0);
-	const size_t o_tidx = cv.take(sparse ? M * std::max<size_t>(1, n_rows) * 4 : 0);
-	if (int rc = h->d_state.ensure(cv.off); rc) return rc;
-	char* base = static_cast<char*>(h->d_state.ptr);
-	// the kept-clean tables: sized by the corpus only, so that they stay where they are from merge to merge
-	Carver cc;
-	const size_t o_hist = cc.take(size_t(rxgpu::kFtHistCopies) * rxgpu::kFtHistStride * 4);   // copies of (fine + coarse)
-	const size_t o_lb_pre = cc.take(((nwords + 1023) / 1024) * 8);
-	const size_t o_bcnt = cc.take(size_t(n_ranges) * 4);
-	const size_t o_sync = cc.take(rxgpu::kFtSyncWords * 4);
-	const size_t o_dbg = cc.take(64 * 8);
-	const size_t o_lb_units = cc.take(size_t(n_ranges) * 8);
-	const size_t o_erank = cc.take(sparse ? 0 : size_t(n_rows) * M * 4);   // last: the regions before it never move when a query needs more rows
-	if (h->clean_docs != N || h->d_clean.bytes < cc.off) {
-		if (int rc = h->d_clean.ensure(cc.off); rc) return rc;
-		h->clean_docs = N;
-		h->clean_dirty = true;
-	}
-	char* cbase = static_cast<char*>(h->d_clean.ptr);
-	const size_t out_need = align256(16) + align256(M * 4) * 2 + align256(M * 2) + align256(M);
-	if (int rc = h->d_out.ensure(out_need); rc) return rc;
-	char* ob = static_cast<char*>(h->d_out.ptr);
-
-	// ---- host staging of the plan (pinned), one upload
-	if (int rc = h->ensure_pinned(std::max(plan_bytes, out_need)); rc) return rc;
-	char* hp = static_cast<char*>(h->h_pinned);
-	std::memset(hp, 0, plan_bytes);
-	float* fc = reinterpret_cast<float*>(hp + o_plan_fc);
-	const float* d_fc = reinterpret_cast<const float*>(base + o_plan_fc);
-	const uint8_t* d_need_sum = reinterpret_cast<const uint8_t*>(d_fc + cfg_floats);
-	uint8_t* need_sum = reinterpret_cast<uint8_t*>(fc + cfg_floats);
-	stage_field_cfg(fc, cfg, nf);
-	for (uint32_t pi = 0; pi < nparts; ++pi) {
-		const QueryTermIn& qt = terms[parts[pi].t_begin];
 		for (uint32_t f = 0; f < nf; ++f) {   // a phrase part: ones (its rows are ranked already; ft_ranges reads field_boost[0] > 0)
-			fc[size_t(6 + pi) * nf + f] = parts[pi].phrase ? 1.0f : qt.opts->field_boost[f];
-			need_sum[size_t(pi) * nf + f] = parts[pi].phrase ? uint8_t(0) : qt.opts->need_sum_rank[f];
+			fc[size_t(6 + ti) * nf + f] = pt.phrase ? 1.0f : qt.opts->field_boost[f];
+			need_sum[size_t(ti) * nf + f] = pt.phrase ? uint8_t(0) : qt.opts->need_sum_rank[f];
 		}
-		point_term_cfg(tcfg[pi], d_fc, d_fc + size_t(6 + pi) * nf, d_need_sum + size_t(pi) * nf, nf);
+		point_term_cfg(tc, d_fc, d_fc + size_t(6 + ti) * nf, d_need_sum + size_t(ti) * nf, nf);
 	}
-	for (uint32_t k = 0; k < nsyn_terms; ++k) {
-		const QueryTermIn& qt = terms[npart_terms + k];
-		const uint32_t ti = nparts + k;
-		for (uint32_t f = 0; f < nf; ++f) {
-			fc[size_t(6 + ti) * nf + f] = qt.opts->field_boost[f];
-			need_sum[size_t(ti) * nf + f] = qt.opts->need_sum_rank[f];
-		}
-		point_term_cfg(tcfg[ti], d_fc, d_fc + size_t(6 + ti) * nf, d_need_sum + size_t(ti) * nf, nf);
+	auto* jobs = reinterpret_cast<rxgpu::FtSynMaskJob*>(hp + L.plan_jobs.off);
+	for (size_t j = 0; j < pl.jobs.size(); ++j) {
+		jobs[j].syn_begin = pl.jobs[j].syn_begin;
+		jobs[j].syn_end = pl.jobs[j].syn_end;
+		jobs[j].out = reinterpret_cast<uint32_t*>(base + L.synmask.off) + j * pl.nwords;
+		tcfg[pl.jobs[j].part].syn_mask = jobs[j].out;
 	}
-	for (size_t j = 0; j < syn_jobs.size(); ++j) {
-		syn_jobs[j].out = reinterpret_cast<uint32_t*>(base + o_synmask) + j * nwords;
-		tcfg[job_part[j]].syn_mask = syn_jobs[j].out;
-	}
-	if (!syns.empty()) std::memcpy(hp + o_plan_syns, syns.data(), syns.size() * sizeof(rxgpu::FtSynonym));
-	if (!syn_jobs.empty()) std::memcpy(hp + o_plan_jobs, syn_jobs.data(), syn_jobs.size() * sizeof(rxgpu::FtSynMaskJob));
-	if (!job_syns.empty()) std::memcpy(hp + o_plan_jsyn, job_syns.data(), job_syns.size() * 4);
-	if (!subs.empty()) std::memcpy(hp + o_plan_subs, subs.data(), subs.size() * sizeof(rxgpu::FtPosSubterm));
-	std::memcpy(hp + o_plan_terms, tcfg.data(), tcfg.size() * sizeof(rxgpu::FtTermCfg));
-	if (!merge_grid.empty()) std::memcpy(hp + o_plan_mgrid, merge_grid.data(), merge_grid.size() * sizeof(rxgpu::FtGridEntry));
+	if (!pl.syns.empty()) std::memcpy(hp + L.plan_syns.off, pl.syns.data(), pl.syns.size() * sizeof(rxgpu::FtSynonym));
+	if (!pl.job_syns.empty()) std::memcpy(hp + L.plan_jsyn.off, pl.job_syns.data(), pl.job_syns.size() * 4);
+	if (!pl.merge_grid.empty()) std::memcpy(hp + L.plan_mgrid.off, pl.merge_grid.data(), pl.merge_grid.size() * sizeof(rxgpu::FtGridEntry));
+}
 
-	if (h->clean_dirty) {
-		RX_HIP(hipMemsetAsync(cbase, 0, h->d_clean.bytes, st));
-		h->clean_dirty = false;
-	}
-	void* hp_dev = nullptr;   // the pinned staging buffer as the device sees it
-	RX_HIP(hipHostGetDevicePointer(&hp_dev, hp, 0));
-
-	rxgpu::FtPlan& p = job.p;
+// FtPlan: the plan's numbers and the addresses of its regions in the lane's buffers
+void fill_ft_plan(const rxgpu_ft_index* h, const MergeQuery& q, const MergePrep& mp, const char* hp, void* hp_dev, rxgpu::FtPlan& p) {
+	const rxgpu::FtMergePlan& pl = mp.plan;
+	const rxgpu::FtStateLayout& L = pl.state;
+	const rxgpu::FtCleanLayout& C = pl.clean;
+	const rxgpu_ft_config* cfg = q.cfg;
+	char* base = static_cast<char*>(h->d_state.ptr);
+	char* cbase = static_cast<char*>(h->d_clean.ptr);
+	char* ob = static_cast<char*>(h->d_out.ptr);
+	const bool prescore = pl.prescore;
 	p = rxgpu::FtPlan{};
-	p.subs = reinterpret_cast<const rxgpu::FtPosSubterm*>(base + o_plan_subs);
-	p.terms = reinterpret_cast<const rxgpu::FtTermCfg*>(base + o_plan_terms);
-	p.merge_grid = reinterpret_cast<const rxgpu::FtGridEntry*>(base + o_plan_mgrid);
-	p.n_merge_entries = uint32_t(merge_grid.size());
-	p.merge_blocks = uint32_t(merge_blocks);
-	p.nterms = nplan_terms;
-	p.n_parts = nparts;
-	p.n_part_qp = n_part_qp;
-	p.syns = reinterpret_cast<const rxgpu::FtSynonym*>(base + o_plan_syns);
-	p.n_syn = nsyn;
-	p.syn_jobs = reinterpret_cast<const rxgpu::FtSynMaskJob*>(base + o_plan_jobs);
-	p.job_syns = reinterpret_cast<const uint32_t*>(base + o_plan_jsyn);
-	p.n_syn_jobs = uint32_t(syn_jobs.size());
-	p.query_len = query_len;
-	p.n_rows = n_rows;
-	p.n_subs = uint32_t(subs.size());
-	p.total_docs = N;
-	p.nwords = nwords;
-	p.max_merged = uint32_t(max_merged);
+	p.subs = reinterpret_cast<const rxgpu::FtPosSubterm*>(base + L.plan_subs.off);
+	p.terms = reinterpret_cast<const rxgpu::FtTermCfg*>(base + L.plan_terms.off);
+	p.merge_grid = reinterpret_cast<const rxgpu::FtGridEntry*>(base + L.plan_mgrid.off);
+	p.n_merge_entries = uint32_t(pl.merge_grid.size());
+	p.merge_blocks = uint32_t(pl.merge_blocks);
+	p.nterms = uint32_t(pl.terms.size());
+	p.n_parts = pl.nparts;
+	p.n_part_qp = pl.n_part_qp;
+	p.syns = reinterpret_cast<const rxgpu::FtSynonym*>(base + L.plan_syns.off);
+	p.n_syn = pl.nsyn;
+	p.syn_jobs = reinterpret_cast<const rxgpu::FtSynMaskJob*>(base + L.plan_jobs.off);
+	p.job_syns = reinterpret_cast<const uint32_t*>(base + L.plan_jsyn.off);
+	p.n_syn_jobs = uint32_t(pl.jobs.size());
+	p.query_len = pl.query_len;
+	p.n_rows = pl.n_rows;
+	p.n_subs = uint32_t(pl.rows.size());
+	p.total_docs = h->total_docs;
+	p.nwords = pl.nwords;
+	p.max_merged = uint32_t(pl.max_merged);
 	p.merge_limit = cfg->merge_limit;
-	p.simple = simple ? 1 : 0;
+	p.simple = q.simple ? 1 : 0;
 	p.prescore = prescore ? 1 : 0;
 	p.check_removed = 1;
 	p.distance_weight = float(cfg->distance_weight);
 	p.distance_boost = float(cfg->distance_boost);
 	p.full_match_boost = cfg->full_match_boost;
 	p.removed = h->d_removed;
-	p.excluded = d_excluded;
-	p.mask = reinterpret_cast<uint32_t*>(base + o_mask);
-	p.score = prescore ? reinterpret_cast<uint16_t*>(base + o_score) : nullptr;
-	p.hist = prescore ? reinterpret_cast<uint32_t*>(cbase + o_hist) : nullptr;
-	p.lookback_pre = prescore ? reinterpret_cast<unsigned long long*>(cbase + o_lb_pre) : nullptr;
-	p.b_rec = reinterpret_cast<uint4*>(base + o_brec);
-	p.bucket_off = reinterpret_cast<uint32_t*>(base + o_boff);
-	p.bucket_cnt = reinterpret_cast<uint32_t*>(cbase + o_bcnt);
-	p.adders = reinterpret_cast<uint32_t*>(base + o_adders);
-	p.n_ranges = n_ranges;
-	p.e_rank = reinterpret_cast<float*>(cbase + o_erank);
-	p.e_idx = reinterpret_cast<uint32_t*>(base + o_eidx);
-	p.e_field = reinterpret_cast<uint8_t*>(base + o_efield);
-	p.sync = reinterpret_cast<uint32_t*>(cbase + o_sync);
+	p.excluded = mp.d_excluded;
+	p.mask = reinterpret_cast<uint32_t*>(base + L.mask.off);
+	p.score = prescore ? reinterpret_cast<uint16_t*>(base + L.score.off) : nullptr;
+	p.hist = prescore ? reinterpret_cast<uint32_t*>(cbase + C.hist.off) : nullptr;
+	p.lookback_pre = prescore ? reinterpret_cast<unsigned long long*>(cbase + C.lb_pre.off) : nullptr;
+	p.b_rec = reinterpret_cast<uint4*>(base + L.brec.off);
+	p.bucket_off = reinterpret_cast<uint32_t*>(base + L.boff.off);
+	p.bucket_cnt = reinterpret_cast<uint32_t*>(cbase + C.bcnt.off);
+	p.adders = reinterpret_cast<uint32_t*>(base + L.adders.off);
+	p.n_ranges = pl.n_ranges;
+	p.e_rank = reinterpret_cast<float*>(cbase + C.erank.off);
+	p.e_idx = reinterpret_cast<uint32_t*>(base + L.eidx.off);
+	p.e_field = reinterpret_cast<uint8_t*>(base + L.efield.off);
+	p.sync = reinterpret_cast<uint32_t*>(cbase + C.sync.off);
 	static const char* const stamps_env = std::getenv("RXGPU_FT_STAMPS");   // (a debugging hook: read once, not once per merge)
-	p.dbg = stamps_env ? reinterpret_cast<unsigned long long*>(cbase + o_dbg) : nullptr;
+	p.dbg = stamps_env ? reinterpret_cast<unsigned long long*>(cbase + C.dbg.off) : nullptr;
 	p.dbg_block = stamps_env ? uint32_t(std::atoi(stamps_env)) : 0;
-	p.out_header = reinterpret_cast<uint32_t*>(ob);
+	p.out_header = reinterpret_cast<uint32_t*>(ob + pl.out.header);
 	p.host_out = hp_dev;
-	p.out_doc = reinterpret_cast<uint32_t*>(ob + align256(16));
-	p.out_proc = reinterpret_cast<float*>(ob + align256(16) + align256(M * 4));
-	p.out_terms_counter = reinterpret_cast<uint16_t*>(ob + align256(16) + 2 * align256(M * 4));
-	p.out_field = reinterpret_cast<uint8_t*>(ob + align256(16) + 2 * align256(M * 4) + align256(M * 2));
-	p.sparse = sparse ? 1 : 0;
+	p.out_doc = reinterpret_cast<uint32_t*>(ob + pl.out.doc);
+	p.out_proc = reinterpret_cast<float*>(ob + pl.out.proc);
+	p.out_terms_counter = reinterpret_cast<uint16_t*>(ob + pl.out.terms_counter);
+	p.out_field = reinterpret_cast<uint8_t*>(ob + pl.out.field);
+	p.sparse = pl.sparse ? 1 : 0;
 	p.removed_bits = h->d_removed_bits;
-	p.excluded_bits = d_excluded_bits;
-	p.lb_units = reinterpret_cast<unsigned long long*>(cbase + o_lb_units);
-	if (sparse) {
-		p.t_doc = reinterpret_cast<uint32_t*>(base + o_tdoc);
-		p.t_pos = reinterpret_cast<uint32_t*>(base + o_tpos);
-		p.t_idx = reinterpret_cast<uint32_t*>(base + o_tidx);
-		for (size_t si = 0; si < subs.size(); ++si) {   // what the unit kernels read of a sub-term, and its attribute word (ft_sparse.hip)
-			const rxgpu::FtPosSubterm& ft = subs[si];
-			const rxgpu::FtTermCfg& tc = tcfg[ft.term];
-			const QueryTermIn& qt = terms[parts[ft.term].t_begin];
-			// calcTermScores (mergerimpl.h:312-315): every field has the same boost, so maxBoostFromFields is field 0's
-			const float proc = ft.proc * qt.opts->field_boost[0] * tc.opts_boost;
-			uint32_t p16 = uint32_t(int32_t(proc)) & 0xFFFFu;   // static_cast<uint16_t>(float) as x86 evaluates it
-			p16 = std::min<uint32_t>(p16, 65535u / 4);
-			uint32_t attr = p16 | (ft.row << 20);
-			if (si == tc.sub_begin) attr |= 1u << 16;
-			if (tc.op == 2) attr |= 1u << 17;
-			if (tc.op == 3) attr |= 1u << 18;
-			p.sp_sub[si].doc = ft.doc;
-			p.sp_sub[si].range_off = ft.range_off;
-			p.sp_sub[si].n = uint32_t(ft.n);
-			p.sp_sub[si].n_ranges = ft.n_ranges;
-			p.sp_sub[si].attr = attr;
+	p.excluded_bits = mp.d_excluded_bits;
+	p.lb_units = reinterpret_cast<unsigned long long*>(cbase + C.lb_units.off);
+	if (pl.sparse) {
+		p.t_doc = reinterpret_cast<uint32_t*>(base + L.tdoc.off);
+		p.t_pos = reinterpret_cast<uint32_t*>(base + L.tpos.off);
+		p.t_idx = reinterpret_cast<uint32_t*>(base + L.tidx.off);
+		const auto* subs = reinterpret_cast<const rxgpu::FtPosSubterm*>(hp + L.plan_subs.off);
+		for (size_t si = 0; si < pl.rows.size(); ++si) {   // what the unit kernels read of a sub-term, and its attribute word (ft_sparse.hip)
+			p.sp_sub[si].doc = subs[si].doc;
+			p.sp_sub[si].range_off = subs[si].range_off;
+			p.sp_sub[si].n = uint32_t(subs[si].n);
+			p.sp_sub[si].n_ranges = subs[si].n_ranges;
+			p.sp_sub[si].attr = pl.rows[si].attr;
 		}
-		for (uint32_t pi = 0; pi < nparts && !simple; ++pi) {   // an AND term without postings empties the mask (buildRestrictingBitmask)
-			if (tcfg[pi].op == 2 && tcfg[pi].sub_begin == tcfg[pi].sub_end) p.sp_empty_and = 1;
-		}
+		p.sp_empty_and = pl.sp_empty_and ? 1 : 0;
 	}
+}
+
+// Step 3: the plan on the device.  `phrases_given`: the rows came from the sharded layer (a shard never runs a query's phrases on its own).
+int execute_plan(rxgpu_ft_index* h, hipStream_t st, const MergeQuery& q, const MergePrep& mp, bool resident, bool phrases_given, MergeJob& job, bool import_now) {
+	const rxgpu::FtMergePlan& pl = mp.plan;
+	const char* who = q.who;
+	const size_t M = size_t(pl.max_merged);
+	// ---- device scratch (one buffer each for the state and for the packed result)
+	if (int rc = h->d_state.ensure(pl.state.bytes); rc) return rc;
+	char* base = static_cast<char*>(h->d_state.ptr);
+	if (h->clean_docs != h->total_docs || h->d_clean.bytes < pl.clean.bytes) {
+		if (int rc = h->d_clean.ensure(pl.clean.bytes); rc) return rc;
+		h->clean_docs = h->total_docs;
+		h->clean_dirty = true;
+	}
+	if (int rc = h->d_out.ensure(pl.out.bytes); rc) return rc;
+	// ---- host staging of the plan (pinned), one upload
+	if (int rc = h->ensure_pinned(std::max(pl.state.plan_bytes, pl.out.bytes)); rc) return rc;
+	char* hp = static_cast<char*>(h->h_pinned);
+	stage_plan_tables(h, q, mp, hp, base);
+	if (h->clean_dirty) {
+		RX_HIP(hipMemsetAsync(h->d_clean.ptr, 0, h->d_clean.bytes, st));
+		h->clean_dirty = false;
+	}
+	void* hp_dev = nullptr;   // the pinned staging buffer as the device sees it
+	RX_HIP(hipHostGetDevicePointer(&hp_dev, hp, 0));
+	rxgpu::FtPlan& p = job.p;
+	fill_ft_plan(h, q, mp, hp, hp_dev, p);
 	if (h->sh_total > 1) {   // a document-range shard: its own ranges, the facts that span the shards arrive between the kernels
 		// (multi-word synonyms are fine: their masks, term counts and the "only parts of a synonym" marks are facts of ONE document, and a
 		// document lies in one shard — ft_syn_masks sees this shard's fragments, the caller drops the marked documents after the union)
 		RX_CHECK(!resident, RXGPU_ERR_LOGIC, std::string(who) + ": a sharded ft index merges into the caller's lists (no resident results)");
-		RX_CHECK(n_phrases == 0 || phrase_mode == 2, RXGPU_ERR_LOGIC, std::string(who) + ": a shard's phrases are run by the sharded layer");
+		RX_CHECK(mp.n_phrases == 0 || phrases_given, RXGPU_ERR_LOGIC, std::string(who) + ": a shard's phrases are run by the sharded layer");
 		p.range_begin = h->sh_range_begin;
 		p.range_count = h->sh_range_count;
 		p.shard_index = h->sh_index;
 		p.n_shards = h->sh_total;
-		p.shard_hist = prescore ? h->sh_hist : nullptr;
+		p.shard_hist = pl.prescore ? h->sh_hist : nullptr;
 		p.shard_pos = h->sh_pos;
-		RX_HIP(hipMemsetAsync(p.adders, 0, std::max<size_t>(1, size_t(n_rows) * n_ranges) * 4, st));   // the other shards' columns
-		RX_HIP(hipMemsetAsync(p.out_doc, 0xFF, M * 4, st));                                              // slots another shard fills stay marked
+		RX_HIP(hipMemsetAsync(p.adders, 0, std::max<size_t>(1, size_t(pl.n_rows) * pl.n_ranges) * 4, st));   // the other shards' columns
+		RX_HIP(hipMemsetAsync(p.out_doc, 0xFF, M * 4, st));                                                    // slots another shard fills stay marked
 	}
-	if (max_areas) {
-		job.area_hdr_bytes = align256(M * nf * 2 * sizeof(uint32_t));
-		job.area_bytes = M * nf * size_t(max_areas) * 3 * sizeof(uint32_t);
+	if (q.max_areas()) {
+		job.area_hdr_bytes = pl.area_hdr_bytes;
+		job.area_bytes = pl.area_bytes;
 		if (int rc = h->d_areas.ensure(job.area_hdr_bytes + job.area_bytes); rc) return rc;
 		RX_HIP(hipMemsetAsync(h->d_areas.ptr, 0, job.area_hdr_bytes, st));
-		p.max_areas = max_areas;
-		p.area_fields = nf;
+		p.max_areas = q.max_areas();
+		p.area_fields = h->num_fields;
 		p.area_hdr = static_cast<uint32_t*>(h->d_areas.ptr);
 		p.out_areas = reinterpret_cast<uint32_t*>(static_cast<char*>(h->d_areas.ptr) + job.area_hdr_bytes);
 	}
-
-	std::memcpy(hp + o_plan_self, &p, sizeof(p));
-	job.d_plan = reinterpret_cast<const rxgpu::FtPlan*>(base + o_plan_self);
+	std::memcpy(hp + pl.state.plan_self.off, &p, sizeof(p));
+	job.d_plan = reinterpret_cast<const rxgpu::FtPlan*>(base + pl.state.plan_self.off);
 	job.dev_base = base;
-	job.max_merged = max_merged;
-	job.merged_postings = merged_postings;
-	job.plan_bytes = plan_bytes;
+	job.max_merged = pl.max_merged;
+	job.merged_postings = pl.merged_postings;
+	job.plan_bytes = pl.state.plan_bytes;
 	job.hp_dev = hp_dev;
-	job.nsyn = nsyn;
-	if (import_now) RX_HIP(rxgpu::launch_ft_import(hp_dev, base, plan_bytes, st));   // plan_bytes is a multiple of 256
-	h->trace_us[1] += since(t_stage);
+	job.nsyn = pl.nsyn;
+	if (import_now) RX_HIP(rxgpu::launch_ft_import(hp_dev, base, pl.state.plan_bytes, st));   // plan_bytes is a multiple of 256
 	return RXGPU_OK;
+}
+
+double us_since(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - a).count(); }
+
+// Rows, limits and layouts of a merge whose phrases have run, then the execution.  `given`: the phrases' rows as the sharded layer settled them.
+int plan_and_execute(rxgpu_ft_index* h, hipStream_t st, const MergeQuery& q, MergePrep& mp, bool resident, bool phrases_given, MergeJob& job, bool import_now,
+					 std::chrono::steady_clock::time_point t_begin) {
+	for (uint32_t pi = 0; pi < mp.plan.nparts; ++pi) {   // (statistics: counted whether or not the checks below let the merge run)
+		if (mp.plan.parts[pi].phrase) h->stat_postings += mp.phrase_rows[pi].postings;
+	}
+	if (rxgpu::FtPlanError e = rxgpu::ft_plan_rows(mp.facts, PhraseView{mp.phrase_rows}, kStructSizes, mp.plan); e) return plan_error(e);
+	h->trace_us[0] += us_since(t_begin);
+	const auto t_stage = std::chrono::steady_clock::now();
+	if (int rc = execute_plan(h, st, q, mp, resident, phrases_given, job, import_now); rc) return rc;
+	h->trace_us[1] += us_since(t_stage);
+	return RXGPU_OK;
+}
+
+// A whole merge prepared on `st`: the query's phrases run here.  job.empty: nothing is merged.
+int prepare_merge(rxgpu_ft_index* h, hipStream_t st, const MergeQuery& q, bool resident, OutRoom room, MergeJob& job, bool import_now) {
+	const auto t_begin = std::chrono::steady_clock::now();
+	MergePrep mp;
+	if (int rc = begin_merge(h, st, q, resident, room, mp); rc) return rc;
+	job.empty = mp.plan.empty;
+	if (job.empty) return RXGPU_OK;
+	if (int rc = run_query_phrases(h, q, mp, false); rc) return rc;
+	return plan_and_execute(h, st, q, mp, resident, false, job, import_now, t_begin);
+}
+
+// A document-range shard, first visit: the query's phrases through their admission pass only — the sharded layer settles the admission cut of
+// the whole index before any shard goes on (finish_phrase).  *empty: nothing is merged, alike on every shard.
+int prepare_shard_phrases(rxgpu_ft_index* h, const MergeQuery& q, std::vector<PhraseRows>& phrases, bool* empty) {
+	MergePrep mp;
+	if (int rc = begin_merge(h, h->stream, q, false, OutRoom{true, q.cfg->merge_limit}, mp); rc) return rc;
+	*empty = mp.plan.empty;
+	if (mp.plan.empty) return RXGPU_OK;
+	if (int rc = run_query_phrases(h, q, mp, true); rc) return rc;
+	phrases = std::move(mp.phrase_rows);
+	return RXGPU_OK;
+}
+
+// A document-range shard, the merge itself.  `phrases`: the rows of the query's phrases, `admitted` holding the sum over the shards (the 2-phase
+// estimate is a fact of the whole index); null: the query has none.
+int prepare_shard_merge(rxgpu_ft_index* h, const MergeQuery& q, const std::vector<PhraseRows>* phrases, MergeJob& job) {
+	if (!phrases) return prepare_merge(h, h->stream, q, false, OutRoom{true, q.cfg->merge_limit}, job, true);
+	const auto t_begin = std::chrono::steady_clock::now();
+	MergePrep mp;
+	if (int rc = begin_merge(h, h->stream, q, false, OutRoom{true, q.cfg->merge_limit}, mp); rc) return rc;
+	job.empty = mp.plan.empty;
+	if (job.empty) return RXGPU_OK;
+	RX_CHECK(phrases->size() == mp.plan.nparts, RXGPU_ERR_LOGIC, std::string(q.who) + ": phrase rows of another query");
+	mp.phrase_rows = *phrases;
+	for (const QueryPartIn& part : mp.plan.parts) mp.n_phrases += part.phrase ? 1 : 0;
+	return plan_and_execute(h, h->stream, q, mp, false, true, job, true, t_begin);
 }
 
 // Second half: the merged documents out of the lane's pinned staging buffer (ft_export wrote them there; the stream has been waited for).
-int collect_merge(rxgpu_ft_index* h, const MergeJob& job, uint32_t* out_doc, float* out_proc, uint8_t* out_field, uint16_t* out_terms_counter, uint64_t* out_n,
-				  int32_t* out_preselected, const char* who) {
+int collect_merge(rxgpu_ft_index* h, const MergeJob& job, const MergeOut& out, const char* who) {
 	const char* hp = static_cast<const char*>(h->h_pinned);
-	const size_t M = size_t(job.max_merged);
-	const uint32_t* hdr = reinterpret_cast<const uint32_t*>(hp);
-	RX_CHECK(hdr[1] == 0, RXGPU_ERR_DEVICE, std::string(who) + ": ordered look-back timed out on the device");
+	const rxgpu::FtOutLayout ol = rxgpu::ft_out_layout(job.max_merged);
+	const uint32_t* hdr = reinterpret_cast<const uint32_t*>(hp + ol.header);
+	if (int rc = check_result_header(hdr, job.max_merged, who); rc) return rc;
 	const uint64_t n = hdr[0];
-	RX_CHECK(n <= job.max_merged, RXGPU_ERR_DEVICE, std::string(who) + ": corrupt result header");
 	h->clean_dirty = false;   // the merge ran to its end: ft_adders / ft_finish handed the tables back zeroed
 	uint64_t kept = n;
 	if (n && job.nsyn) {   // the documents that hold only parts of a multi-word synonym go (mergerimpl.h:533-555): the rest keeps its order
-		const uint32_t* sd = reinterpret_cast<const uint32_t*>(hp + align256(16));
-		const float* sp = reinterpret_cast<const float*>(hp + align256(16) + align256(M * 4));
-		const uint16_t* st_ = reinterpret_cast<const uint16_t*>(hp + align256(16) + 2 * align256(M * 4));
-		const uint8_t* sf = reinterpret_cast<const uint8_t*>(hp + align256(16) + 2 * align256(M * 4) + align256(M * 2));
+		const uint32_t* sd = reinterpret_cast<const uint32_t*>(hp + ol.doc);
+		const float* sp = reinterpret_cast<const float*>(hp + ol.proc);
+		const uint16_t* st_ = reinterpret_cast<const uint16_t*>(hp + ol.terms_counter);
+		const uint8_t* sf = reinterpret_cast<const uint8_t*>(hp + ol.field);
 		kept = 0;
 		for (uint64_t i = 0; i < n; ++i) {
 			if (st_[i] == 0xFFFFu) continue;
-			out_doc[kept] = sd[i];
-			out_proc[kept] = sp[i];
-			if (out_terms_counter) out_terms_counter[kept] = st_[i];
-			out_field[kept] = sf[i];
+			out.doc[kept] = sd[i];
+			out.proc[kept] = sp[i];
+			if (out.terms_counter) out.terms_counter[kept] = st_[i];
+			out.field[kept] = sf[i];
 			++kept;
 		}
 	} else if (n) {
-		std::memcpy(out_doc, hp + align256(16), n * 4);
-		std::memcpy(out_proc, hp + align256(16) + align256(M * 4), n * 4);
-		if (out_terms_counter) std::memcpy(out_terms_counter, hp + align256(16) + 2 * align256(M * 4), n * 2);
-		std::memcpy(out_field, hp + align256(16) + 2 * align256(M * 4) + align256(M * 2), n);
+		std::memcpy(out.doc, hp + ol.doc, n * 4);
+		std::memcpy(out.proc, hp + ol.proc, n * 4);
+		if (out.terms_counter) std::memcpy(out.terms_counter, hp + ol.terms_counter, n * 2);
+		std::memcpy(out.field, hp + ol.field, n);
 	}
-	*out_n = kept;
-	if (out_preselected) *out_preselected = hdr[2] ? 1 : 0;
+	*out.n = kept;
+	if (out.preselected) *out.preselected = hdr[2] ? 1 : 0;
 	return RXGPU_OK;
 }
+
+// RXGPU_FT_STAMPS: the phase stamps of the merge that just ended, summed into the lane
+int read_stamps(rxgpu_ft_index* h, const rxgpu::FtPlan& p) {
+	unsigned long long raw[64];
+	RX_HIP(hipMemcpy(raw, p.dbg, sizeof(raw), hipMemcpyDeviceToHost));
+	RX_HIP(hipMemset(p.dbg, 0, sizeof(raw)));
+	const int groups[][2] = {{0, 16}, {16, 24}, {24, 32}, {32, 48}};
+	for (const auto& g : groups) {
+		for (int k = g[0]; k < g[1]; ++k) {
+			if (raw[k] && raw[g[0]]) h->stamps[k] += double(raw[k] - raw[g[0]]) * 0.01;   // 100 MHz -> us
+		}
+	}
+	return RXGPU_OK;
+}
+
 
 void ft_shards_destroy(rxgpu_ft_shard_set* ss) {
 	if (!ss) return;
@@ -1776,12 +1640,18 @@ inline char* ft_send_ptr(rxgpu_ft_shard_set* ss, int k, size_t s, size_t bytes) 
 
 // One merge over all shards (the caller holds the sharded handle's mutex): the ordinary launch train in its three pieces, the two exchanges
 // between them, every shard's packed result, the slot-wise union.
-int run_merge_sharded(rxgpu_ft_index* parent, const rxgpu_ft_config* cfg, bool simple, const std::vector<QueryTermIn>& terms, const uint32_t* word_ids,
-					  const float* procs, const uint8_t* excluded, uint32_t* out_doc, float* out_proc, uint8_t* out_field, uint16_t* out_terms_counter,
-					  uint64_t cap, uint64_t* out_n, int32_t* out_preselected, const char* who, const SynonymsIn* synonyms = nullptr,
-					  const AreasOut* areas = nullptr) {
+int run_merge_sharded(rxgpu_ft_index* parent, const MergeQuery& q, const MergeOut& out) {
 	rxgpu_ft_shard_set* ss = parent->shard_set;
-	const uint32_t max_areas = areas ? areas->max_areas : 0u;
+	const rxgpu_ft_config* cfg = q.cfg;
+	const std::vector<QueryTermIn>& terms = *q.terms;
+	const float* procs = q.procs;
+	const AreasOut* areas = q.areas;
+	const char* who = q.who;
+	const uint32_t max_areas = q.max_areas();
+	uint32_t* out_doc = out.doc;
+	float* out_proc = out.proc;
+	uint8_t* out_field = out.field;
+	uint16_t* out_terms_counter = out.terms_counter;
 	const size_t S = ss->shards.size();
 	RX_CHECK(ss->n_ranges > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
 	int prev_dev = -1;
@@ -1813,12 +1683,9 @@ int run_merge_sharded(rxgpu_ft_index* parent, const rxgpu_ft_config* cfg, bool s
 	if (any_phrase) {
 		for (size_t s = 0; s < S; ++s) {
 			RX_HIP(hipSetDevice(ss->devices[s]));
-			MergeJob scratch;
-			if (int rc = prepare_merge(ss->shards[s], ss->shards[s]->stream, cfg, simple, terms, word_ids, procs, excluded, true, cfg->merge_limit, who, false, synonyms,
-									   scratch, true, max_areas, &phrases[s], 1);
-				rc)
-				return rc;
-			if (scratch.empty) return RXGPU_OK;   // min(mergeLimit, totalORVids) == 0: alike on every shard
+			bool nothing = false;
+			if (int rc = prepare_shard_phrases(ss->shards[s], q, phrases[s], &nothing); rc) return rc;
+			if (nothing) return RXGPU_OK;   // min(mergeLimit, totalORVids) == 0: alike on every shard
 		}
 		// the admission cut of the whole index (phrasemerger.h:341): the first mergeLimit candidates in (row, document) order — row by row,
 		// inside a row shard after shard (a shard's documents lie before the next one's).  What a shard keeps is a prefix of its own slots.
@@ -1864,16 +1731,13 @@ int run_merge_sharded(rxgpu_ft_index* parent, const rxgpu_ft_config* cfg, bool s
 		active[s] = sh->sh_range_count != 0;
 		sh->sh_hist = static_cast<const uint32_t*>(ss->d_recv[0][ss->shard_rank[s]].ptr);
 		sh->sh_pos = ss->d_pos[ss->shard_rank[s]];
-		if (int rc = prepare_merge(sh, sh->stream, cfg, simple, terms, word_ids, procs, excluded, true, cfg->merge_limit, who, false, synonyms, jobs[s], true, max_areas,
-								   any_phrase ? &phrases[s] : nullptr, any_phrase ? 2 : 0);
-			rc)
-			return rc;
+		if (int rc = prepare_shard_merge(sh, q, any_phrase ? &phrases[s] : nullptr, jobs[s]); rc) return rc;
 		empty = empty || jobs[s].empty;
 		sh->clean_dirty = !jobs[s].empty;   // an error return from here on leaves the kept-clean tables in an unknown state
 	}
 	if (empty) return RXGPU_OK;   // min(mergeLimit, totalORVids) == 0 — decided on the whole index's counts, alike on every shard
 	const uint64_t M = jobs[0].max_merged;
-	RX_CHECK(cap >= M, RXGPU_ERR_OVERFLOW, std::string(who) + ": output buffers too small");
+	RX_CHECK(out.cap >= M, RXGPU_ERR_OVERFLOW, std::string(who) + ": output buffers too small");
 	const bool prescore = jobs[0].p.prescore != 0;
 	auto phase = [&](int ph) -> int {
 		for (size_t s = 0; s < S; ++s) {
@@ -1952,7 +1816,7 @@ int run_merge_sharded(rxgpu_ft_index* parent, const rxgpu_ft_config* cfg, bool s
 	for (size_t s = 0; s < S; ++s) {
 		if (!active[s]) continue;
 		const uint32_t* hdr = static_cast<const uint32_t*>(ss->shards[s]->h_pinned);
-		RX_CHECK(hdr[1] == 0, RXGPU_ERR_DEVICE, std::string(who) + ": ordered look-back timed out on the device");
+		if (int rc = check_result_header(hdr, UINT64_MAX, who); rc) return rc;   // the look-back word; the count once the shards agree on it
 		RX_CHECK(!have_n || hdr[0] == n, RXGPU_ERR_DEVICE, std::string(who) + ": the shards disagree on the number of merged documents");
 		n = hdr[0];
 		have_n = true;
@@ -1962,13 +1826,14 @@ int run_merge_sharded(rxgpu_ft_index* parent, const rxgpu_ft_config* cfg, bool s
 	}
 	RX_CHECK(n <= M, RXGPU_ERR_DEVICE, std::string(who) + ": corrupt result header");
 	std::vector<uint8_t> filled(n, 0);
+	const rxgpu::FtOutLayout ol = rxgpu::ft_out_layout(M);
 	for (size_t s = 0; s < S; ++s) {
 		if (!active[s]) continue;
 		const char* hp = static_cast<const char*>(ss->shards[s]->h_pinned);
-		const uint32_t* sd = reinterpret_cast<const uint32_t*>(hp + align256(16));
-		const float* sp = reinterpret_cast<const float*>(hp + align256(16) + align256(M * 4));
-		const uint16_t* st_ = reinterpret_cast<const uint16_t*>(hp + align256(16) + 2 * align256(M * 4));
-		const uint8_t* sf = reinterpret_cast<const uint8_t*>(hp + align256(16) + 2 * align256(M * 4) + align256(M * 2));
+		const uint32_t* sd = reinterpret_cast<const uint32_t*>(hp + ol.doc);
+		const float* sp = reinterpret_cast<const float*>(hp + ol.proc);
+		const uint16_t* st_ = reinterpret_cast<const uint16_t*>(hp + ol.terms_counter);
+		const uint8_t* sf = reinterpret_cast<const uint8_t*>(hp + ol.field);
 		for (uint64_t i = 0; i < n; ++i) {
 			if (sd[i] == 0xFFFFFFFFu) continue;
 			RX_CHECK(!filled[i], RXGPU_ERR_DEVICE, std::string(who) + ": two shards wrote one merge slot");
@@ -1997,35 +1862,26 @@ int run_merge_sharded(rxgpu_ft_index* parent, const rxgpu_ft_config* cfg, bool s
 		}
 		n = kept;
 	}
-	*out_n = n;
-	if (out_preselected) *out_preselected = presel;
+	*out.n = n;
+	if (out.preselected) *out.preselected = presel;
 	return RXGPU_OK;
 }
 
-
-// Shared implementation of rxgpu_ft_merge_simple_raw / rxgpu_ft_merge_terms_raw.  out_terms_counter may be null (simple).
-int run_merge(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, bool simple, const std::vector<QueryTermIn>& terms, const uint32_t* word_ids,
-			  const float* procs, const uint8_t* excluded, uint32_t* out_doc, float* out_proc, uint8_t* out_field, uint16_t* out_terms_counter,
-			  uint64_t cap, uint64_t* out_n, int32_t* out_preselected, const char* who, bool resident = false, const SynonymsIn* synonyms = nullptr,
-			  const AreasOut* areas = nullptr) {
+// One merge on lane `h` (locked by the caller) into the caller's lists, or — resident — left in HBM for the hybrid fusion.
+int run_merge(rxgpu_ft_index* h, const MergeQuery& q, const MergeOut& out, bool resident = false) {
 	using clk = std::chrono::steady_clock;
+	const char* who = q.who;
 	if (h->shard_set) {   // document-range shards: the same train on every shard, two exchanges between its pieces
 		RX_CHECK(!resident, RXGPU_ERR_LOGIC, std::string(who) + ": a sharded ft index merges into the caller's lists (no resident results)");
-		RX_CHECK(out_doc && out_proc && out_field && (simple || out_terms_counter), RXGPU_ERR_OVERFLOW, std::string(who) + ": output buffers too small");
-		return run_merge_sharded(h, cfg, simple, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected, who,
-								 synonyms, areas);
+		RX_CHECK(out.complete(q.simple), RXGPU_ERR_OVERFLOW, std::string(who) + ": output buffers too small");
+		return run_merge_sharded(h, q, out);
 	}
 	if (int rc = finish_pending(h, who); rc) return rc;
-	auto since = [](clk::time_point a) { return std::chrono::duration<double, std::micro>(clk::now() - a).count(); };
 	hipStream_t st = h->stream;
 	MergeJob job;
-	if (int rc = prepare_merge(h, st, cfg, simple, terms, word_ids, procs, excluded, out_doc && out_proc && out_field && (simple || out_terms_counter), cap, who,
-							   resident, synonyms, job, true, areas ? areas->max_areas : 0u);
-		rc)
-		return rc;
+	if (int rc = prepare_merge(h, st, q, resident, OutRoom{out.complete(q.simple), out.cap}, job, true); rc) return rc;
 	if (job.empty) return RXGPU_OK;
 	const rxgpu::FtPlan& p = job.p;
-	const uint64_t max_merged = job.max_merged, merged_postings = job.merged_postings;
 	const auto t_launch = clk::now();
 	if (!h->ev_a) {
 		RX_HIP(hipEventCreate(&h->ev_a));
@@ -2034,74 +1890,145 @@ int run_merge(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, bool simple, const 
 	// from here on an error return leaves the kept-clean tables in an unknown state: the next merge clears them first
 	h->clean_dirty = true;
 	RX_HIP(hipEventRecord(h->ev_a, st));
-	if (job.p.sparse) {
+	if (p.sparse) {
 		RX_HIP(rxgpu::launch_ft_merge_sparse(job.d_plan, &job.p, 1, st));
 	} else {
 		RX_HIP(rxgpu::launch_ft_merge(job.d_plan, &job.p, 1, st));
 	}
 	RX_HIP(hipEventRecord(h->ev_b, st));
-	(h->root ? h->root : h)->trains_dense += job.p.sparse ? 0 : 1;
-	(h->root ? h->root : h)->trains_sparse += job.p.sparse ? 1 : 0;
+	(h->root ? h->root : h)->trains_dense += p.sparse ? 0 : 1;
+	(h->root ? h->root : h)->trains_sparse += p.sparse ? 1 : 0;
 	if (resident) {   // the result stays where ft_finish wrote it (d_out): the fusion kernel reads it there, nothing travels
 		h->res_pending = true;
 		h->res_has_syn = job.nsyn != 0;   // the fusion skips the documents ft_finish marked (they hold only parts of a synonym)
 		h->prep_done = false;
-		h->res_cap = uint32_t(max_merged);
-		h->stat_postings += merged_postings;
-		h->trace_us[2] += since(t_launch);
+		h->res_cap = uint32_t(job.max_merged);
+		h->stat_postings += job.merged_postings;
+		h->trace_us[2] += us_since(t_launch);
 		h->trace_us[5] += 1;
 		return RXGPU_OK;
 	}
 	RX_HIP(rxgpu::launch_ft_export(job.d_plan, &job.p, 1, st));
+	const AreasOut* areas = q.areas;
 	std::vector<uint32_t> area_hdr;
 	if (areas) {   // {held, insertions} per (document, field) and the areas, as the replay left them (the wait below covers the copies)
-		area_hdr.resize(size_t(max_merged) * h->num_fields * 2);
-		RX_HIP(hipMemcpyAsync(area_hdr.data(), job.p.area_hdr, area_hdr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		RX_HIP(hipMemcpyAsync(areas->areas, job.p.out_areas, job.area_bytes, hipMemcpyDeviceToHost, st));
+		area_hdr.resize(size_t(job.max_merged) * h->num_fields * 2);
+		RX_HIP(hipMemcpyAsync(area_hdr.data(), p.area_hdr, area_hdr.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+		RX_HIP(hipMemcpyAsync(areas->areas, p.out_areas, job.area_bytes, hipMemcpyDeviceToHost, st));
 	}
-	h->trace_us[2] += since(t_launch);
+	h->trace_us[2] += us_since(t_launch);
 	const auto t_wait = clk::now();
 	// (the result is already on its way: ft_export, the last kernel of the train, writes it into the pinned staging buffer)
-	{
-		// a merge is ~0.1 ms of device time: poll for its end instead of sleeping in hipStreamSynchronize (the wake-up alone is tens of
-		// microseconds); anything that takes longer than a few milliseconds falls back to the blocking wait
-		const auto t_poll = clk::now();
-		hipError_t q = hipStreamQuery(st);
-		while (q == hipErrorNotReady && since(t_poll) < 3000.0) q = hipStreamQuery(st);
-		if (q == hipErrorNotReady) {
-			RX_HIP(hipStreamSynchronize(st));
-		} else {
-			RX_HIP(q);
-		}
-	}
+	if (int rc = wait_stream_polled(st); rc) return rc;
 	if (p.dbg) {
-		unsigned long long raw[64];
-		RX_HIP(hipMemcpy(raw, p.dbg, sizeof(raw), hipMemcpyDeviceToHost));
-		RX_HIP(hipMemset(p.dbg, 0, sizeof(raw)));
-		const int groups[][2] = {{0, 16}, {16, 24}, {24, 32}, {32, 48}};
-		for (const auto& g : groups) {
-			for (int k = g[0]; k < g[1]; ++k) {
-				if (raw[k] && raw[g[0]]) h->stamps[k] += double(raw[k] - raw[g[0]]) * 0.01;   // 100 MHz -> us
-			}
-		}
+		if (int rc = read_stamps(h, p); rc) return rc;
 	}
-	h->trace_us[3] += since(t_wait);
+	h->trace_us[3] += us_since(t_wait);
 	const auto t_unpack = clk::now();
 	float ms = 0.f;
 	(void)hipEventElapsedTime(&ms, h->ev_a, h->ev_b);
-	h->stat_postings += merged_postings;
+	h->stat_postings += job.merged_postings;
 	h->stat_ms += ms;
-	if (int rc = collect_merge(h, job, out_doc, out_proc, out_field, out_terms_counter, out_n, out_preselected, who); rc) return rc;
+	if (int rc = collect_merge(h, job, out, who); rc) return rc;
 	if (areas) {
 		RX_HIP(hipStreamSynchronize(st));   // (the polling above may have ended on the export kernel: the two copies behind it too, now)
 		const size_t nf = h->num_fields;
-		for (uint64_t i = 0; i < *out_n; ++i) {
+		for (uint64_t i = 0; i < *out.n; ++i) {
 			for (size_t f = 0; f < nf; ++f) areas->cnt[i * nf + f] = area_hdr[(i * nf + f) * 2];
 		}
 	}
-	h->trace_us[4] += since(t_unpack);
+	h->trace_us[4] += us_since(t_unpack);
 	h->trace_us[5] += 1;
 	return RXGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------- what the entry points share
+// The common head of a merge call: the configuration fits the index, the index has its documents
+int check_merge_head(const rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const char* who) {
+	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
+	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	return RXGPU_OK;
+}
+
+// The terms of a query given as arrays; the classification is QueryMergeData::Empty() / Simple() (querymergedata.h:208; ft_merge_plan.h)
+int query_terms(const char* who, uint32_t nterms, const int32_t* ops, const rxgpu_ft_term_opts* opts, const int32_t* phrase_num, const int32_t* distance,
+				const uint32_t* sub_off, const uint32_t* word_ids, const float* procs, std::vector<QueryTermIn>& terms, bool* empty, bool* simple) {
+	*empty = true;
+	*simple = false;
+	if (nterms == 0) return RXGPU_OK;
+	RX_CHECK(ops && opts && sub_off, RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
+	RX_CHECK(nterms < 0x7FFF, RXGPU_ERR_PARAMS, std::string(who) + ": too many terms");
+	RX_CHECK(sub_off[nterms] == 0 || (word_ids && procs), RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
+	terms.resize(nterms);
+	for (uint32_t t = 0; t < nterms; ++t) {
+		RX_CHECK(ops[t] >= 1 && ops[t] <= 3, RXGPU_ERR_PARAMS, std::string(who) + ": op must be 1 (OR), 2 (AND) or 3 (NOT)");
+		terms[t] = QueryTermIn{ops[t], &opts[t], sub_off[t], sub_off[t + 1], phrase_num ? phrase_num[t] : -1, distance ? distance[t] : 1};
+	}
+	const rxgpu::FtQueryClass c = rxgpu::ft_classify_query(terms.data(), nterms);
+	*empty = c.empty;
+	*simple = c.simple;
+	return RXGPU_OK;
+}
+
+// An rxgpu_ft_query as run_merge takes it: the parts' terms, then — unless the query is Empty(), which looks at the parts only — the
+// synonyms' terms with their tables
+struct ParsedQuery {
+	std::vector<QueryTermIn> terms;
+	SynonymsIn syn;
+	bool empty = false, simple = false;
+	const SynonymsIn* synonyms() const { return syn.nsyn ? &syn : nullptr; }
+	MergeQuery merge_query(const rxgpu_ft_config* cfg, const rxgpu_ft_query* q, const uint8_t* excluded, const char* who) const {
+		MergeQuery mq;
+		mq.cfg = cfg;
+		mq.simple = simple;
+		mq.terms = &terms;
+		mq.word_ids = q->word_ids;
+		mq.procs = q->procs;
+		mq.excluded = excluded;
+		mq.synonyms = synonyms();
+		mq.who = who;
+		return mq;
+	}
+};
+int parse_query(const char* who, const rxgpu_ft_query* q, ParsedQuery& out) {
+	if (int rc = query_terms(who, q->nterms, q->ops, q->opts, q->phrase_num, q->distance, q->sub_off, q->word_ids, q->procs, out.terms, &out.empty, &out.simple); rc) return rc;
+	if (out.empty || !q->nsyn) return RXGPU_OK;
+	RX_CHECK(q->syn_term_off && q->part_syn_off, RXGPU_ERR_PARAMS, std::string(who) + ": null synonym tables");
+	for (uint32_t k = 0; k < q->nsyn_terms; ++k) {
+		const uint32_t t = q->nterms + k;
+		RX_CHECK(q->ops[t] >= 1 && q->ops[t] <= 3, RXGPU_ERR_PARAMS, std::string(who) + ": op must be 1 (OR), 2 (AND) or 3 (NOT)");
+		out.terms.push_back(QueryTermIn{q->ops[t], &q->opts[t], q->sub_off[t], q->sub_off[t + 1], -1, 1});
+	}
+	out.syn.nsyn = q->nsyn;
+	out.syn.first_term = q->nterms;
+	out.syn.syn_term_off = q->syn_term_off;
+	out.syn.part_syn_off = q->part_syn_off;
+	out.syn.part_syn = q->part_syn;
+	out.syn.suppressed = q->suppressed;
+	out.simple = false;
+	return RXGPU_OK;
+}
+
+// A resident call on the handle: its lock, this thread's session, the dictionary, the device; the result of the merge before is forgotten
+struct ResidentCall {
+	std::unique_lock<std::mutex> lk;
+	std::shared_lock<std::shared_mutex> dict_lk;
+	rxgpu::DeviceGuard dg;
+	static std::unique_lock<std::mutex> open(rxgpu_ft_index* h) {
+		std::unique_lock<std::mutex> l(h->mtx);
+		open_resident_session(h, l);
+		return l;
+	}
+	explicit ResidentCall(rxgpu_ft_index* h) : lk(open(h)), dict_lk(h->dict_mtx), dg(h->device) {
+		h->res_cap = 0;
+		h->prep_done = false;
+	}
+};
+int run_resident(rxgpu_ft_index* h, const MergeQuery& q) {
+	uint64_t n = 0;
+	MergeOut out;
+	out.n = &n;
+	return run_merge(h, q, out, true);
 }
 
 }  // namespace
@@ -2109,18 +2036,17 @@ int run_merge(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, bool simple, const 
 int rxgpu_ft_merge_simple_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const rxgpu_ft_term_opts* opts, uint32_t nsub,
 							  const uint32_t* word_ids, const float* procs, const uint8_t* excluded, uint32_t* out_doc, float* out_proc,
 							  uint8_t* out_field, uint64_t cap, uint64_t* out_n) {
+	const char* who = "rxgpu_ft_merge_simple_raw";
 	RX_CHECK(h && cfg && opts && out_n, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_raw: null argument");
 	*out_n = 0;
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_raw: field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, "rxgpu_ft_merge_simple_raw: rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	if (nsub == 0) return RXGPU_OK;
 	RX_CHECK(word_ids && procs && opts->field_boost && opts->need_sum_rank, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_raw: null argument");
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
 	rxgpu::DeviceGuard dg(h->device);
-	std::vector<QueryTermIn> terms{QueryTermIn{1, opts, 0, nsub}};
-	return run_merge(ll.lane, cfg, true, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, nullptr, cap, out_n, nullptr,
-					 "rxgpu_ft_merge_simple_raw");
+	const std::vector<QueryTermIn> terms{QueryTermIn{1, opts, 0, nsub}};
+	return run_merge(ll.lane, MergeQuery{cfg, true, &terms, word_ids, procs, excluded, nullptr, nullptr, who}, MergeOut{out_doc, out_proc, out_field, nullptr, cap, out_n, nullptr});
 }
 
 int rxgpu_ft_set_word_positions(rxgpu_ft_index* h, uint32_t word_id, uint64_t n, const uint32_t* doc, const uint32_t* pos_off, const uint64_t* fpos) {
@@ -2247,8 +2173,8 @@ int rxgpu_ft_set_words_packed_ptrs(rxgpu_ft_index* h, uint32_t nwords, const uin
 	// pinned staging: [streams | (start, end) pairs | array_found_pos | piece -> word | first piece of a word]; everything but the streams
 	// travels first (one copy), the streams follow in chunks so that the gather of the next chunk, the copy of this one and the counting
 	// pass of the previous one overlap
-	const size_t o_off = align256(size_t(total_bytes) + 16), o_afp = o_off + align256(size_t(nwords) * 16), o_sw = o_afp + align256(size_t(nwords) * 8);
-	const size_t o_sf = o_sw + align256(size_t(nsegs) * 4), in_bytes = o_sf + align256((size_t(nwords) + 1) * 4);
+	const size_t o_off = rxgpu::ft_align256(size_t(total_bytes) + 16), o_afp = o_off + rxgpu::ft_align256(size_t(nwords) * 16), o_sw = o_afp + rxgpu::ft_align256(size_t(nwords) * 8);
+	const size_t o_sf = o_sw + rxgpu::ft_align256(size_t(nsegs) * 4), in_bytes = o_sf + rxgpu::ft_align256((size_t(nwords) + 1) * 4);
 	if (int rc = h->d_pk_in.ensure(in_bytes); rc) return rc;
 	if (int rc = h->ensure_pinned(in_bytes); rc) return rc;
 	uint8_t* hp = static_cast<uint8_t*>(h->h_pinned);
@@ -2386,7 +2312,7 @@ int rxgpu_ft_set_words_packed_ptrs(rxgpu_ft_index* h, uint32_t nwords, const uin
 				 std::string("rxgpu_ft_set_words_packed: word ") + std::to_string(word_ids[order[k]]) + ": " + status_text(counts[k].status));
 	}
 	// one pool for the whole batch, every array of every word on a 256-byte boundary (the kernels read document ids 16 bytes at a time)
-	Carver cv;
+	rxgpu::FtCarver cv;
 	std::vector<rxgpu::FtPackedOut> outs(nwords);
 	struct Slices {
 		size_t doc, pos_off, fpos, ent_off, ent_field, ent_tf, ent_first, range_off;
@@ -2546,11 +2472,11 @@ int rxgpu_ft_get_word(rxgpu_ft_index* h, uint32_t word_id, uint64_t* n, uint64_t
 int rxgpu_ft_merge_terms_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint32_t nterms, const int32_t* ops, const rxgpu_ft_term_opts* opts,
 							 const uint32_t* sub_off, const uint32_t* word_ids, const float* procs, const uint8_t* excluded, uint32_t* out_doc,
 							 float* out_proc, uint8_t* out_field, uint16_t* out_terms_counter, uint64_t cap, uint64_t* out_n, int32_t* out_preselected) {
+	const char* who = "rxgpu_ft_merge_terms_raw";
 	RX_CHECK(h && cfg && out_n, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_raw: null argument");
 	*out_n = 0;
 	if (out_preselected) *out_preselected = 0;
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_raw: field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, "rxgpu_ft_merge_terms_raw: rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	// QueryMergeData::Empty() (querymergedata.h:208)
 	if (nterms == 0) return RXGPU_OK;
 	RX_CHECK(ops && opts && sub_off, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_raw: null argument");
@@ -2564,32 +2490,9 @@ int rxgpu_ft_merge_terms_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	rxgpu::DeviceGuard dg(h->device);
 	std::vector<QueryTermIn> terms(nterms);
 	for (uint32_t t = 0; t < nterms; ++t) terms[t] = QueryTermIn{ops[t], &opts[t], sub_off[t], sub_off[t + 1]};
-	return run_merge(ll.lane, cfg, false, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected,
-					 "rxgpu_ft_merge_terms_raw");
+	return run_merge(ll.lane, MergeQuery{cfg, false, &terms, word_ids, procs, excluded, nullptr, nullptr, who},
+					 MergeOut{out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected});
 }
-
-namespace {
-// the checks shared by rxgpu_ft_merge_query_raw / _resident; *empty: QueryMergeData::Empty() (querymergedata.h:208)
-int query_terms(const char* who, uint32_t nterms, const int32_t* ops, const rxgpu_ft_term_opts* opts, const int32_t* phrase_num, const int32_t* distance,
-				const uint32_t* sub_off, const uint32_t* word_ids, const float* procs, std::vector<QueryTermIn>& terms, bool* empty, bool* simple) {
-	*empty = true;
-	*simple = false;
-	if (nterms == 0) return RXGPU_OK;
-	RX_CHECK(ops && opts && sub_off, RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
-	RX_CHECK(nterms < 0x7FFF, RXGPU_ERR_PARAMS, std::string(who) + ": too many terms");
-	RX_CHECK(sub_off[nterms] == 0 || (word_ids && procs), RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
-	terms.resize(nterms);
-	uint32_t nparts = 0;
-	for (uint32_t t = 0; t < nterms; ++t) {
-		RX_CHECK(ops[t] >= 1 && ops[t] <= 3, RXGPU_ERR_PARAMS, std::string(who) + ": op must be 1 (OR), 2 (AND) or 3 (NOT)");
-		terms[t] = QueryTermIn{ops[t], &opts[t], sub_off[t], sub_off[t + 1], phrase_num ? phrase_num[t] : -1, distance ? distance[t] : 1};
-		if (terms[t].phrase_num < 0 || t == 0 || terms[t - 1].phrase_num != terms[t].phrase_num) ++nparts;
-	}
-	*empty = nparts == 1 && ops[0] == 3;
-	*simple = nparts == 1 && ops[0] != 3 && terms[0].phrase_num < 0;
-	return RXGPU_OK;
-}
-}  // namespace
 
 int rxgpu_ft_merge_query_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint32_t nterms, const int32_t* ops, const rxgpu_ft_term_opts* opts,
 							 const int32_t* phrase_num, const int32_t* distance, const uint32_t* sub_off, const uint32_t* word_ids, const float* procs,
@@ -2599,8 +2502,7 @@ int rxgpu_ft_merge_query_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	RX_CHECK(h && cfg && out_n, RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
 	*out_n = 0;
 	if (out_preselected) *out_preselected = 0;
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	std::vector<QueryTermIn> terms;
 	bool empty = false, simple = false;
 	if (int rc = query_terms(who, nterms, ops, opts, phrase_num, distance, sub_off, word_ids, procs, terms, &empty, &simple); rc) return rc;
@@ -2608,7 +2510,8 @@ int rxgpu_ft_merge_query_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
 	rxgpu::DeviceGuard dg(h->device);
-	return run_merge(ll.lane, cfg, simple, terms, word_ids, procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected, who);
+	return run_merge(ll.lane, MergeQuery{cfg, simple, &terms, word_ids, procs, excluded, nullptr, nullptr, who},
+					 MergeOut{out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected});
 }
 
 int rxgpu_ft_merge_query2_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const rxgpu_ft_query* q, const uint8_t* excluded, uint32_t* out_doc, float* out_proc,
@@ -2617,34 +2520,15 @@ int rxgpu_ft_merge_query2_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, con
 	RX_CHECK(h && cfg && q && out_n, RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
 	*out_n = 0;
 	if (out_preselected) *out_preselected = 0;
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	RX_CHECK(q->nsyn > 0 || q->nsyn_terms == 0, RXGPU_ERR_PARAMS, std::string(who) + ": synonym terms without synonyms");
-	std::vector<QueryTermIn> terms;
-	bool empty = false, simple = false;
-	if (int rc = query_terms(who, q->nterms, q->ops, q->opts, q->phrase_num, q->distance, q->sub_off, q->word_ids, q->procs, terms, &empty, &simple); rc) return rc;
-	if (empty) return RXGPU_OK;   // QueryMergeData::Empty() looks at the query parts only
-	SynonymsIn syn;
-	if (q->nsyn) {
-		RX_CHECK(q->syn_term_off && q->part_syn_off, RXGPU_ERR_PARAMS, std::string(who) + ": null synonym tables");
-		for (uint32_t k = 0; k < q->nsyn_terms; ++k) {
-			const uint32_t t = q->nterms + k;
-			RX_CHECK(q->ops[t] >= 1 && q->ops[t] <= 3, RXGPU_ERR_PARAMS, std::string(who) + ": op must be 1 (OR), 2 (AND) or 3 (NOT)");
-			terms.push_back(QueryTermIn{q->ops[t], &q->opts[t], q->sub_off[t], q->sub_off[t + 1], -1, 1});
-		}
-		syn.nsyn = q->nsyn;
-		syn.first_term = q->nterms;
-		syn.syn_term_off = q->syn_term_off;
-		syn.part_syn_off = q->part_syn_off;
-		syn.part_syn = q->part_syn;
-		syn.suppressed = q->suppressed;
-		simple = false;
-	}
+	ParsedQuery pq;
+	if (int rc = parse_query(who, q, pq); rc) return rc;
+	if (pq.empty) return RXGPU_OK;   // QueryMergeData::Empty() looks at the query parts only
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
 	rxgpu::DeviceGuard dg(h->device);
-	return run_merge(ll.lane, cfg, simple, terms, q->word_ids, q->procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected, who,
-					 false, q->nsyn ? &syn : nullptr);
+	return run_merge(ll.lane, pq.merge_query(cfg, q, excluded, who), MergeOut{out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected});
 }
 
 // Merger<IdCont, MergeDataAreas<Area>, ...>::Merge (merger.h:36-57 with kWithRegularAreas): the merge of rxgpu_ft_merge_query2_raw plus, per merged
@@ -2657,22 +2541,18 @@ int rxgpu_ft_merge_query_areas_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg
 	*out_n = 0;
 	if (out_preselected) *out_preselected = 0;
 	RX_CHECK(max_areas_in_doc >= 1 && max_areas_in_doc <= 4096, RXGPU_ERR_PARAMS, std::string(who) + ": max_areas_in_doc must be in [1, 4096] (FTConfig::maxAreasInDoc; unlimited areas stay on the CPU merger)");
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	RX_CHECK(q->nsyn == 0 && q->nsyn_terms == 0, RXGPU_ERR_LOGIC, std::string(who) + ": areas are built for queries without multi-word synonyms");
-	std::vector<QueryTermIn> terms;
-	bool empty = false, simple = false;
-	if (int rc = query_terms(who, q->nterms, q->ops, q->opts, q->phrase_num, q->distance, q->sub_off, q->word_ids, q->procs, terms, &empty, &simple); rc) return rc;
-	if (empty) return RXGPU_OK;
+	ParsedQuery pq;
+	if (int rc = parse_query(who, q, pq); rc) return rc;
+	if (pq.empty) return RXGPU_OK;
 	LaneLock ll;
 	if (int rc = checkout_lane(h, ll); rc) return rc;
 	rxgpu::DeviceGuard dg(h->device);
-	AreasOut ao;
-	ao.max_areas = max_areas_in_doc;
-	ao.cnt = out_area_cnt;
-	ao.areas = out_areas;
-	return run_merge(ll.lane, cfg, simple, terms, q->word_ids, q->procs, excluded, out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected, who,
-					 false, nullptr, &ao);
+	const AreasOut ao{max_areas_in_doc, out_area_cnt, out_areas};
+	MergeQuery mq = pq.merge_query(cfg, q, excluded, who);
+	mq.areas = &ao;
+	return run_merge(ll.lane, mq, MergeOut{out_doc, out_proc, out_field, out_terms_counter, cap, out_n, out_preselected});
 }
 
 // Q queries over one index in ONE launch train (ft_merge.hip: grid.y = query).  The launch floors and the ramp of every kernel's grid are
@@ -2687,8 +2567,8 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 		out_n[i] = 0;
 		if (out_preselected) out_preselected[i] = 0;
 	}
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
+	auto out_of = [&](uint32_t i) { return MergeOut{out_doc[i], out_proc[i], out_field[i], out_terms_counter[i], cap, &out_n[i], out_preselected ? &out_preselected[i] : nullptr}; };
 	// queries with phrases or multi-word synonyms have kernels of their own in front of the train (ft_phrase.hip, ft_syn_masks): one by one
 	std::vector<uint32_t> batched;
 	for (uint32_t i = 0; i < nq; ++i) {
@@ -2699,10 +2579,8 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 			batched.push_back(i);
 			continue;
 		}
-		if (int rc = rxgpu_ft_merge_query2_raw(h, cfg, &q, excluded ? excluded[i] : nullptr, out_doc[i], out_proc[i], out_field[i], out_terms_counter[i], cap, &out_n[i],
-											   out_preselected ? &out_preselected[i] : nullptr);
-			rc)
-			return rc;
+		const MergeOut o = out_of(i);
+		if (int rc = rxgpu_ft_merge_query2_raw(h, cfg, &q, excluded ? excluded[i] : nullptr, o.doc, o.proc, o.field, o.terms_counter, cap, o.n, o.preselected); rc) return rc;
 	}
 	if (batched.empty()) return RXGPU_OK;
 	std::lock_guard<std::mutex> batch_lk(h->batch_mtx);
@@ -2719,7 +2597,6 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 	void* plans_dev_view = nullptr;
 	RX_HIP(hipHostGetDevicePointer(&plans_dev_view, h->h_batch_plans, 0));
 	hipStream_t st = h->batch_stream;
-	using clk = std::chrono::steady_clock;
 	for (size_t c0 = 0; c0 < batched.size(); c0 += rxgpu::kFtBatchMax) {
 		const size_t c1 = std::min(batched.size(), c0 + rxgpu::kFtBatchMax);
 		std::vector<MergeJob> jobs;
@@ -2731,30 +2608,21 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 		for (size_t c = c0; c < c1; ++c) {
 			const uint32_t i = batched[c];
 			const rxgpu_ft_query& q = queries[i];
-			std::vector<QueryTermIn> terms;
-			bool empty = false, simple = false;
-			if (int rc = query_terms(who, q.nterms, q.ops, q.opts, q.phrase_num, q.distance, q.sub_off, q.word_ids, q.procs, terms, &empty, &simple); rc) return rc;
-			if (empty) continue;
+			ParsedQuery pq;   // (plain: no synonyms)
+			if (int rc = parse_query(who, &q, pq); rc) return rc;
+			if (pq.empty) continue;
 			const size_t k = jobs.size();
-			while (h->batch_lanes.size() <= k) {
-				auto lane = std::make_unique<rxgpu_ft_index>();
-				lane->device = h->device;
-				lane->num_fields = h->num_fields;
-				lane->root = h;
+			while (h->batch_lanes.size() <= k) {   // a scratch set per query of the train; the whole train runs on batch_stream
+				std::unique_ptr<rxgpu_ft_index> lane;
+				if (int rc = make_lane(h, false, lane); rc) return rc;
 				h->batch_lanes.push_back(std::move(lane));
 			}
 			rxgpu_ft_index* lane = h->batch_lanes[k].get();
-			lane->total_docs = h->total_docs;
-			lane->d_words = h->d_words;
-			lane->d_avg = h->d_avg;
-			lane->d_removed = h->d_removed;
-			lane->d_removed_bits = h->d_removed_bits;
-			lane->h_avg = h->h_avg;
+			lane_adopt_docs(lane, h);
 			MergeJob job;
-			if (int rc = prepare_merge(lane, st, cfg, simple, terms, q.word_ids, q.procs, excluded ? excluded[i] : nullptr,
-									   out_doc[i] && out_proc[i] && out_field[i] && (simple || out_terms_counter[i]), cap, who, false, nullptr, job, false);
-				rc)
+			if (int rc = prepare_merge(lane, st, pq.merge_query(cfg, &q, excluded ? excluded[i] : nullptr, who), false, OutRoom{out_of(i).complete(pq.simple), cap}, job, false); rc) {
 				return rc;
+			}
 			if (job.empty) continue;
 			pieces.src[k] = job.hp_dev;
 			pieces.dst[k] = job.dev_base;
@@ -2789,16 +2657,7 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 		h->trains_sparse += n_sparse;
 		h->trains_dense += B - n_sparse;
 		RX_HIP(rxgpu::launch_ft_export(d_plans, host_plans.data(), B, st));
-		{
-			const auto t_poll = clk::now();
-			hipError_t qs = hipStreamQuery(st);
-			while (qs == hipErrorNotReady && std::chrono::duration<double, std::micro>(clk::now() - t_poll).count() < 3000.0) qs = hipStreamQuery(st);
-			if (qs == hipErrorNotReady) {
-				RX_HIP(hipStreamSynchronize(st));
-			} else {
-				RX_HIP(qs);
-			}
-		}
+		if (int rc = wait_stream_polled(st); rc) return rc;
 		float ms = 0.f;
 		(void)hipEventElapsedTime(&ms, h->ev_ba, h->ev_bb);
 		h->stat_postings += postings;
@@ -2806,15 +2665,12 @@ int rxgpu_ft_merge_batch_raw(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint
 		h->batch_trains += 1;
 		h->batch_merges += B;
 		for (uint32_t k = 0; k < B; ++k) {
-			const uint32_t i = job_query[k];
-			if (int rc = collect_merge(job_lane[k], jobs[k], out_doc[i], out_proc[i], out_field[i], out_terms_counter[i], &out_n[i],
-									   out_preselected ? &out_preselected[i] : nullptr, who);
-				rc)
-				return rc;
+			if (int rc = collect_merge(job_lane[k], jobs[k], out_of(job_query[k]), who); rc) return rc;
 		}
 	}
 	return RXGPU_OK;
 }
+
 void rxgpu_ft_set_train_mode(int mode) { ft_train_mode()->store(mode < 0 ? -1 : (mode ? 1 : 0), std::memory_order_relaxed); }
 int rxgpu_ft_read_train_stats(rxgpu_ft_index* h, uint64_t* dense_merges, uint64_t* sparse_merges) {
 	RX_CHECK(h && dense_merges && sparse_merges, RXGPU_ERR_PARAMS, "rxgpu_ft_read_train_stats: null argument");
@@ -2836,20 +2692,13 @@ int rxgpu_ft_merge_query_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg,
 	const char* who = "rxgpu_ft_merge_query_resident";
 	RX_CHECK(h && cfg && out_enqueued, RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
 	*out_enqueued = 0;
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	std::vector<QueryTermIn> terms;
 	bool empty = false, simple = false;
 	if (int rc = query_terms(who, nterms, ops, opts, phrase_num, distance, sub_off, word_ids, procs, terms, &empty, &simple); rc) return rc;
-	std::unique_lock<std::mutex> lk(h->mtx);
-	open_resident_session(h, lk);
-	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	rxgpu::DeviceGuard dg(h->device);
-	h->res_cap = 0;
-	h->prep_done = false;
+	ResidentCall call(h);
 	if (empty) return finish_pending(h, who);   // nothing is merged: the fusion sees an empty FT side
-	uint64_t n = 0;
-	if (int rc = run_merge(h, cfg, simple, terms, word_ids, procs, excluded, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr, who, true); rc) return rc;
+	if (int rc = run_resident(h, MergeQuery{cfg, simple, &terms, word_ids, procs, excluded, nullptr, nullptr, who}); rc) return rc;
 	*out_enqueued = h->res_pending ? 1 : 0;
 	return RXGPU_OK;
 }
@@ -2860,39 +2709,13 @@ int rxgpu_ft_merge_query2_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg
 	const char* who = "rxgpu_ft_merge_query2_resident";
 	RX_CHECK(h && cfg && q && out_enqueued, RXGPU_ERR_PARAMS, std::string(who) + ": null argument");
 	*out_enqueued = 0;
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, std::string(who) + ": field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, std::string(who) + ": rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	RX_CHECK(q->nsyn > 0 || q->nsyn_terms == 0, RXGPU_ERR_PARAMS, std::string(who) + ": synonym terms without synonyms");
-	std::vector<QueryTermIn> terms;
-	bool empty = false, simple = false;
-	if (int rc = query_terms(who, q->nterms, q->ops, q->opts, q->phrase_num, q->distance, q->sub_off, q->word_ids, q->procs, terms, &empty, &simple); rc) return rc;
-	SynonymsIn syn;
-	if (!empty && q->nsyn) {
-		RX_CHECK(q->syn_term_off && q->part_syn_off, RXGPU_ERR_PARAMS, std::string(who) + ": null synonym tables");
-		for (uint32_t k = 0; k < q->nsyn_terms; ++k) {
-			const uint32_t t = q->nterms + k;
-			RX_CHECK(q->ops[t] >= 1 && q->ops[t] <= 3, RXGPU_ERR_PARAMS, std::string(who) + ": op must be 1 (OR), 2 (AND) or 3 (NOT)");
-			terms.push_back(QueryTermIn{q->ops[t], &q->opts[t], q->sub_off[t], q->sub_off[t + 1], -1, 1});
-		}
-		syn.nsyn = q->nsyn;
-		syn.first_term = q->nterms;
-		syn.syn_term_off = q->syn_term_off;
-		syn.part_syn_off = q->part_syn_off;
-		syn.part_syn = q->part_syn;
-		syn.suppressed = q->suppressed;
-		simple = false;
-	}
-	std::unique_lock<std::mutex> lk(h->mtx);
-	open_resident_session(h, lk);
-	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	rxgpu::DeviceGuard dg(h->device);
-	h->res_cap = 0;
-	h->prep_done = false;
-	if (empty) return finish_pending(h, who);   // nothing is merged: the fusion sees an empty FT side
-	uint64_t n = 0;
-	if (int rc = run_merge(h, cfg, simple, terms, q->word_ids, q->procs, excluded, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr, who, true, q->nsyn ? &syn : nullptr); rc) {
-		return rc;
-	}
+	ParsedQuery pq;
+	if (int rc = parse_query(who, q, pq); rc) return rc;
+	ResidentCall call(h);
+	if (pq.empty) return finish_pending(h, who);   // nothing is merged: the fusion sees an empty FT side
+	if (int rc = run_resident(h, pq.merge_query(cfg, q, excluded, who)); rc) return rc;
 	*out_enqueued = h->res_pending ? 1 : 0;
 	return RXGPU_OK;
 }
@@ -2900,39 +2723,27 @@ int rxgpu_ft_merge_query2_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg
 // ---------------------------------------------------------------------------------------------------- hybrid: merges that stay in HBM + the fusion
 int rxgpu_ft_merge_simple_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, const rxgpu_ft_term_opts* opts, uint32_t nsub,
 								   const uint32_t* word_ids, const float* procs, const uint8_t* excluded) {
+	const char* who = "rxgpu_ft_merge_simple_resident";
 	RX_CHECK(h && cfg && opts, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_resident: null argument");
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_resident: field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, "rxgpu_ft_merge_simple_resident: rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	RX_CHECK(nsub > 0 && word_ids && procs && opts->field_boost && opts->need_sum_rank, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_simple_resident: null argument");
-	std::unique_lock<std::mutex> lk(h->mtx);
-	open_resident_session(h, lk);
-	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	rxgpu::DeviceGuard dg(h->device);
-	std::vector<QueryTermIn> terms{QueryTermIn{1, opts, 0, nsub}};
-	uint64_t n = 0;
-	h->res_cap = 0;
-	h->prep_done = false;
-	return run_merge(h, cfg, true, terms, word_ids, procs, excluded, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr, "rxgpu_ft_merge_simple_resident", true);
+	ResidentCall call(h);
+	const std::vector<QueryTermIn> terms{QueryTermIn{1, opts, 0, nsub}};
+	return run_resident(h, MergeQuery{cfg, true, &terms, word_ids, procs, excluded, nullptr, nullptr, who});
 }
 
 int rxgpu_ft_merge_terms_resident(rxgpu_ft_index* h, const rxgpu_ft_config* cfg, uint32_t nterms, const int32_t* ops, const rxgpu_ft_term_opts* opts,
 								  const uint32_t* sub_off, const uint32_t* word_ids, const float* procs, const uint8_t* excluded) {
+	const char* who = "rxgpu_ft_merge_terms_resident";
 	RX_CHECK(h && cfg && ops && opts && sub_off, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_resident: null argument");
-	RX_CHECK(cfg->num_fields == h->num_fields, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_resident: field count mismatch");
-	RX_CHECK(h->total_docs > 0, RXGPU_ERR_LOGIC, "rxgpu_ft_merge_terms_resident: rxgpu_ft_set_docs was not called");
+	if (int rc = check_merge_head(h, cfg, who); rc) return rc;
 	RX_CHECK(nterms >= 2 && nterms < 0xFFFF, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_resident: 2 or more terms (one term: rxgpu_ft_merge_simple_resident)");
 	for (uint32_t t = 0; t < nterms; ++t) RX_CHECK(ops[t] >= 1 && ops[t] <= 3, RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_resident: op must be 1 (OR), 2 (AND) or 3 (NOT)");
 	RX_CHECK(sub_off[nterms] == 0 || (word_ids && procs), RXGPU_ERR_PARAMS, "rxgpu_ft_merge_terms_resident: null argument");
-	std::unique_lock<std::mutex> lk(h->mtx);
-	open_resident_session(h, lk);
-	std::shared_lock<std::shared_mutex> dict_lk(h->dict_mtx);
-	rxgpu::DeviceGuard dg(h->device);
+	ResidentCall call(h);
 	std::vector<QueryTermIn> terms(nterms);
 	for (uint32_t t = 0; t < nterms; ++t) terms[t] = QueryTermIn{ops[t], &opts[t], sub_off[t], sub_off[t + 1]};
-	uint64_t n = 0;
-	h->res_cap = 0;
-	h->prep_done = false;
-	return run_merge(h, cfg, false, terms, word_ids, procs, excluded, nullptr, nullptr, nullptr, nullptr, 0, &n, nullptr, "rxgpu_ft_merge_terms_resident", true);
+	return run_resident(h, MergeQuery{cfg, false, &terms, word_ids, procs, excluded, nullptr, nullptr, who});
 }
 
 namespace {
@@ -2954,14 +2765,15 @@ namespace {
 // the FT-side arguments of the two fusion kernels for the resident merge of `h` (M = its max_merged; 0: no resident merge)
 int fuse_ft_args(rxgpu_ft_index* h, uint32_t M, int32_t min_rank, const rxgpu_hybrid_params* params, int metric, const void* d_row_of_doc,
 				 rxgpu::HybridFuseArgs& a) {
-	const size_t key_bytes = align256(size_t(2) * std::max<uint32_t>(M, 1) * 4), cls_bytes = align256(size_t(2) * std::max<uint32_t>(M, 1) * 2);
-	if (int rc = h->d_fuse.ensure(key_bytes + cls_bytes + align256(sizeof(rxgpu::HybridFuseState))); rc) return rc;
+	const size_t key_bytes = rxgpu::ft_align256(size_t(2) * std::max<uint32_t>(M, 1) * 4), cls_bytes = rxgpu::ft_align256(size_t(2) * std::max<uint32_t>(M, 1) * 2);
+	if (int rc = h->d_fuse.ensure(key_bytes + cls_bytes + rxgpu::ft_align256(sizeof(rxgpu::HybridFuseState))); rc) return rc;
 	char* ob = static_cast<char*>(h->d_out.ptr);
 	if (M) {   // the packed layout run_merge gave d_out for max_merged = M
-		a.ft_count_ptr = reinterpret_cast<const uint32_t*>(ob);
-		a.ft_doc = reinterpret_cast<const uint32_t*>(ob + align256(16));
-		a.ft_proc = reinterpret_cast<const float*>(ob + align256(16) + align256(size_t(M) * 4));
-		if (h->res_has_syn) a.ft_terms = reinterpret_cast<const uint16_t*>(ob + align256(16) + 2 * align256(size_t(M) * 4));
+		const rxgpu::FtOutLayout ol = rxgpu::ft_out_layout(M);
+		a.ft_count_ptr = reinterpret_cast<const uint32_t*>(ob + ol.header);
+		a.ft_doc = reinterpret_cast<const uint32_t*>(ob + ol.doc);
+		a.ft_proc = reinterpret_cast<const float*>(ob + ol.proc);
+		if (h->res_has_syn) a.ft_terms = reinterpret_cast<const uint16_t*>(ob + ol.terms_counter);
 	}
 	a.ft_n = 0;
 	a.ft_cap = M;
@@ -3035,7 +2847,7 @@ int rxgpu_hybrid_fuse_resident(rxgpu_ft_index* h, int32_t min_rank, const rxgpu_
 		}
 	}
 	// the result leaves through the pinned staging buffer: the kernel's stores go straight to host memory, no copy-engine start-up
-	const size_t o_ids = 256, o_ranks = o_ids + align256(out_cap * 4), stage = o_ranks + align256(out_cap * 4);
+	const size_t o_ids = 256, o_ranks = o_ids + rxgpu::ft_align256(out_cap * 4), stage = o_ranks + rxgpu::ft_align256(out_cap * 4);
 	if (int rc = h->ensure_pinned(stage); rc) return rc;
 	char* hp = static_cast<char*>(h->h_pinned);
 	void* hp_dev = nullptr;
@@ -3069,25 +2881,11 @@ int rxgpu_hybrid_fuse_resident(rxgpu_ft_index* h, int32_t min_rank, const rxgpu_
 	RX_HIP(rxgpu::launch_hybrid_join(a, st));
 	RX_HIP(hipEventRecord(h->ev_fb, st));
 	h->prep_done = false;
-	{
-		using clk = std::chrono::steady_clock;
-		const auto t_poll = clk::now();
-		hipError_t q = hipStreamQuery(st);
-		while (q == hipErrorNotReady && std::chrono::duration<double, std::micro>(clk::now() - t_poll).count() < 3000.0) q = hipStreamQuery(st);
-		if (q == hipErrorNotReady) {
-			RX_HIP(hipStreamSynchronize(st));
-		} else {
-			RX_HIP(q);
-		}
-	}
-	if (h->res_pending) {   // the merge in front of the fusion has ended too: settle its state without another wait
+	if (int rc = wait_stream_polled(st); rc) return rc;
+	// the merge in front of the fusion has ended too: settle its state without another wait
+	if (h->res_pending) {
 		h->res_pending = false;
-		uint32_t mh[4] = {0, 0, 0, 0};
-		RX_HIP(hipMemcpy(mh, h->d_out.ptr, sizeof(mh), hipMemcpyDeviceToHost));
-		float ms = 0.f;
-		if (h->ev_a && hipEventElapsedTime(&ms, h->ev_a, h->ev_b) == hipSuccess) h->stat_ms += ms;
-		RX_CHECK(mh[1] == 0, RXGPU_ERR_DEVICE, "rxgpu_hybrid_fuse_resident: ordered look-back timed out on the device");
-		h->clean_dirty = false;
+		if (int rc = settle_resident_merge(h, "rxgpu_hybrid_fuse_resident"); rc) return rc;
 	}
 	{
 		float fms = 0.f;
@@ -3148,7 +2946,7 @@ int rxgpu_hybrid_fuse(int device, const rxgpu_hybrid_params* params, int metric,
 	RX_CHECK(device >= 0 && device < ndev, RXGPU_ERR_PARAMS, "rxgpu_hybrid_fuse: no such device");
 	rxgpu::DeviceGuard dg(device);
 	const size_t nf = std::max<uint32_t>(n_ft, 1), nk = std::max<uint32_t>(n_knn, 1), no = size_t(n_ft) + n_knn + 1;
-	Carver cv;
+	rxgpu::FtCarver cv;
 	const size_t o_fid = cv.take(nf * 4), o_fr = cv.take(nf), o_kid = cv.take(nk * 4), o_kr = cv.take(nk * 4), o_key = cv.take(2 * nf * 4),
 				 o_cls = cv.take(2 * nf * 2), o_hdr = cv.take(16), o_oid = cv.take(no * 4), o_or = cv.take(no * 4),
 				 o_state = cv.take(sizeof(rxgpu::HybridFuseState));

@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include "ft_packed_decode.h"
+#include "ft_merge_plan.h"   // the FT constants the host decisions share with the kernels, FtGridEntry, FtSynonym
 
 namespace rxgpu {
 
@@ -200,25 +201,11 @@ struct FtTermCfg {             // what calcTermRank reads: FTConfig + the FtDslO
 	// the documents — OR-ed into the part's term mask before it restricts (buildRestrictingBitmask, mergerimpl.h:347-361); ft_syn_masks
 	const uint32_t* syn_mask;
 };
-// Multi-word synonyms (QueryMergeData::synonyms, querymergedata.h:178-192): their terms follow the query parts in FtPlan::terms (op = OR for
-// the pre-score pass: calcTermScores counts them like any term, mergerimpl.h:393-397, and they never restrict on their own)
-struct FtSynonym {
-	uint32_t term_begin, term_end;   // its terms in FtPlan::terms
-	uint32_t end_qp;                 // qp of its last term (every term takes a qp, NOT terms too: mergerimpl.h:511-514)
-	uint32_t nterms;                 // Synonym::NumTerms()
-};
 struct FtSynMaskJob {                // one AND part's synonym mask
 	uint32_t syn_begin, syn_end;     // into FtPlan::job_syns
 	uint32_t* out;                   // [nwords]
 };
-struct FtGridEntry {           // block range of one sub-term in a posting-side grid (blocks of kFtBlockPostings postings)
-	uint32_t block_base;
-	uint32_t sub;              // index into FtPlan::subs
-};
-constexpr int kFtPassItems = 4;            // postings per thread in the posting-side kernels
-constexpr uint32_t kFtRangeDocs = 8192;    // documents per workgroup of the document-range kernel (ft_ranges); multiple of 32
-constexpr int kFtBlockPostings = 256 * kFtPassItems;
-inline uint32_t ft_pass_blocks(uint64_t n) { return uint32_t((n + kFtBlockPostings - 1) / kFtBlockPostings); }
+// (FtSynonym, FtGridEntry, kFtPassItems, kFtRangeDocs, kFtBlockPostings, ft_pass_blocks: ft_merge_plan.h)
 
 // Everything one merge needs on the device.  Pointers into per-index scratch; scalar members by value (the struct travels as a kernel argument).
 struct FtPlan {
@@ -289,7 +276,7 @@ struct FtPlan {
 	const uint32_t* shard_hist;   // gathered layout: shard s at [shard_pos[s]][kFtFoldWords]
 	const uint32_t* shard_pos;    // [n_shards]
 	// The train for SPARSELY hit document ranges (ft_sparse.hip): one wavefront per (query, range), bitmaps of the range's documents per
-	// sub-term in LDS, nothing per document in HBM.  sparse = 1: the host found the query eligible (ft_sparse_eligible, rxgpu_ft_capi.hip).
+	// sub-term in LDS, nothing per document in HBM.  sparse = 1: the host found the query eligible (ft_sparse_eligible, ft_merge_plan.h).
 	uint8_t sparse;
 	uint8_t sp_empty_and;         // an AND term without postings: no document passes the mask
 	const uint32_t* removed_bits; // [nwords] DocRemoved as one bit per document (null: none removed); built by rxgpu_ft_set_docs
@@ -313,8 +300,7 @@ static_assert(sizeof(FtPlan::SpSub) == 32, "one 32-byte entry per lane");
 constexpr uint32_t kFtFoldWords = 65536 + 1024 + 64;   // one shard's folded histogram (fine + chunk counters), [65536 + 1024] = its mask popcount
 enum : uint32_t { kFtSyncError = 0, kFtSyncPop = 1, kFtSyncPreTicket = 4, kFtSyncNumDocs = 6, kFtSyncDoneFinish = 9,
 				  // the sparse train: threshold score / documents kept at it / flags (bit 0 preselect on, bit 1 every tie is kept), the ticket of ft_sp_select
-				  kFtSyncThrScore = 10, kFtSyncThrDocs = 11, kFtSyncThrFlags = 12, kFtSyncSpTicket = 13, kFtSyncTasks = 14, kFtSyncWords = 16 };
-constexpr uint32_t kFtHistCopies = 8, kFtHistStride = 65536 + 1024;
+				  kFtSyncThrScore = 10, kFtSyncThrDocs = 11, kFtSyncThrFlags = 12, kFtSyncSpTicket = 13, kFtSyncTasks = 14 };   // (their count, kFtSyncWords: ft_merge_plan.h)
 constexpr uint32_t kFtRangeShift = 13;     // log2(kFtRangeDocs)
 static_assert((1u << kFtRangeShift) == kFtRangeDocs, "document ranges are powers of two");
 // Q merges over one index in ONE train (grid.y = query; a single merge is a batch of one): the plans in HBM + their host copy
@@ -326,11 +312,9 @@ hipError_t launch_ft_merge_phase(const FtPlan* plans, const FtPlan* host_plans, 
 // [ft_sp_threshold, ft_sp_select], ft_slot_bases, [ft_sp_place], ft_sp_replay
 hipError_t launch_ft_merge_sparse(const FtPlan* plans, const FtPlan* host_plans, uint32_t nq, hipStream_t st);
 void launch_ft_slot_bases(const FtPlan* plans, uint32_t nq, hipStream_t st);   // ft_merge.hip
-constexpr uint32_t kFtSparseSubs = 16;   // sub-terms (NOT terms' included) a sparse merge holds bitmaps for
 void launch_ft_shard_fold(const FtPlan* plan, uint32_t* dst, hipStream_t st);                                            // hist copies + popcount -> dst [kFtFoldWords]
 void launch_ft_shard_hist_combine(const FtPlan* plan, const uint32_t* gathered, const uint32_t* pos, uint32_t n_shards, hipStream_t st);   // gathered [..][kFtFoldWords]
 void launch_ft_shard_table_sum(uint32_t* table, const uint32_t* gathered, const uint32_t* pos, uint32_t n_shards, uint64_t n, uint64_t stride, hipStream_t st);   // gathered [..][stride]
-constexpr uint32_t kFtBatchMax = 64;
 struct FtImportBatch {             // pieces of one batched upload (pinned staging -> HBM), 16-byte words
 	const void* src[kFtBatchMax + 1];
 	void* dst[kFtBatchMax + 1];

@@ -226,6 +226,25 @@ def test_what_a_sharded_ft_index_does_not_offer_says_so(rxgpu, hostapi, ft):
     m.close()
 
 
+def test_shard_ranges_of_a_small_index(rxgpu, hostapi):
+    """rxgpu_ft_shard_ranges: 60 documents are one 8192-document range.  The cut hands out ceil(1 / 2) = 1 range per shard: shard 0 takes it, the
+    last shard takes what lies behind — nothing."""
+    import ctypes as C
+    m = hostapi.GpuFtMerger(1, devices=[0, 0])
+    words = np.full((60, 1), 7.0, np.float32)
+    words[0] = 0
+    m.set_docs(words, words[1:].mean(axis=0).astype(np.float32))
+    lib = rxgpu.lib()
+    got = []
+    for s in range(2):
+        begin, count = C.c_uint32(99), C.c_uint32(99)
+        assert lib.rxgpu_ft_shard_ranges(m.device_index, s, C.byref(begin), C.byref(count)) == 0
+        got.append((begin.value, count.value))
+    assert got == [(0, 1), (1, 0)]
+    assert lib.rxgpu_ft_shard_ranges(m.device_index, 2, C.byref(begin), C.byref(count)) == -3   # RXGPU_ERR_PARAMS: no such shard
+    m.close()
+
+
 SHARDED_PHRASE_CASES = [
     # (seed, nf, limit, ops, phrases, distances, nsub_range)
     (401, 1, 30000, (1, 1), (0, 0), (1, 8), (1, 4)),                          # the query IS one phrase

@@ -200,6 +200,30 @@ def test_resident_fusion_reports_boundary_ties_and_empty_ft(rxgpu, oracle):
     ix.close()
 
 
+def test_fuse_stats_count_the_resident_fusions(rxgpu):
+    """rxgpu_hybrid_read_stats: the fusions since the last call with the device time of the join and of the prepare kernel; reading resets."""
+    from reindexer_amd import hostapi
+    rng = np.random.default_rng(5)
+    total, d, k = 41, 16, 5
+    words = rng.integers(10, 40, (total, 1)).astype(np.float32)
+    words[0] = 0
+    ftm = hostapi.GpuFtMerger(1)
+    ftm.set_docs(words, words[1:].mean(axis=0).astype(np.float32))
+    ftm.set_word_fpos(0, make_pos_postings(rng, total, 1, 20, 100.0))
+    vm = hostapi.GpuBruteforceMap(1, d, total)
+    vm.add(make_corpus(62, total, d), np.arange(total, dtype=np.uint64) << np.uint64(32))
+    cfg, terms = hostapi.default_ft_config(1), [dict(op=1, opts=hostapi.default_ft_opts(1), subs=[(0, 100.0)])]
+    ftm.read_fuse_stats()
+    for _ in range(3):
+        ids, _, _ = hostapi.hybrid_query_resident(vm, ftm, cfg, terms, make_corpus(63, 1, d)[0], k)
+        assert len(ids) >= k
+    calls, join_ms, prepare_ms = ftm.read_fuse_stats()
+    assert calls == 3 and join_ms > 0.0 and prepare_ms > 0.0
+    assert ftm.read_fuse_stats() == (0, 0.0, 0.0)
+    vm.close()
+    ftm.close()
+
+
 @pytest.mark.parametrize("metric", [1, 2])
 def test_hybrid_query_through_map_and_merger(rxgpu, oracle, metric):
     """rxgpu::host::HybridQueryResident (hybrid_query.h): the Map's resident search + the Merger's resident merge + the fusion, vs the same
