@@ -164,6 +164,18 @@ int rxgpu_search_knn_device(rxgpu_index* h, const void* d_queries, uint32_t nq, 
  * bf16-pruned scan under the current environment.  shadow_available: the bf16 shadow fits in HBM; stats_finite: no row has a NaN or
  * infinite norm (both are facts the index learns on the device). */
 int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite);
+/* Which scan such a call takes: 0 the f32 paths, 1 the bf16-pruned scan, 2 the int8-pruned scan (no device is touched).  The int8 tier
+ * refines a call the automatic mode accepts (RXGPU_SCAN_BF16 unset): a single query on an index of at least 1 GiB of f32 rows
+ * (RXGPU_SCAN_I8_MIN_BYTES moves it) with 128 < dim <= 1024 is pruned over an int8 shadow of the rows (1 byte per element read, +1 byte per
+ * element and +8 bytes per row of HBM, built by the first such call; the bf16 shadow is then not built for single queries) under a per-row
+ * bound that is proven, not tuned: the same rows and distance bits.  RXGPU_SCAN_I8 (environment, read per call): unset = automatic, 0 = this
+ * tier off, 1 = forced for up to 8 queries at any size; RXGPU_SCAN_BF16=0 and =1 both win over it.  shadow_available stands for the shadow of
+ * either tier. */
+int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite);
+/* Candidates the last pruned single-query search through rxgpu_search_knn nominated for the exact re-score, and the capacity of their list
+ * (count > cap: the list overflowed, or the query had no finite bound, and the exact scan answered).  Recorded only while profiling is
+ * enabled (rxgpu_profile_enable). */
+int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap);
 
 /* ---- Pre-filtered brute force: the caller side of `WHERE cond AND KNN(...)` -------------------
  * The reference evaluates such a query by taking the KNN result and filtering it on the host (selectLoop,

@@ -64,6 +64,8 @@ _SIGNATURES = {
     "rxgpu_index_resident_contexts": (_u32, [_vp]),
     "rxgpu_search_knn_device": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "rxgpu_scan_policy": (_i, [_u64, _u32, _u32, _i, _i]),
+    "rxgpu_scan_tier": (_i, [_u64, _u32, _u32, _i, _i]),
+    "rxgpu_index_last_candidates": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "rxgpu_search_knn_subset": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "rxgpu_search_knn_bitmap": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_index_set_lists": (_i, [_vp, _u32, _vp, _vp]),
@@ -194,6 +196,11 @@ def device_arch(device: int = 0) -> str:
 def scan_policy(rows: int, dim: int, nq: int = 1, shadow_available: bool = True, stats_finite: bool = True) -> bool:
     """rxgpu_scan_policy: does such a call take the bf16-pruned scan under the current environment?  Touches no device."""
     return bool(lib().rxgpu_scan_policy(rows, dim, nq, int(shadow_available), int(stats_finite)))
+
+
+def scan_tier(rows: int, dim: int, nq: int = 1, shadow_available: bool = True, stats_finite: bool = True) -> int:
+    """rxgpu_scan_tier: 0 / 1 / 2 = such a call takes the f32 / bf16-pruned / int8-pruned scan under the current environment.  Touches no device."""
+    return int(lib().rxgpu_scan_tier(rows, dim, nq, int(shadow_available), int(stats_finite)))
 
 
 def _f32c(a) -> np.ndarray:
@@ -508,6 +515,12 @@ class VectorIndex:
         n, ms = _u64(0), C.c_double(0.0)
         _check(lib().rxgpu_profile_read(self._h, name.encode(), C.byref(n), C.byref(ms)))
         return int(n.value), float(ms.value)
+
+    def last_candidates(self) -> tuple[int, int]:
+        """(candidates, list capacity) of the last pruned single-query search_knn made while profiling was enabled."""
+        n, cap = _u32(0), _u32(0)
+        _check(lib().rxgpu_index_last_candidates(self._h, C.byref(n), C.byref(cap)))
+        return int(n.value), int(cap.value)
 
 
 class ShardedVectorIndex(VectorIndex):

@@ -12,6 +12,7 @@
 //   6. knn_merge            exact top-kk by (dist,row)
 // A query whose list overflows (adversarial data: massive ties) is redone by the exact fused scan, gated on device.
 // Result: the same ids and distance bits as B sequential reference calls, at one corpus read per <=256 queries.
+#include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
 
@@ -237,29 +238,12 @@ __global__ __launch_bounds__(256) void knn_row_stats(const float* rows, const fl
 	}
 }
 
-// the per-query margin 2*eps_q from |q|^2 = s (see file header)
+// the per-query margin 2*eps_q from |q|^2 = s (see file header); the formula lives in knn_i8_quant.h (f32_query_margin), shared with the host
 // kBf16: the nomination runs on bf16-rounded operands (knn_batched_bf16.hip): + (2^-8 + 2^-18)|q||x| for the two roundings
+static_assert(kL2 == kI8L2 && kIP == kI8IP && kCos == kI8Cos, "one numbering of the metrics");
 template <int kMetric, bool kBf16>
 __device__ __forceinline__ float query_margin(float s, uint32_t dim, const unsigned int* stats) {
-	const float u = 5.9604645e-08f;   // 2^-24
-	// f32 accumulation: covers both summation trees (D-chain vs 64-chain + fold), 10% slack.  The bf16 MFMA adds 16 products per instruction in an
-	// adder tree whose internal rounding mode is not documented: allow 2 ulp-halves per addition and the tree depth on top of the chain (4x)
-	const float gamma = (kBf16 ? 4.4f : 1.1f) * float(dim + 64) * u;
-	// rne_bf16 on q and x: |q~.x~ - q.x| <= ((1+2^-9)^2 - 1) sum|q_i x_i| <= 2^-8 (1 + 2^-10) |q||x|   (only the inner product is affected:
-	// |q|^2 and |x|^2 of the L2 form come from the f32 data)
-	const float gb = kBf16 ? 1.01f * 0.00390625f : 0.0f;
-	const float xmax2 = __uint_as_float(stats[0]);
-	float eps;
-	if constexpr (kMetric == kL2) {
-		// d = (qq + xx) - 2 ip: 2*gamma*|q||x| <= gamma*(qq+xx), plus the roundings of qq, xx and of the reference's own sum; bf16 adds 2*gb*|q||x|
-		eps = 2.0f * gamma * (s + xmax2) + 2.0f * gb * sqrtf(s) * sqrtf(xmax2);
-	} else if constexpr (kMetric == kIP) {
-		eps = (gamma + gb) * sqrtf(s) * sqrtf(xmax2);
-	} else {
-		eps = (gamma + gb + 4.0f * u) * sqrtf(s) * sqrtf(__uint_as_float(stats[1]));
-	}
-	// bf16 MFMA may flush subnormal inputs: at most dim * 2^-126 * (|q| + max|x|), far below the 1e-30 floor added here
-	return 2.0f * eps * 1.01f + (kBf16 ? 1e-30f : 1e-37f);
+	return f32_query_margin<kMetric, kBf16>(s, dim, __uint_as_float(stats[0]), __uint_as_float(stats[1]));
 }
 
 // |q|^2 and the per-query margin; one 64-lane wave per query
@@ -302,6 +286,62 @@ __global__ __launch_bounds__(64) void knn_query_prep(const float* src, uint32_t 
 		q_sq[qi] = s;
 		margin[qi] = mg;
 		cand_cnt[qi] = (s < __builtin_inff() && mg < __builtin_inff()) ? 0u : cap + 1u;
+	}
+}
+
+// The query side of the int8-pruned scan in one launch (knn_scan_i8.hip; arithmetic and bound: knn_i8_quant.h): the padded f32 copy the
+// re-score reads, the query as two int8 planes ([2][ld8] bytes: h, then l), |q|^2 (f32, as knn_query_prep), qinfo = {s_q, |q| rounded up}, the
+// margin of knn_filter_approx, and the candidate counter: 0, or cap + 1 when the query, the margin or the index's statistics are not finite
+// (stats[2]): the exact scan behind the gate answers the query then.  One wavefront per query; the norms and the residual are fp64 sums.
+template <int kMetric>
+__global__ __launch_bounds__(64) void knn_query_prep_i8(const float* src, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
+															 float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap) {
+	const uint32_t qi = blockIdx.x;
+	const int lane = threadIdx.x;
+	const float* q = src + size_t(qi) * dim;
+	float* o = qpad + size_t(qi) * ld8;
+	int8_t* ph = planes + size_t(qi) * 2 * ld8;
+	int8_t* pl = ph + ld8;
+	float s = 0.f, mx = 0.f;
+	double s64 = 0.0;
+	bool bad = false;
+	for (uint32_t i = lane; i < ld8; i += 64) {
+		const float v = i < dim ? q[i] : 0.f;
+		o[i] = v;
+		if (i < dim) {
+			s = __builtin_fmaf(v, v, s);
+			s64 += double(v) * double(v);
+			mx = fmaxf(mx, fabsf(v));
+			bad |= !(fabsf(v) < __builtin_inff());
+		}
+	}
+	for (int off = 32; off; off >>= 1) {
+		s += __shfl_xor(s, off);
+		s64 += __shfl_xor(s64, off);
+		mx = fmaxf(mx, __shfl_xor(mx, off));
+	}
+	const float sq = i8_scale(mx, kI8QueryMax);
+	double r64 = 0.0;
+	for (uint32_t i = lane; i < ld8; i += 64) {
+		const float v = i < dim ? q[i] : 0.f;
+		const int t = i8_quantize(v, sq, kI8QueryMax);
+		int hh, ll;
+		i8_split(t, hh, ll);
+		ph[i] = int8_t(hh);
+		pl[i] = int8_t(ll);
+		const double r = i8_residual(v, sq, t);
+		r64 += r * r;
+	}
+	for (int off = 32; off; off >>= 1) r64 += __shfl_xor(r64, off);
+	bad = __ballot(bad) != 0;
+	if (lane == 0) {
+		const float qn = i8_norm_up(s64), rq = i8_norm_up(r64);
+		const float mg = i8_margin<kMetric>(s, dim, qn, rq, __uint_as_float(stats[0]), __uint_as_float(stats[1]), __uint_as_float(stats[3]), __uint_as_float(stats[4]));
+		q_sq[qi] = s;
+		qinfo[qi] = make_float2(sq, qn);
+		const bool ok = !bad && stats[2] == 0 && s < __builtin_inff() && qn < __builtin_inff() && mg < __builtin_inff();
+		margin[qi] = ok ? mg : __builtin_inff();
+		cand_cnt[qi] = ok ? 0u : cap + 1u;
 	}
 }
 
@@ -447,6 +487,15 @@ void launch_query_prep(int metric, const float* src, uint32_t nq, uint32_t dim, 
 		case kL2: hipLaunchKernelGGL((knn_query_prep<kL2>), dim3(nq), dim3(64), 0, s, src, dim, qpad, ld, stats, q_sq, margin, cand_cnt, cap); break;
 		case kIP: hipLaunchKernelGGL((knn_query_prep<kIP>), dim3(nq), dim3(64), 0, s, src, dim, qpad, ld, stats, q_sq, margin, cand_cnt, cap); break;
 		default: hipLaunchKernelGGL((knn_query_prep<kCos>), dim3(nq), dim3(64), 0, s, src, dim, qpad, ld, stats, q_sq, margin, cand_cnt, cap); break;
+	}
+}
+
+void launch_query_prep_i8(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
+						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s) {
+	switch (metric) {
+		case kL2: hipLaunchKernelGGL((knn_query_prep_i8<kL2>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap); break;
+		case kIP: hipLaunchKernelGGL((knn_query_prep_i8<kIP>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap); break;
+		default: hipLaunchKernelGGL((knn_query_prep_i8<kCos>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap); break;
 	}
 }
 

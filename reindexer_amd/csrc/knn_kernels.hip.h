@@ -71,6 +71,19 @@ struct ScanBf16Params {
 	float* approx;            // [nq][n] approximate distance of every row
 };
 
+// int8-pruned scan (knn_scan_i8.hip: knn_scan_i8 + knn_filter_approx): lower bounds from the int8 shadow, exact tail (knn_i8_quant.h)
+struct ScanI8Params {
+	ScanParams sp;            // n, kk, inv_norms (cosine), part_dist / part_row ([nq][gridDim.x][kk]); the rest unused here
+	const int8_t* codes;      // [n][ld8]
+	const float2* side;       // [n] {s_r, e_r}
+	const int8_t* planes;     // [nq][2][ld8] the query's h and l planes
+	const float2* qinfo;      // [nq] {s_q, |q| rounded up}
+	const float* row_sq;      // L2
+	const float* q_sq;        // L2: [nq]
+	uint32_t ld8;
+	float* lower;             // [nq][n] lower bound of every row's distance
+};
+
 enum : int { kGemmDense = 0, kGemmFilter = 1 };
 
 struct GemmParams {

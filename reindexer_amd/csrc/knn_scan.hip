@@ -5,6 +5,7 @@
 #include <type_traits>
 
 #include "knn_kernels.hip.h"
+#include "knn_scan_common.hip.h"
 #include "rxgpu_internal.h"
 
 #include <cstdlib>
@@ -13,42 +14,11 @@ namespace rxgpu {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kScanThreads = 256;                    // 4 wavefronts per workgroup, one per SIMD
-constexpr int kScanWaves = kScanThreads / kWave;
 constexpr int kMergeThreads = 512;
 constexpr int kMergeWaves = kMergeThreads / kWave;
 constexpr int kMergeAhead = 8;                       // candidate chunks whose loads a merge wavefront keeps in flight
 
-// Workgroup epilogue shared by both scan kernels: fold the per-wave lists into one and store it.
-__device__ __forceinline__ void block_merge_and_store(WaveTopK& top, const ScanParams& p, int lane, int wave) {
-	__shared__ float s_d[kScanWaves][kMaxFusedK];
-	__shared__ uint32_t s_i[kScanWaves][kMaxFusedK];
-	s_d[wave][lane] = top.bd;
-	s_i[wave][lane] = top.bi;
-	__syncthreads();
-	if (wave != 0) return;
-	for (int w = 1; w < kScanWaves; ++w) {
-		const float cd = s_d[w][lane];
-		const uint32_t ci = s_i[w][lane];
-		// lists are sorted: once one entry is rejected the rest of that list is too
-		uint64_t pm = __ballot(ci != kInvalidRow && lane < int(top.kk));
-		while (pm) {
-			const int src = __builtin_ctzll(pm);
-			pm &= pm - 1;
-			const float d = __shfl(cd, src);
-			const uint32_t i = __shfl(ci, src);
-			if (!top.admits(d, i)) break;
-			top.insert(d, i, lane);
-		}
-	}
-	if (lane < int(top.kk)) {
-		const size_t o = (size_t(blockIdx.y) * gridDim.x + blockIdx.x) * top.kk + lane;
-		p.part_dist[o] = top.bd;
-		p.part_row[o] = top.bi;
-	}
-}
-
-// the same for the two-entries-per-lane list (64 < kk <= 128)
+// block_merge_and_store (knn_scan_common.hip.h) for the two-entries-per-lane list (64 < kk <= 128)
 __device__ __forceinline__ void block_merge_and_store(WaveTopK2& top, const ScanParams& p, int lane, int wave) {
 	__shared__ float s_d[kScanWaves][kMaxFusedK2];
 	__shared__ uint32_t s_i[kScanWaves][kMaxFusedK2];
@@ -289,8 +259,8 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_subset_generic(ScanPara
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// bf16-pruned scan (the default for a single query on a large index, see scan_policy_pruned in rxgpu_capi.hip; RXGPU_SCAN_BF16=1 / 0 force it
-// on / off): half the HBM bytes per query, the SAME result bits.
+// bf16-pruned scan (a single query on a large index where the int8 tier of knn_scan_i8.hip does not apply, see scan_policy_tier in
+// rxgpu_capi.hip; RXGPU_SCAN_BF16=1 / 0 force it on / off): half the HBM bytes per query, the SAME result bits.
 //   0. knn_query_prep     (knn_batched.hip) padded copy of the query, |q|^2, the margin 2 eps, cand_cnt = 0 — or cap + 1 for a query without a
 //                         finite bound, which steps 3-4 then leave to the gated exact scan
 //   1. knn_scan_bf16      approximate distance d~ of every row from the bf16 shadow (2 bytes per element), stored ([n] floats) and folded

@@ -1,0 +1,272 @@
+// int8-pruned scan (the default for a single query on a large index whose dimension it serves, see scan_policy_tier in rxgpu_capi.hip;
+// RXGPU_SCAN_I8=1 / 0 force it on / off): ONE byte per element from HBM instead of four, the SAME result bits.
+//   0. knn_query_prep_i8  (knn_batched.hip) padded f32 copy of the query, its two int8 planes, |q|^2, {s_q, |q|^}, the margin, cand_cnt = 0 — or
+//                         cap + 1 for a query (or an index) without a finite bound, which steps 3-4 then leave to the gated exact scan
+//   1. knn_scan_i8        per row the exact integer S_r = dot(t, c_r) from the int8 shadow, d~ and its window [lo_r, up_r]; lo_r is stored
+//                         ([n] floats), up_r is folded into the per-wave top-kk like a distance of the f32 scan
+//   2. knn_merge_lists    -> T, the kk-th smallest upper bound
+//   3. knn_filter_approx  rows with lo_r <= T + margin
+//   4. knn_rescore + knn_merge   EXACT distances of those rows, exact top-kk by (dist, row)
+// The arithmetic, the bound and the soundness argument are in knn_i8_quant.h; nothing here rounds before the integer sum is complete.
+//
+// Mapping.  One 16-lane group owns FOUR consecutive rows per step: lane m loads the 16-byte chunks m, m + 16, ... of each (ld8 / 256 per row;
+// 256 contiguous bytes per group and load, 12 loads per lane and step at 768 dims), double-buffered in registers like knn_scan_fixed.  The two
+// query planes of a lane's chunks stay in registers for the whole kernel.  The four integer sums of a group are reduced over its 16 lanes
+// with a transposing butterfly (4 cross-lane steps instead of 16) that leaves the sum of row j in the lanes with m % 4 == j; lanes m < 4 then
+// own one row each: they have loaded its {s_r, e_r} pair (and |x|^2 or inv_norm) along with the codes, store lo and offer up.  Rows are in
+// increasing order over the lanes of a wavefront and over its steps.
+#include <algorithm>
+#include <cstdlib>
+
+#include "knn_i8_quant.h"
+#include "knn_kernels.hip.h"
+#include "knn_scan_common.hip.h"
+#include "rxgpu_internal.h"
+
+namespace rxgpu {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kI8RowsPerGroup = 4;
+constexpr uint64_t kI8RowsPerWave = 4 * kI8RowsPerGroup;   // rows per wavefront step
+
+__device__ __forceinline__ int i8_dot16(const u32x4& a, const u32x4& b, int acc) {
+	acc = __builtin_amdgcn_sdot4(int(a.x), int(b.x), acc, false);
+	acc = __builtin_amdgcn_sdot4(int(a.y), int(b.y), acc, false);
+	acc = __builtin_amdgcn_sdot4(int(a.z), int(b.z), acc, false);
+	acc = __builtin_amdgcn_sdot4(int(a.w), int(b.w), acc, false);
+	return acc;
+}
+
+// NC8 = ld8 / 256: chunks per lane per row (768 -> 3)
+template <int kMetric, int NC8>
+__global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
+	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t qi = blockIdx.y;
+	u32x4 qh[NC8], ql[NC8];
+	{
+		const u32x4* ph = reinterpret_cast<const u32x4*>(p.planes + size_t(qi) * 2 * p.ld8);
+#pragma unroll
+		for (int t = 0; t < NC8; ++t) {
+			qh[t] = ph[m + 16 * t];
+			ql[t] = ph[16 * NC8 + m + 16 * t];
+		}
+	}
+	const float2 qinfo = p.qinfo[qi];   // {s_q, |q| rounded up}
+	float qq = 0.f;
+	if constexpr (kMetric == kL2) qq = p.q_sq[qi];
+	WaveTopK top;
+	top.init(p.sp.kk);
+	float* lower = p.lower + size_t(qi) * p.sp.n;
+	const uint64_t n = p.sp.n;
+	const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
+	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
+	const uint64_t first = uint64_t(blockIdx.x) * kScanWaves + wave;
+
+	struct Buf {
+		u32x4 x[kI8RowsPerGroup * NC8];
+		float2 side;
+		float aux;
+	};
+	auto issue = [&](Buf& b, uint64_t set) {
+		const uint64_t sc = set < nsets ? set : nsets - 1;   // past the end: re-read the last set (never reduced)
+		const uint64_t r0 = sc * kI8RowsPerWave + uint64_t(g) * kI8RowsPerGroup;
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			uint64_t row = r0 + j;
+			row = row < n ? row : n - 1;
+			const u32x4* src = reinterpret_cast<const u32x4*>(p.codes + row * p.ld8) + m;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) b.x[j * NC8 + t] = __builtin_nontemporal_load(src + 16 * t);
+		}
+		uint64_t mine = r0 + (m & 3);
+		mine = mine < n ? mine : n - 1;
+		b.side = p.side[mine];
+		if constexpr (kMetric == kL2) b.aux = p.row_sq[mine];
+		if constexpr (kMetric == kCos) b.aux = p.sp.inv_norms[mine];
+		if constexpr (kMetric == kIP) b.aux = 0.f;
+	};
+	auto reduce = [&](const Buf& b, uint64_t set) {
+		if (set >= nsets) return;   // wave-uniform
+		int v[kI8RowsPerGroup];
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			int hs = 0, ls = 0;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) {
+				hs = i8_dot16(qh[t], b.x[j * NC8 + t], hs);
+				ls = i8_dot16(ql[t], b.x[j * NC8 + t], ls);
+			}
+			v[j] = hs * 128 + ls;   // this lane's share of dot(t, c): exact (|S| < 2^31, knn_i8_quant.h)
+		}
+		// transposing butterfly over the group's 16 lanes: afterwards lane m holds the complete sum of row m % 4
+		const bool b0 = (m & 1) != 0, b1 = (m & 2) != 0;
+		const int a0 = (b0 ? v[1] : v[0]) + __shfl_xor(b0 ? v[0] : v[1], 1);
+		const int a1 = (b0 ? v[3] : v[2]) + __shfl_xor(b0 ? v[2] : v[3], 1);
+		int s = (b1 ? a1 : a0) + __shfl_xor(b1 ? a0 : a1, 2);
+		s += __shfl_xor(s, 4);
+		s += __shfl_xor(s, 8);
+		const uint64_t row = set * kI8RowsPerWave + uint64_t(g) * kI8RowsPerGroup + (m & 3);
+		const bool valid = row < n && m < kI8RowsPerGroup;
+		float lo, up;
+		i8_bounds(kMetric, i8_ip(qinfo.x, b.side.x, s), qinfo.y, b.side.y, qq, b.aux, lo, up);
+		if (valid) lower[row] = lo;
+		const bool pass = valid && (top.filled < top.kk || up < top.thr_d);
+		uint64_t pm = __ballot(pass);
+		while (pm) {
+			const int src = __builtin_ctzll(pm);
+			pm &= pm - 1;
+			const float d = __shfl(up, src);
+			const uint32_t i = __shfl(uint32_t(row), src);
+			if (top.admits(d, i)) top.insert(d, i, lane);
+		}
+	};
+	if (first < nsets) {
+		Buf xa, xb;
+		issue(xa, first);
+		for (uint64_t set = first; set < nsets; set += 2 * nwaves) {
+			issue(xb, set + nwaves);
+			__builtin_amdgcn_sched_barrier(0);
+			reduce(xa, set);
+			__builtin_amdgcn_sched_barrier(0);
+			issue(xa, set + 2 * nwaves);
+			__builtin_amdgcn_sched_barrier(0);
+			reduce(xb, set + nwaves);
+			__builtin_amdgcn_sched_barrier(0);
+		}
+	}
+	block_merge_and_store(top, p.sp, lane, wave);
+}
+
+// ---- the shadow: codes [n][ld8] (zero pad) and the side pair {s_r, e_r} per row, from the f32 rows (16-byte aligned, stride a multiple of 4
+// floats, as the index keeps them).  One 16-lane group per row, lane m quantises the 16-element chunks m, m + 16, ... (read twice: the scale
+// first); the residual is an fp64 sum over the codes as stored.  Folds max e^2 into stats[3], max
+// (e inv_norm)^2 into stats[4] (cosine) and a non-finite e into stats[2], next to the words of knn_row_stats.
+__global__ __launch_bounds__(256) void knn_i8_build(const float* rows, const float* inv_norms, uint64_t n, uint32_t stride, uint32_t dim, int8_t* codes,
+													 float2* side, uint32_t ld8, unsigned int* stats) {
+	const int lane = threadIdx.x & 63, m = lane & 15;
+	const uint64_t ngroups = uint64_t(gridDim.x) * (blockDim.x / kGroup);
+	const uint64_t gid = (uint64_t(blockIdx.x) * blockDim.x + threadIdx.x) >> 4;
+	const uint64_t rounds = (n + ngroups - 1) / ngroups;
+	const uint32_t nc = ld8 / 256;
+	float me = 0.f, mec = 0.f;
+	bool bad = false;
+	for (uint64_t it = 0; it < rounds; ++it) {   // uniform trip count: every lane takes part in the shuffles
+		const uint64_t row = it * ngroups + gid;
+		const bool ok = row < n;
+		const float* r = rows + (ok ? row : n - 1) * stride;
+		float mx = 0.f;
+		for (uint32_t t = 0; t < nc; ++t) {
+			const uint32_t i0 = (m + 16 * t) * 16;
+#pragma unroll
+			for (uint32_t e = 0; e < 16; e += 4) {
+				if (i0 + e >= dim) continue;
+				const float4 v = *reinterpret_cast<const float4*>(r + i0 + e);   // stride is a multiple of 4 floats: in the row's storage
+				const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+				for (uint32_t c = 0; c < 4; ++c) {
+					if (i0 + e + c < dim) mx = fmaxf(mx, fabsf(x[c]));
+				}
+			}
+		}
+		mx = fmaxf(mx, __shfl_xor(mx, 1));
+		mx = fmaxf(mx, __shfl_xor(mx, 2));
+		mx = fmaxf(mx, __shfl_xor(mx, 4));
+		mx = fmaxf(mx, __shfl_xor(mx, 8));
+		const float s = i8_scale(mx, kI8CodeMax);
+		double r64 = 0.0;
+		for (uint32_t t = 0; t < nc; ++t) {
+			const uint32_t i0 = (m + 16 * t) * 16;
+			uint32_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+			for (uint32_t e = 0; e < 16; e += 4) {
+				if (i0 + e >= dim) continue;
+				const float4 v = *reinterpret_cast<const float4*>(r + i0 + e);
+				const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+				for (uint32_t k = 0; k < 4; ++k) {
+					if (i0 + e + k >= dim) continue;
+					const int c = i8_quantize(x[k], s, kI8CodeMax);
+					const double d = i8_residual(x[k], s, c);
+					r64 += d * d;
+					w[e >> 2] |= (uint32_t(c) & 0xFFu) << (8 * k);
+				}
+			}
+			if (ok) {
+				u32x4 o;
+				o.x = w[0]; o.y = w[1]; o.z = w[2]; o.w = w[3];
+				*reinterpret_cast<u32x4*>(codes + row * ld8 + i0) = o;
+			}
+		}
+		r64 += __shfl_xor(r64, 1);
+		r64 += __shfl_xor(r64, 2);
+		r64 += __shfl_xor(r64, 4);
+		r64 += __shfl_xor(r64, 8);
+		if (ok) {
+			const float e = i8_norm_up(r64);
+			if (m == 0) side[row] = make_float2(s, e);
+			me = fmaxf(me, e * e);
+			bad |= !(e * e < __builtin_inff());
+			if (inv_norms) {
+				const float ei = e * inv_norms[row];
+				mec = fmaxf(mec, ei * ei);
+				bad |= !(ei * ei < __builtin_inff());
+			}
+		}
+	}
+	const bool any_bad = __ballot(bad) != 0;
+	for (int o = 32; o; o >>= 1) {
+		me = fmaxf(me, __shfl_xor(me, o));
+		mec = fmaxf(mec, __shfl_xor(mec, o));
+	}
+	if (lane == 0) {   // non-negative floats order like their bit patterns
+		atomicMax(&stats[3], __float_as_uint(me));
+		atomicMax(&stats[4], __float_as_uint(mec));
+		if (any_bad) atomicMax(&stats[2], 1u);
+	}
+}
+
+// ------------------------------------------------------------------------------------------ launchers
+
+// rows / inv_norms / codes / side point at the first row of the range
+void launch_i8_build(const float* rows, const float* inv_norms, uint64_t n, uint32_t stride, uint32_t dim, int8_t* codes, float2* side, uint32_t ld8,
+					 unsigned int* stats, int cus, hipStream_t s) {
+	if (!n) return;
+	const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((n + 15) / 16, uint64_t(cus) * 8));
+	hipLaunchKernelGGL(knn_i8_build, dim3(uint32_t(blocks)), dim3(256), 0, s, rows, inv_norms, n, stride, dim, codes, side, ld8, stats);
+}
+
+// Load depth: two buffers of 4 rows per group = 2 x 12 KB per wavefront at 768 dims, 96 KiB per buffer set and CU at 2 workgroups per CU (what
+// knn_scan_bf16_blk keeps in flight).  RXGPU_SCAN_I8_WG_PER_CU overrides it (read per call: A/B runs inside one process).
+constexpr int kScanI8WgPerCu = 2;
+uint32_t scan_i8_grid_x(uint64_t n, int cus) {
+	int wg = kScanI8WgPerCu;
+	if (const char* e = getenv("RXGPU_SCAN_I8_WG_PER_CU")) wg = atoi(e);
+	wg = wg < 1 ? 1 : wg > 8 ? 8 : wg;
+	const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
+	const uint64_t want = (nsets + kScanWaves - 1) / kScanWaves;
+	const uint64_t cap = uint64_t(cus) * wg;
+	return uint32_t(want < cap ? (want ? want : 1) : cap);
+}
+
+template <int kMetric>
+static void launch_scan_i8_metric(const ScanI8Params& p, dim3 grid, hipStream_t s) {
+	switch (p.ld8 / 256) {
+		case 1: hipLaunchKernelGGL((knn_scan_i8<kMetric, 1>), grid, dim3(kScanThreads), 0, s, p); break;
+		case 2: hipLaunchKernelGGL((knn_scan_i8<kMetric, 2>), grid, dim3(kScanThreads), 0, s, p); break;
+		case 3: hipLaunchKernelGGL((knn_scan_i8<kMetric, 3>), grid, dim3(kScanThreads), 0, s, p); break;
+		default: hipLaunchKernelGGL((knn_scan_i8<kMetric, 4>), grid, dim3(kScanThreads), 0, s, p); break;
+	}
+}
+// p.ld8 must be i8_ld(dim) of a dimension with i8_dim_supported(dim)
+void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s) {
+	const dim3 grid(gridx, nq);
+	switch (metric) {
+		case kL2: launch_scan_i8_metric<kL2>(p, grid, s); break;
+		case kIP: launch_scan_i8_metric<kIP>(p, grid, s); break;
+		default: launch_scan_i8_metric<kCos>(p, grid, s); break;
+	}
+}
+
+}  // namespace rxgpu

@@ -8,6 +8,7 @@
 #include <numeric>
 
 #include "../../include/rxgpu.h"
+#include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
 
@@ -143,6 +144,7 @@ void rxgpu_search_ctx::release() {
 	d_gcand_d.release();
 	d_redo.release();
 	d_top.release();
+	d_qplanes.release();
 	d_subset.release();
 	d_bitmap.release();
 	d_tiles.release();
@@ -289,8 +291,10 @@ static int batch_min_queries() {
 	return v;
 }
 
-// The three statistics words back on the host (h->mtx held): are the maxima finite and has no NaN row been seen?  Only then does the rounding
-// bound of the bf16-pruned scan mean anything; the automatic scan policy (enqueue_knn) keeps such an index on the f32 scan.
+// The statistics words back on the host (h->mtx held): are the maxima finite and has no NaN row been seen?  Only then does the rounding
+// bound of a pruned scan mean anything; the automatic scan policy (enqueue_knn) keeps such an index on the f32 scan.  Words 3 and 4 (the
+// int8 shadow's residual maxima, knn_scan_i8.hip) report a non-finite value through word 2.
+constexpr size_t kStatsWords = 5;
 int read_stats_finite(rxgpu_index* h, hipStream_t s) {
 	unsigned int w[3] = {0, 0, 0};
 	RX_HIP(hipMemcpyAsync(w, h->d_stats, sizeof(w), hipMemcpyDeviceToHost, s));
@@ -306,7 +310,7 @@ int read_stats_finite(rxgpu_index* h, hipStream_t s) {
 int ensure_row_stats(rxgpu_index* h, hipStream_t s) {
 	std::lock_guard<std::mutex> lk(h->mtx);
 	if (h->stats_valid) return RXGPU_OK;
-	if (!h->d_stats) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats), 3 * sizeof(unsigned int)));
+	if (!h->d_stats) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats), kStatsWords * sizeof(unsigned int)));
 	if (h->metric == RXGPU_METRIC_L2 && h->row_sq_capacity < h->count) {
 		if (h->d_row_sq) (void)hipFree(h->d_row_sq);
 		h->d_row_sq = nullptr;
@@ -314,7 +318,8 @@ int ensure_row_stats(rxgpu_index* h, hipStream_t s) {
 		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_row_sq), std::max<uint64_t>(h->capacity, h->count) * sizeof(float)));
 		h->row_sq_capacity = std::max<uint64_t>(h->capacity, h->count);
 	}
-	RX_HIP(hipMemsetAsync(h->d_stats, 0, 3 * sizeof(unsigned int), s));
+	RX_HIP(hipMemsetAsync(h->d_stats, 0, kStatsWords * sizeof(unsigned int), s));
+	h->i8_valid = false;   // its two words were cleared with the rest: the shadow's next build folds them in again
 	rxgpu::launch_row_stats(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->metric == RXGPU_METRIC_L2 ? h->d_row_sq : nullptr,
 							h->d_stats, h->cus, s);
 	RX_HIP(hipGetLastError());
@@ -351,6 +356,38 @@ int ensure_bf16_shadow(rxgpu_index* h, hipStream_t s) {
 	return RXGPU_OK;
 }
 
+// int8 shadow of the rows for the pruning pass of a single query (knn_scan_i8.hip): 1 byte per element + 8 bytes per row on top of the 4-byte
+// rows; built lazily behind the row statistics (it folds two more maxima into their words) and kept in step by the mutations like the bf16 shadow.
+int ensure_i8_shadow(rxgpu_index* h, hipStream_t s) {
+	if (int rc = ensure_row_stats(h, s); rc) return rc;
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->i8_valid) return RXGPU_OK;
+	const uint32_t ld8 = rxgpu::i8_ld(h->dim);
+	const uint64_t need = std::max<uint64_t>(h->capacity, h->count);
+	if (h->i8_capacity < need) {
+		if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
+		if (h->d_side_i8) (void)hipFree(h->d_side_i8);
+		h->d_codes_i8 = nullptr;
+		h->d_side_i8 = nullptr;
+		h->i8_capacity = 0;
+		if (hipMalloc(reinterpret_cast<void**>(&h->d_codes_i8), need * ld8) != hipSuccess ||
+			hipMalloc(reinterpret_cast<void**>(&h->d_side_i8), need * sizeof(float2)) != hipSuccess) {
+			(void)hipGetLastError();   // not an error of the search: the caller takes the bf16 tier
+			if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
+			h->d_codes_i8 = nullptr;
+			h->d_side_i8 = nullptr;
+			h->i8_unavailable = true;
+			return RXGPU_ERR_NOMEM;
+		}
+		h->i8_capacity = need;
+	}
+	rxgpu::launch_i8_build(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->d_codes_i8, h->d_side_i8, ld8, h->d_stats, h->cus, s);
+	RX_HIP(hipGetLastError());
+	if (int rc = read_stats_finite(h, s); rc) return rc;   // synchronises the stream
+	h->i8_valid = true;
+	return RXGPU_OK;
+}
+
 static int batch_bf16_min_queries() {   // read per call (tests and A/B runs switch it)
 	const char* e = getenv("RXGPU_BATCH_BF16_MIN");   // 0 disables the bf16 nomination path
 	return e ? atoi(e) : 2;   // measured at 10M x 768: 4.8-5.0 ms per batch for 8..256 queries against 6.2-10.6 ms on the f32 rows
@@ -380,6 +417,7 @@ int enqueue_knn_batched_bf16(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	float* margin = q_sq + mt;
 	float* thr = q_sq + 2 * mt;
 	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
+	c->pruned_cap = cap;
 	RX_HIP(hipMemsetAsync(qpad, 0, size_t(mt) * q_stride * sizeof(float), c->stream));
 	RX_HIP(hipMemcpy2DAsync(qpad, q_stride * sizeof(float), d_queries + size_t(q0) * h->dim, h->dim * sizeof(float), h->dim * sizeof(float), cq,
 							hipMemcpyDeviceToDevice, c->stream));
@@ -477,6 +515,7 @@ int enqueue_knn_batched(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_quer
 		float* margin = q_sq + mt;
 		float* thr = q_sq + 2 * mt;
 		uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
+	c->pruned_cap = cap;
 		RX_HIP(hipMemsetAsync(qpad, 0, size_t(mt) * q_stride * sizeof(float), c->stream));
 		RX_HIP(hipMemcpy2DAsync(qpad, q_stride * sizeof(float), d_queries + size_t(q0) * h->dim, h->dim * sizeof(float),
 								h->dim * sizeof(float), cq, hipMemcpyDeviceToDevice, c->stream));
@@ -574,12 +613,38 @@ static uint64_t pruned_auto_min_bytes() {
 	const char* e = getenv("RXGPU_SCAN_BF16_MIN_BYTES");
 	return e && *e ? strtoull(e, nullptr, 10) : kPrunedAutoMinBytes;
 }
-// The whole decision, without a device: does a call with nq queries on rows x dim f32 rows take the bf16-pruned scan?
-static bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite) {
+// The int8 tier (knn_scan_i8.hip) refines a call the automatic mode above already accepts.  RXGPU_SCAN_I8, read per call: 0 = this tier off,
+// 1 = forced at any size (up to kPrunedMaxQueries queries; for tests and A/B), unset = automatic: indexes of at least kPrunedI8AutoMinBytes of
+// f32 rows.  RXGPU_SCAN_BF16=0 (the f32 paths, always) and =1 (the bf16 tier, exactly) both win over it.
+// kPrunedI8AutoMinBytes: the measured crossover against the bf16 tier (and the f32 scan) is 0.6 GB of f32 rows at 768 dims
+// (profiles/scan_i8_crossover.json), rounded up to a power of two and never below 1 GiB, like kPrunedAutoMinBytes.  RXGPU_SCAN_I8_MIN_BYTES
+// overrides it.
+constexpr uint64_t kPrunedI8AutoMinBytes = 1ull << 30;
+static ScanBf16Mode scan_i8_mode() {
+	const char* e = getenv("RXGPU_SCAN_I8");
+	if (!e || !*e) return kScanBf16Auto;
+	return atoi(e) != 0 ? kScanBf16On : kScanBf16Off;
+}
+static uint64_t pruned_i8_auto_min_bytes() {
+	const char* e = getenv("RXGPU_SCAN_I8_MIN_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8AutoMinBytes;
+}
+enum ScanTier { kTierF32 = 0, kTierBf16 = 1, kTierI8 = 2 };
+// The whole decision, without a device: which scan does a call with nq queries on rows x dim f32 rows take?
+static ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool bf16_available, bool i8_available, bool stats_finite) {
 	const ScanBf16Mode mode = scan_bf16_mode();
-	if (mode == kScanBf16Off || !shadow_available || !rxgpu::scan_bf16_supported((dim + 63u) & ~63u)) return false;
-	if (mode == kScanBf16On) return nq <= kPrunedMaxQueries;
-	return nq == 1 && stats_finite && rows * dim * sizeof(float) >= pruned_auto_min_bytes();
+	if (mode == kScanBf16Off) return kTierF32;
+	const ScanBf16Mode i8 = scan_i8_mode();
+	const bool i8_can = mode == kScanBf16Auto && i8 != kScanBf16Off && i8_available && rxgpu::i8_dim_supported(dim);
+	if (i8_can && i8 == kScanBf16On && nq <= kPrunedMaxQueries) return kTierI8;
+	if (!bf16_available || !rxgpu::scan_bf16_supported((dim + 63u) & ~63u)) return kTierF32;
+	if (mode == kScanBf16On) return nq <= kPrunedMaxQueries ? kTierBf16 : kTierF32;
+	if (!(nq == 1 && stats_finite && rows * dim * sizeof(float) >= pruned_auto_min_bytes())) return kTierF32;
+	return i8_can && rows * dim * sizeof(float) >= pruned_i8_auto_min_bytes() ? kTierI8 : kTierBf16;
+}
+// ... does it take a pruned scan at all?
+static bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite) {
+	return scan_policy_tier(rows, dim, nq, shadow_available, shadow_available, stats_finite) != kTierF32;
 }
 constexpr uint32_t kPrunedCap = 4096;
 
@@ -608,6 +673,7 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
 	uint32_t* top_cnt = top_row + size_t(nq) * kk;
 	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
+	c->pruned_cap = cap;
 	// one launch: padded copy of the query, |q|^2, margin, cand_cnt = 0 (cap + 1 for a query without a finite bound: the gated exact scan answers it)
 	rxgpu::launch_query_prep(h->metric, d_queries, nq, h->dim, qpad, ld, h->d_stats, q_sq, margin, cand_cnt, cap, c->stream);
 	rxgpu::ScanBf16Params p{};
@@ -637,6 +703,89 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 	{
 		ProfileScope ps(h, "rescore", c->stream);
 		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, ld, h->stride, h->dim, nq, cap, cand_cnt,
+							  static_cast<uint32_t*>(c->d_cand_row.ptr), static_cast<float*>(c->d_cand_dist.ptr), c->stream);
+	}
+	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
+						d_out_count, nullptr, 0, c->stream);
+	{   // more rows inside the bound than the list holds (massive ties), or no finite bound: the f32 path's own scan + merge, gated on device
+		rxgpu::ScanParams e{};
+		e.rows = h->d_rows;
+		e.inv_norms = h->d_inv_norms;
+		e.queries = d_queries;
+		e.n = h->count;
+		e.stride = h->stride;
+		e.dim = h->dim;
+		e.kk = kk;
+		e.part_dist = p.sp.part_dist;
+		e.part_row = p.sp.part_row;
+		e.gate_cnt = cand_cnt;
+		e.gate_cap = cap;
+		ProfileScope ps(h, "fallback_scan", c->stream);
+		rxgpu::launch_scan(h->metric, e, nq, gridx_exact, c->stream);
+		rxgpu::launch_merge_lists(e.part_dist, e.part_row, gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, cand_cnt, cap);
+	}
+	RX_HIP(hipGetLastError());
+	return RXGPU_OK;
+}
+
+// The int8 tier of the same chain: knn_query_prep_i8 and knn_scan_i8 in front, per-row LOWER bounds where the bf16 chain keeps approximate
+// distances, everything behind the scan as above (same buffers, same cap).
+int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
+						  uint32_t* d_out_row, uint32_t* d_out_count) {
+	if (int rc = ensure_i8_shadow(h, c->stream); rc) return rc;   // (the row statistics first)
+	const uint32_t ld8 = rxgpu::i8_ld(h->dim);
+	const uint32_t gridx = rxgpu::scan_i8_grid_x(h->count, h->cus);
+	const uint32_t gridx_exact = rxgpu::scan_grid_x(h->count, h->cus);   // the gated f32 scan's
+	const uint32_t grid_max = std::max(gridx, gridx_exact);
+	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (h->count + 63) & ~63ull)));
+	if (int rc = c->d_qpad.ensure(size_t(nq) * ld8 * sizeof(float)); rc) return rc;
+	if (int rc = c->d_qplanes.ensure(size_t(nq) * 2 * ld8); rc) return rc;
+	if (int rc = c->d_qstats.ensure(size_t(4) * nq * sizeof(float)); rc) return rc;
+	if (int rc = c->d_dense.ensure(size_t(nq) * h->count * sizeof(float)); rc) return rc;
+	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
+	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
+	if (int rc = c->d_cand_cnt.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
+	float* qpad = static_cast<float*>(c->d_qpad.ptr);
+	float2* qinfo = static_cast<float2*>(c->d_qstats.ptr);   // [nq] pairs, then [nq] |q|^2, [nq] margins
+	float* q_sq = reinterpret_cast<float*>(qinfo + nq);
+	float* margin = q_sq + nq;
+	float* top_dist = static_cast<float*>(c->d_top.ptr);
+	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
+	uint32_t* top_cnt = top_row + size_t(nq) * kk;
+	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
+	c->pruned_cap = cap;
+	rxgpu::launch_query_prep_i8(h->metric, d_queries, nq, h->dim, qpad, static_cast<int8_t*>(c->d_qplanes.ptr), ld8, h->d_stats, q_sq, margin, qinfo,
+								cand_cnt, cap, c->stream);
+	rxgpu::ScanI8Params p{};
+	p.sp.inv_norms = h->d_inv_norms;
+	p.sp.n = h->count;
+	p.sp.kk = kk;
+	p.sp.part_dist = static_cast<float*>(c->d_part_dist.ptr);
+	p.sp.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
+	p.codes = h->d_codes_i8;
+	p.side = h->d_side_i8;
+	p.planes = static_cast<const int8_t*>(c->d_qplanes.ptr);
+	p.qinfo = qinfo;
+	p.row_sq = h->d_row_sq;
+	p.q_sq = q_sq;
+	p.ld8 = ld8;
+	p.lower = static_cast<float*>(c->d_dense.ptr);
+	{
+		ProfileScope ps(h, "scan_i8", c->stream);
+		rxgpu::launch_scan_i8(h->metric, p, nq, gridx, c->stream);
+	}
+	rxgpu::launch_merge_lists(p.sp.part_dist, p.sp.part_row, gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
+	{
+		ProfileScope ps(h, "filter_approx", c->stream);
+		rxgpu::launch_filter_approx(p.lower, h->count, top_dist, top_cnt, kk, margin, static_cast<uint32_t*>(c->d_cand_row.ptr), cand_cnt, cap, nq,
+									h->cus, c->stream);
+	}
+	{
+		ProfileScope ps(h, "rescore", c->stream);
+		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, ld8, h->stride, h->dim, nq, cap, cand_cnt,
 							  static_cast<uint32_t*>(c->d_cand_row.ptr), static_cast<float*>(c->d_cand_dist.ptr), c->stream);
 	}
 	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
@@ -752,10 +901,14 @@ int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries
 int enqueue_knn(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
 				uint32_t* d_out_row, uint32_t* d_out_count) {
 	// (automatic mode asks whether the row statistics are finite: compute them first where everything else already says yes)
-	if (scan_bf16_mode() == kScanBf16Auto && scan_policy_pruned(h->count, h->dim, nq, !h->bf16_unavailable, true)) {
+	if (scan_bf16_mode() == kScanBf16Auto && scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, true) != kTierF32) {
 		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
 	}
-	if (scan_policy_pruned(h->count, h->dim, nq, !h->bf16_unavailable, h->stats_finite)) {
+	if (scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, h->stats_finite) == kTierI8) {
+		const int rc = enqueue_knn_pruned_i8(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
+		if (!(rc == RXGPU_ERR_NOMEM && h->i8_unavailable)) return rc;   // no room for the int8 shadow: the bf16 tier below
+	}
+	if (scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, h->stats_finite) == kTierBf16) {
 		const int rc = enqueue_knn_pruned(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
 		if (!(rc == RXGPU_ERR_NOMEM && h->bf16_unavailable)) return rc;
 	}
@@ -772,6 +925,17 @@ int rxgpu_abi_version(void) { return RXGPU_ABI_VERSION; }
 
 int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
 	return scan_policy_pruned(rows, dim, nq, shadow_available != 0, stats_finite != 0) ? 1 : 0;
+}
+
+int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
+	return int(scan_policy_tier(rows, dim, nq, shadow_available != 0, shadow_available != 0, stats_finite != 0));
+}
+
+int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap) {
+	RX_CHECK(h && out_count && out_cap, RXGPU_ERR_PARAMS, "rxgpu_index_last_candidates: null argument");
+	*out_count = h->last_cand_count.load();
+	*out_cap = h->last_cand_cap.load();
+	return RXGPU_OK;
 }
 
 int rxgpu_device_count(void) {
@@ -857,6 +1021,8 @@ void rxgpu_index_destroy(rxgpu_index* h) {
 	if (h->d_row_sq) (void)hipFree(h->d_row_sq);
 	if (h->d_row_ids) (void)hipFree(h->d_row_ids);
 	if (h->d_rows_bf16) (void)hipFree(h->d_rows_bf16);
+	if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
+	if (h->d_side_i8) (void)hipFree(h->d_side_i8);
 	if (h->d_stats) (void)hipFree(h->d_stats);
 	if (h->d_links0) (void)hipFree(h->d_links0);
 	if (h->d_upper_off) (void)hipFree(h->d_upper_off);
@@ -948,6 +1114,16 @@ int rxgpu_index_upload_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, cons
 			rxgpu::launch_to_bf16(dst, n, h->stride, h->dim, h->d_rows_bf16, ld, h->cus, nullptr, first_row, h->bf16_blocked);
 		}
 	}
+	if (h->i8_valid) {
+		if (h->i8_capacity < first_row + n || !h->stats_valid) {
+			h->i8_valid = false;
+		} else {   // re-quantise the range; its residual maxima join the statistics words
+			const uint32_t ld8 = rxgpu::i8_ld(h->dim);
+			rxgpu::launch_i8_build(dst, h->d_inv_norms ? h->d_inv_norms + first_row : nullptr, n, h->stride, h->dim, h->d_codes_i8 + first_row * ld8,
+								   h->d_side_i8 + first_row, ld8, h->d_stats, h->cus, nullptr);
+			if (int rc = read_stats_finite(h, nullptr); rc) return rc;
+		}
+	}
 	RX_HIP(hipGetLastError());
 	RX_HIP(hipStreamSynchronize(nullptr));
 	return RXGPU_OK;
@@ -975,6 +1151,7 @@ int rxgpu_index_adopt_device_rows(rxgpu_index* h, const void* d_rows, uint64_t n
 	h->count = n;
 	h->stats_valid = false;
 	h->bf16_valid = false;
+	h->i8_valid = false;
 	return RXGPU_OK;
 }
 
@@ -997,6 +1174,11 @@ int rxgpu_index_move_row(rxgpu_index* h, uint64_t from, uint64_t to) {
 		rxgpu::launch_shadow_move(h->d_rows_bf16, ld, from, to, h->bf16_blocked, nullptr);
 		RX_HIP(hipGetLastError());
 		RX_HIP(hipStreamSynchronize(nullptr));
+	}
+	if (h->i8_valid) {
+		const uint32_t ld8 = rxgpu::i8_ld(h->dim);
+		RX_HIP(hipMemcpy(h->d_codes_i8 + to * ld8, h->d_codes_i8 + from * ld8, ld8, hipMemcpyDeviceToDevice));
+		RX_HIP(hipMemcpy(h->d_side_i8 + to, h->d_side_i8 + from, sizeof(float2), hipMemcpyDeviceToDevice));
 	}
 	return RXGPU_OK;
 }
@@ -1023,6 +1205,7 @@ int rxgpu_index_truncate(rxgpu_index* h, uint64_t count) {
 	if (count > h->count) {
 		h->stats_valid = false;
 		h->bf16_valid = false;
+		h->i8_valid = false;
 	}
 	h->count = count;
 	return RXGPU_OK;
@@ -1158,6 +1341,7 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 		if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
 		// kk <= 64: fused / batched / pruned dispatch; 64 < kk <= 128 (e.g. hybrid k = 100): the fused scan with two list entries per lane
 		auto* run = eff <= uint32_t(rxgpu::kMaxFusedK) ? enqueue_knn : enqueue_knn_fused;
+		c->pruned_cap = 0;   // set by a pruned chain
 		if (int rc = run(h, c, static_cast<const float*>(c->d_queries.ptr), nq, eff, static_cast<float*>(c->d_out_dist.ptr),
 						 static_cast<uint32_t*>(c->d_out_row.ptr), static_cast<uint32_t*>(c->d_out_count.ptr));
 			rc)
@@ -1173,6 +1357,12 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 		}
 		RX_HIP(hipMemcpyAsync(out_count, c->d_out_count.ptr, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 		RX_HIP(hipStreamSynchronize(c->stream));
+		if (h->profiling && nq == 1 && c->pruned_cap) {   // rxgpu_index_last_candidates: what the pruned chain of this call nominated
+			uint32_t cnt = 0;
+			RX_HIP(hipMemcpy(&cnt, c->d_cand_cnt.ptr, sizeof(cnt), hipMemcpyDeviceToHost));
+			h->last_cand_count = cnt;
+			h->last_cand_cap = c->pruned_cap;
+		}
 		return RXGPU_OK;
 	}
 

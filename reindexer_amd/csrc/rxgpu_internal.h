@@ -23,6 +23,13 @@ struct ScanBf16Params;
 bool scan_bf16_supported(uint32_t ld);
 uint32_t scan_bf16_grid_x(uint64_t n, int cus);
 void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
+struct ScanI8Params;   // int8-pruned scan (knn_scan_i8.hip; the query side: knn_query_prep_i8 in knn_batched.hip)
+uint32_t scan_i8_grid_x(uint64_t n, int cus);
+void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
+void launch_i8_build(const float* rows, const float* inv_norms, uint64_t n, uint32_t stride, uint32_t dim, int8_t* codes, float2* side, uint32_t ld8,
+					 unsigned int* stats, int cus, hipStream_t s);   // every pointer at the first row of the range
+void launch_query_prep_i8(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
+						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s);
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
 						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s);
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
@@ -416,9 +423,11 @@ struct rxgpu_search_ctx {
 	rxgpu_devbuf d_qpad, d_qstats, d_dense, d_cand_row, d_cand_dist, d_cand_cnt;   // batched path
 	rxgpu_devbuf d_visited, d_gcand_d, d_redo;                                     // HNSW (d_gcand_d: (dist bits, id) entries)
 	rxgpu_devbuf d_helper, d_helper_bits;                                          // HNSW: overflow queue of a batch, bitsets of its helper workgroups
-	rxgpu_devbuf d_top;                                                            // bf16-pruned scan: approximate top lists
+	rxgpu_devbuf d_top;                                                            // bf16- / int8-pruned scan: approximate top lists
+	rxgpu_devbuf d_qplanes;                                                        // int8-pruned scan: the query's two int8 planes
 	rxgpu_devbuf d_ivf;                                                            // IVF: the coarse search's lists, distances, count
 	rxgpu_devbuf d_subset, d_bitmap, d_tiles;                                      // pre-filtered search: row list, allowed-rows bitmap, tile sums
+	uint32_t pruned_cap = 0;   // candidate capacity of the pruned chain the current call enqueued (0: none) — rxgpu_index_last_candidates
 	void* h_pinned = nullptr;
 	size_t h_pinned_bytes = 0;
 	// second stream + events (created on first use): work that does not depend on the query upload — zeroing the visited bitsets of an
@@ -528,6 +537,13 @@ struct rxgpu_index {
 	bool bf16_blocked = true;   // layout of the shadow (knn_kernels.hip.h); RXGPU_SHADOW_BLOCKED=0 when the shadow is first built: row-major (A/B)
 	bool bf16_valid = false;
 	bool bf16_unavailable = false;     // the shadow did not fit in HBM: nominate on the f32 rows instead (still exact, still on the GPU)
+	// int8 shadow of the rows for the pruning pass of a single query (knn_scan_i8.hip), built lazily and kept in step like the bf16 shadow
+	int8_t* d_codes_i8 = nullptr;      // [i8_capacity][i8_ld(dim)]
+	float2* d_side_i8 = nullptr;       // [i8_capacity] {scale, residual bound}
+	uint64_t i8_capacity = 0;
+	bool i8_valid = false;
+	bool i8_unavailable = false;       // it did not fit in HBM: the call takes the bf16 tier
+	std::atomic<uint32_t> last_cand_count{0}, last_cand_cap{0};   // rxgpu_index_last_candidates
 
 	// HNSW graph mirror (rxgpu_hnsw_attach_graph)
 	uint32_t* d_links0 = nullptr;

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
-"""Where does the bf16-pruned single-query scan start to pay?  (GPU box only.)
+"""Where do the bf16-pruned and the int8-pruned single-query scans start to pay?  (GPU box only.)
 
     python tools/scan_policy_crossover.py [--dim 768] [--rows 100000,...,10000000] [--rounds 5] [--queries 40] [--out FILE]
     python tools/scan_policy_crossover.py --ab RXGPU_SCAN_BF16_WG_PER_CU=2,3,4 --rows 10000000   # a tuning knob of the bf16 scan, same method
+    python tools/scan_policy_crossover.py --ab RXGPU_SCAN_I8_WG_PER_CU=2,3 --rows 10000000       # ... of the int8 scan (a knob named RXGPU_SCAN_I8_*)
 
-One process, one resident corpus per size; per size the two series (RXGPU_SCAN_BF16=0 and =1, read by the library on every call) ALTERNATE,
+One process, one resident corpus per size; per size the three series (RXGPU_SCAN_BF16=0, =1, and RXGPU_SCAN_I8=1 with RXGPU_SCAN_BF16 unset,
+read by the library on every call; the int8 series only at dimensions that tier serves) ALTERNATE,
 --rounds times each, every round timing --queries single-query searches through rxgpu_search_knn_device with one synchronisation at the end
 (what bench.py calls ms_per_step).  Reported per size and series: median, min, max of the rounds.  The pruned path "wins" at a size when its
 worst round beats the f32 path's best round; the automatic threshold in rxgpu_capi.hip (kPrunedAutoMinBytes) is the smallest such size in
-bytes of f32 rows, rounded up to a power of two, and never below 1 GiB.
+bytes of f32 rows, rounded up to a power of two, and never below 1 GiB.  The int8 tier's threshold (kPrunedI8AutoMinBytes) follows the same
+rule against the bf16 series.
 """
 import argparse
 import json
@@ -31,6 +34,14 @@ def time_round(ix, q, out_d, out_r, dim, kk, nq, stream, device):
         ix.search_knn_device(q.data_ptr() + i * dim * 4, 1, kk, out_d.data_ptr() + i * kk * 4, out_r.data_ptr() + i * kk * 4, None, stream)
     torch.cuda.synchronize(device)
     return (time.perf_counter() - t0) / nq * 1e3
+
+
+def set_env(env):
+    for k, v in env.items():   # None: unset
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
 
 
 def series(v):
@@ -68,9 +79,14 @@ def main():
     out_r = torch.empty((args.queries, kk), dtype=torch.int32, device=device)
     if args.ab:
         knob, vals = args.ab.split("=", 1)
-        variants = [("%s=%s" % (knob, w), {"RXGPU_SCAN_BF16": "1", knob: w}) for w in vals.split(",")]
+        base = {"RXGPU_SCAN_BF16": None, "RXGPU_SCAN_I8": "1"} if knob.startswith("RXGPU_SCAN_I8") else {"RXGPU_SCAN_BF16": "1", "RXGPU_SCAN_I8": None}
+        variants = [("%s=%s" % (knob, w), {**base, knob: w}) for w in vals.split(",")]
     else:
-        variants = [("f32", {"RXGPU_SCAN_BF16": "0"}), ("pruned", {"RXGPU_SCAN_BF16": "1"})]
+        variants = [("f32", {"RXGPU_SCAN_BF16": "0", "RXGPU_SCAN_I8": None}), ("pruned", {"RXGPU_SCAN_BF16": "1", "RXGPU_SCAN_I8": None})]
+        os.environ.pop("RXGPU_SCAN_BF16", None)
+        os.environ["RXGPU_SCAN_I8"] = "1"
+        if capi.scan_tier(1000, args.dim) == 2:
+            variants.append(("int8", {"RXGPU_SCAN_BF16": None, "RXGPU_SCAN_I8": "1"}))
     result = {"dim": args.dim, "metric": args.metric, "k": args.k, "queries_per_round": args.queries, "rounds": args.rounds,
               "arch": capi.device_arch(0), "ab": args.ab, "sizes": []}
     for n in sizes:
@@ -78,18 +94,20 @@ def main():
             ix.adopt_device_rows(corpus.data_ptr(), n, args.dim, d_inv.data_ptr() if d_inv is not None else None, keepalive=(corpus, d_inv))
             times = {name: [] for name, _ in variants}
             for name, env in variants:   # warm-up: statistics, shadow, buffers
-                os.environ.update(env)
+                set_env(env)
                 time_round(ix, q, out_d, out_r, args.dim, kk, 4, stream, device)
             for _ in range(args.rounds):
                 for name, env in variants:
-                    os.environ.update(env)
+                    set_env(env)
                     times[name].append(time_round(ix, q, out_d, out_r, args.dim, kk, args.queries, stream, device))
             entry = {"rows": n, "f32_bytes": n * args.dim * 4, **{name: series(v) for name, v in times.items()}}
             if not args.ab:
                 entry["pruned_wins_beyond_spread"] = max(times["pruned"]) < min(times["f32"])
+                if "int8" in times:
+                    entry["int8_wins_beyond_spread"] = max(times["int8"]) < min(times["pruned"]) and max(times["int8"]) < min(times["f32"])
             result["sizes"].append(entry)
             print(json.dumps(entry), flush=True)
-    for k_ in ["RXGPU_SCAN_BF16"] + ([args.ab.split("=", 1)[0]] if args.ab else []):
+    for k_ in ["RXGPU_SCAN_BF16", "RXGPU_SCAN_I8"] + ([args.ab.split("=", 1)[0]] if args.ab else []):
         os.environ.pop(k_, None)
     if not args.ab:
         wins = [e["f32_bytes"] for e in result["sizes"] if e["pruned_wins_beyond_spread"]]
@@ -100,6 +118,13 @@ def main():
             p2 = 1 << (first - 1).bit_length()
             result["threshold_bytes"] = max(p2, 1 << 30)
             result["threshold_rule"] = "smallest winning size rounded up to a power of two, not below 1 GiB"
+        if any("int8_wins_beyond_spread" in e for e in result["sizes"]):   # the int8 tier against the bf16 tier (and the f32 scan), same rule
+            wins = [e["f32_bytes"] for e in result["sizes"] if e["int8_wins_beyond_spread"]]
+            losing_above = [e["f32_bytes"] for e in result["sizes"] if not e["int8_wins_beyond_spread"]]
+            first = min((b for b in wins if all(b > l for l in losing_above)), default=None)
+            result["int8_smallest_winning_f32_bytes"] = first
+            if first:
+                result["int8_threshold_bytes"] = max(1 << (first - 1).bit_length(), 1 << 30)
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
