@@ -172,7 +172,7 @@ int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_avail
  * tier off, 1 = forced for up to 8 queries at any size; RXGPU_SCAN_BF16=0 and =1 both win over it.  shadow_available stands for the shadow of
  * either tier. */
 int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite);
-/* Candidates the last pruned single-query search through rxgpu_search_knn nominated for the exact re-score, and the capacity of their list
+/* Candidates the last pruned single-query search through rxgpu_search_knn (or rxgpu_search_knn_subset / _bitmap / _lists) nominated for the exact re-score, and the capacity of their list
  * (count > cap: the list overflowed, or the query had no finite bound, and the exact scan answered).  Recorded only while profiling is
  * enabled (rxgpu_profile_enable). */
 int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap);
@@ -190,18 +190,31 @@ int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint3
  *   allowed (bits at and above `count` are ignored); expanded to the row list on the device; best for dense filters
  *   (count / 8 bytes on the wire).  *out_allowed (optional) = number of allowed rows.
  * Output layout as rxgpu_search_knn: host [nq][kk], out_count[q] = min(kk, allowed rows); any kk.
- * Errors: RXGPU_ERR_PARAMS for an unsorted / out-of-range list or a short bitmap. */
+ * Errors: RXGPU_ERR_PARAMS for an unsorted / out-of-range list or a short bitmap.
+ * Which scan serves them: the f32 gather scan (knn_scan_subset) unless rxgpu_scan_tier_subset() says 2 for the call; then the int8 shadow of
+ * rxgpu_scan_tier is read for the listed rows (1 byte per element instead of 4) and the exact kernels re-score the survivors of its bound:
+ * the same rows and distance bits.  The first such call on an index builds the shadow. */
 int rxgpu_search_knn_subset(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* row_ids, uint64_t n_ids,
 							float* out_dist, uint32_t* out_row, uint32_t* out_count);
 int rxgpu_search_knn_bitmap(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* allowed_words,
 							uint64_t n_words, float* out_dist, uint32_t* out_row, uint32_t* out_count, uint64_t* out_allowed);
+/* Which scan a search over a row list takes (rxgpu_search_knn_subset / _bitmap / _subset_device / _lists and their per-shard calls): 0 the
+ * f32 subset scan, 2 the int8-pruned subset scan (no device is touched; the bf16 tier has no subset form).  n_ids = entries of the list,
+ * kk = min(kk, n_ids) of the call.  0 whenever RXGPU_SCAN_BF16 is 0 or 1, RXGPU_SCAN_I8 is 0, the shadow is not available, the dimension
+ * is outside 128 < dim <= 1024, kk > 64 or the list is empty.  Otherwise RXGPU_SCAN_I8=1 forces 2 for up to 8 queries at any size, and the
+ * automatic rule (RXGPU_SCAN_I8 unset) gives 2 for a single query on an index without a NaN / infinite row norm when the LISTED rows hold
+ * at least RXGPU_SCAN_I8_SUBSET_MIN_BYTES of f32 data (n_ids * dim * 4): an index that only sees selective filters never builds the shadow.
+ * The default of that variable is the maximum value until the crossover against the f32 subset scan is measured (never below 1 GiB then):
+ * without the variable the automatic rule answers 0 and the tier is used only where RXGPU_SCAN_I8=1 forces it.  The environment is read
+ * per call. */
+int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, int shadow_available, int stats_finite);
 
 /* ---- IVF-Flat: faiss::IndexIVFFlat::search as IvfIndex drives it (ivf_index.cc:355-372) in ONE call ----------
  * rxgpu_index_set_lists: the inverted lists over this index's rows as CSR — list_off [nlist + 1] (list_off[0] = 0), list_rows
  *   [list_off[nlist]] internal rows (lists are disjoint); uploaded and kept until the next call.  Set them again after the rows change.
  * rxgpu_search_knn_lists: `coarse` = a flat index of the nlist centroids (same metric family, same device).  The nprobe nearest centroids
  *   are found on the device, their lists are marked in an allowed-rows bitmap, expanded to the ascending row list and scanned
- *   (rxgpu_search_knn_subset's kernels) without a host round trip in between: same result as rxgpu_search_knn_subset over the union of
+ *   (rxgpu_search_knn_subset's kernels, the int8-pruned ones where rxgpu_scan_tier_subset says so) without a host round trip in between: same result as rxgpu_search_knn_subset over the union of
  *   the probed lists.  query = host [dim], already prepared for the metric (cosine: normalised).  Any nprobe (clamped to nlist): up to
  *   128 lists the coarse result never leaves HBM, wider probes fetch the nprobe list ids and send them back.  *out_scanned (optional)
  *   = rows in the probed lists.  Output as rxgpu_search_knn for nq = 1.
@@ -216,7 +229,8 @@ int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* q
 
 /* Device-resident variant on `stream` (no synchronisation): d_row_ids = device [n_ids] uint32, 1 <= n_ids <= count,
  * kk in [1, 128]; d_out_count may be NULL.  The list is TRUSTED (strictly increasing, below count): an id beyond the
- * index would fault the device.  rxgpu_check_row_list_device() verifies a device list (synchronises `stream`). */
+ * index would fault the device.  rxgpu_check_row_list_device() verifies a device list (synchronises `stream`).
+ * Served by the scan rxgpu_scan_tier_subset names (the first int8-pruned call on an index builds the shadow and synchronises once). */
 int rxgpu_search_knn_subset_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, const void* d_row_ids,
 								   uint64_t n_ids, void* d_out_dist, void* d_out_row, void* d_out_count, void* stream);
 int rxgpu_check_row_list_device(rxgpu_index* h, const void* d_row_ids, uint64_t n_ids, void* stream, int32_t* out_ok);

@@ -175,6 +175,7 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_generic(ScanParams p) {
 // hop is off the per-step path and the row loads keep the double-buffered issue order of knn_scan_fixed across chunk boundaries.
 template <int kMetric, int NB, typename TK = WaveTopK>
 __global__ __launch_bounds__(kScanThreads) void knn_scan_subset(ScanParams p, const uint32_t* __restrict__ ids) {
+	if (p.gate_cnt && p.gate_cnt[blockIdx.y] <= p.gate_cap) return;
 	__shared__ float4 s_q[NB * 16];
 	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -240,6 +241,7 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_subset(ScanParams p, co
 // Any dim: one list entry per 16-lane group and step.
 template <int kMetric, typename TK = WaveTopK>
 __global__ __launch_bounds__(kScanThreads) void knn_scan_subset_generic(ScanParams p, const uint32_t* __restrict__ ids) {
+	if (p.gate_cnt && p.gate_cnt[blockIdx.y] <= p.gate_cap) return;
 	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const float* q = p.queries + size_t(blockIdx.y) * p.dim;
@@ -468,7 +470,8 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_bf16_blk(ScanBf16Params
 
 // rows whose approximate distance is within the bound of the kk-th best approximate distance -> candidate list of the query
 __global__ __launch_bounds__(256) void knn_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk,
-														 const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap) {
+														 const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap,
+														 const uint32_t* __restrict__ ids) {
 	const uint32_t qi = blockIdx.y;
 	const int lane = threadIdx.x & 63;
 	if (!(margin[qi] < __builtin_inff())) return;   // no bound for this query (knn_query_prep has set cand_cnt = cap + 1): the exact scan answers it
@@ -484,7 +487,7 @@ __global__ __launch_bounds__(256) void knn_filter_approx(const float* approx, ui
 		if (lane == __builtin_ctzll(pm)) pos0 = atomicAdd(&cand_cnt[qi], uint32_t(__popcll(pm)));
 		pos0 = __shfl(pos0, __builtin_ctzll(pm));
 		const uint32_t pos = pos0 + uint32_t(__popcll(pm & ((1ull << lane) - 1)));
-		if (pass && pos < cap) cand_row[size_t(qi) * cap + pos] = uint32_t(row);
+		if (pass && pos < cap) cand_row[size_t(qi) * cap + pos] = ids ? ids[row] : uint32_t(row);   // a row list: position -> row
 	}
 }
 
@@ -1115,9 +1118,9 @@ void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t
 	}
 }
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
-						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s) {
+						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s, const uint32_t* ids) {
 	const uint32_t gx = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, uint64_t(cus) * 8)));
-	hipLaunchKernelGGL(knn_filter_approx, dim3(gx, nq), dim3(256), 0, s, approx, n, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap);
+	hipLaunchKernelGGL(knn_filter_approx, dim3(gx, nq), dim3(256), 0, s, approx, n, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap, ids);
 }
 
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,

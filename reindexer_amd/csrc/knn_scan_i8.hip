@@ -139,6 +139,140 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
 	block_merge_and_store(top, p.sp, lane, wave);
 }
 
+// ---- the gather form: the same pass over the rows of a list (pre-filtered search and IVF; enqueue_knn_pruned_i8_subset in rxgpu_capi.hip).
+// `ids` are strictly increasing internal rows, p.sp.n of them, trusted exactly as knn_scan_subset (knn_scan.hip) trusts them.  The arithmetic, the
+// lane mapping and the window are knn_scan_i8's (kept apart from it: that kernel is the headline's and stays as measured); what differs is where
+// a row comes from and where its lower bound goes: lo is stored at the LIST POSITION (p.lower is [nq][n_ids], so the store stays coalesced and
+// knn_filter_approx maps position -> row), the upper bound is offered with the real row.
+// kChunked (long lists): a wavefront owns chunks of 64 consecutive entries = 4 steps of 16; ONE coalesced load brings a chunk's ids (lane l:
+// entry l), a step's ids are fetched with cross-lane reads, so the id -> address hop is off the per-step path and the code-row loads stay
+// double-buffered across chunk boundaries, as in knn_scan_subset.  !kChunked (short lists): one set of 16 entries per wavefront step, 4x
+// more wavefronts in flight, no double buffer.  Entries past the end of the list are clamped to its last entry and never reduced, stored or offered.
+constexpr uint64_t kI8SubsetChunk = 64;
+template <int kMetric, int NC8, bool kChunked>
+__global__ __launch_bounds__(kScanThreads) void knn_scan_i8_subset(ScanI8Params p, const uint32_t* __restrict__ ids) {
+	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint32_t qi = blockIdx.y;
+	u32x4 qh[NC8], ql[NC8];
+	{
+		const u32x4* ph = reinterpret_cast<const u32x4*>(p.planes + size_t(qi) * 2 * p.ld8);
+#pragma unroll
+		for (int t = 0; t < NC8; ++t) {
+			qh[t] = ph[m + 16 * t];
+			ql[t] = ph[16 * NC8 + m + 16 * t];
+		}
+	}
+	const float2 qinfo = p.qinfo[qi];
+	float qq = 0.f;
+	if constexpr (kMetric == kL2) qq = p.q_sq[qi];
+	WaveTopK top;
+	top.init(p.sp.kk);
+	const uint64_t n = p.sp.n;   // list entries
+	float* lower = p.lower + size_t(qi) * n;
+	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
+	const uint64_t first = uint64_t(blockIdx.x) * kScanWaves + wave;
+
+	struct Buf {
+		u32x4 x[kI8RowsPerGroup * NC8];
+		float2 side;
+		float aux;
+		uint32_t row;   // the row of entry (m & 3) of this group's four
+	};
+	// idv: the ids of the step's 16 entries in lanes e0 .. e0 + 15
+	auto issue = [&](Buf& b, uint32_t idv, int e0) {
+		const int l0 = e0 + g * kI8RowsPerGroup;
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			const uint64_t row = __shfl(idv, l0 + j);
+			const u32x4* src = reinterpret_cast<const u32x4*>(p.codes + row * p.ld8) + m;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) b.x[j * NC8 + t] = __builtin_nontemporal_load(src + 16 * t);
+		}
+		b.row = __shfl(idv, l0 + (m & 3));
+		b.side = p.side[b.row];
+		if constexpr (kMetric == kL2) b.aux = p.row_sq[b.row];
+		if constexpr (kMetric == kCos) b.aux = p.sp.inv_norms[b.row];
+		if constexpr (kMetric == kIP) b.aux = 0.f;
+	};
+	// base: list position of the step's first entry
+	auto reduce = [&](const Buf& b, uint64_t base) {
+		if (base >= n) return;   // wave-uniform
+		int v[kI8RowsPerGroup];
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			int hs = 0, ls = 0;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) {
+				hs = i8_dot16(qh[t], b.x[j * NC8 + t], hs);
+				ls = i8_dot16(ql[t], b.x[j * NC8 + t], ls);
+			}
+			v[j] = hs * 128 + ls;
+		}
+		const bool b0 = (m & 1) != 0, b1 = (m & 2) != 0;   // knn_scan_i8's transposing butterfly
+		const int a0 = (b0 ? v[1] : v[0]) + __shfl_xor(b0 ? v[0] : v[1], 1);
+		const int a1 = (b0 ? v[3] : v[2]) + __shfl_xor(b0 ? v[2] : v[3], 1);
+		int s = (b1 ? a1 : a0) + __shfl_xor(b1 ? a0 : a1, 2);
+		s += __shfl_xor(s, 4);
+		s += __shfl_xor(s, 8);
+		const uint64_t pos = base + uint64_t(g) * kI8RowsPerGroup + (m & 3);
+		const bool valid = pos < n && m < kI8RowsPerGroup;
+		float lo, up;
+		i8_bounds(kMetric, i8_ip(qinfo.x, b.side.x, s), qinfo.y, b.side.y, qq, b.aux, lo, up);
+		if (valid) lower[pos] = lo;
+		const bool pass = valid && (top.filled < top.kk || up < top.thr_d);
+		uint64_t pm = __ballot(pass);
+		while (pm) {
+			const int src = __builtin_ctzll(pm);
+			pm &= pm - 1;
+			const float d = __shfl(up, src);
+			const uint32_t i = __shfl(b.row, src);
+			if (top.admits(d, i)) top.insert(d, i, lane);
+		}
+	};
+	if constexpr (kChunked) {
+		constexpr int kSteps = int(kI8SubsetChunk / kI8RowsPerWave);   // 4
+		const uint64_t nchunks = (n + kI8SubsetChunk - 1) / kI8SubsetChunk;
+		auto load_ids = [&](uint64_t chunk) -> uint32_t {   // clamped: reading past the list re-reads its last entry
+			const uint64_t cc = chunk < nchunks ? chunk : nchunks - 1;
+			const uint64_t item = cc * kI8SubsetChunk + lane;
+			return ids[item < n ? item : n - 1];
+		};
+		if (first < nchunks) {
+			Buf xa, xb;
+			uint32_t idc = load_ids(first);
+			issue(xa, idc, 0);
+			for (uint64_t chunk = first; chunk < nchunks; chunk += nwaves) {
+				const uint32_t idn = load_ids(chunk + nwaves);   // in flight while this chunk's steps run
+				const uint64_t base = chunk * kI8SubsetChunk;
+#pragma unroll 1
+				for (int t = 0; t < kSteps; t += 2) {
+					issue(xb, idc, (t + 1) * int(kI8RowsPerWave));
+					__builtin_amdgcn_sched_barrier(0);
+					reduce(xa, base + uint64_t(t) * kI8RowsPerWave);
+					__builtin_amdgcn_sched_barrier(0);
+					// step t + 2 of this chunk, or step 0 of this wave's next chunk (harmless re-read after the last one)
+					const bool next = t + 2 >= kSteps;
+					issue(xa, next ? idn : idc, next ? 0 : (t + 2) * int(kI8RowsPerWave));
+					__builtin_amdgcn_sched_barrier(0);
+					reduce(xb, base + uint64_t(t + 1) * kI8RowsPerWave);
+					__builtin_amdgcn_sched_barrier(0);
+				}
+				idc = idn;
+			}
+		}
+	} else {
+		const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
+		for (uint64_t set = first; set < nsets; set += nwaves) {
+			const uint64_t item = set * kI8RowsPerWave + m;
+			Buf xa;
+			issue(xa, ids[item < n ? item : n - 1], 0);
+			reduce(xa, set * kI8RowsPerWave);
+		}
+	}
+	block_merge_and_store(top, p.sp, lane, wave);
+}
+
 // ---- the shadow: codes [n][ld8] (zero pad) and the side pair {s_r, e_r} per row, from the f32 rows (16-byte aligned, stride a multiple of 4
 // floats, as the index keeps them).  One 16-lane group per row, lane m quantises the 16-element chunks m, m + 16, ... (read twice: the scale
 // first); the residual is an fp64 sum over the codes as stored.  Folds max e^2 into stats[3], max
@@ -240,13 +374,29 @@ void launch_i8_build(const float* rows, const float* inv_norms, uint64_t n, uint
 // Load depth: two buffers of 4 rows per group = 2 x 12 KB per wavefront at 768 dims, 96 KiB per buffer set and CU at 2 workgroups per CU (what
 // knn_scan_bf16_blk keeps in flight).  RXGPU_SCAN_I8_WG_PER_CU overrides it (read per call: A/B runs inside one process).
 constexpr int kScanI8WgPerCu = 2;
-uint32_t scan_i8_grid_x(uint64_t n, int cus) {
+static int scan_i8_wg_per_cu() {
 	int wg = kScanI8WgPerCu;
 	if (const char* e = getenv("RXGPU_SCAN_I8_WG_PER_CU")) wg = atoi(e);
-	wg = wg < 1 ? 1 : wg > 8 ? 8 : wg;
+	return wg < 1 ? 1 : wg > 8 ? 8 : wg;
+}
+uint32_t scan_i8_grid_x(uint64_t n, int cus) {
+	const int wg = scan_i8_wg_per_cu();
 	const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
 	const uint64_t want = (nsets + kScanWaves - 1) / kScanWaves;
 	const uint64_t cap = uint64_t(cus) * wg;
+	return uint32_t(want < cap ? (want ? want : 1) : cap);
+}
+
+// The gather form: short lists go to the one-set-per-step kernel (4x more wavefronts in flight), long ones to the chunked, double-buffered
+// one; the same rule as subset_use_chunked of the f32 kernels (knn_scan.hip), over this scan's own workgroups-per-CU figure.
+static bool scan_i8_subset_chunked(uint64_t n_ids, int cus) {
+	return n_ids >= 2 * uint64_t(cus) * scan_i8_wg_per_cu() * kScanWaves * kI8SubsetChunk;
+}
+uint32_t scan_i8_subset_grid_x(uint64_t n_ids, int cus) {
+	const uint64_t per_wave = scan_i8_subset_chunked(n_ids, cus) ? kI8SubsetChunk : kI8RowsPerWave;
+	const uint64_t units = (n_ids + per_wave - 1) / per_wave;
+	const uint64_t want = (units + kScanWaves - 1) / kScanWaves;
+	const uint64_t cap = uint64_t(cus) * scan_i8_wg_per_cu();
 	return uint32_t(want < cap ? (want ? want : 1) : cap);
 }
 
@@ -266,6 +416,33 @@ void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gri
 		case kL2: launch_scan_i8_metric<kL2>(p, grid, s); break;
 		case kIP: launch_scan_i8_metric<kIP>(p, grid, s); break;
 		default: launch_scan_i8_metric<kCos>(p, grid, s); break;
+	}
+}
+
+template <int kMetric, bool kChunked>
+static void launch_scan_i8_subset_metric(const ScanI8Params& p, const uint32_t* ids, dim3 grid, hipStream_t s) {
+	switch (p.ld8 / 256) {
+		case 1: hipLaunchKernelGGL((knn_scan_i8_subset<kMetric, 1, kChunked>), grid, dim3(kScanThreads), 0, s, p, ids); break;
+		case 2: hipLaunchKernelGGL((knn_scan_i8_subset<kMetric, 2, kChunked>), grid, dim3(kScanThreads), 0, s, p, ids); break;
+		case 3: hipLaunchKernelGGL((knn_scan_i8_subset<kMetric, 3, kChunked>), grid, dim3(kScanThreads), 0, s, p, ids); break;
+		default: hipLaunchKernelGGL((knn_scan_i8_subset<kMetric, 4, kChunked>), grid, dim3(kScanThreads), 0, s, p, ids); break;
+	}
+}
+template <bool kChunked>
+static void launch_scan_i8_subset_form(int metric, const ScanI8Params& p, const uint32_t* ids, dim3 grid, hipStream_t s) {
+	switch (metric) {
+		case kL2: launch_scan_i8_subset_metric<kL2, kChunked>(p, ids, grid, s); break;
+		case kIP: launch_scan_i8_subset_metric<kIP, kChunked>(p, ids, grid, s); break;
+		default: launch_scan_i8_subset_metric<kCos, kChunked>(p, ids, grid, s); break;
+	}
+}
+// p.sp.n = number of list entries (>= 1); gridx MUST come from scan_i8_subset_grid_x (it selects the kernel together with this function)
+void launch_scan_i8_subset(int metric, const ScanI8Params& p, const uint32_t* ids, uint32_t nq, uint32_t gridx, int cus, hipStream_t s) {
+	const dim3 grid(gridx, nq);
+	if (scan_i8_subset_chunked(p.sp.n, cus)) {
+		launch_scan_i8_subset_form<true>(metric, p, ids, grid, s);
+	} else {
+		launch_scan_i8_subset_form<false>(metric, p, ids, grid, s);
 	}
 }
 

@@ -646,6 +646,25 @@ static ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool 
 static bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite) {
 	return scan_policy_tier(rows, dim, nq, shadow_available, shadow_available, stats_finite) != kTierF32;
 }
+// The same decision for a search over a ROW LIST (enqueue_knn_subset: pre-filtered search, IVF, their per-shard calls): the f32 subset scan or the
+// int8-pruned one (knn_scan_i8_subset; the bf16 tier has no subset form, so RXGPU_SCAN_BF16=1, "the bf16 tier, exactly", keeps the f32 scan).
+// kk is min(kk, n_ids); the pruned chain keeps one list entry per lane, so kk in 65..128 stays on the f32 subset scan.  The automatic rule
+// counts the f32 bytes of the LISTED rows, not of the index: small lists keep their kernel and an index that only sees selective filters never
+// builds the shadow.  kPrunedI8SubsetAutoMinBytes is meant to be the measured crossover against the f32 subset scan (tools/bench_prefilter_i8.py),
+// rounded up to a power of two and never below 1 GiB.  That crossover has NOT been measured yet, so the default is the
+// maximum value: the tier is forced-only (RXGPU_SCAN_I8=1) or opted into with RXGPU_SCAN_I8_SUBSET_MIN_BYTES, which overrides the default.
+constexpr uint64_t kPrunedI8SubsetAutoMinBytes = ~0ull;
+static uint64_t pruned_i8_subset_auto_min_bytes() {
+	const char* e = getenv("RXGPU_SCAN_I8_SUBSET_MIN_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8SubsetAutoMinBytes;
+}
+static ScanTier scan_policy_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, bool i8_available, bool stats_finite) {
+	if (scan_bf16_mode() != kScanBf16Auto) return kTierF32;
+	const ScanBf16Mode i8 = scan_i8_mode();
+	if (i8 == kScanBf16Off || !i8_available || !rxgpu::i8_dim_supported(dim) || kk > uint32_t(rxgpu::kMaxFusedK) || n_ids == 0) return kTierF32;
+	if (i8 == kScanBf16On) return nq <= kPrunedMaxQueries ? kTierI8 : kTierF32;   // without a finite bound the gate answers, as in the unfiltered tier
+	return nq == 1 && stats_finite && n_ids * dim * sizeof(float) >= pruned_i8_subset_auto_min_bytes() ? kTierI8 : kTierF32;
+}
 constexpr uint32_t kPrunedCap = 4096;
 
 int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
@@ -811,10 +830,119 @@ int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_qu
 	return RXGPU_OK;
 }
 
+// The int8 tier over a row list: enqueue_knn_pruned_i8 with the gather form of the scan.  Lower bounds are kept per LIST POSITION ([nq][n_ids]);
+// the candidate filter maps position -> row, so the re-score and the merges see real rows.  The margin comes from index-wide maxima and is
+// therefore sound for any subset of the rows.  Behind the gate: the f32 subset scan, which is what answers this call off the tier.
+int enqueue_knn_pruned_i8_subset(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids,
+								 uint64_t n_ids, float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count) {
+	if (int rc = ensure_i8_shadow(h, c->stream); rc) return rc;   // (the row statistics first)
+	const uint32_t ld8 = rxgpu::i8_ld(h->dim);
+	const uint32_t gridx = rxgpu::scan_i8_subset_grid_x(n_ids, h->cus);
+	const uint32_t gridx_exact = rxgpu::subset_grid_x(n_ids, h->dim, kk, h->cus);   // the gated f32 subset scan's
+	const uint32_t grid_max = std::max(gridx, gridx_exact);
+	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (n_ids + 63) & ~63ull)));
+	if (int rc = c->d_qpad.ensure(size_t(nq) * ld8 * sizeof(float)); rc) return rc;
+	if (int rc = c->d_qplanes.ensure(size_t(nq) * 2 * ld8); rc) return rc;
+	if (int rc = c->d_qstats.ensure(size_t(4) * nq * sizeof(float)); rc) return rc;
+	if (int rc = c->d_dense.ensure(size_t(nq) * n_ids * sizeof(float)); rc) return rc;
+	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
+	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
+	if (int rc = c->d_cand_cnt.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
+	float* qpad = static_cast<float*>(c->d_qpad.ptr);
+	float2* qinfo = static_cast<float2*>(c->d_qstats.ptr);   // [nq] pairs, then [nq] |q|^2, [nq] margins
+	float* q_sq = reinterpret_cast<float*>(qinfo + nq);
+	float* margin = q_sq + nq;
+	float* top_dist = static_cast<float*>(c->d_top.ptr);
+	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
+	uint32_t* top_cnt = top_row + size_t(nq) * kk;
+	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
+	c->pruned_cap = cap;
+	rxgpu::launch_query_prep_i8(h->metric, d_queries, nq, h->dim, qpad, static_cast<int8_t*>(c->d_qplanes.ptr), ld8, h->d_stats, q_sq, margin, qinfo,
+								cand_cnt, cap, c->stream);
+	rxgpu::ScanI8Params p{};
+	p.sp.inv_norms = h->d_inv_norms;
+	p.sp.n = n_ids;
+	p.sp.kk = kk;
+	p.sp.part_dist = static_cast<float*>(c->d_part_dist.ptr);
+	p.sp.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
+	p.codes = h->d_codes_i8;
+	p.side = h->d_side_i8;
+	p.planes = static_cast<const int8_t*>(c->d_qplanes.ptr);
+	p.qinfo = qinfo;
+	p.row_sq = h->d_row_sq;
+	p.q_sq = q_sq;
+	p.ld8 = ld8;
+	p.lower = static_cast<float*>(c->d_dense.ptr);
+	{
+		ProfileScope ps(h, "scan_i8_subset", c->stream);
+		rxgpu::launch_scan_i8_subset(h->metric, p, d_ids, nq, gridx, h->cus, c->stream);
+	}
+	rxgpu::launch_merge_lists(p.sp.part_dist, p.sp.part_row, gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
+	{
+		ProfileScope ps(h, "filter_approx", c->stream);
+		rxgpu::launch_filter_approx(p.lower, n_ids, top_dist, top_cnt, kk, margin, static_cast<uint32_t*>(c->d_cand_row.ptr), cand_cnt, cap, nq, h->cus,
+									c->stream, d_ids);
+	}
+	{
+		ProfileScope ps(h, "rescore", c->stream);
+		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, ld8, h->stride, h->dim, nq, cap, cand_cnt,
+							  static_cast<uint32_t*>(c->d_cand_row.ptr), static_cast<float*>(c->d_cand_dist.ptr), c->stream);
+	}
+	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
+						d_out_count, nullptr, 0, c->stream);
+	{   // more listed rows inside the bound than the list holds, or no finite bound: the f32 subset scan + its merge, gated on device
+		rxgpu::ScanParams e{};
+		e.rows = h->d_rows;
+		e.inv_norms = h->d_inv_norms;
+		e.queries = d_queries;
+		e.n = n_ids;
+		e.stride = h->stride;
+		e.dim = h->dim;
+		e.kk = kk;
+		e.part_dist = p.sp.part_dist;
+		e.part_row = p.sp.part_row;
+		e.gate_cnt = cand_cnt;
+		e.gate_cap = cap;
+		// While profiling, the slot counts the calls whose gate OPENED for one of the queries (the counts are read back first, which synchronises
+		// the stream): a call the pruned chain answered leaves it at 0, like "scan_subset".
+		bool opened = false;
+		if (h->profiling) {
+			std::vector<uint32_t> cnt(nq);
+			RX_HIP(hipMemcpyAsync(cnt.data(), cand_cnt, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+			RX_HIP(hipStreamSynchronize(c->stream));
+			opened = std::any_of(cnt.begin(), cnt.end(), [&](uint32_t v) { return v > cap; });
+		}
+		auto fallback = [&] {
+			rxgpu::launch_scan_subset(h->metric, e, d_ids, nq, gridx_exact, h->cus, c->stream);
+			rxgpu::launch_merge_lists(e.part_dist, e.part_row, gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, cand_cnt, cap);
+		};
+		if (opened) {
+			ProfileScope ps(h, "fallback_scan", c->stream);
+			fallback();
+		} else {
+			fallback();
+		}
+	}
+	RX_HIP(hipGetLastError());
+	return RXGPU_OK;
+}
+
 // Pre-filtered search, kk <= kMaxFusedK2: gather-scan over the row list + the usual merge (rows in the lists are real rows, so the
-// merge and everything downstream is unchanged).
+// merge and everything downstream is unchanged).  Where scan_policy_tier_subset says so, the int8-pruned chain above answers instead.
 int enqueue_knn_subset(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids,
 					   uint64_t n_ids, float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count) {
+	// (the device entry point may pass kk > n_ids; the chain runs with kk itself, so a kk above one entry per lane stays off the tier whatever the list)
+	const uint32_t eff = kk <= uint32_t(rxgpu::kMaxFusedK) ? uint32_t(std::min<uint64_t>(kk, n_ids)) : kk;
+	if (scan_policy_tier_subset(n_ids, h->dim, nq, eff, !h->i8_unavailable, true) == kTierI8) {
+		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;   // (automatic mode asks whether the row statistics are finite)
+		if (scan_policy_tier_subset(n_ids, h->dim, nq, eff, !h->i8_unavailable, h->stats_finite) == kTierI8) {
+			const int rc = enqueue_knn_pruned_i8_subset(h, c, d_queries, nq, kk, d_ids, n_ids, d_out_dist, d_out_row, d_out_count);
+			if (!(rc == RXGPU_ERR_NOMEM && h->i8_unavailable)) return rc;   // no room for the int8 shadow: the f32 subset scan below
+		}
+	}
 	const uint32_t gridx = rxgpu::subset_grid_x(n_ids, h->dim, kk, h->cus);
 	const size_t part = size_t(nq) * gridx * kk;
 	if (int rc = c->d_part_dist.ensure(part * sizeof(float)); rc) return rc;
@@ -852,6 +980,7 @@ int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries
 		if (int rc = c->d_out_dist.ensure(size_t(nq) * eff * sizeof(float)); rc) return rc;
 		if (int rc = c->d_out_row.ensure(size_t(nq) * eff * sizeof(uint32_t)); rc) return rc;
 		if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
+		c->pruned_cap = 0;   // set by a pruned chain
 		if (int rc = enqueue_knn_subset(h, c, static_cast<const float*>(c->d_queries.ptr), nq, eff, d_ids, n_ids,
 										static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr),
 										static_cast<uint32_t*>(c->d_out_count.ptr));
@@ -863,6 +992,12 @@ int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries
 								hipMemcpyDeviceToHost, c->stream));
 		RX_HIP(hipMemcpyAsync(out_count, c->d_out_count.ptr, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 		RX_HIP(hipStreamSynchronize(c->stream));
+		if (h->profiling && nq == 1 && c->pruned_cap) {   // rxgpu_index_last_candidates, as rxgpu_search_knn records it
+			uint32_t cnt = 0;
+			RX_HIP(hipMemcpy(&cnt, c->d_cand_cnt.ptr, sizeof(cnt), hipMemcpyDeviceToHost));
+			h->last_cand_count = cnt;
+			h->last_cand_cap = c->pruned_cap;
+		}
 		return RXGPU_OK;
 	}
 	// large k: distances of the listed rows + radix select over (dist, position); positions -> rows; final sort of eff entries on the host
@@ -929,6 +1064,10 @@ int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_avail
 
 int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
 	return int(scan_policy_tier(rows, dim, nq, shadow_available != 0, shadow_available != 0, stats_finite != 0));
+}
+
+int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, int shadow_available, int stats_finite) {
+	return int(scan_policy_tier_subset(n_ids, dim, nq, kk, shadow_available != 0, stats_finite != 0));
 }
 
 int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap) {

@@ -26,12 +26,16 @@ void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t
 struct ScanI8Params;   // int8-pruned scan (knn_scan_i8.hip; the query side: knn_query_prep_i8 in knn_batched.hip)
 uint32_t scan_i8_grid_x(uint64_t n, int cus);
 void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
+// the gather form over a row list: p.sp.n = list entries, p.lower [nq][n_ids] by list position; gridx MUST come from scan_i8_subset_grid_x
+uint32_t scan_i8_subset_grid_x(uint64_t n_ids, int cus);
+void launch_scan_i8_subset(int metric, const ScanI8Params& p, const uint32_t* ids, uint32_t nq, uint32_t gridx, int cus, hipStream_t s);
 void launch_i8_build(const float* rows, const float* inv_norms, uint64_t n, uint32_t stride, uint32_t dim, int8_t* codes, float2* side, uint32_t ld8,
 					 unsigned int* stats, int cus, hipStream_t s);   // every pointer at the first row of the range
 void launch_query_prep_i8(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
 						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s);
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
-						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s);
+						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s,
+						  const uint32_t* ids = nullptr);   // ids: approx is indexed by list position and the candidates are ids[position]
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s);
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
