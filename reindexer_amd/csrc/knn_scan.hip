@@ -262,7 +262,7 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_subset_generic(ScanPara
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // bf16-pruned scan (a single query on a large index where the int8 tier of knn_scan_i8.hip does not apply, see scan_policy_tier in
-// rxgpu_capi.hip; RXGPU_SCAN_BF16=1 / 0 force it on / off): half the HBM bytes per query, the SAME result bits.
+// rxgpu_knn_chains.hip; RXGPU_SCAN_BF16=1 / 0 force it on / off): half the HBM bytes per query, the SAME result bits.
 //   0. knn_query_prep     (knn_batched.hip) padded copy of the query, |q|^2, the margin 2 eps, cand_cnt = 0 — or cap + 1 for a query without a
 //                         finite bound, which steps 3-4 then leave to the gated exact scan
 //   1. knn_scan_bf16      approximate distance d~ of every row from the bf16 shadow (2 bytes per element), stored ([n] floats) and folded

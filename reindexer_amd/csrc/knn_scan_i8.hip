@@ -1,4 +1,4 @@
-// int8-pruned scan (the default for a single query on a large index whose dimension it serves, see scan_policy_tier in rxgpu_capi.hip;
+// int8-pruned scan (the default for a single query on a large index whose dimension it serves, see scan_policy_tier in rxgpu_knn_chains.hip;
 // RXGPU_SCAN_I8=1 / 0 force it on / off): ONE byte per element from HBM instead of four, the SAME result bits.
 //   0. knn_query_prep_i8  (knn_batched.hip) padded f32 copy of the query, its two int8 planes, |q|^2, {s_q, |q|^}, the margin, cand_cnt = 0 — or
 //                         cap + 1 for a query (or an index) without a finite bound, which steps 3-4 then leave to the gated exact scan
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
 	block_merge_and_store(top, p.sp, lane, wave);
 }
 
-// ---- the gather form: the same pass over the rows of a list (pre-filtered search and IVF; enqueue_knn_pruned_i8_subset in rxgpu_capi.hip).
+// ---- the gather form: the same pass over the rows of a list (pre-filtered search and IVF; enqueue_knn_pruned_i8 with a row list in rxgpu_knn_chains.hip).
 // `ids` are strictly increasing internal rows, p.sp.n of them, trusted exactly as knn_scan_subset (knn_scan.hip) trusts them.  The arithmetic, the
 // lane mapping and the window are knn_scan_i8's (kept apart from it: that kernel is the headline's and stays as measured); what differs is where
 // a row comes from and where its lower bound goes: lo is stored at the LIST POSITION (p.lower is [nq][n_ids], so the store stays coalesced and

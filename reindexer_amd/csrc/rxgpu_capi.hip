@@ -1,14 +1,12 @@
 // C-ABI implementation (include/rxgpu.h): index storage in HBM, search entry points, instrumentation.
 // Host-side plumbing only — all arithmetic is in the kernels.
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
 
 #include "../../include/rxgpu.h"
-#include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
 
@@ -197,8 +195,12 @@ ProfileScope::~ProfileScope() {
 using rxgpu::acquire_ctx;
 using rxgpu::CtxLease;
 using rxgpu::DeviceGuard;
+using rxgpu::enqueue_knn;
+using rxgpu::enqueue_knn_fused;
+using rxgpu::enqueue_knn_subset;
 using rxgpu::ProfileScope;
 using rxgpu::release_ctx;
+using rxgpu::search_subset_host;
 
 namespace {
 
@@ -250,807 +252,6 @@ rxgpu_search_ctx* stream_ctx(rxgpu_index* h, void* stream) {
 	return c;
 }
 
-// Enqueue scan + merge for nq device-resident queries; results land in d_out_* (device).
-int enqueue_knn_fused(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
-					  uint32_t* d_out_row, uint32_t* d_out_count) {
-	const uint32_t gridx = rxgpu::scan_grid_x(h->count, h->cus);
-	const size_t part = size_t(nq) * gridx * kk;
-	if (int rc = c->d_part_dist.ensure(part * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(part * sizeof(uint32_t)); rc) return rc;
-	rxgpu::ScanParams p{};
-	p.rows = h->d_rows;
-	p.inv_norms = h->d_inv_norms;
-	p.queries = d_queries;
-	p.n = h->count;
-	p.stride = h->stride;
-	p.dim = h->dim;
-	p.kk = kk;
-	p.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-	p.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-	{
-		ProfileScope ps(h, "scan", c->stream);
-		rxgpu::launch_scan(h->metric, p, nq, gridx, c->stream);
-	}
-	{
-		ProfileScope ps(h, "merge", c->stream);
-		rxgpu::launch_merge_lists(p.part_dist, p.part_row, gridx, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream);
-	}
-	RX_HIP(hipGetLastError());
-	return RXGPU_OK;
-}
-
-// ---- batched path (nq >= 2): MFMA candidate generation + exact re-score, see knn_batched.hip ----------------------
-constexpr uint32_t kBatchSampleRows = 32768;
-constexpr uint32_t kBatchSampleRowsBf16 = 131072;   // the sample pass is cheap on the bf16 pipe; a tighter threshold pays for the wider margin
-
-static int batch_min_queries() {
-	static const int v = [] {
-		const char* e = getenv("RXGPU_BATCH_MIN");
-		return e ? atoi(e) : 2;
-	}();
-	return v;
-}
-
-// The statistics words back on the host (h->mtx held): are the maxima finite and has no NaN row been seen?  Only then does the rounding
-// bound of a pruned scan mean anything; the automatic scan policy (enqueue_knn) keeps such an index on the f32 scan.  Words 3 and 4 (the
-// int8 shadow's residual maxima, knn_scan_i8.hip) report a non-finite value through word 2.
-constexpr size_t kStatsWords = 5;
-int read_stats_finite(rxgpu_index* h, hipStream_t s) {
-	unsigned int w[3] = {0, 0, 0};
-	RX_HIP(hipMemcpyAsync(w, h->d_stats, sizeof(w), hipMemcpyDeviceToHost, s));
-	RX_HIP(hipStreamSynchronize(s));
-	float a, b;
-	std::memcpy(&a, &w[0], sizeof(a));
-	std::memcpy(&b, &w[1], sizeof(b));
-	h->stats_finite = std::isfinite(a) && std::isfinite(b) && w[2] == 0;
-	return RXGPU_OK;
-}
-
-// Per-row statistics are cached on the index; recomputed (synchronously, under the index mutex) after any mutation.
-int ensure_row_stats(rxgpu_index* h, hipStream_t s) {
-	std::lock_guard<std::mutex> lk(h->mtx);
-	if (h->stats_valid) return RXGPU_OK;
-	if (!h->d_stats) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats), kStatsWords * sizeof(unsigned int)));
-	if (h->metric == RXGPU_METRIC_L2 && h->row_sq_capacity < h->count) {
-		if (h->d_row_sq) (void)hipFree(h->d_row_sq);
-		h->d_row_sq = nullptr;
-		h->row_sq_capacity = 0;
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_row_sq), std::max<uint64_t>(h->capacity, h->count) * sizeof(float)));
-		h->row_sq_capacity = std::max<uint64_t>(h->capacity, h->count);
-	}
-	RX_HIP(hipMemsetAsync(h->d_stats, 0, kStatsWords * sizeof(unsigned int), s));
-	h->i8_valid = false;   // its two words were cleared with the rest: the shadow's next build folds them in again
-	rxgpu::launch_row_stats(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->metric == RXGPU_METRIC_L2 ? h->d_row_sq : nullptr,
-							h->d_stats, h->cus, s);
-	RX_HIP(hipGetLastError());
-	if (int rc = read_stats_finite(h, s); rc) return rc;   // synchronises the stream
-	h->stats_valid = true;
-	return RXGPU_OK;
-}
-
-// bf16 shadow of the rows for the nomination GEMM: 2 bytes per element on top of the 4-byte rows (HBM is 288 GB: 10M x 768 costs 15.4 GB);
-// rebuilt lazily after any mutation, like the row statistics.
-int ensure_bf16_shadow(rxgpu_index* h, hipStream_t s) {
-	std::lock_guard<std::mutex> lk(h->mtx);
-	if (h->bf16_valid) return RXGPU_OK;
-	const uint32_t ld = (h->dim + 63u) & ~63u;
-	const uint64_t need = (std::max<uint64_t>(h->capacity, h->count) + rxgpu::kShadowTileRows - 1) / rxgpu::kShadowTileRows * rxgpu::kShadowTileRows;   // whole tiles
-	if (h->bf16_capacity < need) {
-		if (h->d_rows_bf16) (void)hipFree(h->d_rows_bf16);
-		h->d_rows_bf16 = nullptr;
-		h->bf16_capacity = 0;
-		const char* e = getenv("RXGPU_SHADOW_BLOCKED");
-		h->bf16_blocked = !(e && atoi(e) == 0);
-		if (hipMalloc(reinterpret_cast<void**>(&h->d_rows_bf16), need * ld * sizeof(uint16_t)) != hipSuccess) {
-			(void)hipGetLastError();   // not an error of the search: the caller falls back to the f32 rows
-			h->d_rows_bf16 = nullptr;
-			h->bf16_unavailable = true;
-			return RXGPU_ERR_NOMEM;
-		}
-		h->bf16_capacity = need;
-	}
-	rxgpu::launch_to_bf16(h->d_rows, h->count, h->stride, h->dim, h->d_rows_bf16, ld, h->cus, s, 0, h->bf16_blocked);
-	RX_HIP(hipGetLastError());
-	RX_HIP(hipStreamSynchronize(s));
-	h->bf16_valid = true;
-	return RXGPU_OK;
-}
-
-// int8 shadow of the rows for the pruning pass of a single query (knn_scan_i8.hip): 1 byte per element + 8 bytes per row on top of the 4-byte
-// rows; built lazily behind the row statistics (it folds two more maxima into their words) and kept in step by the mutations like the bf16 shadow.
-int ensure_i8_shadow(rxgpu_index* h, hipStream_t s) {
-	if (int rc = ensure_row_stats(h, s); rc) return rc;
-	std::lock_guard<std::mutex> lk(h->mtx);
-	if (h->i8_valid) return RXGPU_OK;
-	const uint32_t ld8 = rxgpu::i8_ld(h->dim);
-	const uint64_t need = std::max<uint64_t>(h->capacity, h->count);
-	if (h->i8_capacity < need) {
-		if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
-		if (h->d_side_i8) (void)hipFree(h->d_side_i8);
-		h->d_codes_i8 = nullptr;
-		h->d_side_i8 = nullptr;
-		h->i8_capacity = 0;
-		if (hipMalloc(reinterpret_cast<void**>(&h->d_codes_i8), need * ld8) != hipSuccess ||
-			hipMalloc(reinterpret_cast<void**>(&h->d_side_i8), need * sizeof(float2)) != hipSuccess) {
-			(void)hipGetLastError();   // not an error of the search: the caller takes the bf16 tier
-			if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
-			h->d_codes_i8 = nullptr;
-			h->d_side_i8 = nullptr;
-			h->i8_unavailable = true;
-			return RXGPU_ERR_NOMEM;
-		}
-		h->i8_capacity = need;
-	}
-	rxgpu::launch_i8_build(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->d_codes_i8, h->d_side_i8, ld8, h->d_stats, h->cus, s);
-	RX_HIP(hipGetLastError());
-	if (int rc = read_stats_finite(h, s); rc) return rc;   // synchronises the stream
-	h->i8_valid = true;
-	return RXGPU_OK;
-}
-
-static int batch_bf16_min_queries() {   // read per call (tests and A/B runs switch it)
-	const char* e = getenv("RXGPU_BATCH_BF16_MIN");   // 0 disables the bf16 nomination path
-	return e ? atoi(e) : 2;   // measured at 10M x 768: 4.8-5.0 ms per batch for 8..256 queries against 6.2-10.6 ms on the f32 rows
-}
-
-// Every batch (2..256 queries at a time): nomination on the bf16 MFMA pipe over the bf16 shadow (knn_batched_bf16.hip), then the same exact tail.
-int enqueue_knn_batched_bf16(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t q0, uint32_t cq, uint32_t kk,
-							 float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count) {
-	if (int rc = ensure_bf16_shadow(h, c->stream); rc) return rc;
-	const uint32_t mt = cq <= 128 ? 128 : 256;   // query-tile width of the nomination kernel
-	const uint32_t ld = (h->dim + 63u) & ~63u;
-	const uint32_t q_stride = ld;   // the f32 copy for the exact re-score shares the padded stride
-	const uint64_t ns = std::min<uint64_t>(h->count, kBatchSampleRowsBf16);
-	// nominations per query ~ kk * n / ns, times ~3 for the bf16 margin; 10x headroom, overflow falls back to the exact scan
-	uint64_t cap64 = std::max<uint64_t>(4096, 10 * uint64_t(kk) * ((h->count + ns - 1) / ns));
-	cap64 = std::min<uint64_t>(cap64, std::max<uint64_t>(h->count, 64));
-	const uint32_t cap = uint32_t((cap64 + 63) & ~63ull);
-	if (int rc = c->d_qpad.ensure(size_t(mt) * q_stride * (sizeof(float) + sizeof(uint16_t))); rc) return rc;
-	if (int rc = c->d_qstats.ensure(size_t(3) * mt * sizeof(float)); rc) return rc;
-	if (int rc = c->d_dense.ensure(size_t(mt) * ns * sizeof(float)); rc) return rc;
-	if (int rc = c->d_cand_row.ensure(size_t(mt) * cap * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_dist.ensure(size_t(mt) * cap * sizeof(float)); rc) return rc;
-	if (int rc = c->d_cand_cnt.ensure(size_t(mt) * sizeof(uint32_t)); rc) return rc;
-	float* qpad = static_cast<float*>(c->d_qpad.ptr);
-	uint16_t* qbf = reinterpret_cast<uint16_t*>(qpad + size_t(mt) * q_stride);
-	float* q_sq = static_cast<float*>(c->d_qstats.ptr);
-	float* margin = q_sq + mt;
-	float* thr = q_sq + 2 * mt;
-	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
-	c->pruned_cap = cap;
-	RX_HIP(hipMemsetAsync(qpad, 0, size_t(mt) * q_stride * sizeof(float), c->stream));
-	RX_HIP(hipMemcpy2DAsync(qpad, q_stride * sizeof(float), d_queries + size_t(q0) * h->dim, h->dim * sizeof(float), h->dim * sizeof(float), cq,
-							hipMemcpyDeviceToDevice, c->stream));
-	RX_HIP(hipMemsetAsync(cand_cnt, 0, size_t(mt) * sizeof(uint32_t), c->stream));
-	rxgpu::launch_to_bf16(qpad, mt, q_stride, q_stride, qbf, ld, h->cus, c->stream);
-	rxgpu::launch_query_stats(h->metric, qpad, cq, mt, q_stride, h->dim, h->d_stats, q_sq, margin, true, c->stream);
-
-	rxgpu::GemmBf16Params g{};
-	g.rows = h->d_rows_bf16;
-	g.blocked = (h->bf16_blocked ? 1u : 0u) | ((getenv("RXGPU_GEMM_PRIO") && atoi(getenv("RXGPU_GEMM_PRIO"))) ? 2u : 0u);   // bit 1: s_setprio around the MFMA bursts (A/B)
-	g.queries = qbf;
-	g.inv_norms = h->d_inv_norms;
-	g.row_sq = h->d_row_sq;
-	g.q_sq = q_sq;
-	g.ld = ld;
-	g.nq = cq;
-	auto grid_for = [&](uint64_t rows) { return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((rows + 255) / 256, uint64_t(h->cus)))); };
-	g.n = ns;
-	g.row_step = uint32_t(std::max<uint64_t>(1, h->count / ns));   // strided sample: representative whatever the insertion order
-	g.dense = static_cast<float*>(c->d_dense.ptr);
-	{
-		ProfileScope ps(h, "gemm_sample", c->stream);
-		RX_HIP(rxgpu::launch_gemm_bf16(h->metric, rxgpu::kGemmDense, int(mt), g, grid_for(ns), c->stream));
-	}
-	rxgpu::launch_sample_threshold(g.dense, ns, cq, mt, kk, margin, thr, c->stream);
-	g.n = h->count;
-	g.row_step = 1;
-	g.dense = nullptr;
-	g.thr = thr;
-	g.cand_row = static_cast<uint32_t*>(c->d_cand_row.ptr);
-	g.cand_cnt = cand_cnt;
-	g.cap = cap;
-	{
-		ProfileScope ps(h, "gemm", c->stream);
-		RX_HIP(rxgpu::launch_gemm_bf16(h->metric, rxgpu::kGemmFilter, int(mt), g, grid_for(h->count), c->stream));
-	}
-	{
-		ProfileScope ps(h, "rescore", c->stream);
-		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, q_stride, h->stride, h->dim, cq, cap, cand_cnt, g.cand_row,
-							  static_cast<float*>(c->d_cand_dist.ptr), c->stream);
-	}
-	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), g.cand_row, cap, kk, cq, d_out_dist + size_t(q0) * kk, d_out_row + size_t(q0) * kk,
-						d_out_count ? d_out_count + q0 : nullptr, nullptr, 0, c->stream);
-	{   // overflow fallback, gated on device
-		const uint32_t gridx = rxgpu::scan_grid_x(h->count, h->cus);
-		const size_t part = size_t(cq) * gridx * kk;
-		if (int rc = c->d_part_dist.ensure(part * sizeof(float)); rc) return rc;
-		if (int rc = c->d_part_row.ensure(part * sizeof(uint32_t)); rc) return rc;
-		rxgpu::ScanParams p{};
-		p.rows = h->d_rows;
-		p.inv_norms = h->d_inv_norms;
-		p.queries = d_queries + size_t(q0) * h->dim;
-		p.n = h->count;
-		p.stride = h->stride;
-		p.dim = h->dim;
-		p.kk = kk;
-		p.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-		p.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-		p.gate_cnt = cand_cnt;
-		p.gate_cap = cap;
-		ProfileScope ps(h, "fallback_scan", c->stream);
-		rxgpu::launch_scan(h->metric, p, cq, gridx, c->stream);
-		rxgpu::launch_merge(p.part_dist, p.part_row, gridx * kk, kk, cq, d_out_dist + size_t(q0) * kk, d_out_row + size_t(q0) * kk,
-							d_out_count ? d_out_count + q0 : nullptr, cand_cnt, cap, c->stream);
-	}
-	RX_HIP(hipGetLastError());
-	return RXGPU_OK;
-}
-
-int enqueue_knn_batched(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
-						uint32_t* d_out_row, uint32_t* d_out_count) {
-	if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
-	const uint32_t q_stride = (h->dim + 31u) & ~31u;
-	const uint64_t ns = std::min<uint64_t>(h->count, kBatchSampleRows);
-	// expected nominations per query ~ kk * n / ns (plus the eps margin); 4x headroom, overflow falls back to the exact scan
-	uint64_t cap64 = std::max<uint64_t>(4096, 4 * uint64_t(kk) * ((h->count + ns - 1) / ns));
-	cap64 = std::min<uint64_t>(cap64, std::max<uint64_t>(h->count, 64));
-	const uint32_t cap = uint32_t((cap64 + 63) & ~63ull);
-	for (uint32_t q0 = 0; q0 < nq; q0 += 256) {
-		const uint32_t cq = std::min<uint32_t>(256, nq - q0);
-		if (batch_bf16_min_queries() > 0 && int(cq) >= batch_bf16_min_queries() && !h->bf16_unavailable) {
-			const int rc = enqueue_knn_batched_bf16(h, c, d_queries, q0, cq, kk, d_out_dist, d_out_row, d_out_count);
-			if (rc == RXGPU_OK) continue;
-			if (!(rc == RXGPU_ERR_NOMEM && h->bf16_unavailable)) return rc;   // no room for the shadow: f32 nomination below
-		}
-		const int mt = cq <= 32 ? 32 : cq <= 64 ? 64 : cq <= 128 ? 128 : 256;
-		if (int rc = c->d_qpad.ensure(size_t(mt) * q_stride * sizeof(float)); rc) return rc;
-		if (int rc = c->d_qstats.ensure(size_t(3) * mt * sizeof(float)); rc) return rc;
-		if (int rc = c->d_dense.ensure(size_t(mt) * ns * sizeof(float)); rc) return rc;
-		if (int rc = c->d_cand_row.ensure(size_t(mt) * cap * sizeof(uint32_t)); rc) return rc;
-		if (int rc = c->d_cand_dist.ensure(size_t(mt) * cap * sizeof(float)); rc) return rc;
-		if (int rc = c->d_cand_cnt.ensure(size_t(mt) * sizeof(uint32_t)); rc) return rc;
-		float* qpad = static_cast<float*>(c->d_qpad.ptr);
-		float* q_sq = static_cast<float*>(c->d_qstats.ptr);
-		float* margin = q_sq + mt;
-		float* thr = q_sq + 2 * mt;
-		uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
-	c->pruned_cap = cap;
-		RX_HIP(hipMemsetAsync(qpad, 0, size_t(mt) * q_stride * sizeof(float), c->stream));
-		RX_HIP(hipMemcpy2DAsync(qpad, q_stride * sizeof(float), d_queries + size_t(q0) * h->dim, h->dim * sizeof(float),
-								h->dim * sizeof(float), cq, hipMemcpyDeviceToDevice, c->stream));
-		RX_HIP(hipMemsetAsync(cand_cnt, 0, size_t(mt) * sizeof(uint32_t), c->stream));
-		rxgpu::launch_query_stats(h->metric, qpad, cq, mt, q_stride, h->dim, h->d_stats, q_sq, margin, false, c->stream);
-
-		rxgpu::GemmParams g{};
-		g.rows = h->d_rows;
-		g.inv_norms = h->d_inv_norms;
-		g.row_sq = h->d_row_sq;
-		g.queries = qpad;
-		g.q_sq = q_sq;
-		g.stride = h->stride;
-		g.dim = h->dim;
-		g.nq = cq;
-		g.q_stride = q_stride;
-		const uint32_t wg_per_cu = uint32_t(std::max<size_t>(1, std::min<size_t>(4, (160 * 1024) / rxgpu::gemm_lds_bytes(mt))));
-		auto grid_for = [&](uint64_t rows) {
-			const uint64_t tiles = (rows + 127) / 128;
-			return uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(tiles, uint64_t(h->cus) * wg_per_cu)));
-		};
-		// 2. sample (strided: representative whatever the insertion order)
-		g.n = ns;
-		g.row_step = uint32_t(std::max<uint64_t>(1, h->count / ns));
-		g.dense = static_cast<float*>(c->d_dense.ptr);
-		{
-			ProfileScope ps(h, "gemm_sample", c->stream);
-			RX_HIP(rxgpu::launch_gemm(h->metric, mt, rxgpu::kGemmDense, g, grid_for(ns), c->stream));
-		}
-		// 3. thresholds
-		rxgpu::launch_sample_threshold(g.dense, ns, cq, mt, kk, margin, thr, c->stream);
-		// 4. filter pass over the whole corpus
-		g.n = h->count;
-		g.row_step = 1;
-		g.dense = nullptr;
-		g.thr = thr;
-		g.cand_row = static_cast<uint32_t*>(c->d_cand_row.ptr);
-		g.cand_cnt = cand_cnt;
-		g.cap = cap;
-		{
-			ProfileScope ps(h, "gemm", c->stream);
-			RX_HIP(rxgpu::launch_gemm(h->metric, mt, rxgpu::kGemmFilter, g, grid_for(h->count), c->stream));
-		}
-		// 5. exact re-score, 6. exact top-kk
-		{
-			ProfileScope ps(h, "rescore", c->stream);
-			rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, q_stride, h->stride, h->dim, cq, cap, cand_cnt, g.cand_row,
-								  static_cast<float*>(c->d_cand_dist.ptr), c->stream);
-		}
-		rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), g.cand_row, cap, kk, cq, d_out_dist + size_t(q0) * kk,
-							d_out_row + size_t(q0) * kk, d_out_count ? d_out_count + q0 : nullptr, nullptr, 0, c->stream);
-		// overflow fallback, gated on device: exact fused scan only for queries with cand_cnt > cap
-		{
-			const uint32_t gridx = rxgpu::scan_grid_x(h->count, h->cus);
-			const size_t part = size_t(cq) * gridx * kk;
-			if (int rc = c->d_part_dist.ensure(part * sizeof(float)); rc) return rc;
-			if (int rc = c->d_part_row.ensure(part * sizeof(uint32_t)); rc) return rc;
-			rxgpu::ScanParams p{};
-			p.rows = h->d_rows;
-			p.inv_norms = h->d_inv_norms;
-			p.queries = d_queries + size_t(q0) * h->dim;
-			p.n = h->count;
-			p.stride = h->stride;
-			p.dim = h->dim;
-			p.kk = kk;
-			p.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-			p.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-			p.gate_cnt = cand_cnt;
-			p.gate_cap = cap;
-			ProfileScope ps(h, "fallback_scan", c->stream);
-			rxgpu::launch_scan(h->metric, p, cq, gridx, c->stream);
-			rxgpu::launch_merge(p.part_dist, p.part_row, gridx * kk, kk, cq, d_out_dist + size_t(q0) * kk, d_out_row + size_t(q0) * kk,
-								d_out_count ? d_out_count + q0 : nullptr, cand_cnt, cap, c->stream);
-		}
-		RX_HIP(hipGetLastError());
-	}
-	return RXGPU_OK;
-}
-
-// bf16-pruned scan for one .. a few queries: 2 bytes per element from HBM instead of 4, exact result (knn_scan.hip).
-// RXGPU_SCAN_BF16, read per call (a process can switch it for A/B runs): 1 = forced on (up to kPrunedMaxQueries queries, any size), 0 = forced
-// off (the f32 paths, always), unset = automatic: single queries on indexes of at least kPrunedAutoMinBytes of f32 rows.
-enum ScanBf16Mode { kScanBf16Off = 0, kScanBf16On = 1, kScanBf16Auto = 2 };
-static ScanBf16Mode scan_bf16_mode() {
-	const char* e = getenv("RXGPU_SCAN_BF16");
-	if (!e || !*e) return kScanBf16Auto;
-	return atoi(e) != 0 ? kScanBf16On : kScanBf16Off;
-}
-constexpr uint32_t kPrunedMaxQueries = 8;
-// Automatic mode: the pruned path pays a fixed tail per query (filter, re-score, two merges, the gated scan) and saves half the streaming; it
-// also costs +2 bytes per element of HBM.  Never below 1 GiB (small indexes keep the f32 kernel and their footprint); measured crossover in
-// profiles/scan_policy_crossover.json.  RXGPU_SCAN_BF16_MIN_BYTES overrides it (tests exercise the decision on small corpora).
-constexpr uint64_t kPrunedAutoMinBytes = 1ull << 30;
-static uint64_t pruned_auto_min_bytes() {
-	const char* e = getenv("RXGPU_SCAN_BF16_MIN_BYTES");
-	return e && *e ? strtoull(e, nullptr, 10) : kPrunedAutoMinBytes;
-}
-// The int8 tier (knn_scan_i8.hip) refines a call the automatic mode above already accepts.  RXGPU_SCAN_I8, read per call: 0 = this tier off,
-// 1 = forced at any size (up to kPrunedMaxQueries queries; for tests and A/B), unset = automatic: indexes of at least kPrunedI8AutoMinBytes of
-// f32 rows.  RXGPU_SCAN_BF16=0 (the f32 paths, always) and =1 (the bf16 tier, exactly) both win over it.
-// kPrunedI8AutoMinBytes: the measured crossover against the bf16 tier (and the f32 scan) is 0.6 GB of f32 rows at 768 dims
-// (profiles/scan_i8_crossover.json), rounded up to a power of two and never below 1 GiB, like kPrunedAutoMinBytes.  RXGPU_SCAN_I8_MIN_BYTES
-// overrides it.
-constexpr uint64_t kPrunedI8AutoMinBytes = 1ull << 30;
-static ScanBf16Mode scan_i8_mode() {
-	const char* e = getenv("RXGPU_SCAN_I8");
-	if (!e || !*e) return kScanBf16Auto;
-	return atoi(e) != 0 ? kScanBf16On : kScanBf16Off;
-}
-static uint64_t pruned_i8_auto_min_bytes() {
-	const char* e = getenv("RXGPU_SCAN_I8_MIN_BYTES");
-	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8AutoMinBytes;
-}
-enum ScanTier { kTierF32 = 0, kTierBf16 = 1, kTierI8 = 2 };
-// The whole decision, without a device: which scan does a call with nq queries on rows x dim f32 rows take?
-static ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool bf16_available, bool i8_available, bool stats_finite) {
-	const ScanBf16Mode mode = scan_bf16_mode();
-	if (mode == kScanBf16Off) return kTierF32;
-	const ScanBf16Mode i8 = scan_i8_mode();
-	const bool i8_can = mode == kScanBf16Auto && i8 != kScanBf16Off && i8_available && rxgpu::i8_dim_supported(dim);
-	if (i8_can && i8 == kScanBf16On && nq <= kPrunedMaxQueries) return kTierI8;
-	if (!bf16_available || !rxgpu::scan_bf16_supported((dim + 63u) & ~63u)) return kTierF32;
-	if (mode == kScanBf16On) return nq <= kPrunedMaxQueries ? kTierBf16 : kTierF32;
-	if (!(nq == 1 && stats_finite && rows * dim * sizeof(float) >= pruned_auto_min_bytes())) return kTierF32;
-	return i8_can && rows * dim * sizeof(float) >= pruned_i8_auto_min_bytes() ? kTierI8 : kTierBf16;
-}
-// ... does it take a pruned scan at all?
-static bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite) {
-	return scan_policy_tier(rows, dim, nq, shadow_available, shadow_available, stats_finite) != kTierF32;
-}
-// The same decision for a search over a ROW LIST (enqueue_knn_subset: pre-filtered search, IVF, their per-shard calls): the f32 subset scan or the
-// int8-pruned one (knn_scan_i8_subset; the bf16 tier has no subset form, so RXGPU_SCAN_BF16=1, "the bf16 tier, exactly", keeps the f32 scan).
-// kk is min(kk, n_ids); the pruned chain keeps one list entry per lane, so kk in 65..128 stays on the f32 subset scan.  The automatic rule
-// counts the f32 bytes of the LISTED rows, not of the index: small lists keep their kernel and an index that only sees selective filters never
-// builds the shadow.  kPrunedI8SubsetAutoMinBytes is meant to be the measured crossover against the f32 subset scan (tools/bench_prefilter_i8.py),
-// rounded up to a power of two and never below 1 GiB.  That crossover has NOT been measured yet, so the default is the
-// maximum value: the tier is forced-only (RXGPU_SCAN_I8=1) or opted into with RXGPU_SCAN_I8_SUBSET_MIN_BYTES, which overrides the default.
-constexpr uint64_t kPrunedI8SubsetAutoMinBytes = ~0ull;
-static uint64_t pruned_i8_subset_auto_min_bytes() {
-	const char* e = getenv("RXGPU_SCAN_I8_SUBSET_MIN_BYTES");
-	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8SubsetAutoMinBytes;
-}
-static ScanTier scan_policy_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, bool i8_available, bool stats_finite) {
-	if (scan_bf16_mode() != kScanBf16Auto) return kTierF32;
-	const ScanBf16Mode i8 = scan_i8_mode();
-	if (i8 == kScanBf16Off || !i8_available || !rxgpu::i8_dim_supported(dim) || kk > uint32_t(rxgpu::kMaxFusedK) || n_ids == 0) return kTierF32;
-	if (i8 == kScanBf16On) return nq <= kPrunedMaxQueries ? kTierI8 : kTierF32;   // without a finite bound the gate answers, as in the unfiltered tier
-	return nq == 1 && stats_finite && n_ids * dim * sizeof(float) >= pruned_i8_subset_auto_min_bytes() ? kTierI8 : kTierF32;
-}
-constexpr uint32_t kPrunedCap = 4096;
-
-int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
-					   uint32_t* d_out_row, uint32_t* d_out_count) {
-	if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
-	if (int rc = ensure_bf16_shadow(h, c->stream); rc) return rc;
-	const uint32_t ld = (h->dim + 63u) & ~63u;
-	const uint32_t gridx = rxgpu::scan_bf16_grid_x(h->count, h->cus);   // the bf16 scan's grid
-	const uint32_t gridx_exact = rxgpu::scan_grid_x(h->count, h->cus);   // the gated f32 scan's
-	const uint32_t grid_max = std::max(gridx, gridx_exact);
-	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (h->count + 63) & ~63ull)));
-	if (int rc = c->d_qpad.ensure(size_t(nq) * ld * sizeof(float)); rc) return rc;
-	if (int rc = c->d_qstats.ensure(size_t(2) * nq * sizeof(float)); rc) return rc;
-	if (int rc = c->d_dense.ensure(size_t(nq) * h->count * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
-	if (int rc = c->d_cand_cnt.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
-	float* qpad = static_cast<float*>(c->d_qpad.ptr);
-	float* q_sq = static_cast<float*>(c->d_qstats.ptr);
-	float* margin = q_sq + nq;
-	float* top_dist = static_cast<float*>(c->d_top.ptr);
-	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
-	uint32_t* top_cnt = top_row + size_t(nq) * kk;
-	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
-	c->pruned_cap = cap;
-	// one launch: padded copy of the query, |q|^2, margin, cand_cnt = 0 (cap + 1 for a query without a finite bound: the gated exact scan answers it)
-	rxgpu::launch_query_prep(h->metric, d_queries, nq, h->dim, qpad, ld, h->d_stats, q_sq, margin, cand_cnt, cap, c->stream);
-	rxgpu::ScanBf16Params p{};
-	p.sp.inv_norms = h->d_inv_norms;
-	p.sp.n = h->count;
-	p.sp.kk = kk;
-	p.sp.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-	p.sp.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-	p.rows16 = h->d_rows_bf16;
-	p.blocked = h->bf16_blocked ? 1u : 0u;
-	p.queries32 = qpad;
-	p.row_sq = h->d_row_sq;
-	p.q_sq = q_sq;
-	p.ld = ld;
-	p.approx = static_cast<float*>(c->d_dense.ptr);
-	{
-		ProfileScope ps(h, "scan_bf16", c->stream);
-		rxgpu::launch_scan_bf16(h->metric, p, nq, gridx, c->stream);
-	}
-	// (the scan leaves sorted lists like the f32 scan: the list merge, 4 us against 28 for the insertion merge in the kernel trace of the headline)
-	rxgpu::launch_merge_lists(p.sp.part_dist, p.sp.part_row, gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
-	{
-		ProfileScope ps(h, "filter_approx", c->stream);
-		rxgpu::launch_filter_approx(p.approx, h->count, top_dist, top_cnt, kk, margin, static_cast<uint32_t*>(c->d_cand_row.ptr), cand_cnt, cap, nq,
-									h->cus, c->stream);
-	}
-	{
-		ProfileScope ps(h, "rescore", c->stream);
-		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, ld, h->stride, h->dim, nq, cap, cand_cnt,
-							  static_cast<uint32_t*>(c->d_cand_row.ptr), static_cast<float*>(c->d_cand_dist.ptr), c->stream);
-	}
-	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
-						d_out_count, nullptr, 0, c->stream);
-	{   // more rows inside the bound than the list holds (massive ties), or no finite bound: the f32 path's own scan + merge, gated on device
-		rxgpu::ScanParams e{};
-		e.rows = h->d_rows;
-		e.inv_norms = h->d_inv_norms;
-		e.queries = d_queries;
-		e.n = h->count;
-		e.stride = h->stride;
-		e.dim = h->dim;
-		e.kk = kk;
-		e.part_dist = p.sp.part_dist;
-		e.part_row = p.sp.part_row;
-		e.gate_cnt = cand_cnt;
-		e.gate_cap = cap;
-		ProfileScope ps(h, "fallback_scan", c->stream);
-		rxgpu::launch_scan(h->metric, e, nq, gridx_exact, c->stream);
-		rxgpu::launch_merge_lists(e.part_dist, e.part_row, gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, cand_cnt, cap);
-	}
-	RX_HIP(hipGetLastError());
-	return RXGPU_OK;
-}
-
-// The int8 tier of the same chain: knn_query_prep_i8 and knn_scan_i8 in front, per-row LOWER bounds where the bf16 chain keeps approximate
-// distances, everything behind the scan as above (same buffers, same cap).
-int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
-						  uint32_t* d_out_row, uint32_t* d_out_count) {
-	if (int rc = ensure_i8_shadow(h, c->stream); rc) return rc;   // (the row statistics first)
-	const uint32_t ld8 = rxgpu::i8_ld(h->dim);
-	const uint32_t gridx = rxgpu::scan_i8_grid_x(h->count, h->cus);
-	const uint32_t gridx_exact = rxgpu::scan_grid_x(h->count, h->cus);   // the gated f32 scan's
-	const uint32_t grid_max = std::max(gridx, gridx_exact);
-	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (h->count + 63) & ~63ull)));
-	if (int rc = c->d_qpad.ensure(size_t(nq) * ld8 * sizeof(float)); rc) return rc;
-	if (int rc = c->d_qplanes.ensure(size_t(nq) * 2 * ld8); rc) return rc;
-	if (int rc = c->d_qstats.ensure(size_t(4) * nq * sizeof(float)); rc) return rc;
-	if (int rc = c->d_dense.ensure(size_t(nq) * h->count * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
-	if (int rc = c->d_cand_cnt.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
-	float* qpad = static_cast<float*>(c->d_qpad.ptr);
-	float2* qinfo = static_cast<float2*>(c->d_qstats.ptr);   // [nq] pairs, then [nq] |q|^2, [nq] margins
-	float* q_sq = reinterpret_cast<float*>(qinfo + nq);
-	float* margin = q_sq + nq;
-	float* top_dist = static_cast<float*>(c->d_top.ptr);
-	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
-	uint32_t* top_cnt = top_row + size_t(nq) * kk;
-	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
-	c->pruned_cap = cap;
-	rxgpu::launch_query_prep_i8(h->metric, d_queries, nq, h->dim, qpad, static_cast<int8_t*>(c->d_qplanes.ptr), ld8, h->d_stats, q_sq, margin, qinfo,
-								cand_cnt, cap, c->stream);
-	rxgpu::ScanI8Params p{};
-	p.sp.inv_norms = h->d_inv_norms;
-	p.sp.n = h->count;
-	p.sp.kk = kk;
-	p.sp.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-	p.sp.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-	p.codes = h->d_codes_i8;
-	p.side = h->d_side_i8;
-	p.planes = static_cast<const int8_t*>(c->d_qplanes.ptr);
-	p.qinfo = qinfo;
-	p.row_sq = h->d_row_sq;
-	p.q_sq = q_sq;
-	p.ld8 = ld8;
-	p.lower = static_cast<float*>(c->d_dense.ptr);
-	{
-		ProfileScope ps(h, "scan_i8", c->stream);
-		rxgpu::launch_scan_i8(h->metric, p, nq, gridx, c->stream);
-	}
-	rxgpu::launch_merge_lists(p.sp.part_dist, p.sp.part_row, gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
-	{
-		ProfileScope ps(h, "filter_approx", c->stream);
-		rxgpu::launch_filter_approx(p.lower, h->count, top_dist, top_cnt, kk, margin, static_cast<uint32_t*>(c->d_cand_row.ptr), cand_cnt, cap, nq,
-									h->cus, c->stream);
-	}
-	{
-		ProfileScope ps(h, "rescore", c->stream);
-		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, ld8, h->stride, h->dim, nq, cap, cand_cnt,
-							  static_cast<uint32_t*>(c->d_cand_row.ptr), static_cast<float*>(c->d_cand_dist.ptr), c->stream);
-	}
-	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
-						d_out_count, nullptr, 0, c->stream);
-	{   // more rows inside the bound than the list holds (massive ties), or no finite bound: the f32 path's own scan + merge, gated on device
-		rxgpu::ScanParams e{};
-		e.rows = h->d_rows;
-		e.inv_norms = h->d_inv_norms;
-		e.queries = d_queries;
-		e.n = h->count;
-		e.stride = h->stride;
-		e.dim = h->dim;
-		e.kk = kk;
-		e.part_dist = p.sp.part_dist;
-		e.part_row = p.sp.part_row;
-		e.gate_cnt = cand_cnt;
-		e.gate_cap = cap;
-		ProfileScope ps(h, "fallback_scan", c->stream);
-		rxgpu::launch_scan(h->metric, e, nq, gridx_exact, c->stream);
-		rxgpu::launch_merge_lists(e.part_dist, e.part_row, gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, cand_cnt, cap);
-	}
-	RX_HIP(hipGetLastError());
-	return RXGPU_OK;
-}
-
-// The int8 tier over a row list: enqueue_knn_pruned_i8 with the gather form of the scan.  Lower bounds are kept per LIST POSITION ([nq][n_ids]);
-// the candidate filter maps position -> row, so the re-score and the merges see real rows.  The margin comes from index-wide maxima and is
-// therefore sound for any subset of the rows.  Behind the gate: the f32 subset scan, which is what answers this call off the tier.
-int enqueue_knn_pruned_i8_subset(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids,
-								 uint64_t n_ids, float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count) {
-	if (int rc = ensure_i8_shadow(h, c->stream); rc) return rc;   // (the row statistics first)
-	const uint32_t ld8 = rxgpu::i8_ld(h->dim);
-	const uint32_t gridx = rxgpu::scan_i8_subset_grid_x(n_ids, h->cus);
-	const uint32_t gridx_exact = rxgpu::subset_grid_x(n_ids, h->dim, kk, h->cus);   // the gated f32 subset scan's
-	const uint32_t grid_max = std::max(gridx, gridx_exact);
-	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (n_ids + 63) & ~63ull)));
-	if (int rc = c->d_qpad.ensure(size_t(nq) * ld8 * sizeof(float)); rc) return rc;
-	if (int rc = c->d_qplanes.ensure(size_t(nq) * 2 * ld8); rc) return rc;
-	if (int rc = c->d_qstats.ensure(size_t(4) * nq * sizeof(float)); rc) return rc;
-	if (int rc = c->d_dense.ensure(size_t(nq) * n_ids * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
-	if (int rc = c->d_cand_cnt.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
-	float* qpad = static_cast<float*>(c->d_qpad.ptr);
-	float2* qinfo = static_cast<float2*>(c->d_qstats.ptr);   // [nq] pairs, then [nq] |q|^2, [nq] margins
-	float* q_sq = reinterpret_cast<float*>(qinfo + nq);
-	float* margin = q_sq + nq;
-	float* top_dist = static_cast<float*>(c->d_top.ptr);
-	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
-	uint32_t* top_cnt = top_row + size_t(nq) * kk;
-	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
-	c->pruned_cap = cap;
-	rxgpu::launch_query_prep_i8(h->metric, d_queries, nq, h->dim, qpad, static_cast<int8_t*>(c->d_qplanes.ptr), ld8, h->d_stats, q_sq, margin, qinfo,
-								cand_cnt, cap, c->stream);
-	rxgpu::ScanI8Params p{};
-	p.sp.inv_norms = h->d_inv_norms;
-	p.sp.n = n_ids;
-	p.sp.kk = kk;
-	p.sp.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-	p.sp.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-	p.codes = h->d_codes_i8;
-	p.side = h->d_side_i8;
-	p.planes = static_cast<const int8_t*>(c->d_qplanes.ptr);
-	p.qinfo = qinfo;
-	p.row_sq = h->d_row_sq;
-	p.q_sq = q_sq;
-	p.ld8 = ld8;
-	p.lower = static_cast<float*>(c->d_dense.ptr);
-	{
-		ProfileScope ps(h, "scan_i8_subset", c->stream);
-		rxgpu::launch_scan_i8_subset(h->metric, p, d_ids, nq, gridx, h->cus, c->stream);
-	}
-	rxgpu::launch_merge_lists(p.sp.part_dist, p.sp.part_row, gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
-	{
-		ProfileScope ps(h, "filter_approx", c->stream);
-		rxgpu::launch_filter_approx(p.lower, n_ids, top_dist, top_cnt, kk, margin, static_cast<uint32_t*>(c->d_cand_row.ptr), cand_cnt, cap, nq, h->cus,
-									c->stream, d_ids);
-	}
-	{
-		ProfileScope ps(h, "rescore", c->stream);
-		rxgpu::launch_rescore(h->metric, h->d_rows, h->d_inv_norms, qpad, ld8, h->stride, h->dim, nq, cap, cand_cnt,
-							  static_cast<uint32_t*>(c->d_cand_row.ptr), static_cast<float*>(c->d_cand_dist.ptr), c->stream);
-	}
-	rxgpu::launch_merge(static_cast<float*>(c->d_cand_dist.ptr), static_cast<uint32_t*>(c->d_cand_row.ptr), cap, kk, nq, d_out_dist, d_out_row,
-						d_out_count, nullptr, 0, c->stream);
-	{   // more listed rows inside the bound than the list holds, or no finite bound: the f32 subset scan + its merge, gated on device
-		rxgpu::ScanParams e{};
-		e.rows = h->d_rows;
-		e.inv_norms = h->d_inv_norms;
-		e.queries = d_queries;
-		e.n = n_ids;
-		e.stride = h->stride;
-		e.dim = h->dim;
-		e.kk = kk;
-		e.part_dist = p.sp.part_dist;
-		e.part_row = p.sp.part_row;
-		e.gate_cnt = cand_cnt;
-		e.gate_cap = cap;
-		// While profiling, the slot counts the calls whose gate OPENED for one of the queries (the counts are read back first, which synchronises
-		// the stream): a call the pruned chain answered leaves it at 0, like "scan_subset".
-		bool opened = false;
-		if (h->profiling) {
-			std::vector<uint32_t> cnt(nq);
-			RX_HIP(hipMemcpyAsync(cnt.data(), cand_cnt, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-			RX_HIP(hipStreamSynchronize(c->stream));
-			opened = std::any_of(cnt.begin(), cnt.end(), [&](uint32_t v) { return v > cap; });
-		}
-		auto fallback = [&] {
-			rxgpu::launch_scan_subset(h->metric, e, d_ids, nq, gridx_exact, h->cus, c->stream);
-			rxgpu::launch_merge_lists(e.part_dist, e.part_row, gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, cand_cnt, cap);
-		};
-		if (opened) {
-			ProfileScope ps(h, "fallback_scan", c->stream);
-			fallback();
-		} else {
-			fallback();
-		}
-	}
-	RX_HIP(hipGetLastError());
-	return RXGPU_OK;
-}
-
-// Pre-filtered search, kk <= kMaxFusedK2: gather-scan over the row list + the usual merge (rows in the lists are real rows, so the
-// merge and everything downstream is unchanged).  Where scan_policy_tier_subset says so, the int8-pruned chain above answers instead.
-int enqueue_knn_subset(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids,
-					   uint64_t n_ids, float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count) {
-	// (the device entry point may pass kk > n_ids; the chain runs with kk itself, so a kk above one entry per lane stays off the tier whatever the list)
-	const uint32_t eff = kk <= uint32_t(rxgpu::kMaxFusedK) ? uint32_t(std::min<uint64_t>(kk, n_ids)) : kk;
-	if (scan_policy_tier_subset(n_ids, h->dim, nq, eff, !h->i8_unavailable, true) == kTierI8) {
-		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;   // (automatic mode asks whether the row statistics are finite)
-		if (scan_policy_tier_subset(n_ids, h->dim, nq, eff, !h->i8_unavailable, h->stats_finite) == kTierI8) {
-			const int rc = enqueue_knn_pruned_i8_subset(h, c, d_queries, nq, kk, d_ids, n_ids, d_out_dist, d_out_row, d_out_count);
-			if (!(rc == RXGPU_ERR_NOMEM && h->i8_unavailable)) return rc;   // no room for the int8 shadow: the f32 subset scan below
-		}
-	}
-	const uint32_t gridx = rxgpu::subset_grid_x(n_ids, h->dim, kk, h->cus);
-	const size_t part = size_t(nq) * gridx * kk;
-	if (int rc = c->d_part_dist.ensure(part * sizeof(float)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(part * sizeof(uint32_t)); rc) return rc;
-	rxgpu::ScanParams p{};
-	p.rows = h->d_rows;
-	p.inv_norms = h->d_inv_norms;
-	p.queries = d_queries;
-	p.n = n_ids;
-	p.stride = h->stride;
-	p.dim = h->dim;
-	p.kk = kk;
-	p.part_dist = static_cast<float*>(c->d_part_dist.ptr);
-	p.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
-	{
-		ProfileScope ps(h, "scan_subset", c->stream);
-		rxgpu::launch_scan_subset(h->metric, p, d_ids, nq, gridx, h->cus, c->stream);
-	}
-	{
-		ProfileScope ps(h, "merge", c->stream);
-		rxgpu::launch_merge_lists(p.part_dist, p.part_row, gridx, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream);
-	}
-	RX_HIP(hipGetLastError());
-	return RXGPU_OK;
-}
-
-// Host-facing tail shared by rxgpu_search_knn_subset / _bitmap: queries on the host, the row list already in HBM.
-int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids,
-					   uint64_t n_ids, float* out_dist, uint32_t* out_row, uint32_t* out_count) {
-	const uint32_t eff = uint32_t(std::min<uint64_t>(kk, n_ids));
-	const size_t qbytes = size_t(nq) * h->dim * sizeof(float);
-	if (int rc = c->d_queries.ensure(qbytes); rc) return rc;
-	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, queries, qbytes, hipMemcpyHostToDevice, c->stream));
-	if (eff <= uint32_t(rxgpu::kMaxFusedK2)) {
-		if (int rc = c->d_out_dist.ensure(size_t(nq) * eff * sizeof(float)); rc) return rc;
-		if (int rc = c->d_out_row.ensure(size_t(nq) * eff * sizeof(uint32_t)); rc) return rc;
-		if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
-		c->pruned_cap = 0;   // set by a pruned chain
-		if (int rc = enqueue_knn_subset(h, c, static_cast<const float*>(c->d_queries.ptr), nq, eff, d_ids, n_ids,
-										static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr),
-										static_cast<uint32_t*>(c->d_out_count.ptr));
-			rc)
-			return rc;
-		RX_HIP(hipMemcpy2DAsync(out_dist, kk * sizeof(float), c->d_out_dist.ptr, eff * sizeof(float), eff * sizeof(float), nq,
-								hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipMemcpy2DAsync(out_row, kk * sizeof(uint32_t), c->d_out_row.ptr, eff * sizeof(uint32_t), eff * sizeof(uint32_t), nq,
-								hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipMemcpyAsync(out_count, c->d_out_count.ptr, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipStreamSynchronize(c->stream));
-		if (h->profiling && nq == 1 && c->pruned_cap) {   // rxgpu_index_last_candidates, as rxgpu_search_knn records it
-			uint32_t cnt = 0;
-			RX_HIP(hipMemcpy(&cnt, c->d_cand_cnt.ptr, sizeof(cnt), hipMemcpyDeviceToHost));
-			h->last_cand_count = cnt;
-			h->last_cand_cap = c->pruned_cap;
-		}
-		return RXGPU_OK;
-	}
-	// large k: distances of the listed rows + radix select over (dist, position); positions -> rows; final sort of eff entries on the host
-	RX_CHECK(n_ids <= (1ull << 28), RXGPU_ERR_PARAMS, "pre-filtered search with k > 128: the row list must not exceed 2^28 entries");
-	if (int rc = c->d_misc.ensure(n_ids * sizeof(float)); rc) return rc;
-	if (int rc = c->d_select.ensure(rxgpu::select_scratch_bytes(n_ids)); rc) return rc;
-	if (int rc = c->d_out_dist.ensure(size_t(eff) * sizeof(float)); rc) return rc;
-	if (int rc = c->d_out_row.ensure(size_t(eff) * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_part_row.ensure(size_t(eff) * sizeof(uint32_t)); rc) return rc;
-	std::vector<float> hd(eff);
-	std::vector<uint32_t> hr(eff), order(eff);
-	for (uint32_t q = 0; q < nq; ++q) {
-		{
-			ProfileScope ps(h, "scan_subset", c->stream);
-			rxgpu::launch_distances(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr) + size_t(q) * h->dim,
-									h->stride, h->dim, d_ids, uint32_t(n_ids), static_cast<float*>(c->d_misc.ptr), c->stream);
-		}
-		rxgpu::launch_select_smallest(static_cast<const float*>(c->d_misc.ptr), n_ids, eff, c->d_select.ptr, static_cast<float*>(c->d_out_dist.ptr),
-									  static_cast<uint32_t*>(c->d_out_row.ptr), c->stream);
-		rxgpu::launch_gather_u32(d_ids, static_cast<const uint32_t*>(c->d_out_row.ptr), eff, static_cast<uint32_t*>(c->d_part_row.ptr), c->stream);
-		RX_HIP(hipGetLastError());
-		RX_HIP(hipMemcpyAsync(hd.data(), c->d_out_dist.ptr, size_t(eff) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipMemcpyAsync(hr.data(), c->d_part_row.ptr, size_t(eff) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipStreamSynchronize(c->stream));
-		std::iota(order.begin(), order.end(), 0u);
-		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hd[a] < hd[b] || (!(hd[b] < hd[a]) && hr[a] < hr[b]); });
-		for (uint32_t i = 0; i < eff; ++i) {
-			out_dist[size_t(q) * kk + i] = hd[order[i]];
-			out_row[size_t(q) * kk + i] = hr[order[i]];
-		}
-		out_count[q] = eff;
-	}
-	return RXGPU_OK;
-}
-
-int enqueue_knn(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist,
-				uint32_t* d_out_row, uint32_t* d_out_count) {
-	// (automatic mode asks whether the row statistics are finite: compute them first where everything else already says yes)
-	if (scan_bf16_mode() == kScanBf16Auto && scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, true) != kTierF32) {
-		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
-	}
-	if (scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, h->stats_finite) == kTierI8) {
-		const int rc = enqueue_knn_pruned_i8(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
-		if (!(rc == RXGPU_ERR_NOMEM && h->i8_unavailable)) return rc;   // no room for the int8 shadow: the bf16 tier below
-	}
-	if (scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, h->stats_finite) == kTierBf16) {
-		const int rc = enqueue_knn_pruned(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
-		if (!(rc == RXGPU_ERR_NOMEM && h->bf16_unavailable)) return rc;
-	}
-	if (int(nq) >= batch_min_queries() && nq >= 2) return enqueue_knn_batched(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
-	return enqueue_knn_fused(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1059,15 +260,15 @@ const char* rxgpu_last_error(void) { return rxgpu::g_err.c_str(); }
 int rxgpu_abi_version(void) { return RXGPU_ABI_VERSION; }
 
 int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
-	return scan_policy_pruned(rows, dim, nq, shadow_available != 0, stats_finite != 0) ? 1 : 0;
+	return rxgpu::scan_policy_pruned(rows, dim, nq, shadow_available != 0, stats_finite != 0) ? 1 : 0;
 }
 
 int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
-	return int(scan_policy_tier(rows, dim, nq, shadow_available != 0, shadow_available != 0, stats_finite != 0));
+	return int(rxgpu::scan_policy_tier(rows, dim, nq, shadow_available != 0, shadow_available != 0, stats_finite != 0));
 }
 
 int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, int shadow_available, int stats_finite) {
-	return int(scan_policy_tier_subset(n_ids, dim, nq, kk, shadow_available != 0, stats_finite != 0));
+	return int(rxgpu::scan_policy_tier_subset(n_ids, dim, nq, kk, shadow_available != 0, stats_finite != 0));
 }
 
 int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap) {
@@ -1157,12 +358,8 @@ void rxgpu_index_destroy(rxgpu_index* h) {
 		if (h->d_rows) (void)hipFree(h->d_rows);
 		if (h->d_inv_norms) (void)hipFree(h->d_inv_norms);
 	}
-	if (h->d_row_sq) (void)hipFree(h->d_row_sq);
+	rxgpu::derived_free(h);
 	if (h->d_row_ids) (void)hipFree(h->d_row_ids);
-	if (h->d_rows_bf16) (void)hipFree(h->d_rows_bf16);
-	if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
-	if (h->d_side_i8) (void)hipFree(h->d_side_i8);
-	if (h->d_stats) (void)hipFree(h->d_stats);
 	if (h->d_links0) (void)hipFree(h->d_links0);
 	if (h->d_upper_off) (void)hipFree(h->d_upper_off);
 	if (h->d_upper) (void)hipFree(h->d_upper);
@@ -1233,39 +430,7 @@ int rxgpu_index_upload_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, cons
 		RX_HIP(hipMemcpy(h->d_inv_norms + first_row, inv_norms, n * sizeof(float), hipMemcpyHostToDevice));
 	}
 	h->count = std::max(h->count, first_row + n);
-	// Derived data follows the mutation incrementally (a full recompute streams the whole corpus: 4 ms per 10M x 768 rows).  The row
-	// statistics are maxima entering an error BOUND, so folding the new rows in (and never shrinking on deletes) keeps them valid.
-	std::lock_guard<std::mutex> lk(h->mtx);
-	if (h->stats_valid) {
-		if (h->metric == RXGPU_METRIC_L2 && h->row_sq_capacity < first_row + n) {
-			h->stats_valid = false;
-		} else {
-			rxgpu::launch_row_stats(dst, h->d_inv_norms ? h->d_inv_norms + first_row : nullptr, n, h->stride, h->dim,
-									h->metric == RXGPU_METRIC_L2 ? h->d_row_sq + first_row : nullptr, h->d_stats, h->cus, nullptr);
-			if (int rc = read_stats_finite(h, nullptr); rc) return rc;   // maxima never shrink: an index that has held a non-finite row stays on the f32 scan
-		}
-	}
-	if (h->bf16_valid) {
-		if (h->bf16_capacity < first_row + n) {
-			h->bf16_valid = false;
-		} else {
-			const uint32_t ld = (h->dim + 63u) & ~63u;
-			rxgpu::launch_to_bf16(dst, n, h->stride, h->dim, h->d_rows_bf16, ld, h->cus, nullptr, first_row, h->bf16_blocked);
-		}
-	}
-	if (h->i8_valid) {
-		if (h->i8_capacity < first_row + n || !h->stats_valid) {
-			h->i8_valid = false;
-		} else {   // re-quantise the range; its residual maxima join the statistics words
-			const uint32_t ld8 = rxgpu::i8_ld(h->dim);
-			rxgpu::launch_i8_build(dst, h->d_inv_norms ? h->d_inv_norms + first_row : nullptr, n, h->stride, h->dim, h->d_codes_i8 + first_row * ld8,
-								   h->d_side_i8 + first_row, ld8, h->d_stats, h->cus, nullptr);
-			if (int rc = read_stats_finite(h, nullptr); rc) return rc;
-		}
-	}
-	RX_HIP(hipGetLastError());
-	RX_HIP(hipStreamSynchronize(nullptr));
-	return RXGPU_OK;
+	return rxgpu::derived_follow_upload(h, first_row, n);
 }
 
 int rxgpu_index_adopt_device_rows(rxgpu_index* h, const void* d_rows, uint64_t n, uint32_t row_stride, const void* d_inv_norms) {
@@ -1288,9 +453,7 @@ int rxgpu_index_adopt_device_rows(rxgpu_index* h, const void* d_rows, uint64_t n
 	h->stride = row_stride;
 	h->capacity = n;
 	h->count = n;
-	h->stats_valid = false;
-	h->bf16_valid = false;
-	h->i8_valid = false;
+	rxgpu::derived_invalidate(h);
 	return RXGPU_OK;
 }
 
@@ -1304,22 +467,7 @@ int rxgpu_index_move_row(rxgpu_index* h, uint64_t from, uint64_t to) {
 	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel reads what changes here
 	RX_HIP(hipMemcpy(h->d_rows + to * h->stride, h->d_rows + from * h->stride, h->stride * sizeof(float), hipMemcpyDeviceToDevice));
 	if (h->d_inv_norms) RX_HIP(hipMemcpy(h->d_inv_norms + to, h->d_inv_norms + from, sizeof(float), hipMemcpyDeviceToDevice));
-	std::lock_guard<std::mutex> lk(h->mtx);
-	if (h->stats_valid && h->metric == RXGPU_METRIC_L2) {
-		RX_HIP(hipMemcpy(h->d_row_sq + to, h->d_row_sq + from, sizeof(float), hipMemcpyDeviceToDevice));
-	}
-	if (h->bf16_valid) {
-		const uint32_t ld = (h->dim + 63u) & ~63u;
-		rxgpu::launch_shadow_move(h->d_rows_bf16, ld, from, to, h->bf16_blocked, nullptr);
-		RX_HIP(hipGetLastError());
-		RX_HIP(hipStreamSynchronize(nullptr));
-	}
-	if (h->i8_valid) {
-		const uint32_t ld8 = rxgpu::i8_ld(h->dim);
-		RX_HIP(hipMemcpy(h->d_codes_i8 + to * ld8, h->d_codes_i8 + from * ld8, ld8, hipMemcpyDeviceToDevice));
-		RX_HIP(hipMemcpy(h->d_side_i8 + to, h->d_side_i8 + from, sizeof(float2), hipMemcpyDeviceToDevice));
-	}
-	return RXGPU_OK;
+	return rxgpu::derived_follow_move(h, from, to);
 }
 
 int rxgpu_index_download_row(rxgpu_index* h, uint64_t row, float* out_row, float* out_inv_norm) {
@@ -1341,11 +489,7 @@ int rxgpu_index_truncate(rxgpu_index* h, uint64_t count) {
 	RX_CHECK(count <= h->capacity, RXGPU_ERR_PARAMS, "rxgpu_index_truncate: count exceeds capacity");
 	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel reads what changes here
 	// shrinking keeps the statistics (upper bounds stay upper bounds) and the shadow (rows past count are never read)
-	if (count > h->count) {
-		h->stats_valid = false;
-		h->bf16_valid = false;
-		h->i8_valid = false;
-	}
+	if (count > h->count) rxgpu::derived_invalidate(h);
 	h->count = count;
 	return RXGPU_OK;
 }
@@ -1485,24 +629,7 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 						 static_cast<uint32_t*>(c->d_out_row.ptr), static_cast<uint32_t*>(c->d_out_count.ptr));
 			rc)
 			return rc;
-		if (eff == kk) {
-			RX_HIP(hipMemcpyAsync(out_dist, c->d_out_dist.ptr, size_t(nq) * eff * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-			RX_HIP(hipMemcpyAsync(out_row, c->d_out_row.ptr, size_t(nq) * eff * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-		} else {
-			RX_HIP(hipMemcpy2DAsync(out_dist, kk * sizeof(float), c->d_out_dist.ptr, eff * sizeof(float), eff * sizeof(float), nq,
-									hipMemcpyDeviceToHost, c->stream));
-			RX_HIP(hipMemcpy2DAsync(out_row, kk * sizeof(uint32_t), c->d_out_row.ptr, eff * sizeof(uint32_t), eff * sizeof(uint32_t), nq,
-									hipMemcpyDeviceToHost, c->stream));
-		}
-		RX_HIP(hipMemcpyAsync(out_count, c->d_out_count.ptr, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-		RX_HIP(hipStreamSynchronize(c->stream));
-		if (h->profiling && nq == 1 && c->pruned_cap) {   // rxgpu_index_last_candidates: what the pruned chain of this call nominated
-			uint32_t cnt = 0;
-			RX_HIP(hipMemcpy(&cnt, c->d_cand_cnt.ptr, sizeof(cnt), hipMemcpyDeviceToHost));
-			h->last_cand_count = cnt;
-			h->last_cand_cap = c->pruned_cap;
-		}
-		return RXGPU_OK;
+		return rxgpu::copy_back_knn(h, c, nq, kk, eff, out_dist, out_row, out_count);
 	}
 
 	// large-k path: distance pass + radix select per query, final (dist,row) sort of kk entries on the host
@@ -1512,7 +639,7 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 	if (int rc = c->d_out_row.ensure(size_t(eff) * sizeof(uint32_t)); rc) return rc;
 	const uint32_t gridx = rxgpu::scan_grid_x(h->count, h->cus);
 	std::vector<float> hd(eff);
-	std::vector<uint32_t> hr(eff), order(eff);
+	std::vector<uint32_t> hr(eff);
 	for (uint32_t q = 0; q < nq; ++q) {
 		{
 			ProfileScope ps(h, "scan", c->stream);
@@ -1528,14 +655,7 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 		RX_HIP(hipMemcpyAsync(hd.data(), c->d_out_dist.ptr, size_t(eff) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 		RX_HIP(hipMemcpyAsync(hr.data(), c->d_out_row.ptr, size_t(eff) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 		RX_HIP(hipStreamSynchronize(c->stream));
-		std::iota(order.begin(), order.end(), 0u);
-		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-			return hd[a] < hd[b] || (!(hd[b] < hd[a]) && hr[a] < hr[b]);
-		});
-		for (uint32_t i = 0; i < eff; ++i) {
-			out_dist[size_t(q) * kk + i] = hd[order[i]];
-			out_row[size_t(q) * kk + i] = hr[order[i]];
-		}
+		rxgpu::sort_dist_row(hd, hr, out_dist + size_t(q) * kk, out_row + size_t(q) * kk);
 		out_count[q] = eff;
 	}
 	return RXGPU_OK;

@@ -1,0 +1,184 @@
+// Data derived from the rows of an index: the row statistics, the bf16 shadow and the int8 shadow.  Built lazily by the search chains
+// (ensure_*), kept in step by the mutations of rxgpu_capi.hip through the four derived_* calls below.  Host-side plumbing only.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "../../include/rxgpu.h"
+#include "knn_i8_quant.h"
+#include "knn_kernels.hip.h"
+#include "rxgpu_internal.h"
+
+namespace rxgpu {
+namespace {
+
+// The statistics words back on the host (h->mtx held): are the maxima finite and has no NaN row been seen?  Only then does the rounding
+// bound of a pruned scan mean anything; the automatic scan policy (enqueue_knn) keeps such an index on the f32 scan.  Words 3 and 4 (the
+// int8 shadow's residual maxima, knn_scan_i8.hip) report a non-finite value through word 2.
+constexpr size_t kStatsWords = 5;
+int read_stats_finite(rxgpu_index* h, hipStream_t s) {
+	unsigned int w[3] = {0, 0, 0};
+	RX_HIP(hipMemcpyAsync(w, h->d_stats, sizeof(w), hipMemcpyDeviceToHost, s));
+	RX_HIP(hipStreamSynchronize(s));
+	float a, b;
+	std::memcpy(&a, &w[0], sizeof(a));
+	std::memcpy(&b, &w[1], sizeof(b));
+	h->stats_finite = std::isfinite(a) && std::isfinite(b) && w[2] == 0;
+	return RXGPU_OK;
+}
+
+uint32_t bf16_ld(const rxgpu_index* h) { return (h->dim + 63u) & ~63u; }
+
+}  // namespace
+
+// Per-row statistics are cached on the index; recomputed (synchronously, under the index mutex) after any mutation.
+int ensure_row_stats(rxgpu_index* h, hipStream_t s) {
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->stats_valid) return RXGPU_OK;
+	if (!h->d_stats) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats), kStatsWords * sizeof(unsigned int)));
+	if (h->metric == RXGPU_METRIC_L2 && h->row_sq_capacity < h->count) {
+		if (h->d_row_sq) (void)hipFree(h->d_row_sq);
+		h->d_row_sq = nullptr;
+		h->row_sq_capacity = 0;
+		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_row_sq), std::max<uint64_t>(h->capacity, h->count) * sizeof(float)));
+		h->row_sq_capacity = std::max<uint64_t>(h->capacity, h->count);
+	}
+	RX_HIP(hipMemsetAsync(h->d_stats, 0, kStatsWords * sizeof(unsigned int), s));
+	h->i8_valid = false;   // its two words were cleared with the rest: the shadow's next build folds them in again
+	launch_row_stats(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->metric == RXGPU_METRIC_L2 ? h->d_row_sq : nullptr, h->d_stats, h->cus, s);
+	RX_HIP(hipGetLastError());
+	if (int rc = read_stats_finite(h, s); rc) return rc;   // synchronises the stream
+	h->stats_valid = true;
+	return RXGPU_OK;
+}
+
+// bf16 shadow of the rows for the nomination GEMM: 2 bytes per element on top of the 4-byte rows (HBM is 288 GB: 10M x 768 costs 15.4 GB);
+// rebuilt lazily after any mutation, like the row statistics.
+int ensure_bf16_shadow(rxgpu_index* h, hipStream_t s) {
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->bf16_valid) return RXGPU_OK;
+	const uint32_t ld = bf16_ld(h);
+	const uint64_t need = (std::max<uint64_t>(h->capacity, h->count) + kShadowTileRows - 1) / kShadowTileRows * kShadowTileRows;   // whole tiles
+	if (h->bf16_capacity < need) {
+		if (h->d_rows_bf16) (void)hipFree(h->d_rows_bf16);
+		h->d_rows_bf16 = nullptr;
+		h->bf16_capacity = 0;
+		const char* e = getenv("RXGPU_SHADOW_BLOCKED");
+		h->bf16_blocked = !(e && atoi(e) == 0);
+		if (hipMalloc(reinterpret_cast<void**>(&h->d_rows_bf16), need * ld * sizeof(uint16_t)) != hipSuccess) {
+			(void)hipGetLastError();   // not an error of the search: the caller falls back to the f32 rows
+			h->d_rows_bf16 = nullptr;
+			h->bf16_unavailable = true;
+			return RXGPU_ERR_NOMEM;
+		}
+		h->bf16_capacity = need;
+	}
+	launch_to_bf16(h->d_rows, h->count, h->stride, h->dim, h->d_rows_bf16, ld, h->cus, s, 0, h->bf16_blocked);
+	RX_HIP(hipGetLastError());
+	RX_HIP(hipStreamSynchronize(s));
+	h->bf16_valid = true;
+	return RXGPU_OK;
+}
+
+// int8 shadow of the rows for the pruning pass of a single query (knn_scan_i8.hip): 1 byte per element + 8 bytes per row on top of the 4-byte
+// rows; built lazily behind the row statistics (it folds two more maxima into their words) and kept in step by the mutations like the bf16 shadow.
+int ensure_i8_shadow(rxgpu_index* h, hipStream_t s) {
+	if (int rc = ensure_row_stats(h, s); rc) return rc;
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->i8_valid) return RXGPU_OK;
+	const uint32_t ld8 = i8_ld(h->dim);
+	const uint64_t need = std::max<uint64_t>(h->capacity, h->count);
+	if (h->i8_capacity < need) {
+		if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
+		if (h->d_side_i8) (void)hipFree(h->d_side_i8);
+		h->d_codes_i8 = nullptr;
+		h->d_side_i8 = nullptr;
+		h->i8_capacity = 0;
+		if (hipMalloc(reinterpret_cast<void**>(&h->d_codes_i8), need * ld8) != hipSuccess ||
+			hipMalloc(reinterpret_cast<void**>(&h->d_side_i8), need * sizeof(float2)) != hipSuccess) {
+			(void)hipGetLastError();   // not an error of the search: the caller takes the bf16 tier
+			if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
+			h->d_codes_i8 = nullptr;
+			h->d_side_i8 = nullptr;
+			h->i8_unavailable = true;
+			return RXGPU_ERR_NOMEM;
+		}
+		h->i8_capacity = need;
+	}
+	launch_i8_build(h->d_rows, h->d_inv_norms, h->count, h->stride, h->dim, h->d_codes_i8, h->d_side_i8, ld8, h->d_stats, h->cus, s);
+	RX_HIP(hipGetLastError());
+	if (int rc = read_stats_finite(h, s); rc) return rc;   // synchronises the stream
+	h->i8_valid = true;
+	return RXGPU_OK;
+}
+
+void derived_invalidate(rxgpu_index* h) {
+	h->stats_valid = false;
+	h->bf16_valid = false;
+	h->i8_valid = false;
+}
+
+// Derived data follows the mutation incrementally (a full recompute streams the whole corpus: 4 ms per 10M x 768 rows).  The row
+// statistics are maxima entering an error BOUND, so folding the new rows in (and never shrinking on deletes) keeps them valid.
+int derived_follow_upload(rxgpu_index* h, uint64_t first_row, uint64_t n) {
+	const float* rows = h->d_rows + first_row * h->stride;
+	const float* inv_norms = h->d_inv_norms ? h->d_inv_norms + first_row : nullptr;
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->stats_valid) {
+		if (h->metric == RXGPU_METRIC_L2 && h->row_sq_capacity < first_row + n) {
+			h->stats_valid = false;
+		} else {
+			launch_row_stats(rows, inv_norms, n, h->stride, h->dim, h->metric == RXGPU_METRIC_L2 ? h->d_row_sq + first_row : nullptr, h->d_stats, h->cus,
+							 nullptr);
+			if (int rc = read_stats_finite(h, nullptr); rc) return rc;   // maxima never shrink: an index that has held a non-finite row stays on the f32 scan
+		}
+	}
+	if (h->bf16_valid) {
+		if (h->bf16_capacity < first_row + n) {
+			h->bf16_valid = false;
+		} else {
+			launch_to_bf16(rows, n, h->stride, h->dim, h->d_rows_bf16, bf16_ld(h), h->cus, nullptr, first_row, h->bf16_blocked);
+		}
+	}
+	if (h->i8_valid) {
+		if (h->i8_capacity < first_row + n || !h->stats_valid) {
+			h->i8_valid = false;
+		} else {   // re-quantise the range; its residual maxima join the statistics words
+			const uint32_t ld8 = i8_ld(h->dim);
+			launch_i8_build(rows, inv_norms, n, h->stride, h->dim, h->d_codes_i8 + first_row * ld8, h->d_side_i8 + first_row, ld8, h->d_stats, h->cus, nullptr);
+			if (int rc = read_stats_finite(h, nullptr); rc) return rc;
+		}
+	}
+	RX_HIP(hipGetLastError());
+	RX_HIP(hipStreamSynchronize(nullptr));
+	return RXGPU_OK;
+}
+
+int derived_follow_move(rxgpu_index* h, uint64_t from, uint64_t to) {
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->stats_valid && h->metric == RXGPU_METRIC_L2) {
+		RX_HIP(hipMemcpy(h->d_row_sq + to, h->d_row_sq + from, sizeof(float), hipMemcpyDeviceToDevice));
+	}
+	if (h->bf16_valid) {
+		launch_shadow_move(h->d_rows_bf16, bf16_ld(h), from, to, h->bf16_blocked, nullptr);
+		RX_HIP(hipGetLastError());
+		RX_HIP(hipStreamSynchronize(nullptr));
+	}
+	if (h->i8_valid) {
+		const uint32_t ld8 = i8_ld(h->dim);
+		RX_HIP(hipMemcpy(h->d_codes_i8 + to * ld8, h->d_codes_i8 + from * ld8, ld8, hipMemcpyDeviceToDevice));
+		RX_HIP(hipMemcpy(h->d_side_i8 + to, h->d_side_i8 + from, sizeof(float2), hipMemcpyDeviceToDevice));
+	}
+	return RXGPU_OK;
+}
+
+void derived_free(rxgpu_index* h) {
+	if (h->d_row_sq) (void)hipFree(h->d_row_sq);
+	if (h->d_rows_bf16) (void)hipFree(h->d_rows_bf16);
+	if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
+	if (h->d_side_i8) (void)hipFree(h->d_side_i8);
+	if (h->d_stats) (void)hipFree(h->d_stats);
+}
+
+}  // namespace rxgpu

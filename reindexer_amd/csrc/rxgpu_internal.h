@@ -613,4 +613,31 @@ struct ProfileScope {
 	ProfileScope(rxgpu_index* h_, const char* n, hipStream_t s_);
 	~ProfileScope();
 };
+
+// Data derived from the rows (rxgpu_derived.hip): row statistics, bf16 shadow, int8 shadow.  The chains build them lazily ...
+int ensure_row_stats(rxgpu_index* h, hipStream_t s);
+int ensure_bf16_shadow(rxgpu_index* h, hipStream_t s);   // RXGPU_ERR_NOMEM + h->bf16_unavailable: it does not fit, the caller takes the f32 rows
+int ensure_i8_shadow(rxgpu_index* h, hipStream_t s);     // (the row statistics first)  RXGPU_ERR_NOMEM + h->i8_unavailable: the caller takes the bf16 tier
+// ... and the mutations keep them in step
+void derived_invalidate(rxgpu_index* h);                                        // the rows changed wholesale: everything is rebuilt at its next use
+int derived_follow_upload(rxgpu_index* h, uint64_t first_row, uint64_t n);      // rows [first_row, first_row + n) were written
+int derived_follow_move(rxgpu_index* h, uint64_t from, uint64_t to);            // row `from` was copied over row `to`
+void derived_free(rxgpu_index* h);                                              // the index is being destroyed
+
+// The chains of brute-force KNN (rxgpu_knn_chains.hip), as far as the entry points call them.  nq device-resident queries, results in d_out_* (device).
+int enqueue_knn(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist, uint32_t* d_out_row,
+				uint32_t* d_out_count);   // kk <= kMaxFusedK: fused / batched / pruned, as the scan policy says
+int enqueue_knn_fused(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist, uint32_t* d_out_row,
+					  uint32_t* d_out_count);   // kk <= kMaxFusedK2
+int enqueue_knn_subset(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids, uint64_t n_ids,
+					   float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count);   // over an ascending row list in HBM
+int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids, uint64_t n_ids,
+					   float* out_dist, uint32_t* out_row, uint32_t* out_count);   // ... queries and results on the host, any kk
+int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk, uint32_t eff, float* out_dist, uint32_t* out_row, uint32_t* out_count);
+void sort_dist_row(const std::vector<float>& hd, const std::vector<uint32_t>& hr, float* out_dist, uint32_t* out_row);
+// the scan policy, without a device (rxgpu_scan_policy, rxgpu_scan_tier, rxgpu_scan_tier_subset)
+enum ScanTier { kTierF32 = 0, kTierBf16 = 1, kTierI8 = 2 };
+bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite);
+ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool bf16_available, bool i8_available, bool stats_finite);
+ScanTier scan_policy_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, bool i8_available, bool stats_finite);
 }  // namespace rxgpu

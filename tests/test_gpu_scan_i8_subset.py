@@ -1,4 +1,4 @@
-"""-m gpu: the int8 shadow tier of the searches over a ROW LIST (knn_scan_i8_subset in knn_scan_i8.hip, enqueue_knn_pruned_i8_subset): the
+"""-m gpu: the int8 shadow tier of the searches over a ROW LIST (knn_scan_i8_subset in knn_scan_i8.hip, enqueue_knn_pruned_i8 with a row list): the
 pre-filtered search (rxgpu_search_knn_subset / _bitmap / _subset_device), IVF (rxgpu_search_knn_lists) and their per-shard calls.
 
 The yardstick of every comparison is THE SAME BUILD with RXGPU_SCAN_BF16=0, the f32 subset path that test_gpu_prefilter.py pins to the

@@ -1,4 +1,4 @@
-"""The default scan policy of a single query (rxgpu_capi.hip: scan_policy_pruned / enqueue_knn).
+"""The default scan policy of a single query (rxgpu_knn_chains.hip: scan_policy_pruned / enqueue_knn).
 
 RXGPU_SCAN_BF16 unset = automatic: nq == 1 on an index of at least RXGPU_SCAN_BF16_MIN_BYTES (default 1 GiB) of f32 rows takes the bf16-pruned
 scan where the dimension is supported, the shadow fits and the row statistics are finite; 0 = the f32 paths always; 1 = forced on.  The

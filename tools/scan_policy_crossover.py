@@ -9,7 +9,7 @@ One process, one resident corpus per size; per size the three series (RXGPU_SCAN
 read by the library on every call; the int8 series only at dimensions that tier serves) ALTERNATE,
 --rounds times each, every round timing --queries single-query searches through rxgpu_search_knn_device with one synchronisation at the end
 (what bench.py calls ms_per_step).  Reported per size and series: median, min, max of the rounds.  The pruned path "wins" at a size when its
-worst round beats the f32 path's best round; the automatic threshold in rxgpu_capi.hip (kPrunedAutoMinBytes) is the smallest such size in
+worst round beats the f32 path's best round; the automatic threshold in rxgpu_knn_chains.hip (kPrunedAutoMinBytes) is the smallest such size in
 bytes of f32 rows, rounded up to a power of two, and never below 1 GiB.  The int8 tier's threshold (kPrunedI8AutoMinBytes) follows the same
 rule against the bf16 series.
 """
