@@ -176,6 +176,25 @@ int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_availab
  * (count > cap: the list overflowed, or the query had no finite bound, and the exact scan answered).  Recorded only while profiling is
  * enabled (rxgpu_profile_enable). */
 int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap);
+/* Test instrumentation: copies a named internal buffer of a single-device index to the host.  Reads only - nothing is built, invalidated or
+ * changed.  *out_bytes is always set to the size needed; RXGPU_ERR_OVERFLOW when cap_bytes is smaller (out may be NULL then),
+ * RXGPU_ERR_PARAMS for an unknown name or a sharded handle (inspect its rxgpu_index_shard handles), RXGPU_ERR_LOGIC when the buffer does
+ * not exist (a shadow that is not built or is stale, no pruned call recorded, a name the tier or the metric does not have).
+ * Derived data, for the count rows the index holds:
+ *   "stats"      5 uint32: bits of max |x|^2, of max (|x| inv_norm)^2 (cosine), 1 once a non-finite row was seen, bits of max e^2 and of
+ *                max (e inv_norm)^2 (cosine) of the int8 shadow
+ *   "row_sq"     [count] float |x|^2 (L2 only)
+ *   "codes_i8"   [count][dim rounded up to 256] int8 codes          "side_i8"  [count] float pairs {s_r, e_r}
+ *   "rows_bf16"  [count][dim rounded up to 64] bf16 words, ROW-MAJOR whatever layout the shadow has on the device
+ * The last single-query search a pruned chain answered while profiling was enabled (recorded with rxgpu_index_last_candidates; the
+ * snapshot is what that chain left in its buffers and is valid UNTIL THE NEXT CALL ON THE INDEX, which may reuse them):
+ *   "pruned_values"     [n] float: the lower bound lo (int8 tier) or the approximate distance (bf16 tier) per row - per LIST POSITION when
+ *                       the search ran over a row list (n = its entries)
+ *   "pruned_margin", "pruned_q_sq"   1 float each: what knn_filter_approx adds to T; |q|^2
+ *   "pruned_qinfo"      int8 tier: 2 floats {s_q, |q| rounded up}       "pruned_qplanes"  int8 tier: [2][dim rounded up to 256] int8 (h, then l)
+ *   "pruned_top"        kk floats (the merged list of the pruning scan, ascending; its last entry is T) and 1 uint32, the entries it holds
+ *   "pruned_cand_rows"  [min(candidates, capacity)] uint32 rows the filter nominated, in no particular order */
+int rxgpu_index_inspect(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
 
 /* ---- Pre-filtered brute force: the caller side of `WHERE cond AND KNN(...)` -------------------
  * The reference evaluates such a query by taking the KNN result and filtering it on the host (selectLoop,

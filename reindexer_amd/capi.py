@@ -67,6 +67,7 @@ _SIGNATURES = {
     "rxgpu_scan_tier": (_i, [_u64, _u32, _u32, _i, _i]),
     "rxgpu_scan_tier_subset": (_i, [_u64, _u32, _u32, _u32, _i, _i]),
     "rxgpu_index_last_candidates": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
+    "rxgpu_index_inspect": (_i, [_vp, C.c_char_p, _vp, _u64, C.POINTER(_u64)]),
     "rxgpu_search_knn_subset": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "rxgpu_search_knn_bitmap": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_index_set_lists": (_i, [_vp, _u32, _vp, _vp]),
@@ -528,6 +529,22 @@ class VectorIndex:
         n, cap = _u32(0), _u32(0)
         _check(lib().rxgpu_index_last_candidates(self._h, C.byref(n), C.byref(cap)))
         return int(n.value), int(cap.value)
+
+    _INSPECT_DTYPES = {"stats": np.uint32, "row_sq": np.float32, "codes_i8": np.int8, "side_i8": np.float32, "rows_bf16": np.uint16,
+                       "pruned_values": np.float32, "pruned_margin": np.float32, "pruned_q_sq": np.float32, "pruned_qinfo": np.float32,
+                       "pruned_qplanes": np.int8, "pruned_top": np.uint32, "pruned_cand_rows": np.uint32}
+
+    def inspect(self, name: str) -> np.ndarray:
+        """rxgpu_index_inspect: a named internal buffer as a flat array (test instrumentation; include/rxgpu.h lists the names and shapes).
+        "pruned_top" comes as kk + 1 uint32 words: the bits of the kk list values, then the number of entries."""
+        need = _u64(0)
+        rc = lib().rxgpu_index_inspect(self._h, name.encode(), None, 0, C.byref(need))
+        if rc != RXGPU_ERR_OVERFLOW:
+            _check(rc)
+        out = np.empty(int(need.value), np.uint8)
+        if out.size:
+            _check(lib().rxgpu_index_inspect(self._h, name.encode(), out.ctypes.data, out.size, C.byref(need)))
+        return out.view(self._INSPECT_DTYPES.get(name, np.uint8))
 
 
 class ShardedVectorIndex(VectorIndex):

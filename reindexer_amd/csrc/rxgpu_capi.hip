@@ -278,6 +278,14 @@ int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint3
 	return RXGPU_OK;
 }
 
+int rxgpu_index_inspect(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes) {
+	RX_CHECK(h && what && out_bytes, RXGPU_ERR_PARAMS, "rxgpu_index_inspect: null argument");
+	*out_bytes = 0;
+	RX_CHECK(!h->shard_set, RXGPU_ERR_PARAMS, "rxgpu_index_inspect: single-device indexes only (inspect the rxgpu_index_shard handles)");
+	DeviceGuard dg(h->device);
+	return rxgpu::inspect_index(h, what, out, cap_bytes, out_bytes);
+}
+
 int rxgpu_device_count(void) {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess) {

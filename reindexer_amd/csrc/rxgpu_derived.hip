@@ -4,6 +4,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
+#include <string>
+#include <vector>
 
 #include "../../include/rxgpu.h"
 #include "knn_i8_quant.h"
@@ -169,6 +172,104 @@ int derived_follow_move(rxgpu_index* h, uint64_t from, uint64_t to) {
 		const uint32_t ld8 = i8_ld(h->dim);
 		RX_HIP(hipMemcpy(h->d_codes_i8 + to * ld8, h->d_codes_i8 + from * ld8, ld8, hipMemcpyDeviceToDevice));
 		RX_HIP(hipMemcpy(h->d_side_i8 + to, h->d_side_i8 + from, sizeof(float2), hipMemcpyDeviceToDevice));
+	}
+	return RXGPU_OK;
+}
+
+// rxgpu_index_inspect: a named internal buffer copied to the host, for tests.  Reads only: nothing is built, invalidated or changed, so a
+// buffer that was never built (or is stale) is RXGPU_ERR_LOGIC.  The index-level names cover the `count` rows the index holds; the
+// pruned_* names are the buffers of the context the last recorded pruned call ran in (copy_back_knn), as that chain left them.
+int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes) {
+	const std::string name(what);
+	std::lock_guard<std::mutex> lk(h->mtx);
+	// pieces [device pointer, bytes] of the answer, in order
+	struct Piece {
+		const void* src;
+		uint64_t bytes;
+	};
+	std::vector<Piece> pieces;
+	bool deblock = false;
+	auto missing = [&](const char* why) {
+		set_error(std::string("rxgpu_index_inspect: ") + what + ": " + why);
+		return RXGPU_ERR_LOGIC;
+	};
+	const uint64_t n = h->count;
+	if (name == "stats") {
+		if (!h->stats_valid || !h->d_stats) return missing("the row statistics are not built");
+		pieces.push_back({h->d_stats, kStatsWords * sizeof(unsigned int)});
+	} else if (name == "row_sq") {
+		if (h->metric != RXGPU_METRIC_L2 || !h->stats_valid || !h->d_row_sq) return missing("no |x|^2 per row (L2 with row statistics only)");
+		pieces.push_back({h->d_row_sq, n * sizeof(float)});
+	} else if (name == "codes_i8" || name == "side_i8") {
+		if (!h->i8_valid) return missing("the int8 shadow is not built");
+		if (name == "codes_i8") {
+			pieces.push_back({h->d_codes_i8, n * i8_ld(h->dim)});
+		} else {
+			pieces.push_back({h->d_side_i8, n * sizeof(float2)});
+		}
+	} else if (name == "rows_bf16") {
+		if (!h->bf16_valid) return missing("the bf16 shadow is not built");
+		deblock = h->bf16_blocked;
+		pieces.push_back({h->d_rows_bf16, n * bf16_ld(h) * sizeof(uint16_t)});
+	} else if (name.rfind("pruned_", 0) == 0) {
+		const rxgpu_search_ctx* c = h->last_pruned_ctx;
+		const uint32_t kk = h->last_pruned_kk;
+		const bool i8 = h->last_pruned_i8;
+		const float* qstats = c ? static_cast<const float*>(c->d_qstats.ptr) : nullptr;   // one query: [{s_q, |q|^}] |q|^2, margin
+		const float* q_sq = qstats ? qstats + (i8 ? 2 : 0) : nullptr;
+		const char* known[] = {"pruned_values", "pruned_margin", "pruned_q_sq", "pruned_qinfo", "pruned_qplanes", "pruned_top", "pruned_cand_rows"};
+		if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return name == k; }) == std::end(known)) {
+			set_error(std::string("rxgpu_index_inspect: unknown buffer ") + what);
+			return RXGPU_ERR_PARAMS;
+		}
+		if (!c) return missing("no pruned single-query call is recorded (profiling on, one query, a pruned chain)");
+		if (name == "pruned_values") {
+			pieces.push_back({c->d_dense.ptr, h->last_pruned_n * sizeof(float)});
+		} else if (name == "pruned_margin") {
+			pieces.push_back({q_sq + 1, sizeof(float)});
+		} else if (name == "pruned_q_sq") {
+			pieces.push_back({q_sq, sizeof(float)});
+		} else if (name == "pruned_qinfo") {
+			if (!i8) return missing("the bf16 tier keeps no {s_q, |q|^} pair");
+			pieces.push_back({qstats, 2 * sizeof(float)});
+		} else if (name == "pruned_qplanes") {
+			if (!i8) return missing("the bf16 tier keeps no query planes");
+			pieces.push_back({c->d_qplanes.ptr, 2ull * h->last_pruned_ld});
+		} else if (name == "pruned_top") {   // d_top of one query: [kk] values, [kk] rows, the count
+			const float* top = static_cast<const float*>(c->d_top.ptr);
+			pieces.push_back({top, kk * sizeof(float)});
+			pieces.push_back({top + 2 * size_t(kk), sizeof(uint32_t)});
+		} else {
+			pieces.push_back({c->d_cand_row.ptr, uint64_t(std::min(h->last_cand_count.load(), h->last_cand_cap.load())) * sizeof(uint32_t)});
+		}
+	} else {
+		set_error(std::string("rxgpu_index_inspect: unknown buffer ") + what);
+		return RXGPU_ERR_PARAMS;
+	}
+	uint64_t need = 0;
+	for (const Piece& p : pieces) need += p.bytes;
+	*out_bytes = need;
+	if (cap_bytes < need || (need && !out)) {
+		set_error(std::string("rxgpu_index_inspect: ") + what + " needs " + std::to_string(need) + " bytes");
+		return RXGPU_ERR_OVERFLOW;
+	}
+	if (!need) return RXGPU_OK;
+	if (deblock) {   // the tile-blocked shadow ([tile of 256 rows][32-element k-block][row][32]) back to [count][ld]: whole tiles to the host, then a loop
+		const uint32_t ld = bf16_ld(h);
+		const uint64_t tiles = (n + kShadowTileRows - 1) / kShadowTileRows;
+		std::vector<uint16_t> raw(tiles * kShadowTileRows * ld);
+		RX_HIP(hipMemcpy(raw.data(), h->d_rows_bf16, raw.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+		uint16_t* dst = static_cast<uint16_t*>(out);
+		for (uint64_t r = 0; r < n; ++r) {
+			const uint64_t base = shadow_elem_base(r, ld, true);
+			for (uint32_t k = 0; k < ld; ++k) dst[r * ld + k] = raw[base + uint64_t(k / 32) * shadow_stage_step(true) + k % 32];
+		}
+		return RXGPU_OK;
+	}
+	char* dst = static_cast<char*>(out);
+	for (const Piece& p : pieces) {
+		RX_HIP(hipMemcpy(dst, p.src, p.bytes, hipMemcpyDeviceToHost));
+		dst += p.bytes;
 	}
 	return RXGPU_OK;
 }

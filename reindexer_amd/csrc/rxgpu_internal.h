@@ -432,6 +432,11 @@ struct rxgpu_search_ctx {
 	rxgpu_devbuf d_ivf;                                                            // IVF: the coarse search's lists, distances, count
 	rxgpu_devbuf d_subset, d_bitmap, d_tiles;                                      // pre-filtered search: row list, allowed-rows bitmap, tile sums
 	uint32_t pruned_cap = 0;   // candidate capacity of the pruned chain the current call enqueued (0: none) — rxgpu_index_last_candidates
+	// ... and what else rxgpu_index_inspect needs to find that chain's buffers again (set with pruned_cap): rows or list entries scanned, kk,
+	// the padded query stride, and the tier (int8: d_qplanes and the {s_q, |q|^} pair in front of d_qstats exist)
+	uint64_t pruned_n = 0;
+	uint32_t pruned_kk = 0, pruned_ld = 0;
+	bool pruned_i8 = false;
 	void* h_pinned = nullptr;
 	size_t h_pinned_bytes = 0;
 	// second stream + events (created on first use): work that does not depend on the query upload — zeroing the visited bitsets of an
@@ -548,6 +553,12 @@ struct rxgpu_index {
 	bool i8_valid = false;
 	bool i8_unavailable = false;       // it did not fit in HBM: the call takes the bf16 tier
 	std::atomic<uint32_t> last_cand_count{0}, last_cand_cap{0};   // rxgpu_index_last_candidates
+	// rxgpu_index_inspect: the context the last profiled single-query pruned call ran in (idle in the pool since, so its buffers hold what the
+	// chain left until the next call on the index takes it), with that call's sizes.  Guarded by mtx; null: none recorded.
+	rxgpu_search_ctx* last_pruned_ctx = nullptr;
+	uint64_t last_pruned_n = 0;
+	uint32_t last_pruned_kk = 0, last_pruned_ld = 0;
+	bool last_pruned_i8 = false;
 
 	// HNSW graph mirror (rxgpu_hnsw_attach_graph)
 	uint32_t* d_links0 = nullptr;
@@ -623,6 +634,8 @@ void derived_invalidate(rxgpu_index* h);                                        
 int derived_follow_upload(rxgpu_index* h, uint64_t first_row, uint64_t n);      // rows [first_row, first_row + n) were written
 int derived_follow_move(rxgpu_index* h, uint64_t from, uint64_t to);            // row `from` was copied over row `to`
 void derived_free(rxgpu_index* h);                                              // the index is being destroyed
+// a named internal buffer copied to the host (rxgpu_index_inspect; test instrumentation, reads only)
+int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
 
 // The chains of brute-force KNN (rxgpu_knn_chains.hip), as far as the entry points call them.  nq device-resident queries, results in d_out_* (device).
 int enqueue_knn(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist, uint32_t* d_out_row,

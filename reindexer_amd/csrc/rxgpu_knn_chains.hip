@@ -399,6 +399,10 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	uint32_t* cand_row = static_cast<uint32_t*>(c->d_cand_row.ptr);
 	float* cand_dist = static_cast<float*>(c->d_cand_dist.ptr);
 	c->pruned_cap = cap;
+	c->pruned_n = f.n;
+	c->pruned_kk = kk;
+	c->pruned_ld = f.ld;
+	c->pruned_i8 = f.planes;
 	f.prep(h, c, d_queries, nq, f, b);
 	const ScanParams e = scan_params(h, c, d_queries, f.n, kk, b.cand_cnt, cap);   // the exact scan behind the gate
 	{
@@ -568,6 +572,17 @@ int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk,
 		RX_HIP(hipMemcpy(&cnt, c->d_cand_cnt.ptr, sizeof(cnt), hipMemcpyDeviceToHost));
 		h->last_cand_count = cnt;
 		h->last_cand_cap = c->pruned_cap;
+		// rxgpu_index_inspect reads the chain's buffers out of this context later.  The exact scan behind the gate writes the part buffers
+		// and the result only (launch_scan / launch_scan_subset, launch_merge_lists), never d_dense, d_top, d_qstats, d_qplanes or d_cand_row.
+		std::lock_guard<std::mutex> lk(h->mtx);
+		h->last_pruned_ctx = c;
+		h->last_pruned_n = c->pruned_n;
+		h->last_pruned_kk = c->pruned_kk;
+		h->last_pruned_ld = c->pruned_ld;
+		h->last_pruned_i8 = c->pruned_i8;
+	} else if (h->profiling) {   // another chain answered: whatever context it ran in may be the recorded one
+		std::lock_guard<std::mutex> lk(h->mtx);
+		h->last_pruned_ctx = nullptr;
 	}
 	return RXGPU_OK;
 }

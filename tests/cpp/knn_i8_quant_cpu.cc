@@ -27,6 +27,12 @@ void i8_cpu_quantize_row(const float* x, uint32_t dim, int8_t* codes, float* sca
 	*resid = rxgpu::i8_norm_up(r64);
 }
 
+// the same for n rows: x[n][dim], codes[n][ld8], scale[n], resid[n]
+void i8_cpu_quantize_rows(const float* x, uint64_t n, uint32_t dim, int8_t* codes, float* scale, float* resid) {
+	const uint32_t ld8 = rxgpu::i8_ld(dim);
+	for (uint64_t r = 0; r < n; ++r) i8_cpu_quantize_row(x + r * dim, dim, codes + r * ld8, scale + r, resid + r);
+}
+
 // one query as knn_query_prep_i8 leaves it: planes h[ld8], l[ld8], t[ld8]; info = {s_q, |q| rounded up, r_q, |q|^2 (f32 fmaf chain)}
 void i8_cpu_quantize_query(const float* q, uint32_t dim, int8_t* h, int8_t* l, int32_t* t, float* info) {
 	float mx = 0.f, s = 0.f;
@@ -91,6 +97,19 @@ void i8_cpu_margin(int metric, float s, uint32_t dim, float qn_up, float rq_up, 
 	out[1] = metric == rxgpu::kI8L2   ? rxgpu::i8_margin<rxgpu::kI8L2>(s, dim, qn_up, rq_up, xmax2, xcmax2, emax2, ecmax2)
 			 : metric == rxgpu::kI8IP ? rxgpu::i8_margin<rxgpu::kI8IP>(s, dim, qn_up, rq_up, xmax2, xcmax2, emax2, ecmax2)
 									  : rxgpu::i8_margin<rxgpu::kI8Cos>(s, dim, qn_up, rq_up, xmax2, xcmax2, emax2, ecmax2);
+}
+
+// the per-query margin of an f32 (bf16 = 0) or bf16 nomination, as knn_query_stats / knn_query_prep form it
+float i8_cpu_f32_margin(int metric, int bf16, float s, uint32_t dim, float xmax2, float xcmax2) {
+	using namespace rxgpu;
+	if (bf16) {
+		return metric == kI8L2 ? f32_query_margin<kI8L2, true>(s, dim, xmax2, xcmax2)
+			   : metric == kI8IP ? f32_query_margin<kI8IP, true>(s, dim, xmax2, xcmax2)
+								 : f32_query_margin<kI8Cos, true>(s, dim, xmax2, xcmax2);
+	}
+	return metric == kI8L2 ? f32_query_margin<kI8L2, false>(s, dim, xmax2, xcmax2)
+		   : metric == kI8IP ? f32_query_margin<kI8IP, false>(s, dim, xmax2, xcmax2)
+							 : f32_query_margin<kI8Cos, false>(s, dim, xmax2, xcmax2);
 }
 
 int i8_cpu_dim_supported(uint32_t dim) { return rxgpu::i8_dim_supported(dim) ? 1 : 0; }

@@ -3,57 +3,17 @@ on the CPU against float64: the stored residual bounds the real one, the approxi
 add up to, [lo, up] (+ the per-query part) brackets the float64 distance, the query planes reconstruct, the integer sum cannot overflow; and
 rxgpu_scan_tier decides as include/rxgpu.h documents (no device is touched)."""
 import ctypes as C
-from pathlib import Path
 
 import numpy as np
 import pytest
 
-LIB = Path(__file__).resolve().parent / "cpp" / "libknn_i8_quant_cpu.so"
-F, I8, I32, U32, U64 = C.c_float, C.c_int8, C.c_int32, C.c_uint32, C.c_uint64
-PF, PI8, PI32 = C.POINTER(F), C.POINTER(I8), C.POINTER(I32)
-L2, IP, COS = 0, 1, 2
+from . import i8_model
+from .i8_model import COS, IP, L2, PF, PI8, PI32, _p, quantize_queries, quantize_rows
 
 
 @pytest.fixture(scope="module")
 def lib():
-    assert LIB.exists(), f"{LIB} is missing: run `python -m reindexer_amd.build`"
-    so = C.CDLL(str(LIB))
-    so.i8_cpu_quantize_row.argtypes = [PF, U32, PI8, PF, PF]
-    so.i8_cpu_quantize_query.argtypes = [PF, U32, PI8, PI8, PI32, PF]
-    so.i8_cpu_dot.argtypes = [PI8, PI8, PI8, U32, C.POINTER(C.c_int)]
-    so.i8_cpu_dot.restype = I32
-    so.i8_cpu_bounds_many.argtypes = [C.c_int, U64, PF, PF, PI32, PF, PF, PF, PF, PF]
-    so.i8_cpu_margin.argtypes = [C.c_int, F, U32, F, F, F, F, F, F, PF]
-    so.i8_cpu_ld.argtypes = [U32]
-    so.i8_cpu_ld.restype = U32
-    so.i8_cpu_dim_supported.argtypes = [U32]
-    return so
-
-
-def _p(a, t):
-    return a.ctypes.data_as(t)
-
-
-def quantize_rows(lib, rows):
-    n, d = rows.shape
-    ld8 = lib.i8_cpu_ld(d)
-    codes = np.zeros((n, ld8), np.int8)
-    scale, resid = np.zeros(n, np.float32), np.zeros(n, np.float32)
-    for r in range(n):
-        row = np.ascontiguousarray(rows[r])
-        lib.i8_cpu_quantize_row(_p(row, PF), d, _p(codes[r], PI8), _p(scale[r:], PF), _p(resid[r:], PF))
-    return codes, scale, resid
-
-
-def quantize_queries(lib, queries):
-    n, d = queries.shape
-    ld8 = lib.i8_cpu_ld(d)
-    h, l, t = np.zeros((n, ld8), np.int8), np.zeros((n, ld8), np.int8), np.zeros((n, ld8), np.int32)
-    info = np.zeros((n, 4), np.float32)
-    for q in range(n):
-        row = np.ascontiguousarray(queries[q])
-        lib.i8_cpu_quantize_query(_p(row, PF), d, _p(h[q], PI8), _p(l[q], PI8), _p(t[q], PI32), _p(info[q], PF))
-    return h, l, t, info
+    return i8_model.load()
 
 
 def corpus(d, seed):
