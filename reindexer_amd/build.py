@@ -115,6 +115,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "ft_merge_plan.h", INCLUDE / "rxgpu.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{INCLUDE}", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # the decisions of one packed upload compiled for the host (CPU check of the plan rxgpu_ft_set_words_packed_ptrs executes)
+    src = tdir / "ft_packed_plan_cpu.cc"
+    if src.exists():
+        out = tdir / "libft_packed_plan_cpu.so"
+        if force or _stale(out, [src, CSRC / "ft_packed_plan.h", CSRC / "ft_merge_plan.h", CSRC / "ft_packed_decode.h", INCLUDE / "rxgpu.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{INCLUDE}", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     # the arithmetic of the int8 shadow tier compiled for the host (CPU check of the quantisation and the bound the kernels use)
     src = tdir / "knn_i8_quant_cpu.cc"
     if src.exists():

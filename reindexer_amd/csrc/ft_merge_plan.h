@@ -1,4 +1,4 @@
-// The decisions of ONE BM25 merge, without HIP: what prepare_merge (rxgpu_ft_capi.hip) decides before it touches the device — the query
+// The decisions of ONE BM25 merge, without HIP: what prepare_merge (rxgpu_ft_merge.hip) decides before it touches the device — the query
 // parts, the volume and the 2-phase gate's host half, the launch train, the table of merged sub-term rows with its grid, the synonym mask
 // jobs, the layouts of the three device buffers and every engine limit that is a fact of the query alone.  Inputs are plain facts (the
 // caller looks the words up in the dictionary and says what it found), so the rules compile with a host compiler and are pinned on the CPU

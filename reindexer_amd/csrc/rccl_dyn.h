@@ -1,4 +1,4 @@
-// RCCL through dlopen: the entry points the sharded indexes use (rxgpu_sharded.hip: float_vector shards; rxgpu_ft_capi.hip: ft_fast
+// RCCL through dlopen: the entry points the sharded indexes use (rxgpu_sharded.hip: float_vector shards; rxgpu_ft_sharded.hip: ft_fast
 // document-range shards), resolved once by the first index that asks.
 #pragma once
 

@@ -220,7 +220,7 @@ long rxhost_bf_select(void* h, const float* key, size_t dim, long k, int has_rad
 // ---------------------------------------------------------------------------------------------- HNSW graph builder
 #include "hnsw_graph.h"
 
-// ---- the admission cut of a phrase over document-range shards (csrc/ft_phrase_cut.h: what rxgpu_ft_capi.hip runs between the shards' admission
+// ---- the admission cut of a phrase over document-range shards (csrc/ft_phrase_cut.h: what rxgpu_ft_sharded.hip runs between the shards' admission
 // passes), for the CPU suite: counts [shards][rows] (a shard whose first entry is 0xFFFFFFFF admitted nothing), keep [shards] out.
 #include "../csrc/ft_phrase_cut.h"
 extern "C" void rxhost_ft_shard_phrase_cut(const uint32_t* counts, size_t shards, size_t rows, uint64_t mergeLimit, uint64_t* keep) {

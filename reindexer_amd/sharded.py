@@ -277,7 +277,7 @@ class ShardedBruteforceGpu:
 class ShardedFtExchange:
     """ft_fast merge over DOCUMENT-RANGE shards, one rank per shard (SURVEY 8e "BM25"): what crosses the ranks, and what every rank derives
     from it.  The same two exchanges rxgpu_ft_create_sharded runs between the kernels of its launch train inside one process
-    (rxgpu_ft_capi.hip, run_merge_sharded), here over torch.distributed — the one-process-per-GPU deployment; the local merger is injected
+    (rxgpu_ft_sharded.hip, run_merge_sharded), here over torch.distributed — the one-process-per-GPU deployment; the local merger is injected
     (on a GPU box the rank's rxgpu shard, in tests/test_sharded_gloo.py the CPU oracle), so the exchange logic runs unchanged under gloo.
 
       1. every rank's pre-score histogram (65536 counters: documents of its range inside the restricting mask, not removed, by uint16
