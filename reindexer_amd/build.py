@@ -64,11 +64,11 @@ def build_device(force: bool = False) -> Path:
         if force or _stale(obj, [src] + headers):
             todo.append((src, obj))
     if todo:
-        with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4, int(os.environ.get("MAX_JOBS", 16)))) as ex:
             list(ex.map(lambda so: _run([HIPCC, *flags, "-c", so[0], "-o", so[1]]), todo))
     objs = [objdir / (src.stem + ".o") for src in srcs]
     if force or todo or _stale(out, objs):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", out, "-ldl", "-Wl,-rpath,/opt/rocm/lib"])   # RCCL is dlopen'ed by the first sharded index (rxgpu_sharded.hip)
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", out, "-ldl", "-Wl,-rpath,/opt/rocm/lib"])   # RCCL is dlopen'ed by the first sharded index (rxgpu_rccl.hip)
     return out
 
 
@@ -121,6 +121,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         out = tdir / "libft_packed_plan_cpu.so"
         if force or _stale(out, [src, CSRC / "ft_packed_plan.h", CSRC / "ft_merge_plan.h", CSRC / "ft_packed_decode.h", INCLUDE / "rxgpu.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{INCLUDE}", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
+    # the decisions of a row-range sharded index compiled for the host (CPU check of the plan rxgpu_sharded.hip executes)
+    src = tdir / "shard_plan_cpu.cc"
+    if src.exists():
+        out = tdir / "libshard_plan_cpu.so"
+        if force or _stale(out, [src, CSRC / "shard_plan.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
     # the arithmetic of the int8 shadow tier compiled for the host (CPU check of the quantisation and the bound the kernels use)
     src = tdir / "knn_i8_quant_cpu.cc"

@@ -1,4 +1,4 @@
-// RCCL through dlopen: the entry points the sharded indexes use (rxgpu_sharded.hip: float_vector shards; rxgpu_ft_sharded.hip: ft_fast
+// RCCL through dlopen (rxgpu_rccl.hip): the entry points the sharded indexes use (rxgpu_sharded.hip: float_vector shards; rxgpu_ft_sharded.hip: ft_fast
 // document-range shards), resolved once by the first index that asks.
 #pragma once
 
@@ -23,7 +23,7 @@ struct RcclApi {
 	std::string why;   // non-empty: not available, and why
 };
 
-const RcclApi& rccl_api();   // rxgpu_sharded.hip
+const RcclApi& rccl_api();   // rxgpu_rccl.hip
 
 // The communicators over one list of distinct devices, shared by every sharded index of the process over that list and kept until the
 // process ends: ncclCommInitAll costs hundreds of milliseconds, proxy threads and device buffers per communicator, and namespaces (and
@@ -35,6 +35,6 @@ struct RcclCommSet {
 	std::mutex mtx;
 };
 // nullptr + *why when RCCL is not there or ncclCommInitAll fails (the caller falls back to the host path)
-std::shared_ptr<RcclCommSet> rccl_comm_set(const std::vector<int>& devices, std::string* why);   // rxgpu_sharded.hip
+std::shared_ptr<RcclCommSet> rccl_comm_set(const std::vector<int>& devices, std::string* why);   // rxgpu_rccl.hip
 
 }  // namespace rxgpu

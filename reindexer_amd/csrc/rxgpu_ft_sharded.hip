@@ -7,6 +7,7 @@
 
 #include "rxgpu_ft_internal.h"
 #include "ft_phrase_cut.h"
+#include "shard_plan.h"
 
 using namespace rxgpu;   // the cross-unit types and functions: rxgpu_ft_internal.h
 
@@ -420,24 +421,19 @@ int rxgpu_ft_create_sharded(uint32_t num_fields, uint32_t n_devices, const int* 
 		set_error(msg);
 		return rc;
 	};
-	std::vector<uint32_t> per_rank;
 	for (uint32_t s = 0; s < n_devices; ++s) {
 		rxgpu_ft_index* sh = nullptr;
 		if (int rc = rxgpu_ft_create(num_fields, devices[s], &sh); rc) return fail(rc);
 		ss->shards.push_back(sh);
 		ss->devices.push_back(devices[s]);
-		uint32_t r = 0;
-		while (r < ss->rank_dev.size() && ss->rank_dev[r] != devices[s]) ++r;
-		if (r == ss->rank_dev.size()) {
-			ss->rank_dev.push_back(devices[s]);
-			per_rank.push_back(0);
-		}
-		ss->shard_rank.push_back(r);
-		ss->shard_slot.push_back(per_rank[r]++);
 	}
-	ss->nranks = uint32_t(ss->rank_dev.size());
-	ss->slots = *std::max_element(per_rank.begin(), per_rank.end());
-	for (uint32_t s = 0; s < n_devices; ++s) ss->pos.push_back(ss->shard_rank[s] * ss->slots + ss->shard_slot[s]);
+	const rxgpu::RankLayout lay = rxgpu::rank_layout(devices, n_devices);   // shard_plan.h: the layout of the float_vector shards' exchange
+	ss->nranks = lay.nranks;
+	ss->slots = lay.slots;
+	ss->rank_dev = lay.rank_dev;
+	ss->shard_rank = lay.shard_rank;
+	ss->shard_slot = lay.shard_slot;
+	ss->pos = lay.pos;
 	ss->rstream.assign(ss->nranks, nullptr);
 	ss->ev_rank.assign(ss->nranks, nullptr);
 	ss->d_pos.assign(ss->nranks, nullptr);

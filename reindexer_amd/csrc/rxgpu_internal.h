@@ -609,6 +609,8 @@ namespace rxgpu {
 // Check out a scratch context with its own stream (host-synchronous searches), and hand it back (rxgpu_capi.hip).
 rxgpu_search_ctx* acquire_ctx(rxgpu_index* h);
 void release_ctx(rxgpu_index* h, rxgpu_search_ctx* c);
+// the calling thread took a resident context of h (rxgpu_search_knn_resident): when the thread ends, the context goes back to h's pool
+void resident_thread_uses(rxgpu_index* h);
 // ... handed back when the scope ends
 struct CtxLease {
 	rxgpu_index* h;
@@ -647,7 +649,7 @@ int enqueue_knn_subset(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* d_ids, uint64_t n_ids,
 					   float* out_dist, uint32_t* out_row, uint32_t* out_count);   // ... queries and results on the host, any kk
 int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk, uint32_t eff, float* out_dist, uint32_t* out_row, uint32_t* out_count);
-void sort_dist_row(const std::vector<float>& hd, const std::vector<uint32_t>& hr, float* out_dist, uint32_t* out_row);
+void sort_dist_row(const std::vector<float>& hd, const std::vector<uint32_t>& hr, float* out_dist, uint32_t* out_row);   // by dist_row_less (shard_plan.h)
 // the scan policy, without a device (rxgpu_scan_policy, rxgpu_scan_tier, rxgpu_scan_tier_subset)
 enum ScanTier { kTierF32 = 0, kTierBf16 = 1, kTierI8 = 2 };
 bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite);

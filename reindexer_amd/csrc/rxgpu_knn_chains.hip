@@ -1,14 +1,14 @@
 // The host-side chains of brute-force KNN: which scan a call takes (the policy), and the launches of each chain — fused f32 scan, batched
 // nomination (f32 / bf16 GEMM) with its exact tail, the pruned chains (bf16 / int8 / int8 over a row list) with theirs, the pre-filtered
-// scan.  Called by the entry points of rxgpu_capi.hip through rxgpu_internal.h.  Host-side plumbing only — all arithmetic is in the kernels.
+// scan.  Called by the entry points of rxgpu_knn_search.hip through rxgpu_internal.h.  Host-side plumbing only — all arithmetic is in the kernels.
 #include <algorithm>
 #include <cstdlib>
-#include <numeric>
 
 #include "../../include/rxgpu.h"
 #include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
+#include "shard_plan.h"   // dist_row_less
 
 namespace rxgpu {
 namespace {
@@ -587,14 +587,15 @@ int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk,
 	return RXGPU_OK;
 }
 
-// Large k: the selected entries (any order) sorted by (dist, row) into the caller's arrays.
+// The selected entries of a large k, or the hits of a range call (any order), sorted by (dist, row) into the caller's arrays: the one
+// comparator of every host-side sort, dist_row_less — a strict weak order with NaN distances too (they sort last).
 void sort_dist_row(const std::vector<float>& hd, const std::vector<uint32_t>& hr, float* out_dist, uint32_t* out_row) {
-	std::vector<uint32_t> order(hd.size());
-	std::iota(order.begin(), order.end(), 0u);
-	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return hd[a] < hd[b] || (!(hd[b] < hd[a]) && hr[a] < hr[b]); });
-	for (size_t i = 0; i < order.size(); ++i) {
-		out_dist[i] = hd[order[i]];
-		out_row[i] = hr[order[i]];
+	std::vector<std::pair<float, uint32_t>> all(hd.size());
+	for (size_t i = 0; i < all.size(); ++i) all[i] = {hd[i], hr[i]};
+	std::sort(all.begin(), all.end(), dist_row_less);
+	for (size_t i = 0; i < all.size(); ++i) {
+		out_dist[i] = all[i].first;
+		out_row[i] = all[i].second;
 	}
 }
 

@@ -1,0 +1,531 @@
+// The search entry points of the C-ABI (include/rxgpu.h) over float_vector rows: brute force on the host, the device and resident, pre-filtered
+// by row list or bitmap, IVF, range, single distances, and the device-side helpers of the one-process-per-GPU deployment.  Contexts, index
+// lifetime and the mutations are rxgpu_capi.hip; the chains these calls enqueue are rxgpu_knn_chains.hip.  Host-side plumbing only — all
+// arithmetic is in the kernels.
+#include <algorithm>
+#include <cstring>
+
+#include "../../include/rxgpu.h"
+#include "knn_kernels.hip.h"
+#include "rxgpu_internal.h"
+#include "shard_plan.h"   // check_row_list
+
+using rxgpu::acquire_ctx;
+using rxgpu::CtxLease;
+using rxgpu::DeviceGuard;
+using rxgpu::enqueue_knn;
+using rxgpu::enqueue_knn_fused;
+using rxgpu::enqueue_knn_subset;
+using rxgpu::ProfileScope;
+using rxgpu::search_subset_host;
+using rxgpu::set_error;
+
+namespace {
+
+// Scratch bound to a caller-owned stream: stream order makes reuse safe without synchronising.
+rxgpu_search_ctx* stream_ctx(rxgpu_index* h, void* stream) {
+	std::lock_guard<std::mutex> lk(h->mtx);
+	auto it = h->stream_ctx.find(stream);
+	if (it != h->stream_ctx.end()) return it->second;
+	auto* c = new rxgpu_search_ctx();
+	c->stream = static_cast<hipStream_t>(stream);
+	c->own_stream = false;
+	h->stream_ctx[stream] = c;
+	return c;
+}
+
+// the row list of a pre-filtered call on the host (the plan's ordered rule over one shard)
+int check_rows_host(const rxgpu_index* h, const uint32_t* row_ids, uint64_t n_ids, const char* who) {
+	RX_CHECK(rxgpu::check_row_list(row_ids, n_ids, h->count, true) == rxgpu::kRowListOk, RXGPU_ERR_PARAMS,
+			 std::string(who) + ": row_ids must be strictly increasing and below the row count");
+	return RXGPU_OK;
+}
+
+// The allowed-rows bitmap in c->d_bitmap (one bit per row, enqueued on c->stream) -> the ascending row list in c->d_subset: tile counts, their
+// total read back (*total; the stream is idle behind it), then — expand, and any row allowed — the expansion.  head() enqueues what still
+// writes the bitmap; it runs inside the first of the two profile scopes filed under `slot`.
+template <class Head>
+int bitmap_to_row_list(rxgpu_index* h, rxgpu_search_ctx* c, const char* slot, bool expand, unsigned long long* total, Head&& head) {
+	const uint32_t tiles = rxgpu::bitmap_tiles(h->count);
+	if (int rc = c->d_tiles.ensure(size_t(2) * tiles * sizeof(uint32_t) + sizeof(unsigned long long)); rc) return rc;
+	uint32_t* tile_scratch = static_cast<uint32_t*>(c->d_tiles.ptr);
+	unsigned long long* d_total = reinterpret_cast<unsigned long long*>(tile_scratch + size_t(2) * tiles);   // 8-byte aligned: 2 * tiles words
+	{
+		ProfileScope ps(h, slot, c->stream);
+		head();
+		rxgpu::launch_bitmap_count(static_cast<const uint32_t*>(c->d_bitmap.ptr), h->count, tile_scratch, d_total, c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	*total = 0;
+	RX_HIP(hipMemcpyAsync(total, d_total, sizeof(*total), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	if (*total == 0 || !expand) return RXGPU_OK;
+	if (int rc = c->d_subset.ensure(*total * sizeof(uint32_t)); rc) return rc;
+	{
+		ProfileScope ps(h, slot, c->stream);
+		rxgpu::launch_bitmap_expand(static_cast<const uint32_t*>(c->d_bitmap.ptr), h->count, tile_scratch, static_cast<uint32_t*>(c->d_subset.ptr), *total,
+									c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	return RXGPU_OK;
+}
+
+// The tail of every range call, behind its launch: the hits were counted in c->d_out_count and the first min(hits, cap) written to
+// c->d_out_dist / d_out_row in any order.  More hits than cap: *out_total says how many, nothing is written.  Else sorted by (dist, row).
+int range_tail(rxgpu_search_ctx* c, float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total, const char* who) {
+	RX_HIP(hipGetLastError());
+	unsigned long long total = 0;
+	RX_HIP(hipMemcpyAsync(&total, c->d_out_count.ptr, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	*out_total = total;
+	if (total > cap) {
+		set_error(std::string(who) + ": output buffer too small");
+		return RXGPU_ERR_OVERFLOW;
+	}
+	if (total == 0) return RXGPU_OK;
+	std::vector<float> hd(total);
+	std::vector<uint32_t> hr(total);
+	RX_HIP(hipMemcpy(hd.data(), c->d_out_dist.ptr, total * sizeof(float), hipMemcpyDeviceToHost));
+	RX_HIP(hipMemcpy(hr.data(), c->d_out_row.ptr, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	rxgpu::sort_dist_row(hd, hr, out_dist, out_row);
+	return RXGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rxgpu_search_knn_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, void* d_out_dist, void* d_out_row,
+							void* d_out_count, void* stream) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_device: not available on a sharded index");
+	RX_CHECK(nq > 0 && d_queries && d_out_dist && d_out_row, RXGPU_ERR_PARAMS, "rxgpu_search_knn_device: null argument");
+	RX_CHECK(kk > 0 && kk <= uint32_t(rxgpu::kMaxFusedK), RXGPU_ERR_PARAMS, "rxgpu_search_knn_device: kk must be in [1, 64]");
+	RX_CHECK(h->count > 0, RXGPU_ERR_PARAMS, "rxgpu_search_knn_device: index is empty");
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = stream_ctx(h, stream);
+	return enqueue_knn(h, c, static_cast<const float*>(d_queries), nq, kk, static_cast<float*>(d_out_dist),
+					   static_cast<uint32_t*>(d_out_row), static_cast<uint32_t*>(d_out_count));
+}
+
+// One query, the result LEFT IN HBM: enqueued on the calling thread's resident stream, nothing waited for.  The buffers belong to the index
+// and hold this result until the SAME THREAD's next resident search on it (other threads have buffers of their own); a consumer on another
+// stream orders itself behind *stream.
+int rxgpu_search_knn_resident(rxgpu_index* h, const float* query, uint32_t kk, void** d_dist, void** d_row, void** d_count, void** stream,
+							  uint32_t* entries) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(query && d_dist && d_row && d_count && stream && entries, RXGPU_ERR_PARAMS, "rxgpu_search_knn_resident: null argument");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_resident: not available on a sharded index");
+	RX_CHECK(kk >= 1 && kk <= uint32_t(rxgpu::kMaxFusedK2), RXGPU_ERR_PARAMS, "rxgpu_search_knn_resident: kk must be in [1, 128]");
+	RX_CHECK(h->count > 0, RXGPU_ERR_PARAMS, "rxgpu_search_knn_resident: index is empty");
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = nullptr;
+	{   // this thread's resident context (created on its first resident search; searches of one thread are sequential)
+		std::lock_guard<std::mutex> lk(h->resident_mtx);
+		rxgpu_search_ctx*& slot = h->resident_ctx[std::this_thread::get_id()];
+		if (!slot) {
+			slot = acquire_ctx(h);
+			if (slot) rxgpu::resident_thread_uses(h);
+		}
+		c = slot;
+	}
+	if (!c) return RXGPU_ERR_DEVICE;
+	const uint32_t eff = uint32_t(std::min<uint64_t>(kk, h->count));
+	const size_t qbytes = size_t(h->dim) * sizeof(float);
+	if (int rc = c->d_queries.ensure(qbytes); rc) return rc;
+	if (int rc = c->ensure_pinned(qbytes); rc) return rc;
+	RX_HIP(hipStreamSynchronize(c->stream));   // the staging copy of the query before this one has been read (normally long ago)
+	std::memcpy(c->h_pinned, query, qbytes);
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, c->h_pinned, qbytes, hipMemcpyHostToDevice, c->stream));
+	if (int rc = c->d_out_dist.ensure(size_t(eff) * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(size_t(eff) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_count.ensure(sizeof(uint32_t)); rc) return rc;
+	auto* run = eff <= uint32_t(rxgpu::kMaxFusedK) ? enqueue_knn : enqueue_knn_fused;
+	if (int rc = run(h, c, static_cast<const float*>(c->d_queries.ptr), 1, eff, static_cast<float*>(c->d_out_dist.ptr),
+					 static_cast<uint32_t*>(c->d_out_row.ptr), static_cast<uint32_t*>(c->d_out_count.ptr));
+		rc)
+		return rc;
+	*d_dist = c->d_out_dist.ptr;
+	*d_row = c->d_out_row.ptr;
+	*d_count = c->d_out_count.ptr;
+	*stream = c->stream;
+	*entries = eff;
+	return RXGPU_OK;
+}
+
+uint32_t rxgpu_index_resident_contexts(rxgpu_index* h) {
+	if (!h || h->shard_set) return 0;
+	std::lock_guard<std::mutex> lk(h->resident_mtx);
+	return uint32_t(h->resident_ctx.size());
+}
+
+int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t kk, float* out_dist, uint32_t* out_row,
+					 uint32_t* out_count) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(queries && out_dist && out_row && out_count, RXGPU_ERR_PARAMS, "rxgpu_search_knn: null argument");
+	if (nq == 0) return RXGPU_OK;
+	if (h->count == 0 || kk == 0) {   // bruteforce.cc:106-108
+		std::fill(out_count, out_count + nq, 0u);
+		return RXGPU_OK;
+	}
+	if (h->shard_set) return rxgpu::sharded_search_knn_impl(h, queries, nq, kk, nullptr, 0, out_dist, out_row, out_count);
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	const uint32_t eff = uint32_t(std::min<uint64_t>(kk, h->count));
+	const size_t qbytes = size_t(nq) * h->dim * sizeof(float);
+	if (int rc = c->d_queries.ensure(qbytes); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, queries, qbytes, hipMemcpyHostToDevice, c->stream));
+
+	if (eff <= uint32_t(rxgpu::kMaxFusedK2)) {
+		if (int rc = c->d_out_dist.ensure(size_t(nq) * eff * sizeof(float)); rc) return rc;
+		if (int rc = c->d_out_row.ensure(size_t(nq) * eff * sizeof(uint32_t)); rc) return rc;
+		if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
+		// kk <= 64: fused / batched / pruned dispatch; 64 < kk <= 128 (e.g. hybrid k = 100): the fused scan with two list entries per lane
+		auto* run = eff <= uint32_t(rxgpu::kMaxFusedK) ? enqueue_knn : enqueue_knn_fused;
+		c->pruned_cap = 0;   // set by a pruned chain
+		if (int rc = run(h, c, static_cast<const float*>(c->d_queries.ptr), nq, eff, static_cast<float*>(c->d_out_dist.ptr),
+						 static_cast<uint32_t*>(c->d_out_row.ptr), static_cast<uint32_t*>(c->d_out_count.ptr));
+			rc)
+			return rc;
+		return rxgpu::copy_back_knn(h, c, nq, kk, eff, out_dist, out_row, out_count);
+	}
+
+	// large-k path: distance pass + radix select per query, final (dist,row) sort of kk entries on the host
+	if (int rc = c->d_misc.ensure(h->count * sizeof(float)); rc) return rc;
+	if (int rc = c->d_select.ensure(rxgpu::select_scratch_bytes(h->count)); rc) return rc;
+	if (int rc = c->d_out_dist.ensure(size_t(eff) * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(size_t(eff) * sizeof(uint32_t)); rc) return rc;
+	const uint32_t gridx = rxgpu::scan_grid_x(h->count, h->cus);
+	std::vector<float> hd(eff);
+	std::vector<uint32_t> hr(eff);
+	for (uint32_t q = 0; q < nq; ++q) {
+		{
+			ProfileScope ps(h, "scan", c->stream);
+			rxgpu::launch_all_distances(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr) + size_t(q) * h->dim,
+										h->count, h->stride, h->dim, static_cast<float*>(c->d_misc.ptr), gridx, c->stream);
+		}
+		{
+			ProfileScope ps(h, "select", c->stream);
+			rxgpu::launch_select_smallest(static_cast<const float*>(c->d_misc.ptr), h->count, eff, c->d_select.ptr,
+										  static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), c->stream);
+		}
+		RX_HIP(hipGetLastError());
+		RX_HIP(hipMemcpyAsync(hd.data(), c->d_out_dist.ptr, size_t(eff) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+		RX_HIP(hipMemcpyAsync(hr.data(), c->d_out_row.ptr, size_t(eff) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+		RX_HIP(hipStreamSynchronize(c->stream));
+		rxgpu::sort_dist_row(hd, hr, out_dist + size_t(q) * kk, out_row + size_t(q) * kk);
+		out_count[q] = eff;
+	}
+	return RXGPU_OK;
+}
+
+int rxgpu_search_knn_subset(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* row_ids, uint64_t n_ids,
+							float* out_dist, uint32_t* out_row, uint32_t* out_count) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(queries && out_dist && out_row && out_count && (n_ids == 0 || row_ids), RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset: null argument");
+	if (h->shard_set) {   // differs from the single-device branch below, and is kept: kk == 0 is refused here, and the row list's messages are the fan-out's
+		if (nq == 0) return RXGPU_OK;
+		RX_CHECK(kk >= 1, RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset: kk must be >= 1");
+		if (n_ids == 0) {
+			std::fill(out_count, out_count + nq, 0u);
+			return RXGPU_OK;
+		}
+		return rxgpu::sharded_search_knn_impl(h, queries, nq, kk, row_ids, n_ids, out_dist, out_row, out_count);
+	}
+	if (nq == 0) return RXGPU_OK;
+	if (int rc = check_rows_host(h, row_ids, n_ids, "rxgpu_search_knn_subset"); rc) return rc;
+	if (n_ids == 0 || kk == 0) {
+		std::fill(out_count, out_count + nq, 0u);
+		return RXGPU_OK;
+	}
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	if (int rc = c->d_subset.ensure(n_ids * sizeof(uint32_t)); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_subset.ptr, row_ids, n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	return search_subset_host(h, c, queries, nq, kk, static_cast<const uint32_t*>(c->d_subset.ptr), n_ids, out_dist, out_row, out_count);
+}
+
+int rxgpu_search_knn_bitmap(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t kk, const uint32_t* allowed_words, uint64_t n_words,
+							float* out_dist, uint32_t* out_row, uint32_t* out_count, uint64_t* out_allowed) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_bitmap: not available on a sharded index");
+	RX_CHECK(queries && out_dist && out_row && out_count && allowed_words, RXGPU_ERR_PARAMS, "rxgpu_search_knn_bitmap: null argument");
+	const uint64_t need_words = (h->count + 31) / 32;
+	RX_CHECK(n_words >= need_words, RXGPU_ERR_PARAMS, "rxgpu_search_knn_bitmap: the bitmap must cover every row (ceil(count / 32) words)");
+	if (out_allowed) *out_allowed = 0;
+	if (nq == 0) return RXGPU_OK;
+	if (h->count == 0) {
+		std::fill(out_count, out_count + nq, 0u);
+		return RXGPU_OK;
+	}
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	if (int rc = c->d_bitmap.ensure(need_words * sizeof(uint32_t)); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_bitmap.ptr, allowed_words, need_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	unsigned long long total = 0;
+	if (int rc = bitmap_to_row_list(h, c, "bitmap", kk != 0, &total, [] {}); rc) return rc;
+	if (out_allowed) *out_allowed = total;
+	if (total == 0 || kk == 0) {
+		std::fill(out_count, out_count + nq, 0u);
+		return RXGPU_OK;
+	}
+	return search_subset_host(h, c, queries, nq, kk, static_cast<const uint32_t*>(c->d_subset.ptr), total, out_dist, out_row, out_count);
+}
+
+int rxgpu_index_set_lists(rxgpu_index* h, uint32_t nlist, const uint64_t* list_off, const uint32_t* list_rows) {
+	RX_CHECK(h && list_off && nlist > 0, RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: null argument");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_index_set_lists: not available on a sharded index");
+	RX_CHECK(list_off[0] == 0, RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: offsets start at 0");
+	for (uint32_t l = 0; l < nlist; ++l) RX_CHECK(list_off[l] <= list_off[l + 1], RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: offsets must not decrease");
+	const uint64_t total = list_off[nlist];
+	RX_CHECK(total <= h->count && (total == 0 || list_rows), RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: more listed rows than the index holds");
+	for (uint64_t i = 0; i < total; ++i) RX_CHECK(list_rows[i] < h->count, RXGPU_ERR_PARAMS, "rxgpu_index_set_lists: row out of range");
+	DeviceGuard dg(h->device);
+	RX_HIP(rxgpu::device_wait_all(h->device));
+	if (h->d_list_off) (void)hipFree(h->d_list_off);
+	if (h->d_list_rows) (void)hipFree(h->d_list_rows);
+	h->d_list_off = nullptr;
+	h->d_list_rows = nullptr;
+	h->nlist = 0;
+	RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_list_off), (size_t(nlist) + 1) * sizeof(uint64_t)));
+	RX_HIP(hipMemcpy(h->d_list_off, list_off, (size_t(nlist) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+	if (total) {
+		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_list_rows), total * sizeof(uint32_t)));
+		RX_HIP(hipMemcpy(h->d_list_rows, list_rows, total * sizeof(uint32_t), hipMemcpyHostToDevice));
+	}
+	h->nlist = nlist;
+	h->lists_rows = total;
+	h->lists_count = h->count;
+	return RXGPU_OK;
+}
+
+namespace {
+// The probed lists of one query as an ascending row list in c->d_subset, everything on the device: nprobe nearest centroids (the coarse
+// quantiser's search; up to 128 lists its result never leaves HBM, wider probes fetch the list ids — nprobe words — and send them back),
+// lists -> allowed-rows bitmap -> row list.  *total = rows to scan.
+int ivf_probe_rows(rxgpu_index* h, rxgpu_index* coarse, rxgpu_search_ctx* c, const float* query, uint32_t nprobe, unsigned long long* total) {
+	const size_t qbytes = size_t(h->dim) * sizeof(float);
+	if (int rc = c->d_queries.ensure(qbytes); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, qbytes, hipMemcpyHostToDevice, c->stream));
+	const size_t o_lists = 0, o_dist = size_t(nprobe) * 4, o_cnt = o_dist + size_t(nprobe) * 4;
+	if (int rc = c->d_ivf.ensure(o_cnt + 256); rc) return rc;
+	char* ivf = static_cast<char*>(c->d_ivf.ptr);
+	if (nprobe <= uint32_t(rxgpu::kMaxFusedK2)) {
+		rxgpu_search_ctx* cc = stream_ctx(coarse, c->stream);
+		auto* run = nprobe <= uint32_t(rxgpu::kMaxFusedK) ? enqueue_knn : enqueue_knn_fused;
+		if (int rc = run(coarse, cc, static_cast<const float*>(c->d_queries.ptr), 1, nprobe, reinterpret_cast<float*>(ivf + o_dist),
+						 reinterpret_cast<uint32_t*>(ivf + o_lists), reinterpret_cast<uint32_t*>(ivf + o_cnt));
+			rc)
+			return rc;
+	} else {
+		std::vector<float> cd(nprobe);
+		std::vector<uint32_t> cl(nprobe);
+		uint32_t cnt = 0;
+		if (int rc = rxgpu_search_knn(coarse, query, 1, nprobe, cd.data(), cl.data(), &cnt); rc) return rc;
+		RX_HIP(hipMemcpyAsync(ivf + o_lists, cl.data(), size_t(cnt) * 4, hipMemcpyHostToDevice, c->stream));
+		RX_HIP(hipMemcpyAsync(ivf + o_cnt, &cnt, 4, hipMemcpyHostToDevice, c->stream));
+		RX_HIP(hipStreamSynchronize(c->stream));   // cl / cnt live on this frame
+	}
+	const uint64_t need_words = (h->count + 31) / 32;
+	if (int rc = c->d_bitmap.ensure(need_words * sizeof(uint32_t)); rc) return rc;
+	RX_HIP(hipMemsetAsync(c->d_bitmap.ptr, 0, need_words * sizeof(uint32_t), c->stream));
+	return bitmap_to_row_list(h, c, "ivf_lists", true, total, [&] {
+		rxgpu::launch_ivf_mark_lists(reinterpret_cast<const uint32_t*>(ivf + o_lists), reinterpret_cast<const uint32_t*>(ivf + o_cnt), nprobe, h->d_list_off,
+									 h->d_list_rows, static_cast<uint32_t*>(c->d_bitmap.ptr), c->stream);
+	});
+}
+int ivf_check(rxgpu_index* h, rxgpu_index* coarse, const char* who) {
+	if (h->shard_set || coarse->shard_set) {
+		set_error(std::string(who) + ": not available on a sharded index");
+		return RXGPU_ERR_LOGIC;
+	}
+	RX_CHECK(h->nlist > 0 && h->lists_count == h->count, RXGPU_ERR_LOGIC, std::string(who) + ": inverted lists are not set / out of date");
+	RX_CHECK(coarse->count == h->nlist && coarse->dim == h->dim && coarse->device == h->device, RXGPU_ERR_PARAMS,
+			 std::string(who) + ": the coarse index must hold one centroid per list, same dimension, same device");
+	return RXGPU_OK;
+}
+}  // namespace
+
+int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, uint32_t kk, float* out_dist,
+						   uint32_t* out_row, uint32_t* out_count, uint64_t* out_scanned) {
+	RX_CHECK(h && coarse && query && out_dist && out_row && out_count, RXGPU_ERR_PARAMS, "rxgpu_search_knn_lists: null argument");
+	if (int rc = ivf_check(h, coarse, "rxgpu_search_knn_lists"); rc) return rc;
+	if (out_scanned) *out_scanned = 0;
+	*out_count = 0;
+	if (h->count == 0 || kk == 0) return RXGPU_OK;
+	nprobe = std::max<uint32_t>(1, std::min<uint32_t>(nprobe, h->nlist));
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	unsigned long long total = 0;
+	if (int rc = ivf_probe_rows(h, coarse, c, query, nprobe, &total); rc) return rc;
+	if (out_scanned) *out_scanned = total;
+	if (total == 0) return RXGPU_OK;
+	return search_subset_host(h, c, query, 1, kk, static_cast<const uint32_t*>(c->d_subset.ptr), total, out_dist, out_row, out_count);
+}
+
+namespace {
+// range search over a row list that lies in c->d_subset (query in c->d_queries): the tail of rxgpu_search_range_subset
+int range_subset_on_device(rxgpu_index* h, rxgpu_search_ctx* c, uint64_t n_ids, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
+						   uint64_t* out_total, const char* who) {
+	const uint64_t dcap = std::min<uint64_t>(cap, n_ids);
+	if (int rc = c->d_out_dist.ensure(std::max<uint64_t>(dcap, 1) * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(std::max<uint64_t>(dcap, 1) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_count.ensure(sizeof(unsigned long long)); rc) return rc;
+	RX_HIP(hipMemsetAsync(c->d_out_count.ptr, 0, sizeof(unsigned long long), c->stream));
+	{
+		ProfileScope ps(h, "range_subset", c->stream);
+		rxgpu::launch_range_subset(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr),
+								   static_cast<const uint32_t*>(c->d_subset.ptr), n_ids, h->stride, h->dim, radius, inclusive,
+								   static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
+								   static_cast<unsigned long long*>(c->d_out_count.ptr), rxgpu::scan_grid_x(n_ids, h->cus), c->stream);
+	}
+	return range_tail(c, out_dist, out_row, cap, out_total, who);
+}
+}  // namespace
+
+int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, float radius, int inclusive, float* out_dist,
+							 uint32_t* out_row, uint64_t cap, uint64_t* out_total, uint64_t* out_scanned) {
+	RX_CHECK(h && coarse && query && out_total && (cap == 0 || (out_dist && out_row)), RXGPU_ERR_PARAMS, "rxgpu_search_range_lists: null argument");
+	if (int rc = ivf_check(h, coarse, "rxgpu_search_range_lists"); rc) return rc;
+	if (out_scanned) *out_scanned = 0;
+	*out_total = 0;
+	if (h->count == 0) return RXGPU_OK;
+	nprobe = std::max<uint32_t>(1, std::min<uint32_t>(nprobe, h->nlist));
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	unsigned long long total = 0;
+	if (int rc = ivf_probe_rows(h, coarse, c, query, nprobe, &total); rc) return rc;
+	if (out_scanned) *out_scanned = total;
+	if (total == 0) return RXGPU_OK;
+	return range_subset_on_device(h, c, total, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_lists");
+}
+
+int rxgpu_search_knn_subset_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, const void* d_row_ids, uint64_t n_ids,
+								   void* d_out_dist, void* d_out_row, void* d_out_count, void* stream) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_search_knn_subset_device: not available on a sharded index");
+	RX_CHECK(nq > 0 && d_queries && d_row_ids && d_out_dist && d_out_row, RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset_device: null argument");
+	RX_CHECK(kk > 0 && kk <= uint32_t(rxgpu::kMaxFusedK2), RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset_device: kk must be in [1, 128]");
+	RX_CHECK(n_ids > 0 && n_ids <= h->count, RXGPU_ERR_PARAMS, "rxgpu_search_knn_subset_device: the row list must hold 1..count entries");
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = stream_ctx(h, stream);
+	return enqueue_knn_subset(h, c, static_cast<const float*>(d_queries), nq, kk, static_cast<const uint32_t*>(d_row_ids), n_ids,
+							  static_cast<float*>(d_out_dist), static_cast<uint32_t*>(d_out_row), static_cast<uint32_t*>(d_out_count));
+}
+
+int rxgpu_check_row_list_device(rxgpu_index* h, const void* d_row_ids, uint64_t n_ids, void* stream, int32_t* out_ok) {
+	RX_CHECK(h && out_ok && (n_ids == 0 || d_row_ids), RXGPU_ERR_PARAMS, "rxgpu_check_row_list_device: null argument");
+	*out_ok = 1;
+	if (n_ids == 0) return RXGPU_OK;
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = stream_ctx(h, stream);
+	if (int rc = c->d_tiles.ensure(sizeof(uint32_t)); rc) return rc;
+	RX_HIP(hipMemsetAsync(c->d_tiles.ptr, 0, sizeof(uint32_t), c->stream));
+	rxgpu::launch_check_row_list(static_cast<const uint32_t*>(d_row_ids), n_ids, h->count, static_cast<uint32_t*>(c->d_tiles.ptr), h->cus, c->stream);
+	RX_HIP(hipGetLastError());
+	uint32_t bad = 0;
+	RX_HIP(hipMemcpyAsync(&bad, c->d_tiles.ptr, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	*out_ok = bad ? 0 : 1;
+	return RXGPU_OK;
+}
+
+int rxgpu_merge_shards_device(const void* d_gathered, uint32_t world, uint32_t nq, uint32_t kk, uint32_t shard_rows, void* d_out_dist,
+							  void* d_out_row, void* d_out_count, void* stream) {
+	RX_CHECK(d_gathered && d_out_dist && d_out_row, RXGPU_ERR_PARAMS, "rxgpu_merge_shards_device: null argument");
+	RX_CHECK(world >= 1 && nq >= 1 && kk >= 1 && kk <= uint32_t(rxgpu::kMaxFusedK), RXGPU_ERR_PARAMS, "rxgpu_merge_shards_device: bad shape");
+	RX_CHECK(uint64_t(world) * shard_rows <= 0xFFFFFFFEull, RXGPU_ERR_PARAMS, "rxgpu_merge_shards_device: global rows must fit 32 bits");
+	rxgpu::launch_merge_shards(static_cast<const uint32_t*>(d_gathered), world, nq, kk, shard_rows, static_cast<float*>(d_out_dist),
+							   static_cast<uint32_t*>(d_out_row), static_cast<uint32_t*>(d_out_count), static_cast<hipStream_t>(stream));
+	RX_HIP(hipGetLastError());
+	return RXGPU_OK;
+}
+
+int rxgpu_search_range(rxgpu_index* h, const float* query, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
+					   uint64_t* out_total) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(query && out_total && (cap == 0 || (out_dist && out_row)), RXGPU_ERR_PARAMS, "rxgpu_search_range: null argument");
+	*out_total = 0;
+	// (a sharded call that overflows leaves the first cap hits in the buffers, the tail below writes none: both are kept)
+	if (h->shard_set) return rxgpu::sharded_search_range_impl(h, query, radius, inclusive, nullptr, 0, out_dist, out_row, cap, out_total);
+	if (h->count == 0) return RXGPU_OK;   // bruteforce.cc:132-134
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	const uint64_t dcap = std::min<uint64_t>(cap, h->count);
+	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_dist.ensure(std::max<uint64_t>(dcap, 1) * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(std::max<uint64_t>(dcap, 1) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_count.ensure(sizeof(unsigned long long)); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, h->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	RX_HIP(hipMemsetAsync(c->d_out_count.ptr, 0, sizeof(unsigned long long), c->stream));
+	{
+		ProfileScope ps(h, "range", c->stream);
+		rxgpu::launch_range(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr), h->count, h->stride, h->dim,
+							radius, inclusive, static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
+							static_cast<unsigned long long*>(c->d_out_count.ptr), rxgpu::scan_grid_x(h->count, h->cus), c->stream);
+	}
+	return range_tail(c, out_dist, out_row, cap, out_total, "rxgpu_search_range");
+}
+
+int rxgpu_search_range_subset(rxgpu_index* h, const float* query, float radius, int inclusive, const uint32_t* row_ids, uint64_t n_ids,
+							  float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(query && out_total && (cap == 0 || (out_dist && out_row)) && (n_ids == 0 || row_ids), RXGPU_ERR_PARAMS,
+			 "rxgpu_search_range_subset: null argument");
+	*out_total = 0;
+	if (h->shard_set) {   // (the fan-out checks the row list, with a message of its own)
+		if (n_ids == 0) return RXGPU_OK;
+		return rxgpu::sharded_search_range_impl(h, query, radius, inclusive, row_ids, n_ids, out_dist, out_row, cap, out_total);
+	}
+	if (int rc = check_rows_host(h, row_ids, n_ids, "rxgpu_search_range_subset"); rc) return rc;
+	if (n_ids == 0) return RXGPU_OK;
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
+	if (int rc = c->d_subset.ensure(n_ids * sizeof(uint32_t)); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, h->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	RX_HIP(hipMemcpyAsync(c->d_subset.ptr, row_ids, n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	return range_subset_on_device(h, c, n_ids, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_subset");
+}
+
+int rxgpu_distances(rxgpu_index* h, const float* query, const uint32_t* rows, uint32_t n, float* out_dist) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(query && (n == 0 || (rows && out_dist)), RXGPU_ERR_PARAMS, "rxgpu_distances: null argument");
+	if (n == 0) return RXGPU_OK;
+	if (h->shard_set) return rxgpu::sharded_distances(h, query, rows, n, out_dist);
+	for (uint32_t i = 0; i < n; ++i) RX_CHECK(rows[i] < h->count, RXGPU_ERR_PARAMS, "rxgpu_distances: row out of range");
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(size_t(n) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_dist.ensure(size_t(n) * sizeof(float)); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, h->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	RX_HIP(hipMemcpyAsync(c->d_out_row.ptr, rows, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	{
+		ProfileScope ps(h, "distances", c->stream);
+		rxgpu::launch_distances(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr), h->stride, h->dim,
+							static_cast<const uint32_t*>(c->d_out_row.ptr), n, static_cast<float*>(c->d_out_dist.ptr), c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	RX_HIP(hipMemcpyAsync(out_dist, c->d_out_dist.ptr, size_t(n) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	return RXGPU_OK;
+}
+
+}  // extern "C"
