@@ -193,7 +193,10 @@ int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint3
  *   "pruned_margin", "pruned_q_sq"   1 float each: what knn_filter_approx adds to T; |q|^2
  *   "pruned_qinfo"      int8 tier: 2 floats {s_q, |q| rounded up}       "pruned_qplanes"  int8 tier: [2][dim rounded up to 256] int8 (h, then l)
  *   "pruned_top"        kk floats (the merged list of the pruning scan, ascending; its last entry is T) and 1 uint32, the entries it holds
- *   "pruned_cand_rows"  [min(candidates, capacity)] uint32 rows the filter nominated, in no particular order */
+ *   "pruned_cand_rows"  [min(candidates, capacity)] uint32 rows the filter nominated, in no particular order
+ *   "pruned_emit_cnt"   int8 tier over every row, emitting scan: [4 x workgroups of the scan] uint32, the entries wavefront w emitted
+ *   "pruned_emitted"    ... and [n] pairs {float lo, uint32 row}: the wavefronts' segments back to back (knn_emit_plan.h), segment w valid
+ *                       up to its count, rows ascending */
 int rxgpu_index_inspect(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
 
 /* ---- Pre-filtered brute force: the caller side of `WHERE cond AND KNN(...)` -------------------

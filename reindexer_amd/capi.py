@@ -532,11 +532,13 @@ class VectorIndex:
 
     _INSPECT_DTYPES = {"stats": np.uint32, "row_sq": np.float32, "codes_i8": np.int8, "side_i8": np.float32, "rows_bf16": np.uint16,
                        "pruned_values": np.float32, "pruned_margin": np.float32, "pruned_q_sq": np.float32, "pruned_qinfo": np.float32,
-                       "pruned_qplanes": np.int8, "pruned_top": np.uint32, "pruned_cand_rows": np.uint32}
+                       "pruned_qplanes": np.int8, "pruned_top": np.uint32, "pruned_cand_rows": np.uint32,
+                       "pruned_emit_cnt": np.uint32, "pruned_emitted": np.uint32}
 
     def inspect(self, name: str) -> np.ndarray:
         """rxgpu_index_inspect: a named internal buffer as a flat array (test instrumentation; include/rxgpu.h lists the names and shapes).
-        "pruned_top" comes as kk + 1 uint32 words: the bits of the kk list values, then the number of entries."""
+        "pruned_top" comes as kk + 1 uint32 words: the bits of the kk list values, then the number of entries; "pruned_emitted" as 2 n words:
+        per entry the bits of lo, then the row."""
         need = _u64(0)
         rc = lib().rxgpu_index_inspect(self._h, name.encode(), None, 0, C.byref(need))
         if rc != RXGPU_ERR_OVERFLOW:

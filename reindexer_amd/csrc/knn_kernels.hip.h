@@ -20,6 +20,7 @@
 
 #include <atomic>
 
+#include "knn_emit_plan.h"     // EmitEntry, EmitPlan: where knn_scan_i8 puts the rows it emits
 #include "hnsw_launch_plan.h"   // kHnswMaxEf, kHnswLdsCandEf, kHnswCandLds, kHnswSortedMaxEf, kHnswSortedMaxEfDel: the constants the host-side policy reads too
 
 namespace rxgpu {
@@ -82,6 +83,14 @@ struct ScanI8Params {
 	const float* q_sq;        // L2: [nq]
 	uint32_t ld8;
 	float* lower;             // [nq][n] lower bound of every row's distance
+};
+
+// ... and what its emitting form (kEmit) needs on top: the query's margin, the segments and the counts (knn_emit_plan.h)
+struct ScanI8Emit {
+	const float* margin;      // [nq]
+	EmitEntry* emit;          // [nq][n] the wavefronts' segments back to back
+	uint32_t* emit_cnt;       // [nq][nwaves] entries in each segment
+	EmitPlan plan;            // emit_plan(n, gridDim.x)
 };
 
 enum : int { kGemmDense = 0, kGemmFilter = 1 };

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_subset_generic(ScanPara
 //                         into the per-wave top-kk exactly like the f32 scan
 //   2. knn_merge_lists    -> d~_(kk), the kk-th best approximate distance (the scan leaves sorted per-workgroup lists)
 //   3. knn_filter_approx  rows with d~ <= d~_(kk) + 2 eps  (eps = the rigorous bf16 bound of knn_query_stats<.., true>)
-//   4. knn_rescore + knn_merge   EXACT distances of those few dozen rows, exact top-kk by (dist, row)
+//   4. knn_rescore, the gated exact scan, knn_merge_final   EXACT distances of those few dozen rows, exact top-kk by (dist, row)
 // Soundness: a row r of the true top-kk has d~_r <= d_r + eps <= D_kk + eps, and D_kk <= kk-th smallest of (d~ + eps) = d~_(kk) + eps.
 // One 16-lane group owns a row: lane m loads the 16-byte chunks m, m + 16, ... (8 bf16 each; 256 contiguous bytes per group per load),
 // widens them to f32 (exact) and runs four fmaf chains against the f32 query fragment it keeps in registers.
@@ -491,15 +491,46 @@ __global__ __launch_bounds__(256) void knn_filter_approx(const float* approx, ui
 	}
 }
 
-// One workgroup per query: fold `total` candidate (dist,row) pairs (invalid rows skipped) into the sorted top-kk.
-__global__ __launch_bounds__(kMergeThreads) void knn_merge(const float* part_dist, const uint32_t* part_row, uint32_t total,
-															uint32_t kk, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-															const uint32_t* gate_cnt, uint32_t gate_cap) {
-	__shared__ float s_d[kMergeWaves][kMaxFusedK];
-	__shared__ uint32_t s_i[kMergeWaves][kMaxFusedK];
-	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;
+// knn_filter_approx over what knn_scan_i8 emitted (knn_emit_plan.h) instead of a value per row: the same early return, the same threshold, the
+// same append.  Workgroups stride over the wavefronts' segments and read emit_cnt[w] entries of each; an entry stays when lo <= thr.  The
+// emitted rows are a superset of {lo <= thr} (knn_scan_i8), so the candidate set is the one knn_filter_approx finds over all rows.
+__global__ __launch_bounds__(256) void knn_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, EmitPlan plan, const float* top_dist,
+														  const uint32_t* top_count, uint32_t kk, const float* margin, uint32_t* cand_row,
+														  uint32_t* cand_cnt, uint32_t cap) {
+	const uint32_t qi = blockIdx.y;
+	const int lane = threadIdx.x & 63;
+	if (!(margin[qi] < __builtin_inff())) return;   // no bound for this query: nothing was emitted, the exact scan answers it
+	const float thr = (top_count[qi] >= kk ? top_dist[size_t(qi) * kk + kk - 1] : __builtin_inff()) + margin[qi];
+	const EmitEntry* all = emit + size_t(qi) * plan.n;
+	const uint32_t* counts = emit_cnt + size_t(qi) * plan.nwaves;
+	for (uint64_t w = blockIdx.x; w < plan.nwaves; w += gridDim.x) {
+		const uint64_t room = emit_rows_of(plan, w);
+		uint64_t cnt = counts[w];
+		cnt = cnt < room ? cnt : room;   // (a count is never above its segment; nothing may read past it whatever the buffer holds)
+		const EmitEntry* seg = all + emit_segment_offset(plan, w);
+		for (uint64_t base = 0; base < cnt; base += blockDim.x) {   // workgroup-uniform trip count
+			const uint64_t at = base + threadIdx.x;
+			EmitEntry ent;
+			ent.lo = __builtin_inff();
+			ent.row = kInvalidRow;
+			if (at < cnt) ent = seg[at];
+			const bool pass = at < cnt && ent.lo <= thr;
+			const uint64_t pm = __ballot(pass);
+			if (!pm) continue;
+			uint32_t pos0 = 0;
+			if (lane == __builtin_ctzll(pm)) pos0 = atomicAdd(&cand_cnt[qi], uint32_t(__popcll(pm)));
+			pos0 = __shfl(pos0, __builtin_ctzll(pm));
+			const uint32_t pos = pos0 + uint32_t(__popcll(pm & ((1ull << lane) - 1)));
+			if (pass && pos < cap) cand_row[size_t(qi) * cap + pos] = ent.row;
+		}
+	}
+}
+
+// Fold `total` candidate (dist,row) pairs at part_*[base ..] (invalid rows skipped) into the sorted top-kk of query blockIdx.x, by all
+// kMergeThreads threads.  s_d / s_i: [kMergeWaves][kMaxFusedK] words of LDS each.
+__device__ __forceinline__ void merge_fold(const float* part_dist, const uint32_t* part_row, size_t base, uint32_t total, uint32_t kk, float* out_dist,
+										   uint32_t* out_row, uint32_t* out_count, float* s_d, uint32_t* s_i) {
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const size_t base = size_t(blockIdx.x) * total;
 	WaveTopK top;
 	top.init(kk);
 	// kMergeAhead chunks of 64 candidates per trip, all their loads issued together: one chunk per trip left every trip behind its own
@@ -529,13 +560,13 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge(const float* part_dis
 			}
 		}
 	}
-	s_d[wave][lane] = top.bd;
-	s_i[wave][lane] = top.bi;
+	s_d[wave * kMaxFusedK + lane] = top.bd;
+	s_i[wave * kMaxFusedK + lane] = top.bi;
 	__syncthreads();
 	if (wave != 0) return;
 	for (int w = 1; w < kMergeWaves; ++w) {
-		const float cd = s_d[w][lane];
-		const uint32_t ci = s_i[w][lane];
+		const float cd = s_d[w * kMaxFusedK + lane];
+		const uint32_t ci = s_i[w * kMaxFusedK + lane];
 		uint64_t pm = __ballot(ci != kInvalidRow && lane < int(kk));
 		while (pm) {
 			const int src = __builtin_ctzll(pm);
@@ -551,6 +582,16 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge(const float* part_dis
 		out_row[size_t(blockIdx.x) * kk + lane] = top.bi;
 	}
 	if (lane == 0 && out_count) out_count[blockIdx.x] = top.filled;
+}
+
+// One workgroup per query: merge_fold over the query's `total` pairs.
+__global__ __launch_bounds__(kMergeThreads) void knn_merge(const float* part_dist, const uint32_t* part_row, uint32_t total,
+															uint32_t kk, float* out_dist, uint32_t* out_row, uint32_t* out_count,
+															const uint32_t* gate_cnt, uint32_t gate_cap) {
+	__shared__ float s_d[kMergeWaves * kMaxFusedK];
+	__shared__ uint32_t s_i[kMergeWaves * kMaxFusedK];
+	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;
+	merge_fold(part_dist, part_row, size_t(blockIdx.x) * total, total, kk, out_dist, out_row, out_count, s_d, s_i);
 }
 
 // knn_merge for 64 < kk <= 128 (two entries per lane)
@@ -654,14 +695,11 @@ template <typename TK>
 __device__ void merge_by_insertion(const float* part_dist, const uint32_t* part_row, size_t base, uint32_t total, uint32_t kk, float* out_dist,
 								   uint32_t* out_row, uint32_t* out_count, float* s_d, uint32_t* s_i);
 
+// the merge of query blockIdx.x; s_key / s_val: [kMergeHeadsMax], s_n: one word of LDS
 template <typename TK>
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
-																  float* out_dist, uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt,
-																  uint32_t gate_cap) {
-	__shared__ unsigned long long s_key[kMergeHeadsMax];
-	__shared__ float s_val[kMergeHeadsMax];
-	__shared__ uint32_t s_n;
-	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;   // workgroup-uniform (knn_merge's gate)
+__device__ __forceinline__ void merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, float* out_dist, uint32_t* out_row,
+											uint32_t* out_count, unsigned long long* s_key, float* s_val, uint32_t* s_np) {
+	uint32_t& s_n = *s_np;
 	const uint32_t tid = threadIdx.x, total = nlists * kk;
 	const size_t base = size_t(blockIdx.x) * total;
 	bool serial = nlists < kk || nlists > kMergeHeadsMax;
@@ -722,6 +760,34 @@ __global__ __launch_bounds__(kMergeThreads) void knn_merge_lists(const float* pa
 	}
 	// the insertion merge over the same lists (LDS reused for the wavefronts' lists)
 	merge_by_insertion<TK>(part_dist, part_row, base, total, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
+}
+
+template <typename TK>
+__global__ __launch_bounds__(kMergeThreads) void knn_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
+																  float* out_dist, uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt,
+																  uint32_t gate_cap) {
+	__shared__ unsigned long long s_key[kMergeHeadsMax];
+	__shared__ float s_val[kMergeHeadsMax];
+	__shared__ uint32_t s_n;
+	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;   // workgroup-uniform (knn_merge's gate)
+	merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
+}
+
+// The one merge at the end of a pruned chain (rxgpu_knn_chains.hip), one workgroup per query.  Gate closed (cand_cnt <= cap): the pruned chain
+// answers — merge_fold over the cand_cnt re-scored candidates.  Gate open: the exact scan behind the gate has run — merge_lists over its lists.
+template <typename TK>
+__global__ __launch_bounds__(kMergeThreads) void knn_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap,
+																  const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
+																  float* out_dist, uint32_t* out_row, uint32_t* out_count) {
+	__shared__ unsigned long long s_key[kMergeHeadsMax];
+	__shared__ float s_val[kMergeHeadsMax];
+	__shared__ uint32_t s_n;
+	const uint32_t cnt = cand_cnt[blockIdx.x];   // workgroup-uniform
+	if (cnt <= cap) {
+		merge_fold(cand_dist, cand_row, size_t(blockIdx.x) * cap, cnt, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
+	} else {
+		merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
+	}
 }
 
 __device__ __forceinline__ void merge_store_list(const WaveTopK& t, float* d, uint32_t* i, int lane) {
@@ -1123,6 +1189,12 @@ void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist
 	hipLaunchKernelGGL(knn_filter_approx, dim3(gx, nq), dim3(256), 0, s, approx, n, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap, ids);
 }
 
+void launch_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count, uint32_t kk,
+						   const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s) {
+	const uint32_t gx = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(plan.nwaves, uint64_t(cus) * 8)));
+	hipLaunchKernelGGL(knn_filter_emitted, dim3(gx, nq), dim3(256), 0, s, emit, emit_cnt, plan, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap);
+}
+
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s) {
 	if (kk > uint32_t(kMaxFusedK)) {   // 64 < kk <= 128: never gated (the batched / pruned paths keep kk <= 64)
@@ -1142,6 +1214,19 @@ void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32
 	} else {
 		hipLaunchKernelGGL((knn_merge_lists<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
 						   gate_cnt, gate_cap);
+	}
+}
+
+// the end of a pruned chain: the candidates (cand_cnt <= cap) or the exact scan's nlists sorted lists (knn_merge_final)
+void launch_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap, const float* part_dist,
+						const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row, uint32_t* out_count,
+						hipStream_t s) {
+	if (kk > uint32_t(kMaxFusedK)) {   // (the pruned chains keep kk <= 64: the candidate fold holds one entry per lane)
+		hipLaunchKernelGGL((knn_merge_final<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, cand_dist, cand_row, cand_cnt, cap, part_dist, part_row, nlists, kk,
+						   out_dist, out_row, out_count);
+	} else {
+		hipLaunchKernelGGL((knn_merge_final<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, cand_dist, cand_row, cand_cnt, cap, part_dist, part_row, nlists, kk,
+						   out_dist, out_row, out_count);
 	}
 }
 

@@ -2,22 +2,25 @@
 // RXGPU_SCAN_I8=1 / 0 force it on / off): ONE byte per element from HBM instead of four, the SAME result bits.
 //   0. knn_query_prep_i8  (knn_batched.hip) padded f32 copy of the query, its two int8 planes, |q|^2, {s_q, |q|^}, the margin, cand_cnt = 0 — or
 //                         cap + 1 for a query (or an index) without a finite bound, which steps 3-4 then leave to the gated exact scan
-//   1. knn_scan_i8        per row the exact integer S_r = dot(t, c_r) from the int8 shadow, d~ and its window [lo_r, up_r]; lo_r is stored
-//                         ([n] floats), up_r is folded into the per-wave top-kk like a distance of the f32 scan
+//   1. knn_scan_i8        per row the exact integer S_r = dot(t, c_r) from the int8 shadow, d~ and its window [lo_r, up_r]; up_r is folded into
+//                         the per-wave top-kk like a distance of the f32 scan; {lo_r, r} is EMITTED into the wavefront's segment
+//                         (knn_emit_plan.h) when lo_r is within the margin of the wavefront's own running threshold, a superset of step 3's rows
+//                         (RXGPU_SCAN_I8_EMIT=0, and the gather form: lo_r of every row is stored instead, [n] floats)
 //   2. knn_merge_lists    -> T, the kk-th smallest upper bound
-//   3. knn_filter_approx  rows with lo_r <= T + margin
-//   4. knn_rescore + knn_merge   EXACT distances of those rows, exact top-kk by (dist, row)
+//   3. knn_filter_emitted the emitted rows with lo_r <= T + margin (knn_filter_approx over the stored values in the store-all sequence)
+//   4. knn_rescore, the gated exact scan, knn_merge_final   EXACT distances of those rows, exact top-kk by (dist, row)
 // The arithmetic, the bound and the soundness argument are in knn_i8_quant.h; nothing here rounds before the integer sum is complete.
 //
 // Mapping.  One 16-lane group owns FOUR consecutive rows per step: lane m loads the 16-byte chunks m, m + 16, ... of each (ld8 / 256 per row;
 // 256 contiguous bytes per group and load, 12 loads per lane and step at 768 dims), double-buffered in registers like knn_scan_fixed.  The two
 // query planes of a lane's chunks stay in registers for the whole kernel.  The four integer sums of a group are reduced over its 16 lanes
 // with a transposing butterfly (4 cross-lane steps instead of 16) that leaves the sum of row j in the lanes with m % 4 == j; lanes m < 4 then
-// own one row each: they have loaded its {s_r, e_r} pair (and |x|^2 or inv_norm) along with the codes, store lo and offer up.  Rows are in
+// own one row each: they have loaded its {s_r, e_r} pair (and |x|^2 or inv_norm) along with the codes, emit (or store) lo and offer up.  Rows are in
 // increasing order over the lanes of a wavefront and over its steps.
 #include <algorithm>
 #include <cstdlib>
 
+#include "knn_emit_plan.h"
 #include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "knn_scan_common.hip.h"
@@ -38,9 +41,19 @@ __device__ __forceinline__ int i8_dot16(const u32x4& a, const u32x4& b, int acc)
 	return acc;
 }
 
+static_assert(kI8RowsPerWave == kEmitRowsPerSet && kScanWaves == int(kEmitWavesPerBlock), "knn_emit_plan.h lays the segments out for this mapping");
+
 // NC8 = ld8 / 256: chunks per lane per row (768 -> 3)
-template <int kMetric, int NC8>
-__global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
+// kEmit: instead of leaving lo of every row for knn_filter_approx to read back, the wavefront appends {lo, row} of the rows that can still be
+// candidates to its own segment of e.emit (knn_emit_plan.h).  The threshold the filter needs is T, the kk-th smallest up of ALL rows; thr_d of
+// the wavefront's own top-kk is the kk-th smallest up of a subset, hence >= T (+inf until the list is full), and f32 addition is monotone, so
+// lo <= thr_d + margin holds wherever lo <= T + margin does: the emitted rows are a superset of the candidates, and knn_filter_emitted, which
+// holds them against the final T, leaves exactly the set knn_filter_approx finds.  Wave-local: ballot, prefix popcount, a running count in a
+// wave-uniform register; no atomics, entries in ascending row order.  A NaN lo or a margin that is not finite emits nothing (the prep has
+// set cand_cnt = cap + 1 for such a query: the gated exact scan answers).
+// kKeep: lo of every row goes to p.lower as well (a call that records for rxgpu_index_inspect, and the RXGPU_SCAN_I8_EMIT=0 sequence).
+template <int kMetric, int NC8, bool kEmit, bool kKeep>
+__global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p, ScanI8Emit e) {
 	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	const uint32_t qi = blockIdx.y;
@@ -63,6 +76,13 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
 	const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
 	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
 	const uint64_t first = uint64_t(blockIdx.x) * kScanWaves + wave;
+	float margin = 0.f;
+	EmitEntry* seg = nullptr;
+	uint32_t emitted = 0;   // wave-uniform
+	if constexpr (kEmit) {
+		margin = e.margin[qi];
+		seg = e.emit + size_t(qi) * n + emit_segment_offset(e.plan, first);
+	}
 
 	struct Buf {
 		u32x4 x[kI8RowsPerGroup * NC8];
@@ -111,7 +131,21 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
 		const bool valid = row < n && m < kI8RowsPerGroup;
 		float lo, up;
 		i8_bounds(kMetric, i8_ip(qinfo.x, b.side.x, s), qinfo.y, b.side.y, qq, b.aux, lo, up);
-		if (valid) lower[row] = lo;
+		if constexpr (kKeep) {
+			if (valid) lower[row] = lo;
+		}
+		if constexpr (kEmit) {   // against the threshold BEFORE this step's rows are offered
+			const float bound = top.thr_d + margin;
+			const bool em = valid && margin < __builtin_inff() && lo <= bound;
+			const uint64_t emask = __ballot(em);
+			if (em) {
+				EmitEntry ent;
+				ent.lo = lo;
+				ent.row = uint32_t(row);
+				seg[emitted + uint32_t(__popcll(emask & ((1ull << lane) - 1)))] = ent;
+			}
+			emitted += uint32_t(__popcll(emask));
+		}
 		const bool pass = valid && (top.filled < top.kk || up < top.thr_d);
 		uint64_t pm = __ballot(pass);
 		while (pm) {
@@ -135,6 +169,9 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8(ScanI8Params p) {
 			reduce(xb, set + nwaves);
 			__builtin_amdgcn_sched_barrier(0);
 		}
+	}
+	if constexpr (kEmit) {   // every wavefront of the grid, the idle ones too: the filter reads all nwaves counts
+		if (lane == 0) e.emit_cnt[size_t(qi) * nwaves + first] = emitted;
 	}
 	block_merge_and_store(top, p.sp, lane, wave);
 }
@@ -400,22 +437,33 @@ uint32_t scan_i8_subset_grid_x(uint64_t n_ids, int cus) {
 	return uint32_t(want < cap ? (want ? want : 1) : cap);
 }
 
-template <int kMetric>
-static void launch_scan_i8_metric(const ScanI8Params& p, dim3 grid, hipStream_t s) {
+template <int kMetric, bool kEmit, bool kKeep>
+static void launch_scan_i8_metric(const ScanI8Params& p, const ScanI8Emit& e, dim3 grid, hipStream_t s) {
 	switch (p.ld8 / 256) {
-		case 1: hipLaunchKernelGGL((knn_scan_i8<kMetric, 1>), grid, dim3(kScanThreads), 0, s, p); break;
-		case 2: hipLaunchKernelGGL((knn_scan_i8<kMetric, 2>), grid, dim3(kScanThreads), 0, s, p); break;
-		case 3: hipLaunchKernelGGL((knn_scan_i8<kMetric, 3>), grid, dim3(kScanThreads), 0, s, p); break;
-		default: hipLaunchKernelGGL((knn_scan_i8<kMetric, 4>), grid, dim3(kScanThreads), 0, s, p); break;
+		case 1: hipLaunchKernelGGL((knn_scan_i8<kMetric, 1, kEmit, kKeep>), grid, dim3(kScanThreads), 0, s, p, e); break;
+		case 2: hipLaunchKernelGGL((knn_scan_i8<kMetric, 2, kEmit, kKeep>), grid, dim3(kScanThreads), 0, s, p, e); break;
+		case 3: hipLaunchKernelGGL((knn_scan_i8<kMetric, 3, kEmit, kKeep>), grid, dim3(kScanThreads), 0, s, p, e); break;
+		default: hipLaunchKernelGGL((knn_scan_i8<kMetric, 4, kEmit, kKeep>), grid, dim3(kScanThreads), 0, s, p, e); break;
 	}
 }
-// p.ld8 must be i8_ld(dim) of a dimension with i8_dim_supported(dim)
-void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s) {
-	const dim3 grid(gridx, nq);
+template <bool kEmit, bool kKeep>
+static void launch_scan_i8_form(int metric, const ScanI8Params& p, const ScanI8Emit& e, dim3 grid, hipStream_t s) {
 	switch (metric) {
-		case kL2: launch_scan_i8_metric<kL2>(p, grid, s); break;
-		case kIP: launch_scan_i8_metric<kIP>(p, grid, s); break;
-		default: launch_scan_i8_metric<kCos>(p, grid, s); break;
+		case kL2: launch_scan_i8_metric<kL2, kEmit, kKeep>(p, e, grid, s); break;
+		case kIP: launch_scan_i8_metric<kIP, kEmit, kKeep>(p, e, grid, s); break;
+		default: launch_scan_i8_metric<kCos, kEmit, kKeep>(p, e, grid, s); break;
+	}
+}
+// p.ld8 must be i8_ld(dim) of a dimension with i8_dim_supported(dim).  emit null: the store-all form (p.lower gets lo of every row, nothing is
+// emitted); else e->plan must be emit_plan(p.sp.n, gridx), and keep says whether p.lower is written as well.
+void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s, const ScanI8Emit* emit, bool keep) {
+	const dim3 grid(gridx, nq);
+	if (!emit) {
+		launch_scan_i8_form<false, true>(metric, p, ScanI8Emit{}, grid, s);
+	} else if (keep) {
+		launch_scan_i8_form<true, true>(metric, p, *emit, grid, s);
+	} else {
+		launch_scan_i8_form<true, false>(metric, p, *emit, grid, s);
 	}
 }
 

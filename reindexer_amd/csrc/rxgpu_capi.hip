@@ -142,6 +142,8 @@ void rxgpu_search_ctx::release() {
 	d_redo.release();
 	d_top.release();
 	d_qplanes.release();
+	d_emit.release();
+	d_emit_cnt.release();
 	d_subset.release();
 	d_bitmap.release();
 	d_tiles.release();

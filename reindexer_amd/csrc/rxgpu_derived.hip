@@ -217,7 +217,8 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 		const bool i8 = h->last_pruned_i8;
 		const float* qstats = c ? static_cast<const float*>(c->d_qstats.ptr) : nullptr;   // one query: [{s_q, |q|^}] |q|^2, margin
 		const float* q_sq = qstats ? qstats + (i8 ? 2 : 0) : nullptr;
-		const char* known[] = {"pruned_values", "pruned_margin", "pruned_q_sq", "pruned_qinfo", "pruned_qplanes", "pruned_top", "pruned_cand_rows"};
+		const char* known[] = {"pruned_values", "pruned_margin", "pruned_q_sq", "pruned_qinfo", "pruned_qplanes", "pruned_top", "pruned_cand_rows",
+								   "pruned_emit_cnt", "pruned_emitted"};
 		if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return name == k; }) == std::end(known)) {
 			set_error(std::string("rxgpu_index_inspect: unknown buffer ") + what);
 			return RXGPU_ERR_PARAMS;
@@ -235,6 +236,13 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 		} else if (name == "pruned_qplanes") {
 			if (!i8) return missing("the bf16 tier keeps no query planes");
 			pieces.push_back({c->d_qplanes.ptr, 2ull * h->last_pruned_ld});
+		} else if (name == "pruned_emit_cnt" || name == "pruned_emitted") {   // what the emitting int8 scan left (knn_emit_plan.h), one query
+			if (!h->last_pruned_emit_gridx) return missing("the recorded call's scan emitted nothing (the bf16 tier, a row list, RXGPU_SCAN_I8_EMIT=0)");
+			if (name == "pruned_emit_cnt") {   // [wavefronts of the grid] entries per segment
+				pieces.push_back({c->d_emit_cnt.ptr, emit_count_bytes(h->last_pruned_emit_gridx, 1)});
+			} else {   // [n] {lo, row} pairs: the segments back to back, each valid up to its count
+				pieces.push_back({c->d_emit.ptr, emit_buffer_bytes(h->last_pruned_n, 1)});
+			}
 		} else if (name == "pruned_top") {   // d_top of one query: [kk] values, [kk] rows, the count
 			const float* top = static_cast<const float*>(c->d_top.ptr);
 			pieces.push_back({top, kk * sizeof(float)});

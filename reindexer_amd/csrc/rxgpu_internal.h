@@ -25,7 +25,8 @@ uint32_t scan_bf16_grid_x(uint64_t n, int cus);
 void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
 struct ScanI8Params;   // int8-pruned scan (knn_scan_i8.hip; the query side: knn_query_prep_i8 in knn_batched.hip)
 uint32_t scan_i8_grid_x(uint64_t n, int cus);
-void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
+struct ScanI8Emit;     // its emitting form (knn_emit_plan.h): null = lo of every row into p.lower and nothing emitted; keep: p.lower is written as well
+void launch_scan_i8(int metric, const ScanI8Params& p, uint32_t nq, uint32_t gridx, hipStream_t s, const ScanI8Emit* emit = nullptr, bool keep = true);
 // the gather form over a row list: p.sp.n = list entries, p.lower [nq][n_ids] by list position; gridx MUST come from scan_i8_subset_grid_x
 uint32_t scan_i8_subset_grid_x(uint64_t n_ids, int cus);
 void launch_scan_i8_subset(int metric, const ScanI8Params& p, const uint32_t* ids, uint32_t nq, uint32_t gridx, int cus, hipStream_t s);
@@ -36,11 +37,20 @@ void launch_query_prep_i8(int metric, const float* src, uint32_t nq, uint32_t di
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
 						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s,
 						  const uint32_t* ids = nullptr);   // ids: approx is indexed by list position and the candidates are ids[position]
+struct EmitEntry;
+struct EmitPlan;
+void launch_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count, uint32_t kk,
+						   const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus,
+						   hipStream_t s);   // launch_filter_approx over what knn_scan_i8 emitted
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s);
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
 						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt = nullptr,
 						uint32_t gate_cap = 0);   // the partial results are sorted lists of kk entries: no serial insertions; gated like launch_merge
+// the one merge at the end of a pruned chain: per query the cand_cnt re-scored candidates (cand_cnt <= cap), else the exact scan's sorted lists
+void launch_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap, const float* part_dist,
+						const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row, uint32_t* out_count,
+						hipStream_t s);
 void launch_merge_shards(const uint32_t* gathered, uint32_t world, uint32_t nq, uint32_t kk, uint32_t shard_rows, float* out_dist,
 						 uint32_t* out_row, uint32_t* out_count, hipStream_t s, const uint32_t* slot_base = nullptr, bool sorted = true);
 // one shard's HNSW result (unordered, counts <= k) into its [nq][kk] | [nq][kk] slot of the exchange's send buffer, padded with invalid entries
@@ -429,6 +439,7 @@ struct rxgpu_search_ctx {
 	rxgpu_devbuf d_helper, d_helper_bits;                                          // HNSW: overflow queue of a batch, bitsets of its helper workgroups
 	rxgpu_devbuf d_top;                                                            // bf16- / int8-pruned scan: approximate top lists
 	rxgpu_devbuf d_qplanes;                                                        // int8-pruned scan: the query's two int8 planes
+	rxgpu_devbuf d_emit, d_emit_cnt;                                               // int8-pruned scan: the rows it emitted and their count per wavefront (knn_emit_plan.h)
 	rxgpu_devbuf d_ivf;                                                            // IVF: the coarse search's lists, distances, count
 	rxgpu_devbuf d_subset, d_bitmap, d_tiles;                                      // pre-filtered search: row list, allowed-rows bitmap, tile sums
 	uint32_t pruned_cap = 0;   // candidate capacity of the pruned chain the current call enqueued (0: none) — rxgpu_index_last_candidates
@@ -437,6 +448,10 @@ struct rxgpu_search_ctx {
 	uint64_t pruned_n = 0;
 	uint32_t pruned_kk = 0, pruned_ld = 0;
 	bool pruned_i8 = false;
+	uint32_t pruned_emit_gridx = 0;   // the grid of the int8 scan when it emitted (0: it stored a value per row and emitted nothing)
+	// Set by a host entry point that ends in copy_back_knn, in front of the enqueue, when the call will be recorded for rxgpu_index_inspect
+	// (profiling, one query); cleared by copy_back_knn.  The emitting int8 scan then keeps its value per row as well ("pruned_values").
+	bool keep_values = false;
 	void* h_pinned = nullptr;
 	size_t h_pinned_bytes = 0;
 	// second stream + events (created on first use): work that does not depend on the query upload — zeroing the visited bitsets of an
@@ -559,6 +574,7 @@ struct rxgpu_index {
 	uint64_t last_pruned_n = 0;
 	uint32_t last_pruned_kk = 0, last_pruned_ld = 0;
 	bool last_pruned_i8 = false;
+	uint32_t last_pruned_emit_gridx = 0;
 
 	// HNSW graph mirror (rxgpu_hnsw_attach_graph)
 	uint32_t* d_links0 = nullptr;

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "../../include/rxgpu.h"
+#include "knn_emit_plan.h"
 #include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
@@ -336,6 +337,12 @@ namespace {
 // rows that can still belong to the result are filtered out of the values, re-scored exactly and merged.  Queries with more such rows than
 // the candidate list holds (massive ties), or without a finite bound, are answered by the exact f32 scan behind a gate on the device.
 constexpr uint32_t kPrunedCap = 4096;
+// RXGPU_SCAN_I8_EMIT, read per call (A/B runs inside one process): 0 = the int8 scan stores a value per row and knn_filter_approx reads them
+// all back (the sequence before the scan emitted); else / unset = the scan emits, knn_filter_emitted reads what it emitted.
+bool scan_i8_emits() {
+	const char* e = getenv("RXGPU_SCAN_I8_EMIT");
+	return !(e && *e && atoi(e) == 0);
+}
 
 // What the chain carves out of the context's buffers for its front.
 struct PrunedBufs {
@@ -343,9 +350,13 @@ struct PrunedBufs {
 	float* qstats;        // [nq][qstats_floats - 2] whatever else the front keeps per query
 	float* q_sq;          // [nq]
 	float* margin;        // [nq]
-	float* values;        // [nq][n] the scan's value per row (list position)
+	float* values;        // [nq][n] the scan's value per row (list position); an emitting front writes it only where keep is set
 	uint32_t* cand_cnt;   // [nq]
 	uint32_t cap;
+	// an emitting front (PrunedFront::emits): the rows the scan emitted, and whether it keeps a value per row as well
+	EmitEntry* emit;      // [nq][n]
+	uint32_t* emit_cnt;   // [nq][wavefronts of the scan's grid]
+	bool keep;
 };
 // The front of a pruned chain: the only place where the tiers differ.
 struct PrunedFront {
@@ -353,6 +364,9 @@ struct PrunedFront {
 	uint32_t ld;              // padded query stride (floats)
 	uint32_t qstats_floats;   // d_qstats floats per query: |q|^2 and the margin, behind whatever the front adds
 	bool planes;              // d_qplanes is needed
+	// Which filter form the scan feeds.  false: a value per row in b.values, knn_filter_approx reads all of them.  true: the scan emits the rows
+	// that can still be candidates (knn_emit_plan.h), knn_filter_emitted reads those; b.values is written only for a recording call (b.keep).
+	bool emits;
 	uint64_t n;               // rows scanned: the index's, or the entries of ids
 	const uint32_t* ids;      // the row list (null: every row); decides the exact scan behind the gate as well
 	uint32_t gridx;           // the pruning scan's grid ...
@@ -378,7 +392,14 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 		if (int rc = c->d_qplanes.ensure(size_t(nq) * 2 * f.ld); rc) return rc;
 	}
 	if (int rc = c->d_qstats.ensure(size_t(f.qstats_floats) * nq * sizeof(float)); rc) return rc;
-	if (int rc = c->d_dense.ensure(size_t(nq) * f.n * sizeof(float)); rc) return rc;
+	const bool keep = !f.emits || c->keep_values;
+	if (keep) {
+		if (int rc = c->d_dense.ensure(size_t(nq) * f.n * sizeof(float)); rc) return rc;
+	}
+	if (f.emits) {
+		if (int rc = c->d_emit.ensure(emit_buffer_bytes(f.n, nq)); rc) return rc;
+		if (int rc = c->d_emit_cnt.ensure(emit_count_bytes(f.gridx, nq)); rc) return rc;
+	}
 	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
 	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
@@ -393,6 +414,9 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	b.values = static_cast<float*>(c->d_dense.ptr);
 	b.cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
 	b.cap = cap;
+	b.emit = static_cast<EmitEntry*>(c->d_emit.ptr);
+	b.emit_cnt = static_cast<uint32_t*>(c->d_emit_cnt.ptr);
+	b.keep = keep;
 	float* top_dist = static_cast<float*>(c->d_top.ptr);
 	uint32_t* top_row = reinterpret_cast<uint32_t*>(top_dist + size_t(nq) * kk);
 	uint32_t* top_cnt = top_row + size_t(nq) * kk;
@@ -403,6 +427,7 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	c->pruned_kk = kk;
 	c->pruned_ld = f.ld;
 	c->pruned_i8 = f.planes;
+	c->pruned_emit_gridx = f.emits ? f.gridx : 0;
 	f.prep(h, c, d_queries, nq, f, b);
 	const ScanParams e = scan_params(h, c, d_queries, f.n, kk, b.cand_cnt, cap);   // the exact scan behind the gate
 	{
@@ -413,14 +438,17 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	launch_merge_lists(e.part_dist, e.part_row, f.gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
 	{
 		ProfileScope ps(h, "filter_approx", c->stream);
-		launch_filter_approx(b.values, f.n, top_dist, top_cnt, kk, b.margin, cand_row, b.cand_cnt, cap, nq, h->cus, c->stream, f.ids);
+		if (f.emits) {
+			launch_filter_emitted(b.emit, b.emit_cnt, emit_plan(f.n, f.gridx), top_dist, top_cnt, kk, b.margin, cand_row, b.cand_cnt, cap, nq, h->cus, c->stream);
+		} else {
+			launch_filter_approx(b.values, f.n, top_dist, top_cnt, kk, b.margin, cand_row, b.cand_cnt, cap, nq, h->cus, c->stream, f.ids);
+		}
 	}
 	{
 		ProfileScope ps(h, "rescore", c->stream);
 		launch_rescore(h->metric, h->d_rows, h->d_inv_norms, b.qpad, f.ld, h->stride, h->dim, nq, cap, b.cand_cnt, cand_row, cand_dist, c->stream);
 	}
-	launch_merge(cand_dist, cand_row, cap, kk, nq, d_out_dist, d_out_row, d_out_count, nullptr, 0, c->stream);
-	{   // more rows inside the bound than the list holds (massive ties), or no finite bound: the f32 path's own scan + merge, gated on device
+	{   // more rows inside the bound than the list holds (massive ties), or no finite bound: the f32 path's own scan, gated on device
 		bool file_slot = !f.fallback_slot_when_opened;
 		if (f.fallback_slot_when_opened && h->profiling) {
 			std::vector<uint32_t> cnt(nq);
@@ -434,7 +462,6 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 			} else {
 				launch_scan(h->metric, e, nq, f.gridx_exact, c->stream);
 			}
-			launch_merge_lists(e.part_dist, e.part_row, f.gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream, b.cand_cnt, cap);
 		};
 		if (file_slot) {
 			ProfileScope ps(h, "fallback_scan", c->stream);
@@ -443,6 +470,8 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 			fallback();
 		}
 	}
+	// one merge: the re-scored candidates of a query the pruned chain answers, the exact scan's lists of a query whose gate opened
+	launch_merge_final(cand_dist, cand_row, b.cand_cnt, cap, e.part_dist, e.part_row, f.gridx_exact, kk, nq, d_out_dist, d_out_row, d_out_count, c->stream);
 	RX_HIP(hipGetLastError());
 	return RXGPU_OK;
 }
@@ -492,6 +521,7 @@ int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_qu
 	f.planes = true;
 	f.n = d_ids ? n_ids : h->count;
 	f.ids = d_ids;
+	f.emits = !d_ids && scan_i8_emits();   // (the gather form keeps a value per list position)
 	f.gridx = d_ids ? scan_i8_subset_grid_x(n_ids, h->cus) : scan_i8_grid_x(h->count, h->cus);
 	f.gridx_exact = d_ids ? subset_grid_x(n_ids, h->dim, kk, h->cus) : scan_grid_x(h->count, h->cus);
 	f.scan_slot = d_ids ? "scan_i8_subset" : "scan_i8";
@@ -513,6 +543,13 @@ int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_qu
 		p.lower = b.values;
 		if (f.ids) {
 			launch_scan_i8_subset(h->metric, p, f.ids, nq, f.gridx, h->cus, c->stream);
+		} else if (f.emits) {
+			ScanI8Emit e{};
+			e.margin = b.margin;
+			e.emit = b.emit;
+			e.emit_cnt = b.emit_cnt;
+			e.plan = emit_plan(f.n, f.gridx);
+			launch_scan_i8(h->metric, p, nq, f.gridx, c->stream, &e, b.keep);
 		} else {
 			launch_scan_i8(h->metric, p, nq, f.gridx, c->stream);
 		}
@@ -567,19 +604,22 @@ int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk,
 	}
 	RX_HIP(hipMemcpyAsync(out_count, c->d_out_count.ptr, size_t(nq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
 	RX_HIP(hipStreamSynchronize(c->stream));
-	if (h->profiling && nq == 1 && c->pruned_cap) {
+	const bool kept = c->keep_values;
+	c->keep_values = false;
+	if (h->profiling && nq == 1 && c->pruned_cap && (kept || !c->pruned_emit_gridx)) {
 		uint32_t cnt = 0;
 		RX_HIP(hipMemcpy(&cnt, c->d_cand_cnt.ptr, sizeof(cnt), hipMemcpyDeviceToHost));
 		h->last_cand_count = cnt;
 		h->last_cand_cap = c->pruned_cap;
 		// rxgpu_index_inspect reads the chain's buffers out of this context later.  The exact scan behind the gate writes the part buffers
-		// and the result only (launch_scan / launch_scan_subset, launch_merge_lists), never d_dense, d_top, d_qstats, d_qplanes or d_cand_row.
+		// and the result only (launch_scan / launch_scan_subset, launch_merge_final), never d_dense, d_emit, d_emit_cnt, d_top, d_qstats, d_qplanes or d_cand_row.
 		std::lock_guard<std::mutex> lk(h->mtx);
 		h->last_pruned_ctx = c;
 		h->last_pruned_n = c->pruned_n;
 		h->last_pruned_kk = c->pruned_kk;
 		h->last_pruned_ld = c->pruned_ld;
 		h->last_pruned_i8 = c->pruned_i8;
+		h->last_pruned_emit_gridx = c->pruned_emit_gridx;
 	} else if (h->profiling) {   // another chain answered: whatever context it ran in may be the recorded one
 		std::lock_guard<std::mutex> lk(h->mtx);
 		h->last_pruned_ctx = nullptr;
@@ -611,11 +651,14 @@ int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries
 		if (int rc = c->d_out_row.ensure(size_t(nq) * eff * sizeof(uint32_t)); rc) return rc;
 		if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
 		c->pruned_cap = 0;   // set by a pruned chain
+		c->keep_values = h->profiling && nq == 1;   // what copy_back_knn records (it clears the flag)
 		if (int rc = enqueue_knn_subset(h, c, static_cast<const float*>(c->d_queries.ptr), nq, eff, d_ids, n_ids,
 										static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr),
 										static_cast<uint32_t*>(c->d_out_count.ptr));
-			rc)
+			rc) {
+			c->keep_values = false;
 			return rc;
+		}
 		return copy_back_knn(h, c, nq, kk, eff, out_dist, out_row, out_count);
 	}
 	// large k: distances of the listed rows + radix select over (dist, position); positions -> rows; final sort of eff entries on the host

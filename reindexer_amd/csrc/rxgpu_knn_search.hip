@@ -185,10 +185,13 @@ int rxgpu_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t
 		// kk <= 64: fused / batched / pruned dispatch; 64 < kk <= 128 (e.g. hybrid k = 100): the fused scan with two list entries per lane
 		auto* run = eff <= uint32_t(rxgpu::kMaxFusedK) ? enqueue_knn : enqueue_knn_fused;
 		c->pruned_cap = 0;   // set by a pruned chain
+		c->keep_values = h->profiling && nq == 1;   // what copy_back_knn records (it clears the flag)
 		if (int rc = run(h, c, static_cast<const float*>(c->d_queries.ptr), nq, eff, static_cast<float*>(c->d_out_dist.ptr),
 						 static_cast<uint32_t*>(c->d_out_row.ptr), static_cast<uint32_t*>(c->d_out_count.ptr));
-			rc)
+			rc) {
+			c->keep_values = false;
 			return rc;
+		}
 		return rxgpu::copy_back_knn(h, c, nq, kk, eff, out_dist, out_row, out_count);
 	}
 
