@@ -173,8 +173,9 @@ int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_avail
  * either tier. */
 int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite);
 /* Candidates the last pruned single-query search through rxgpu_search_knn (or rxgpu_search_knn_subset / _bitmap / _lists) nominated for the exact re-score, and the capacity of their list
- * (count > cap: the list overflowed, or the query had no finite bound, and the exact scan answered).  Recorded only while profiling is
- * enabled (rxgpu_profile_enable). */
+ * (count > cap: the list overflowed, or the query had no finite bound, and the exact scan answered).  A range call the int8 tier served
+ * (rxgpu_scan_tier_range) records its candidates and the size of its list the same way.  Recorded only while profiling is enabled
+ * (rxgpu_profile_enable). */
 int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap);
 /* Test instrumentation: copies a named internal buffer of a single-device index to the host.  Reads only - nothing is built, invalidated or
  * changed.  *out_bytes is always set to the size needed; RXGPU_ERR_OVERFLOW when cap_bytes is smaller (out may be NULL then),
@@ -241,8 +242,8 @@ int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t k
  *   128 lists the coarse result never leaves HBM, wider probes fetch the nprobe list ids and send them back.  *out_scanned (optional)
  *   = rows in the probed lists.  Output as rxgpu_search_knn for nq = 1.
  * rxgpu_search_range_lists: IndexIVFFlat::range_search (ivf_index.cc:212-272 drives it) over the same device lists — probed lists ->
- *   row list on the device -> the range kernel of rxgpu_search_range_subset; output, overflow protocol and ordering as
- *   rxgpu_search_range_subset. */
+ *   row list on the device -> the range kernels of rxgpu_search_range_subset (the int8-pruned one where rxgpu_scan_tier_range says so
+ *   for the rows of the probed lists); output, overflow protocol and ordering as rxgpu_search_range_subset. */
 int rxgpu_index_set_lists(rxgpu_index* h, uint32_t nlist, const uint64_t* list_off, const uint32_t* list_rows);
 int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, uint32_t kk, float* out_dist,
 						   uint32_t* out_row, uint32_t* out_count, uint64_t* out_scanned);
@@ -261,6 +262,9 @@ int rxgpu_check_row_list_device(rxgpu_index* h, const void* d_row_ids, uint64_t 
  * `inclusive`), sorted by (dist, row); *out_total = number of hits; RXGPU_ERR_OVERFLOW when it exceeds `cap` (call again with
  * cap >= *out_total).  Stands in for the list scan of faiss::IndexIVFFlat::range_search as the reference's IvfIndex calls it
  * (ivf_index.cc:212-272) — the probed inverted lists are the row list. */
+/* Which kernel reads the rows: the f32 gather kernel (knn_range_subset) unless rxgpu_scan_tier_range(n_ids, dim, 1, ...) says 2; then the
+ * int8 shadow is read for the listed rows and the exact kernel re-scores the rows its bound cannot exclude - the same total, rows and
+ * distance bits (see rxgpu_search_range). */
 int rxgpu_search_range_subset(rxgpu_index* h, const float* query, float radius, int inclusive, const uint32_t* row_ids, uint64_t n_ids,
 							  float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total);
 
@@ -274,9 +278,26 @@ int rxgpu_merge_shards_device(const void* d_gathered, uint32_t world, uint32_t n
 
 /* BruteforceSearch::SearchRange (bruteforce.cc:129-143): every row with dist < radius (inclusive != 0: dist <= radius;
  * the inclusive form serves the tie replay above).  Rows are returned sorted by (dist,row); *out_total receives the
- * number of hits; at most cap are written; RXGPU_ERR_OVERFLOW if out_total > cap (call again with a larger buffer). */
+ * number of hits; at most cap are written; RXGPU_ERR_OVERFLOW if out_total > cap (call again with a larger buffer).
+ *
+ * Which kernel reads the rows: the f32 kernel (knn_range) unless rxgpu_scan_tier_range() says 2 for the call.  Then the int8 shadow of
+ * rxgpu_scan_tier is scanned (1 byte per element instead of 4; the first such call on an index builds it): a row can be a hit only if the
+ * lower bound of its distance is within the query's margin of the radius, those rows are collected in a candidate list of
+ * min(rows, max(4096, 2 min(cap, rows))) entries, and the exact kernel re-scores them and applies the real test - the same *out_total, rows,
+ * distance bits and overflow protocol.  More candidates than the list holds (a boundary zone that full, a radius of +inf), a query or an
+ * index without a finite bound, or no room for the shadow: the f32 kernel answers the call. */
 int rxgpu_search_range(rxgpu_index* h, const float* query, float radius, int inclusive, float* out_dist, uint32_t* out_row,
 					   uint64_t cap, uint64_t* out_total);
+/* Which kernel a range call takes (rxgpu_search_range, rxgpu_search_range_subset, rxgpu_search_range_lists and their per-shard calls): 0
+ * the f32 range kernel, 2 the int8-pruned one (no device is touched; there is no bf16 form).  rows = the rows scanned: the index's, or the
+ * entries of the list when `listed`.  0 whenever RXGPU_SCAN_BF16 is 0 or 1, RXGPU_SCAN_I8 is 0, the shadow is not available, the
+ * dimension is outside 128 < dim <= 1024 or there are no rows.  Otherwise RXGPU_SCAN_I8=1 forces 2 at any size, and the automatic rule
+ * (RXGPU_SCAN_I8 unset) gives 2 on an index without a NaN / infinite row norm when the scanned rows hold at least
+ * RXGPU_SCAN_I8_RANGE_MIN_BYTES of f32 data (rows * dim * 4; default 16 GiB, the measured size from which the tier wins whatever the
+ * number of hits, profiles/range_i8_ab.json) - and, for a list, at least RXGPU_SCAN_I8_SUBSET_MIN_BYTES as well, whose default is still
+ * the maximum value: a list call takes the tier only where that variable or RXGPU_SCAN_I8=1 asks for it.  The environment is read per
+ * call. */
+int rxgpu_scan_tier_range(uint64_t rows, uint32_t dim, int listed, int shadow_available, int stats_finite);
 
 /* Distances of one query against an explicit list of rows (DistCalculator::operator()(q,row,id), hnswlib.h:147-165);
  * used for exact re-scoring and by tests. */

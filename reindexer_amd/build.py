@@ -136,6 +136,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "knn_i8_quant.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-ffp-contract=off", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # the range bound of the int8 shadow tier compiled for the host (CPU check of the threshold knn_range_i8 compares against)
+    src = tdir / "knn_i8_range_cpu.cc"
+    if src.exists():
+        out = tdir / "libknn_i8_range_cpu.so"
+        if force or _stale(out, [src, CSRC / "knn_i8_quant.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-ffp-contract=off", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     # the segment layout of the emitting int8 scan as a stand-alone program (CPU check of the plan knn_scan_i8 and knn_filter_emitted share)
     src = tdir / "knn_emit_plan_cpu.cc"
     if src.exists():

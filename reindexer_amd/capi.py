@@ -66,6 +66,7 @@ _SIGNATURES = {
     "rxgpu_scan_policy": (_i, [_u64, _u32, _u32, _i, _i]),
     "rxgpu_scan_tier": (_i, [_u64, _u32, _u32, _i, _i]),
     "rxgpu_scan_tier_subset": (_i, [_u64, _u32, _u32, _u32, _i, _i]),
+    "rxgpu_scan_tier_range": (_i, [_u64, _u32, _i, _i, _i]),
     "rxgpu_index_last_candidates": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "rxgpu_index_inspect": (_i, [_vp, C.c_char_p, _vp, _u64, C.POINTER(_u64)]),
     "rxgpu_search_knn_subset": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
@@ -203,6 +204,12 @@ def scan_policy(rows: int, dim: int, nq: int = 1, shadow_available: bool = True,
 def scan_tier(rows: int, dim: int, nq: int = 1, shadow_available: bool = True, stats_finite: bool = True) -> int:
     """rxgpu_scan_tier: 0 / 1 / 2 = such a call takes the f32 / bf16-pruned / int8-pruned scan under the current environment.  Touches no device."""
     return int(lib().rxgpu_scan_tier(rows, dim, nq, int(shadow_available), int(stats_finite)))
+
+
+def scan_tier_range(rows: int, dim: int, listed: bool = False, shadow_available: bool = True, stats_finite: bool = True) -> int:
+    """rxgpu_scan_tier_range: 0 / 2 = a range call that scans `rows` rows (the index's, or the entries of a row list when `listed`) takes the
+    f32 / int8-pruned range kernel under the current environment.  Touches no device."""
+    return int(lib().rxgpu_scan_tier_range(rows, dim, int(listed), int(shadow_available), int(stats_finite)))
 
 
 def scan_tier_subset(n_ids: int, dim: int, nq: int = 1, kk: int = 10, shadow_available: bool = True, stats_finite: bool = True) -> int:

@@ -23,6 +23,16 @@
 // top-kk.  With T = the kk-th smallest up_r, delta = the f32 error of the exact kernels' own distances (half of f32_query_margin) and D_kk
 // the kk-th best exact distance: kk rows have d <= up + G + delta <= T + G + delta, so D_kk <= T + G + delta, and every row of the true
 // top-kk has lo_r <= d_r + G + delta <= T + 2 G + 2 delta.  knn_filter_approx therefore runs over the lo_r with margin = 2 delta + 2 G.
+//
+// Range search (knn_range_i8 in knn_scan_i8.hip, i8_range_bound below).  A row is a hit when the exact kernels' f32 distance d_r satisfies
+// d_r < radius (or <=), so a hit has, as real numbers, lo_r <= d_r + G + delta <= radius + G + delta = radius + margin / 2: half of the
+// margin the query prep writes is spare.  The kernel compares against t = fl(radius + margin), moved one float outward.  The f32 rounding of that
+// sum cannot eat the spare half, however large |radius| is against the margin: lo_r is itself an f32 and rounding to nearest is monotone, so
+// lo_r <= radius + margin / 2 <= radius + margin (margin >= 0) gives lo_r = fl(lo_r) <= fl(radius + margin) <= t.  (Where ulp(radius)
+// exceeds the margin the sum rounds back to radius, and a float lo_r <= radius + margin / 2 < the float above radius is <= radius as well.)
+// The outward step is not needed for this; it covers a sum evaluated in another rounding mode.  A NaN radius gives t = NaN, which no row
+// passes, and the f32 kernel finds no hit either; a margin that is not finite means there is no bound: t = +inf, every row passes (the
+// query prep has set cand_cnt = cap + 1 for such a query and the kernel emits nothing: the f32 kernel answers the call).
 #pragma once
 
 #include <cmath>
@@ -123,6 +133,26 @@ template <int kMetric>
 RX_I8_HD inline float i8_margin(float s, uint32_t dim, float qn_up, float rq_up, float xmax2, float xcmax2, float emax2, float ecmax2) {
 	const float g = kMetric == kI8Cos ? i8_margin_global(kMetric, qn_up, rq_up, xcmax2, ecmax2) : i8_margin_global(kMetric, qn_up, rq_up, xmax2, emax2);
 	return (f32_query_margin<kMetric, false>(s, dim, xmax2, xcmax2) + 2.0f * g) * 1.0001f;
+}
+
+// The threshold of a range scan: every row whose exact-kernel distance is <= radius has lo_r <= i8_range_bound(radius, margin), with margin
+// = i8_margin of the query (the argument is in the file header).  NaN radius: NaN (no row passes); no finite margin: +inf (no bound).
+RX_I8_HD inline float i8_range_bound(float radius, float margin) {
+	if (!(radius == radius)) return radius;
+	if (!(margin < HUGE_VALF)) return HUGE_VALF;
+	float t = radius + margin;
+	if (!(::fabsf(t) < HUGE_VALF)) return t;   // +-inf stays
+	uint32_t b;
+	__builtin_memcpy(&b, &t, sizeof(b));
+	if (t > 0.0f) {
+		++b;   // the next float up (the largest finite one becomes +inf)
+	} else if (t < 0.0f) {
+		--b;   // towards zero
+	} else {
+		b = 1u;   // +-0: the smallest positive subnormal
+	}
+	__builtin_memcpy(&t, &b, sizeof(b));
+	return t;
 }
 
 RX_I8_HD inline float i8_ip(float s_q, float s_r, int32_t S) { return (s_q * s_r) * float(S); }

@@ -93,6 +93,16 @@ struct ScanI8Emit {
 	EmitPlan plan;            // emit_plan(n, gridDim.x)
 };
 
+// ... and what its range forms (knn_range_i8, knn_range_i8_subset: one query) take instead of the top lists: the radius, and where the rows
+// whose lower bound is within the query's margin of it are compacted
+struct RangeI8Cand {
+	float radius;
+	const float* margin;      // [1] the query's margin (knn_query_prep_i8); not finite: nothing is emitted
+	uint32_t* cand_cnt;       // [1] counts every candidate, past ccap too (the prep has set it to 0, or to ccap + 1: no finite bound)
+	uint32_t* cand_row;       // [ccap] rows, written while the position is below ccap
+	uint32_t ccap;
+};
+
 enum : int { kGemmDense = 0, kGemmFilter = 1 };
 
 struct GemmParams {

@@ -984,6 +984,42 @@ __global__ __launch_bounds__(kScanThreads) void knn_range_subset(RangeParams p, 
 	}
 }
 
+// The exact tail of the int8 range forms (knn_range_i8 / knn_range_i8_subset in knn_scan_i8.hip): knn_range_subset over the candidate rows,
+// their number read on the device.  More candidates than the list holds (or no finite bound: the query prep left ccap + 1): nothing is done,
+// the host launches the f32 kernel.  The distance is knn_range's (the same two functions over the same query), so are the test and the
+// counter protocol: p.counter counts every hit, the first p.cap are written.
+template <int kMetric>
+__global__ __launch_bounds__(kScanThreads) void knn_range_rescore(RangeParams p, const uint32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ cand_row,
+																   uint32_t ccap) {
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
+	const uint32_t have = *cand_cnt;
+	if (have > ccap || have == 0) return;
+	const uint64_t n = have;
+	const uint64_t nquads = (n + kRowsPerWave - 1) / kRowsPerWave;
+	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
+	for (uint64_t quad = uint64_t(blockIdx.x) * kScanWaves + wave; quad < nquads; quad += nwaves) {
+		const uint64_t item = quad * kRowsPerWave + g;
+		const bool valid = item < n;
+		const uint64_t row = cand_row[valid ? item : n - 1];
+		const float sum = group_distance_generic<kMetric>(p.rows + row * p.stride, p.query, p.dim, m);
+		const float dist = metric_epilogue<kMetric>(sum, p.inv_norms, row);
+		const bool hit = valid && m == 0 && (p.inclusive ? dist <= p.radius : dist < p.radius);
+		const uint64_t hm = __ballot(hit);
+		if (hm) {
+			unsigned long long basePos = 0;
+			if (lane == 0) basePos = atomicAdd(p.counter, (unsigned long long)__popcll(hm));
+			basePos = __shfl(basePos, 0);
+			if (hit) {
+				const uint64_t pos = basePos + __popcll(hm & ((1ull << lane) - 1));
+				if (pos < p.cap) {
+					p.out_dist[pos] = dist;
+					p.out_row[pos] = uint32_t(row);
+				}
+			}
+		}
+	}
+}
+
 // DistCalculator::operator()(q,row,id) for an explicit row list: one 16-lane group per row.
 template <int kMetric>
 __global__ __launch_bounds__(256) void knn_distances(const float* rows, const float* inv_norms, const float* query, uint32_t stride,
@@ -1261,6 +1297,18 @@ void launch_range_subset(int metric, const float* rows, const float* inv_norms, 
 		case kL2: hipLaunchKernelGGL((knn_range_subset<kL2>), dim3(gridx), dim3(kScanThreads), 0, s, p, ids); break;
 		case kIP: hipLaunchKernelGGL((knn_range_subset<kIP>), dim3(gridx), dim3(kScanThreads), 0, s, p, ids); break;
 		default: hipLaunchKernelGGL((knn_range_subset<kCos>), dim3(gridx), dim3(kScanThreads), 0, s, p, ids); break;
+	}
+}
+
+// cand_cnt / cand_row / ccap: what knn_range_i8 left; the grid covers ccap candidates
+void launch_range_rescore(int metric, const float* rows, const float* inv_norms, const float* query, const uint32_t* cand_cnt, const uint32_t* cand_row,
+						  uint32_t ccap, uint32_t stride, uint32_t dim, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
+						  unsigned long long* counter, uint32_t gridx, hipStream_t s) {
+	RangeParams p{rows, inv_norms, query, 0, stride, dim, radius, inclusive, out_dist, out_row, cap, counter};
+	switch (metric) {
+		case kL2: hipLaunchKernelGGL((knn_range_rescore<kL2>), dim3(gridx), dim3(kScanThreads), 0, s, p, cand_cnt, cand_row, ccap); break;
+		case kIP: hipLaunchKernelGGL((knn_range_rescore<kIP>), dim3(gridx), dim3(kScanThreads), 0, s, p, cand_cnt, cand_row, ccap); break;
+		default: hipLaunchKernelGGL((knn_range_rescore<kCos>), dim3(gridx), dim3(kScanThreads), 0, s, p, cand_cnt, cand_row, ccap); break;
 	}
 }
 

@@ -310,6 +310,187 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8_subset(ScanI8Params 
 	block_merge_and_store(top, p.sp, lane, wave);
 }
 
+// ---- the range forms (BruteforceSearch::SearchRange from the shadow; enqueue_range_pruned_i8 in rxgpu_knn_chains.hip): one query, no top lists.
+// A row can be a hit of the exact kernels only if lo_r <= i8_range_bound(radius, margin) (knn_i8_quant.h); those rows are compacted into
+// c.cand_row the way knn_range compacts its hits (ballot, one atomicAdd per wavefront step that has any, prefix popcount), and
+// knn_range_rescore (knn_scan.hip) holds them against the radius with the exact distance.  The counter counts past c.ccap: the host then
+// hands the call to the f32 kernel.  Lane mapping, loads, double buffer and butterfly are knn_scan_i8's, kept apart from it (that kernel is
+// the headline's and stays as measured); what is gone is everything the top lists needed.
+template <int kMetric, int NC8>
+__global__ __launch_bounds__(kScanThreads) void knn_range_i8(ScanI8Params p, RangeI8Cand c) {
+	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	u32x4 qh[NC8], ql[NC8];
+	{
+		const u32x4* ph = reinterpret_cast<const u32x4*>(p.planes);
+#pragma unroll
+		for (int t = 0; t < NC8; ++t) {
+			qh[t] = ph[m + 16 * t];
+			ql[t] = ph[16 * NC8 + m + 16 * t];
+		}
+	}
+	const float2 qinfo = p.qinfo[0];   // {s_q, |q| rounded up}
+	float qq = 0.f;
+	if constexpr (kMetric == kL2) qq = p.q_sq[0];
+	const float margin = c.margin[0];
+	const float bound = i8_range_bound(c.radius, margin);   // wave-uniform
+	const bool bounded = margin < __builtin_inff();
+	const uint64_t n = p.sp.n;
+	const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
+	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
+	const uint64_t first = uint64_t(blockIdx.x) * kScanWaves + wave;
+
+	struct Buf {
+		u32x4 x[kI8RowsPerGroup * NC8];
+		float2 side;
+		float aux;
+	};
+	auto issue = [&](Buf& b, uint64_t set) {
+		const uint64_t sc = set < nsets ? set : nsets - 1;   // past the end: re-read the last set (never reduced)
+		const uint64_t r0 = sc * kI8RowsPerWave + uint64_t(g) * kI8RowsPerGroup;
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			uint64_t row = r0 + j;
+			row = row < n ? row : n - 1;
+			const u32x4* src = reinterpret_cast<const u32x4*>(p.codes + row * p.ld8) + m;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) b.x[j * NC8 + t] = __builtin_nontemporal_load(src + 16 * t);
+		}
+		uint64_t mine = r0 + (m & 3);
+		mine = mine < n ? mine : n - 1;
+		b.side = p.side[mine];
+		if constexpr (kMetric == kL2) b.aux = p.row_sq[mine];
+		if constexpr (kMetric == kCos) b.aux = p.sp.inv_norms[mine];
+		if constexpr (kMetric == kIP) b.aux = 0.f;
+	};
+	auto reduce = [&](const Buf& b, uint64_t set) {
+		if (set >= nsets) return;   // wave-uniform
+		int v[kI8RowsPerGroup];
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			int hs = 0, ls = 0;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) {
+				hs = i8_dot16(qh[t], b.x[j * NC8 + t], hs);
+				ls = i8_dot16(ql[t], b.x[j * NC8 + t], ls);
+			}
+			v[j] = hs * 128 + ls;
+		}
+		const bool b0 = (m & 1) != 0, b1 = (m & 2) != 0;   // knn_scan_i8's transposing butterfly
+		const int a0 = (b0 ? v[1] : v[0]) + __shfl_xor(b0 ? v[0] : v[1], 1);
+		const int a1 = (b0 ? v[3] : v[2]) + __shfl_xor(b0 ? v[2] : v[3], 1);
+		int s = (b1 ? a1 : a0) + __shfl_xor(b1 ? a0 : a1, 2);
+		s += __shfl_xor(s, 4);
+		s += __shfl_xor(s, 8);
+		const uint64_t row = set * kI8RowsPerWave + uint64_t(g) * kI8RowsPerGroup + (m & 3);
+		const bool valid = row < n && m < kI8RowsPerGroup;
+		float lo, up;
+		i8_bounds(kMetric, i8_ip(qinfo.x, b.side.x, s), qinfo.y, b.side.y, qq, b.aux, lo, up);
+		const bool em = valid && bounded && lo <= bound;   // (a NaN lo or bound: no candidate)
+		const uint64_t emask = __ballot(em);
+		if (emask) {
+			uint32_t base = 0;
+			if (lane == 0) base = atomicAdd(c.cand_cnt, uint32_t(__popcll(emask)));
+			base = __shfl(base, 0);
+			if (em) {
+				const uint64_t pos = uint64_t(base) + uint32_t(__popcll(emask & ((1ull << lane) - 1)));
+				if (pos < c.ccap) c.cand_row[pos] = uint32_t(row);
+			}
+		}
+	};
+	if (first < nsets) {
+		Buf xa, xb;
+		issue(xa, first);
+		for (uint64_t set = first; set < nsets; set += 2 * nwaves) {
+			issue(xb, set + nwaves);
+			__builtin_amdgcn_sched_barrier(0);
+			reduce(xa, set);
+			__builtin_amdgcn_sched_barrier(0);
+			issue(xa, set + 2 * nwaves);
+			__builtin_amdgcn_sched_barrier(0);
+			reduce(xb, set + nwaves);
+			__builtin_amdgcn_sched_barrier(0);
+		}
+	}
+}
+
+// The gather form over a strictly increasing row list (p.sp.n entries, trusted as knn_scan_i8_subset trusts them): one set of 16 entries per
+// wavefront step, as that kernel's !kChunked form; the candidate written is the real row.  Entries past the end of the list are clamped to
+// its last entry and never reduced or emitted.
+template <int kMetric, int NC8>
+__global__ __launch_bounds__(kScanThreads) void knn_range_i8_subset(ScanI8Params p, RangeI8Cand c, const uint32_t* __restrict__ ids) {
+	const int lane = threadIdx.x & 63, m = lane & 15, g = lane >> 4;
+	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	u32x4 qh[NC8], ql[NC8];
+	{
+		const u32x4* ph = reinterpret_cast<const u32x4*>(p.planes);
+#pragma unroll
+		for (int t = 0; t < NC8; ++t) {
+			qh[t] = ph[m + 16 * t];
+			ql[t] = ph[16 * NC8 + m + 16 * t];
+		}
+	}
+	const float2 qinfo = p.qinfo[0];
+	float qq = 0.f;
+	if constexpr (kMetric == kL2) qq = p.q_sq[0];
+	const float margin = c.margin[0];
+	const float bound = i8_range_bound(c.radius, margin);
+	const bool bounded = margin < __builtin_inff();
+	const uint64_t n = p.sp.n;   // list entries
+	const uint64_t nsets = (n + kI8RowsPerWave - 1) / kI8RowsPerWave;
+	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
+	for (uint64_t set = uint64_t(blockIdx.x) * kScanWaves + wave; set < nsets; set += nwaves) {
+		const uint64_t item = set * kI8RowsPerWave + m;
+		const uint32_t idv = ids[item < n ? item : n - 1];   // the ids of the step's 16 entries in lanes 0 .. 15
+		const int l0 = g * kI8RowsPerGroup;
+		u32x4 x[kI8RowsPerGroup * NC8];
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			const uint64_t row = __shfl(idv, l0 + j);
+			const u32x4* src = reinterpret_cast<const u32x4*>(p.codes + row * p.ld8) + m;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) x[j * NC8 + t] = __builtin_nontemporal_load(src + 16 * t);
+		}
+		const uint32_t mine = __shfl(idv, l0 + (m & 3));   // the row of entry (m & 3) of this group's four
+		const float2 side = p.side[mine];
+		float aux = 0.f;
+		if constexpr (kMetric == kL2) aux = p.row_sq[mine];
+		if constexpr (kMetric == kCos) aux = p.sp.inv_norms[mine];
+		int v[kI8RowsPerGroup];
+#pragma unroll
+		for (int j = 0; j < kI8RowsPerGroup; ++j) {
+			int hs = 0, ls = 0;
+#pragma unroll
+			for (int t = 0; t < NC8; ++t) {
+				hs = i8_dot16(qh[t], x[j * NC8 + t], hs);
+				ls = i8_dot16(ql[t], x[j * NC8 + t], ls);
+			}
+			v[j] = hs * 128 + ls;
+		}
+		const bool b0 = (m & 1) != 0, b1 = (m & 2) != 0;   // knn_scan_i8's transposing butterfly
+		const int a0 = (b0 ? v[1] : v[0]) + __shfl_xor(b0 ? v[0] : v[1], 1);
+		const int a1 = (b0 ? v[3] : v[2]) + __shfl_xor(b0 ? v[2] : v[3], 1);
+		int s = (b1 ? a1 : a0) + __shfl_xor(b1 ? a0 : a1, 2);
+		s += __shfl_xor(s, 4);
+		s += __shfl_xor(s, 8);
+		const uint64_t pos = set * kI8RowsPerWave + uint64_t(g) * kI8RowsPerGroup + (m & 3);
+		const bool valid = pos < n && m < kI8RowsPerGroup;
+		float lo, up;
+		i8_bounds(kMetric, i8_ip(qinfo.x, side.x, s), qinfo.y, side.y, qq, aux, lo, up);
+		const bool em = valid && bounded && lo <= bound;
+		const uint64_t emask = __ballot(em);
+		if (emask) {
+			uint32_t base = 0;
+			if (lane == 0) base = atomicAdd(c.cand_cnt, uint32_t(__popcll(emask)));
+			base = __shfl(base, 0);
+			if (em) {
+				const uint64_t at = uint64_t(base) + uint32_t(__popcll(emask & ((1ull << lane) - 1)));
+				if (at < c.ccap) c.cand_row[at] = mine;
+			}
+		}
+	}
+}
+
 // ---- the shadow: codes [n][ld8] (zero pad) and the side pair {s_r, e_r} per row, from the f32 rows (16-byte aligned, stride a multiple of 4
 // floats, as the index keeps them).  One 16-lane group per row, lane m quantises the 16-element chunks m, m + 16, ... (read twice: the scale
 // first); the residual is an fp64 sum over the codes as stored.  Folds max e^2 into stats[3], max
@@ -491,6 +672,42 @@ void launch_scan_i8_subset(int metric, const ScanI8Params& p, const uint32_t* id
 		launch_scan_i8_subset_form<true>(metric, p, ids, grid, s);
 	} else {
 		launch_scan_i8_subset_form<false>(metric, p, ids, grid, s);
+	}
+}
+
+template <int kMetric>
+static void launch_range_i8_metric(const ScanI8Params& p, const RangeI8Cand& c, const uint32_t* ids, dim3 grid, hipStream_t s) {
+	if (ids) {
+		switch (p.ld8 / 256) {
+			case 1: hipLaunchKernelGGL((knn_range_i8_subset<kMetric, 1>), grid, dim3(kScanThreads), 0, s, p, c, ids); break;
+			case 2: hipLaunchKernelGGL((knn_range_i8_subset<kMetric, 2>), grid, dim3(kScanThreads), 0, s, p, c, ids); break;
+			case 3: hipLaunchKernelGGL((knn_range_i8_subset<kMetric, 3>), grid, dim3(kScanThreads), 0, s, p, c, ids); break;
+			default: hipLaunchKernelGGL((knn_range_i8_subset<kMetric, 4>), grid, dim3(kScanThreads), 0, s, p, c, ids); break;
+		}
+		return;
+	}
+	switch (p.ld8 / 256) {
+		case 1: hipLaunchKernelGGL((knn_range_i8<kMetric, 1>), grid, dim3(kScanThreads), 0, s, p, c); break;
+		case 2: hipLaunchKernelGGL((knn_range_i8<kMetric, 2>), grid, dim3(kScanThreads), 0, s, p, c); break;
+		case 3: hipLaunchKernelGGL((knn_range_i8<kMetric, 3>), grid, dim3(kScanThreads), 0, s, p, c); break;
+		default: hipLaunchKernelGGL((knn_range_i8<kMetric, 4>), grid, dim3(kScanThreads), 0, s, p, c); break;
+	}
+}
+// The range forms, one query: p.sp.n rows (ids null) or list entries (>= 1), p.ld8 as for launch_scan_i8; p.lower and the part buffers are not
+// touched.  The grid is sized here: scan_i8_grid_x for the whole index, one set of 16 entries per wavefront step over a list.
+void launch_range_i8(int metric, const ScanI8Params& p, const RangeI8Cand& c, const uint32_t* ids, int cus, hipStream_t s) {
+	uint32_t gridx = scan_i8_grid_x(p.sp.n, cus);
+	if (ids) {
+		const uint64_t nsets = (p.sp.n + kI8RowsPerWave - 1) / kI8RowsPerWave;
+		const uint64_t want = (nsets + kScanWaves - 1) / kScanWaves;
+		const uint64_t cap = uint64_t(cus) * scan_i8_wg_per_cu();   // as scan_i8_subset_grid_x sizes the one-set-per-step form
+		gridx = uint32_t(want < cap ? (want ? want : 1) : cap);
+	}
+	const dim3 grid(gridx);
+	switch (metric) {
+		case kL2: launch_range_i8_metric<kL2>(p, c, ids, grid, s); break;
+		case kIP: launch_range_i8_metric<kIP>(p, c, ids, grid, s); break;
+		default: launch_range_i8_metric<kCos>(p, c, ids, grid, s); break;
 	}
 }
 

@@ -258,6 +258,10 @@ int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t k
 	return int(rxgpu::scan_policy_tier_subset(n_ids, dim, nq, kk, shadow_available != 0, stats_finite != 0));
 }
 
+int rxgpu_scan_tier_range(uint64_t rows, uint32_t dim, int listed, int shadow_available, int stats_finite) {
+	return int(rxgpu::scan_policy_tier_range(rows, dim, listed != 0, shadow_available != 0, stats_finite != 0));
+}
+
 int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint32_t* out_cap) {
 	RX_CHECK(h && out_count && out_cap, RXGPU_ERR_PARAMS, "rxgpu_index_last_candidates: null argument");
 	*out_count = h->last_cand_count.load();

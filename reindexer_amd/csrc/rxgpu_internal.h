@@ -64,6 +64,13 @@ void launch_range_subset(int metric, const float* rows, const float* inv_norms, 
 						 unsigned long long* counter, uint32_t gridx, hipStream_t s);
 void launch_distances(int metric, const float* rows, const float* inv_norms, const float* query, uint32_t stride, uint32_t dim,
 					  const uint32_t* ids, uint32_t n, float* out, hipStream_t s);
+// range search from the int8 shadow, one query: the pruning scan (knn_scan_i8.hip; ids null = every row, else p.sp.n list entries) and its exact
+// tail over the candidates it left (knn_scan.hip), which does nothing when there are more than ccap
+struct RangeI8Cand;
+void launch_range_i8(int metric, const ScanI8Params& p, const RangeI8Cand& c, const uint32_t* ids, int cus, hipStream_t s);
+void launch_range_rescore(int metric, const float* rows, const float* inv_norms, const float* query, const uint32_t* cand_cnt, const uint32_t* cand_row,
+						  uint32_t ccap, uint32_t stride, uint32_t dim, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
+						  unsigned long long* counter, uint32_t gridx, hipStream_t s);
 
 // Pre-filtered search (knn_scan.hip: knn_scan_subset; knn_subset.hip: bitmap -> row list)
 uint32_t subset_grid_x(uint64_t n_ids, uint32_t dim, uint32_t kk, int cus);
@@ -666,9 +673,15 @@ int search_subset_host(rxgpu_index* h, rxgpu_search_ctx* c, const float* queries
 					   float* out_dist, uint32_t* out_row, uint32_t* out_count);   // ... queries and results on the host, any kk
 int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk, uint32_t eff, float* out_dist, uint32_t* out_row, uint32_t* out_count);
 void sort_dist_row(const std::vector<float>& hd, const std::vector<uint32_t>& hr, float* out_dist, uint32_t* out_row);   // by dist_row_less (shard_plan.h)
-// the scan policy, without a device (rxgpu_scan_policy, rxgpu_scan_tier, rxgpu_scan_tier_subset)
+// the scan policy, without a device (rxgpu_scan_policy, rxgpu_scan_tier, rxgpu_scan_tier_subset, rxgpu_scan_tier_range)
 enum ScanTier { kTierF32 = 0, kTierBf16 = 1, kTierI8 = 2 };
 bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite);
 ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool bf16_available, bool i8_available, bool stats_finite);
 ScanTier scan_policy_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, bool i8_available, bool stats_finite);
+ScanTier scan_policy_tier_range(uint64_t rows, uint32_t dim, bool list, bool i8_available, bool stats_finite);   // rxgpu_scan_tier_range
+// The int8 front of a range call whose query lies in c->d_queries (d_ids null: every row, else n list entries in HBM) and whose counter
+// c->d_out_count is zero: query prep, pruning scan, exact tail into c->d_out_dist / d_out_row (dcap entries).  *ccap = the candidate list's
+// size; the caller reads c->d_cand_cnt back with the hit count, and more candidates than *ccap mean the tail did nothing.
+int enqueue_range_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const uint32_t* d_ids, uint64_t n, float radius, int inclusive, uint64_t cap, uint64_t dcap,
+							uint32_t* ccap);
 }  // namespace rxgpu

@@ -298,6 +298,17 @@ uint64_t pruned_i8_subset_auto_min_bytes() {
 	const char* e = getenv("RXGPU_SCAN_I8_SUBSET_MIN_BYTES");
 	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8SubsetAutoMinBytes;
 }
+// ... and for a RANGE call (scan_policy_tier_range).  kPrunedI8RangeAutoMinBytes is the measured crossover against the f32 range kernel
+// (tools/bench_range_i8.py, profiles/range_i8_ab.json: 10M .. 350k x 768, radii of 10 / 1 000 / 100 000 hits and the tie replay), rounded up to
+// a power of two and never below 1 GiB.  The tier wins every shape beyond the spread from 15.4 GB of f32 rows on (1.19 against 8.24 ms per
+// call at 10M x 768, 10 hits); below that it still wins the small results at every size measured (0.13 against 0.35 ms at 1 GiB) but only
+// ties at 100 000 hits, where the host-side sort of the hits is the call.  The rule asks for every shape: 2^34.  RXGPU_SCAN_I8_RANGE_MIN_BYTES
+// overrides it.
+constexpr uint64_t kPrunedI8RangeAutoMinBytes = 1ull << 34;
+uint64_t pruned_i8_range_auto_min_bytes() {
+	const char* e = getenv("RXGPU_SCAN_I8_RANGE_MIN_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8RangeAutoMinBytes;
+}
 
 }  // namespace
 
@@ -328,6 +339,20 @@ ScanTier scan_policy_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint
 	if (i8 == kScanBf16Off || !i8_available || !i8_dim_supported(dim) || kk > uint32_t(kMaxFusedK) || n_ids == 0) return kTierF32;
 	if (i8 == kScanBf16On) return nq <= kPrunedMaxQueries ? kTierI8 : kTierF32;   // without a finite bound the gate answers, as in the unfiltered tier
 	return nq == 1 && stats_finite && n_ids * dim * sizeof(float) >= pruned_i8_subset_auto_min_bytes() ? kTierI8 : kTierF32;
+}
+
+// The same decision for a RANGE call (one query; rxgpu_search_range, _subset, _lists and their per-shard calls): the f32 range kernel or the
+// int8-pruned one (knn_range_i8 / knn_range_i8_subset).  rows: the rows scanned, the index's or the entries of the list.  There is no bf16
+// form, so RXGPU_SCAN_BF16=1 keeps the f32 kernel like =0.  The automatic rule counts the f32 bytes of the scanned rows against
+// RXGPU_SCAN_I8_RANGE_MIN_BYTES, and a list call against RXGPU_SCAN_I8_SUBSET_MIN_BYTES as well, like a KNN search over a list.
+ScanTier scan_policy_tier_range(uint64_t rows, uint32_t dim, bool list, bool i8_available, bool stats_finite) {
+	if (scan_bf16_mode() != kScanBf16Auto) return kTierF32;
+	const ScanBf16Mode i8 = scan_i8_mode();
+	if (i8 == kScanBf16Off || !i8_available || !i8_dim_supported(dim) || rows == 0) return kTierF32;
+	if (i8 == kScanBf16On) return kTierI8;   // without a finite bound the f32 kernel answers behind the scan
+	const uint64_t bytes = rows * dim * sizeof(float);
+	if (!stats_finite || bytes < pruned_i8_range_auto_min_bytes()) return kTierF32;
+	return list && bytes < pruned_i8_subset_auto_min_bytes() ? kTierF32 : kTierI8;
 }
 
 namespace {
@@ -558,6 +583,58 @@ int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_qu
 }
 
 }  // namespace
+
+// Range search from the int8 shadow (declared in rxgpu_internal.h; the entry points and the f32 kernel behind it: rxgpu_knn_search.hip).  The
+// candidate list is sized from the caller's cap, never from a guess about the hits: min(n, max(kPrunedCap, 2 min(cap, n))), so a call whose
+// hits fit the caller's buffer fits the list too unless the boundary zone holds as many rows again as the buffer.
+int enqueue_range_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const uint32_t* d_ids, uint64_t n, float radius, int inclusive, uint64_t cap, uint64_t dcap,
+							uint32_t* ccap_out) {
+	if (int rc = ensure_i8_shadow(h, c->stream); rc) return rc;
+	const uint32_t ccap = uint32_t(std::min<uint64_t>(n, std::max<uint64_t>(kPrunedCap, 2 * std::min<uint64_t>(cap, n))));
+	const uint32_t ld = i8_ld(h->dim);
+	if (int rc = c->d_qpad.ensure(size_t(ld) * sizeof(float)); rc) return rc;
+	if (int rc = c->d_qplanes.ensure(size_t(2) * ld); rc) return rc;
+	if (int rc = c->d_qstats.ensure(4 * sizeof(float)); rc) return rc;
+	if (int rc = c->d_cand_row.ensure(size_t(ccap) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_cand_cnt.ensure(sizeof(uint32_t)); rc) return rc;
+	float* qstats = static_cast<float*>(c->d_qstats.ptr);   // {s_q, |q|^}, |q|^2, margin: the layout of the KNN chain's front
+	float* q_sq = qstats + 2;
+	float* margin = qstats + 3;
+	uint32_t* cand_cnt = static_cast<uint32_t*>(c->d_cand_cnt.ptr);
+	uint32_t* cand_row = static_cast<uint32_t*>(c->d_cand_row.ptr);
+	const float* query = static_cast<const float*>(c->d_queries.ptr);
+	launch_query_prep_i8(h->metric, query, 1, h->dim, static_cast<float*>(c->d_qpad.ptr), static_cast<int8_t*>(c->d_qplanes.ptr), ld, h->d_stats, q_sq, margin,
+						 reinterpret_cast<float2*>(qstats), cand_cnt, ccap, c->stream);
+	{
+		ProfileScope ps(h, d_ids ? "range_i8_subset" : "range_i8", c->stream);
+		ScanI8Params p{};
+		p.sp.inv_norms = h->d_inv_norms;
+		p.sp.n = n;
+		p.codes = h->d_codes_i8;
+		p.side = h->d_side_i8;
+		p.planes = static_cast<const int8_t*>(c->d_qplanes.ptr);
+		p.qinfo = reinterpret_cast<const float2*>(qstats);
+		p.row_sq = h->d_row_sq;
+		p.q_sq = q_sq;
+		p.ld8 = ld;
+		RangeI8Cand rc{};
+		rc.radius = radius;
+		rc.margin = margin;
+		rc.cand_cnt = cand_cnt;
+		rc.cand_row = cand_row;
+		rc.ccap = ccap;
+		launch_range_i8(h->metric, p, rc, d_ids, h->cus, c->stream);
+	}
+	{
+		ProfileScope ps(h, "range_rescore", c->stream);
+		launch_range_rescore(h->metric, h->d_rows, h->d_inv_norms, query, cand_cnt, cand_row, ccap, h->stride, h->dim, radius, inclusive,
+							 static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
+							 static_cast<unsigned long long*>(c->d_out_count.ptr), scan_grid_x(ccap, h->cus), c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	*ccap_out = ccap;
+	return RXGPU_OK;
+}
 
 // Pre-filtered search, kk <= kMaxFusedK2: gather-scan over the row list + the usual merge (rows in the lists are real rows, so the
 // merge and everything downstream is unchanged).  Where scan_policy_tier_subset says so, the int8-pruned chain above answers instead.

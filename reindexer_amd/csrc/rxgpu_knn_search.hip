@@ -70,13 +70,9 @@ int bitmap_to_row_list(rxgpu_index* h, rxgpu_search_ctx* c, const char* slot, bo
 	return RXGPU_OK;
 }
 
-// The tail of every range call, behind its launch: the hits were counted in c->d_out_count and the first min(hits, cap) written to
-// c->d_out_dist / d_out_row in any order.  More hits than cap: *out_total says how many, nothing is written.  Else sorted by (dist, row).
-int range_tail(rxgpu_search_ctx* c, float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total, const char* who) {
-	RX_HIP(hipGetLastError());
-	unsigned long long total = 0;
-	RX_HIP(hipMemcpyAsync(&total, c->d_out_count.ptr, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-	RX_HIP(hipStreamSynchronize(c->stream));
+// The end of every range call once the stream is idle and the hit count known: the first min(total, cap) hits lie in c->d_out_dist /
+// d_out_row in any order.  More hits than cap: *out_total says how many, nothing is written.  Else sorted by (dist, row).
+int range_finish(rxgpu_search_ctx* c, unsigned long long total, float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total, const char* who) {
 	*out_total = total;
 	if (total > cap) {
 		set_error(std::string(who) + ": output buffer too small");
@@ -89,6 +85,66 @@ int range_tail(rxgpu_search_ctx* c, float* out_dist, uint32_t* out_row, uint64_t
 	RX_HIP(hipMemcpy(hr.data(), c->d_out_row.ptr, total * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	rxgpu::sort_dist_row(hd, hr, out_dist, out_row);
 	return RXGPU_OK;
+}
+
+// The tail of a range call, behind its launch: the hits were counted in c->d_out_count.
+int range_tail(rxgpu_search_ctx* c, float* out_dist, uint32_t* out_row, uint64_t cap, uint64_t* out_total, const char* who) {
+	RX_HIP(hipGetLastError());
+	unsigned long long total = 0;
+	RX_HIP(hipMemcpyAsync(&total, c->d_out_count.ptr, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	return range_finish(c, total, out_dist, out_row, cap, out_total, who);
+}
+
+// One range search on the device, for both entry shapes: the query lies in c->d_queries; listed: the row list (n entries) lies in c->d_subset, else
+// the n rows of the index are scanned.  Where rxgpu_scan_tier_range says so the int8 shadow serves the call (enqueue_range_pruned_i8): the
+// candidate count comes back with the hit count in the tail's one synchronisation, and more candidates than the list holds (an overfull
+// boundary zone, a radius of +inf, a query or an index without a finite bound) or no room for the shadow leave the call to the f32 kernel.
+int range_on_device(rxgpu_index* h, rxgpu_search_ctx* c, bool listed, uint64_t n, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
+					uint64_t* out_total, const char* who) {
+	const uint32_t* d_ids = listed ? static_cast<const uint32_t*>(c->d_subset.ptr) : nullptr;
+	const uint64_t dcap = std::min<uint64_t>(cap, n);
+	if (int rc = c->d_out_dist.ensure(std::max<uint64_t>(dcap, 1) * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(std::max<uint64_t>(dcap, 1) * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_count.ensure(sizeof(unsigned long long)); rc) return rc;
+	RX_HIP(hipMemsetAsync(c->d_out_count.ptr, 0, sizeof(unsigned long long), c->stream));
+	if (rxgpu::scan_policy_tier_range(n, h->dim, listed, !h->i8_unavailable, true) == rxgpu::kTierI8) {
+		if (int rc = rxgpu::ensure_row_stats(h, c->stream); rc) return rc;   // (automatic mode asks whether the row statistics are finite)
+		if (rxgpu::scan_policy_tier_range(n, h->dim, listed, !h->i8_unavailable, h->stats_finite) == rxgpu::kTierI8) {
+			uint32_t ccap = 0;
+			const int rc = rxgpu::enqueue_range_pruned_i8(h, c, d_ids, n, radius, inclusive, cap, dcap, &ccap);
+			if (rc == RXGPU_OK) {
+				unsigned long long total = 0;
+				uint32_t cand = 0;
+				RX_HIP(hipMemcpyAsync(&total, c->d_out_count.ptr, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+				RX_HIP(hipMemcpyAsync(&cand, c->d_cand_cnt.ptr, sizeof(cand), hipMemcpyDeviceToHost, c->stream));
+				RX_HIP(hipStreamSynchronize(c->stream));
+				if (h->profiling) {   // rxgpu_index_last_candidates; the KNN chain rxgpu_index_inspect may have recorded is not this call's
+					h->last_cand_count = cand;
+					h->last_cand_cap = ccap;
+					std::lock_guard<std::mutex> lk(h->mtx);
+					h->last_pruned_ctx = nullptr;
+				}
+				if (cand <= ccap) return range_finish(c, total, out_dist, out_row, cap, out_total, who);
+				// (the exact tail did nothing: the counter is still zero)
+			} else if (!(rc == RXGPU_ERR_NOMEM && h->i8_unavailable)) {
+				return rc;
+			}
+		}
+	}
+	{
+		ProfileScope ps(h, listed ? "range_subset" : "range", c->stream);
+		if (listed) {
+			rxgpu::launch_range_subset(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr), d_ids, n, h->stride, h->dim, radius,
+									   inclusive, static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
+									   static_cast<unsigned long long*>(c->d_out_count.ptr), rxgpu::scan_grid_x(n, h->cus), c->stream);
+		} else {
+			rxgpu::launch_range(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr), n, h->stride, h->dim, radius, inclusive,
+								static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
+								static_cast<unsigned long long*>(c->d_out_count.ptr), rxgpu::scan_grid_x(n, h->cus), c->stream);
+		}
+	}
+	return range_tail(c, out_dist, out_row, cap, out_total, who);
 }
 
 }  // namespace
@@ -374,26 +430,6 @@ int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* que
 	return search_subset_host(h, c, query, 1, kk, static_cast<const uint32_t*>(c->d_subset.ptr), total, out_dist, out_row, out_count);
 }
 
-namespace {
-// range search over a row list that lies in c->d_subset (query in c->d_queries): the tail of rxgpu_search_range_subset
-int range_subset_on_device(rxgpu_index* h, rxgpu_search_ctx* c, uint64_t n_ids, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
-						   uint64_t* out_total, const char* who) {
-	const uint64_t dcap = std::min<uint64_t>(cap, n_ids);
-	if (int rc = c->d_out_dist.ensure(std::max<uint64_t>(dcap, 1) * sizeof(float)); rc) return rc;
-	if (int rc = c->d_out_row.ensure(std::max<uint64_t>(dcap, 1) * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_out_count.ensure(sizeof(unsigned long long)); rc) return rc;
-	RX_HIP(hipMemsetAsync(c->d_out_count.ptr, 0, sizeof(unsigned long long), c->stream));
-	{
-		ProfileScope ps(h, "range_subset", c->stream);
-		rxgpu::launch_range_subset(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr),
-								   static_cast<const uint32_t*>(c->d_subset.ptr), n_ids, h->stride, h->dim, radius, inclusive,
-								   static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
-								   static_cast<unsigned long long*>(c->d_out_count.ptr), rxgpu::scan_grid_x(n_ids, h->cus), c->stream);
-	}
-	return range_tail(c, out_dist, out_row, cap, out_total, who);
-}
-}  // namespace
-
 int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, float radius, int inclusive, float* out_dist,
 							 uint32_t* out_row, uint64_t cap, uint64_t* out_total, uint64_t* out_scanned) {
 	RX_CHECK(h && coarse && query && out_total && (cap == 0 || (out_dist && out_row)), RXGPU_ERR_PARAMS, "rxgpu_search_range_lists: null argument");
@@ -410,7 +446,7 @@ int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* q
 	if (int rc = ivf_probe_rows(h, coarse, c, query, nprobe, &total); rc) return rc;
 	if (out_scanned) *out_scanned = total;
 	if (total == 0) return RXGPU_OK;
-	return range_subset_on_device(h, c, total, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_lists");
+	return range_on_device(h, c, true, total, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_lists");
 }
 
 int rxgpu_search_knn_subset_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, const void* d_row_ids, uint64_t n_ids,
@@ -466,20 +502,9 @@ int rxgpu_search_range(rxgpu_index* h, const float* query, float radius, int inc
 	rxgpu_search_ctx* c = acquire_ctx(h);
 	if (!c) return RXGPU_ERR_DEVICE;
 	CtxLease lease{h, c};
-	const uint64_t dcap = std::min<uint64_t>(cap, h->count);
 	if (int rc = c->d_queries.ensure(h->dim * sizeof(float)); rc) return rc;
-	if (int rc = c->d_out_dist.ensure(std::max<uint64_t>(dcap, 1) * sizeof(float)); rc) return rc;
-	if (int rc = c->d_out_row.ensure(std::max<uint64_t>(dcap, 1) * sizeof(uint32_t)); rc) return rc;
-	if (int rc = c->d_out_count.ensure(sizeof(unsigned long long)); rc) return rc;
 	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, h->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
-	RX_HIP(hipMemsetAsync(c->d_out_count.ptr, 0, sizeof(unsigned long long), c->stream));
-	{
-		ProfileScope ps(h, "range", c->stream);
-		rxgpu::launch_range(h->metric, h->d_rows, h->d_inv_norms, static_cast<const float*>(c->d_queries.ptr), h->count, h->stride, h->dim,
-							radius, inclusive, static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr), dcap,
-							static_cast<unsigned long long*>(c->d_out_count.ptr), rxgpu::scan_grid_x(h->count, h->cus), c->stream);
-	}
-	return range_tail(c, out_dist, out_row, cap, out_total, "rxgpu_search_range");
+	return range_on_device(h, c, false, h->count, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range");
 }
 
 int rxgpu_search_range_subset(rxgpu_index* h, const float* query, float radius, int inclusive, const uint32_t* row_ids, uint64_t n_ids,
@@ -502,7 +527,7 @@ int rxgpu_search_range_subset(rxgpu_index* h, const float* query, float radius, 
 	if (int rc = c->d_subset.ensure(n_ids * sizeof(uint32_t)); rc) return rc;
 	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, query, h->dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
 	RX_HIP(hipMemcpyAsync(c->d_subset.ptr, row_ids, n_ids * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	return range_subset_on_device(h, c, n_ids, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_subset");
+	return range_on_device(h, c, true, n_ids, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_subset");
 }
 
 int rxgpu_distances(rxgpu_index* h, const float* query, const uint32_t* rows, uint32_t n, float* out_dist) {
