@@ -57,7 +57,8 @@ int rxgpu_device_arch(int device, char* name, size_t cap);
  * ------------------------------------------------------------------------------------------------------- */
 
 /* BruteforceSearch::BruteforceSearch(metric, dim, maxElements)  bruteforce.cc:11-18.
- * Allocates capacity * row_stride floats of HBM on `device` (row_stride = dim rounded up to 4 floats). */
+ * Allocates capacity * row_stride floats of HBM on `device` (row_stride = dim rounded up to 4 floats; ask rxgpu_index_row_stride rather than
+ * compute it: RXGPU_ROW_ALIGN, an experiment of rxgpu_capi.hip that is no part of this ABI, enlarges it). */
 int rxgpu_index_create(int metric, uint32_t dim, uint64_t capacity, int device, rxgpu_index** out);
 void rxgpu_index_destroy(rxgpu_index* h);
 
@@ -105,8 +106,15 @@ int rxgpu_index_reserve(rxgpu_index* h, uint64_t capacity);
 int rxgpu_index_upload_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, const float* rows, const float* inv_norms);
 
 /* Zero-copy alternative: adopt caller-owned device memory (e.g. a torch tensor) as the row storage.
- * d_rows: [n][row_stride] floats, row_stride >= dim, row_stride % 4 == 0, 16-byte aligned; d_inv_norms: [n] or NULL.
- * The caller keeps ownership and must keep the memory alive and unchanged while adopted. */
+ * d_rows: [n][row_stride] floats, row_stride >= dim, row_stride % 4 == 0, 16-byte aligned; d_inv_norms: [n] floats, or NULL
+ * where the metric is not cosine.  RXGPU_ERR_PARAMS for a row_stride or a d_rows that breaks these rules and for cosine without d_inv_norms.
+ * Only the first dim floats of a row are data.  The floats between dim and row_stride, and whatever lies in front of row 0 or behind row
+ * n - 1 (of the rows and of the norms), are unspecified and never read as data: they may hold anything, NaN included, and no result
+ * depends on them.  Row offsets are 64-bit: n * row_stride may exceed 2^32 floats (row_stride = 2^20 with n = 4160 is tested), n itself
+ * stays below 2^32 - 1.  Every search entry point gives, over such storage, the counts, rows and distance bits it gives over an owned
+ * index with the same rows (tests/test_gpu_row_layout.py).  A second adoption replaces the first and drops everything derived from it.
+ * The caller keeps ownership and must keep the memory alive and unchanged while adopted; rxgpu_index_upload_rows, rxgpu_index_move_row and
+ * rxgpu_index_reserve return RXGPU_ERR_LOGIC on adopted storage. */
 int rxgpu_index_adopt_device_rows(rxgpu_index* h, const void* d_rows, uint64_t n, uint32_t row_stride, const void* d_inv_norms);
 
 /* Device side of RemovePoint's swap-with-last (bruteforce.cc:70-86): copy row `from` over row `to` (incl. norm). */
