@@ -380,6 +380,20 @@ int rxgpu_hnsw_attach_sq8(rxgpu_index* h, const uint8_t* codes, const float* cor
  * added to or updated in a quantised graph (addPoint with a quantizer, hnswalg.h:1480-1495) — D + 4 bytes per row instead of the whole
  * table again.  The table is sized by the index capacity. */
 int rxgpu_hnsw_upload_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, const uint8_t* codes, const float* corr, float alpha_2);
+/* Device side of Quantize / of points added to a quantised graph: codes + corrective offsets of rows [first_row, first_row + n) computed
+ * ON THE DEVICE from the index's float rows (owned or adopted, at the index's row stride) with the caller's parameters (Sq8Params: minQ,
+ * alpha, delta, alpha_2).  Same table, same range rules as rxgpu_hnsw_upload_sq8_rows (first_row <= rows that have codes,
+ * first_row + n <= count; the table is sized by capacity): a hole or a range past count is RXGPU_ERR_PARAMS, n == 0 is RXGPU_OK, a sharded
+ * handle is RXGPU_ERR_LOGIC (the shard handles take the call).  Result: byte for byte and bit for bit what Quantizer::quantize gives for
+ * those rows under the index's metric (quantizer.h:93-124; inner product and cosine share a branch); an offset that comes out NaN — a row
+ * with an infinite component — carries the reference platform's default NaN.  Rows with a NaN component are outside the contract (the
+ * reference's float -> uint8 conversion is undefined for them): they get some code and some offset.  Synchronises. */
+int rxgpu_hnsw_quantize_sq8(rxgpu_index* h, uint64_t first_row, uint64_t n, float min_q, float alpha, float delta, float alpha_2);
+/* Test instrumentation: rows [first_row, first_row + n) of the code table and their corrective offsets back to the host (either may be
+ * NULL).  Rows without codes: RXGPU_ERR_LOGIC. */
+int rxgpu_hnsw_read_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, uint8_t* out_codes, float* out_corr);
+/* Rows coded on the device (rxgpu_hnsw_quantize_sq8), launches and their device time since the last call (any may be NULL). */
+int rxgpu_hnsw_read_sq8_quantize_stats(rxgpu_index* h, uint64_t* rows, uint64_t* launches, double* kernel_ms);
 /* SearchKnn on the SQ8 graph.  The caller quantises the queries the way prepareData does (hnswalg.h:510-529): query_codes [nq][dim],
  * query_corr [nq], query_norm_coef [nq] (1 for L2 / IP, queryNormCoef for cosine, hnswalg.h:1855-1863).  Same outputs as
  * rxgpu_hnsw_search_knn. */

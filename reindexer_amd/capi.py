@@ -90,6 +90,9 @@ _SIGNATURES = {
     "rxgpu_hnsw_read_stats4": (_i, [_vp, _vp]),
     "rxgpu_hnsw_attach_sq8": (_i, [_vp, _vp, _vp, _u64, _f]),
     "rxgpu_hnsw_upload_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp, _f]),
+    "rxgpu_hnsw_quantize_sq8": (_i, [_vp, _u64, _u64, _f, _f, _f, _f]),
+    "rxgpu_hnsw_read_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp]),
+    "rxgpu_hnsw_read_sq8_quantize_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
     "rxgpu_hnsw_search_knn_sq8": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "rxgpu_hnsw_search_knn_sq8_posted": (_i, [_vp, _vp, _f, _f, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "rxgpu_hnsw_read_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
@@ -480,6 +483,31 @@ class VectorIndex:
         if codes.shape[0] != corr.shape[0]:
             raise ValueError("one corrective offset per code row")
         _check(lib().rxgpu_hnsw_attach_sq8(self._h, codes.ctypes.data, corr.ctypes.data, codes.shape[0], float(alpha_2)))
+
+    def hnsw_upload_sq8_rows(self, first_row: int, codes, corr, alpha_2: float) -> None:
+        codes = np.ascontiguousarray(codes, np.uint8).reshape(-1, self.dim)
+        corr = _f32c(corr).reshape(-1)
+        if codes.shape[0] != corr.shape[0]:
+            raise ValueError("one corrective offset per code row")
+        _check(lib().rxgpu_hnsw_upload_sq8_rows(self._h, first_row, codes.shape[0], codes.ctypes.data, corr.ctypes.data, float(alpha_2)))
+
+    def hnsw_quantize_sq8(self, first_row: int, n: int, min_q: float, alpha: float, delta: float, alpha_2: float) -> None:
+        """Codes and corrective offsets of rows [first_row, first_row + n) computed on the device from the index's float rows
+        (rxgpu_hnsw_quantize_sq8): what Quantizer::quantize gives, bit for bit."""
+        _check(lib().rxgpu_hnsw_quantize_sq8(self._h, first_row, n, float(min_q), float(alpha), float(delta), float(alpha_2)))
+
+    def hnsw_read_sq8_rows(self, first_row: int, n: int):
+        """(codes [n][dim] u8, corr [n] f32) of the code table (test instrumentation)."""
+        codes = np.empty((n, self.dim), np.uint8)
+        corr = np.empty(n, np.float32)
+        _check(lib().rxgpu_hnsw_read_sq8_rows(self._h, first_row, n, codes.ctypes.data, corr.ctypes.data))
+        return codes, corr
+
+    def hnsw_read_sq8_quantize_stats(self):
+        """(rows coded on the device, launches, kernel milliseconds) since the last call."""
+        rows, launches, ms = _u64(0), _u64(0), C.c_double(0.0)
+        _check(lib().rxgpu_hnsw_read_sq8_quantize_stats(self._h, C.byref(rows), C.byref(launches), C.byref(ms)))
+        return int(rows.value), int(launches.value), float(ms.value)
 
     def hnsw_search_knn_sq8(self, qcodes, qcorr, qnorm, k: int, ef: int = 0):
         qc = np.ascontiguousarray(qcodes, np.uint8).reshape(-1, self.dim)

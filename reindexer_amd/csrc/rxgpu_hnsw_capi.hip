@@ -832,6 +832,36 @@ int rxgpu_hnsw_update_deleted(rxgpu_index* h, const uint8_t* deleted, uint64_t n
 	return RXGPU_OK;
 }
 
+namespace {
+// The code table of h with room for `rows` rows (the three entry points that write it come through here).  It is allocated for the index
+// CAPACITY, like the float rows; where it has to grow — the first rows, or the index was reserved larger since — the rows that have codes
+// are copied into the new one.  + 4 bytes: the word loads of the last row's last block stay inside the allocation whatever dim % 4 is.
+// The caller has quiesced the resident kernel and holds the device.
+int sq8_table_ensure(rxgpu_index* h, uint64_t rows, const char* who) {
+	if (h->sq8_cap >= rows) return RXGPU_OK;
+	const uint64_t cap = std::max<uint64_t>(h->capacity, h->count);
+	RX_HIP(rxgpu::device_wait_all(h->device));
+	uint8_t* nc = nullptr;
+	float* nr = nullptr;
+	RX_HIP(hipMalloc(reinterpret_cast<void**>(&nc), size_t(cap) * h->dim + 4));
+	if (hipMalloc(reinterpret_cast<void**>(&nr), size_t(cap) * sizeof(float)) != hipSuccess) {
+		(void)hipFree(nc);
+		set_error(std::string(who) + ": not enough memory for the corrective offsets");
+		return RXGPU_ERR_NOMEM;
+	}
+	if (h->sq8_n) {
+		RX_HIP(hipMemcpy(nc, h->d_codes, size_t(h->sq8_n) * h->dim, hipMemcpyDeviceToDevice));
+		RX_HIP(hipMemcpy(nr, h->d_corr, size_t(h->sq8_n) * sizeof(float), hipMemcpyDeviceToDevice));
+	}
+	if (h->d_codes) (void)hipFree(h->d_codes);
+	if (h->d_corr) (void)hipFree(h->d_corr);
+	h->d_codes = nc;
+	h->d_corr = nr;
+	h->sq8_cap = cap;
+	return RXGPU_OK;
+}
+}  // namespace
+
 // Rows [first_row, first_row + n) of the code table: the device side of a point added to / updated in a quantised graph (addPoint with a
 // quantizer, hnswalg.h:1480-1495).  The table is allocated for the index CAPACITY (like the rows), so an upsert is a copy of its own D + 4
 // bytes, not a re-upload of the table.
@@ -843,27 +873,7 @@ int rxgpu_hnsw_upload_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, c
 	RX_CHECK(first_row <= h->sq8_n && first_row + n <= h->count, RXGPU_ERR_PARAMS, "rxgpu_hnsw_upload_sq8_rows: rows follow the table without a hole and stay below count");
 	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel over the codes reads what changes (or moves) here
 	DeviceGuard dg(h->device);
-	const uint64_t cap = std::max<uint64_t>(h->capacity, h->count);
-	if (h->sq8_cap < first_row + n) {   // first rows, or the index was reserved larger since: a new table, the old rows copied over
-		RX_HIP(rxgpu::device_wait_all(h->device));
-		uint8_t* nc = nullptr;
-		float* nr = nullptr;
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&nc), size_t(cap) * h->dim + 4));
-		if (hipMalloc(reinterpret_cast<void**>(&nr), size_t(cap) * sizeof(float)) != hipSuccess) {
-			(void)hipFree(nc);
-			set_error("rxgpu_hnsw_upload_sq8_rows: not enough memory for the corrective offsets");
-			return RXGPU_ERR_NOMEM;
-		}
-		if (h->sq8_n) {
-			RX_HIP(hipMemcpy(nc, h->d_codes, size_t(h->sq8_n) * h->dim, hipMemcpyDeviceToDevice));
-			RX_HIP(hipMemcpy(nr, h->d_corr, size_t(h->sq8_n) * sizeof(float), hipMemcpyDeviceToDevice));
-		}
-		if (h->d_codes) (void)hipFree(h->d_codes);
-		if (h->d_corr) (void)hipFree(h->d_corr);
-		h->d_codes = nc;
-		h->d_corr = nr;
-		h->sq8_cap = cap;
-	}
+	if (int rc = sq8_table_ensure(h, first_row + n, "rxgpu_hnsw_upload_sq8_rows"); rc) return rc;
 	RX_HIP(hipMemcpy(h->d_codes + size_t(first_row) * h->dim, codes, size_t(n) * h->dim, hipMemcpyHostToDevice));
 	RX_HIP(hipMemcpy(h->d_corr + first_row, corr, size_t(n) * sizeof(float), hipMemcpyHostToDevice));
 	h->sq8_alpha2 = alpha_2;
@@ -886,17 +896,73 @@ int rxgpu_hnsw_attach_sq8(rxgpu_index* h, const uint8_t* codes, const float* cor
 	h->sq8_n = 0;
 	h->sq8_cap = 0;
 	if (count) {
-		// sized by the index capacity: rows added later are patched in (rxgpu_hnsw_upload_sq8_rows)
-		// + 4 bytes: the word loads of the last row's last block stay inside the allocation whatever dim % 4 is
-		const uint64_t cap = std::max<uint64_t>(h->capacity, count);
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_codes), size_t(cap) * h->dim + 4));
-		RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_corr), size_t(cap) * sizeof(float)));
-		h->sq8_cap = cap;
+		// a fresh table, sized by the index capacity: rows added later are patched in (rxgpu_hnsw_upload_sq8_rows / rxgpu_hnsw_quantize_sq8)
+		if (int rc = sq8_table_ensure(h, count, "rxgpu_hnsw_attach_sq8"); rc) return rc;
 		RX_HIP(hipMemcpy(h->d_codes, codes, size_t(count) * h->dim, hipMemcpyHostToDevice));
 		RX_HIP(hipMemcpy(h->d_corr, corr, size_t(count) * sizeof(float), hipMemcpyHostToDevice));
 	}
 	h->sq8_alpha2 = alpha_2;
 	h->sq8_n = count;
+	return RXGPU_OK;
+}
+
+// Quantizer::quantize where the rows are (hnsw_sq8_quantize.hip): what the Map used to compute on one host thread and upload — on the first
+// Quantize, on every re-quantisation, after every bulk change — is one pass over rows the device already holds.
+int rxgpu_hnsw_quantize_sq8(rxgpu_index* h, uint64_t first_row, uint64_t n, float min_q, float alpha, float delta, float alpha_2) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_hnsw_quantize_sq8: not available on a sharded index");
+	if (n == 0) return RXGPU_OK;
+	RX_CHECK(first_row <= h->sq8_n && first_row <= h->count && n <= h->count - first_row, RXGPU_ERR_PARAMS,
+			 "rxgpu_hnsw_quantize_sq8: rows follow the table without a hole and stay below count");
+	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel over the codes reads what changes (or moves) here
+	DeviceGuard dg(h->device);
+	if (int rc = sq8_table_ensure(h, first_row + n, "rxgpu_hnsw_quantize_sq8"); rc) return rc;
+	hipEvent_t a = nullptr, b = nullptr;
+	RX_HIP(hipEventCreate(&a));
+	if (hipError_t e = hipEventCreate(&b); e != hipSuccess) {
+		(void)hipEventDestroy(a);
+		RX_HIP(e);
+	}
+	float ms = 0.f;
+	hipError_t e = hipEventRecord(a, nullptr);
+	if (e == hipSuccess) {
+		rxgpu::launch_hnsw_sq8_quantize(h->metric, h->d_rows, h->stride, h->dim, first_row, n, min_q, alpha, delta, h->d_codes, h->d_corr, nullptr);
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipEventRecord(b, nullptr);
+	if (e == hipSuccess) e = hipEventSynchronize(b);
+	if (e == hipSuccess) e = hipEventElapsedTime(&ms, a, b);
+	(void)hipEventDestroy(a);
+	(void)hipEventDestroy(b);
+	RX_HIP(e);
+	h->sq8_alpha2 = alpha_2;
+	h->sq8_n = std::min<uint64_t>(h->count, std::max<uint64_t>(h->sq8_n, first_row + n));   // codes behind a count that shrank since are no rows
+	h->sq8_dev_rows += n;
+	h->sq8_dev_launches += 1;
+	h->sq8_dev_ms += double(ms);
+	return RXGPU_OK;
+}
+
+int rxgpu_hnsw_read_sq8_rows(rxgpu_index* h, uint64_t first_row, uint64_t n, uint8_t* out_codes, float* out_corr) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_hnsw_read_sq8_rows: not available on a sharded index");
+	if (n == 0) return RXGPU_OK;
+	RX_CHECK(first_row <= h->sq8_n && n <= h->sq8_n - first_row, RXGPU_ERR_LOGIC, "rxgpu_hnsw_read_sq8_rows: rows without codes");
+	rxgpu::hnsw_server_quiesce(h);   // a copy on the default stream would wait for the resident kernel's lifetime
+	DeviceGuard dg(h->device);
+	if (out_codes) RX_HIP(hipMemcpy(out_codes, h->d_codes + size_t(first_row) * h->dim, size_t(n) * h->dim, hipMemcpyDeviceToHost));
+	if (out_corr) RX_HIP(hipMemcpy(out_corr, h->d_corr + first_row, size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+	return RXGPU_OK;
+}
+
+int rxgpu_hnsw_read_sq8_quantize_stats(rxgpu_index* h, uint64_t* rows, uint64_t* launches, double* kernel_ms) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	if (rows) *rows = h->sq8_dev_rows;
+	if (launches) *launches = h->sq8_dev_launches;
+	if (kernel_ms) *kernel_ms = h->sq8_dev_ms;
+	h->sq8_dev_rows = 0;
+	h->sq8_dev_launches = 0;
+	h->sq8_dev_ms = 0.0;
 	return RXGPU_OK;
 }
 

@@ -123,6 +123,9 @@ size_t hnsw_server_lds_bytes(const HnswParams& p);
 bool hnsw_server_sq8_serves(uint32_t dim, bool bare);   // the resident kernel over SQ8 codes exists for this embedding size
 struct HnswPatch;
 void launch_hnsw_patch(const HnswPatch& p, uint32_t n_dirty, hipStream_t s);
+// Quantizer::quantize on the device (hnsw_sq8_quantize.hip): codes [..][dim] and corrective offsets of rows [first_row, first_row + n)
+void launch_hnsw_sq8_quantize(int metric, const float* rows, uint32_t stride, uint32_t dim, uint64_t first_row, uint64_t n, float min_q, float alpha,
+							  float delta, uint8_t* codes, float* corr, hipStream_t s);
 struct HnswStream;
 void launch_hnsw_stream(int metric, const HnswParams& p, const HnswStream& s, uint32_t batch, int mode, bool lds, hipStream_t st);
 struct HnswRange;
@@ -598,6 +601,8 @@ struct rxgpu_index {
 	float* d_corr = nullptr;
 	float sq8_alpha2 = 0.f;
 	uint64_t sq8_n = 0, sq8_cap = 0;   // rows with codes / rows the tables are allocated for
+	uint64_t sq8_dev_rows = 0, sq8_dev_launches = 0;   // rxgpu_hnsw_quantize_sq8 since rxgpu_hnsw_read_sq8_quantize_stats: rows coded, launches,
+	double sq8_dev_ms = 0.0;                           // and the kernel's time between two events
 	uint64_t graph_n = 0, graph_deleted = 0;
 	uint64_t graph_rows_cap = 0, graph_upper_cap = 0, graph_upper_used = 0;   // allocated level-0 rows / upper blocks (rxgpu_hnsw_patch_graph grows in place)
 	uint32_t graph_M = 0, graph_maxM0 = 0;

@@ -1,5 +1,6 @@
 #include "gpu_hnsw_map.h"
 
+#include <cstdlib>
 #include <cstring>
 
 #include <algorithm>
@@ -491,9 +492,23 @@ void GpuHnswMap::syncDevice() const {
 }
 
 // hnswalg.h:443-470 (the quantising copy) and :1480-1495 (points added to a quantised graph): codes + corrective offsets of every stored
-// vector under the Map's parameters.  The whole code table is re-sent after a mutation — D bytes a row, a quarter of the float rows.
+// vector under the Map's parameters.  The float rows are on the device already (syncDevice() sent them a few lines earlier), so the codes
+// are computed there (rxgpu_hnsw_quantize_sq8: the same bytes, no host pass over the rows, no code buffer, no upload).
+// RXGPU_SQ8_QUANTIZE=host, read at every sync of the codes, keeps the host's loop and the upload of the table (A/B runs).
+static bool sq8QuantizeOnHost() noexcept {
+	const char* e = std::getenv("RXGPU_SQ8_QUANTIZE");
+	return e && std::strcmp(e, "host") == 0;
+}
+
 void GpuHnswMap::attachCodes() const {
 	const size_t n = graph_.Count(), dim = graph_.Dim();
+	if (n && !sq8QuantizeOnHost()) {
+		if (rxgpu_hnsw_quantize_sq8(dev_, 0, n, sq8_.minQ, sq8_.alpha, sq8_.delta, sq8_.alpha_2) != RXGPU_OK) throwDevice("SQ8 coding on the device failed");
+		deviceCodedRows_ += n;
+		codesDirty_ = false;
+		syncedCodes_ = n;
+		return;
+	}
 	std::vector<uint8_t> codes(n * dim);
 	std::vector<float> corr(n);
 	for (size_t i = 0; i < n; ++i) corr[i] = Sq8Quantize(graph_.Metric(), sq8_, graph_.Vector(tableint(i)), dim, 1.f, codes.data() + i * dim);
@@ -510,7 +525,11 @@ void GpuHnswMap::patchCodes(const std::vector<tableint>& dirty, size_t n) const 
 		const float corr = Sq8Quantize(graph_.Metric(), sq8_, graph_.Vector(id), dim, 1.f, code.data());
 		if (rxgpu_hnsw_upload_sq8_rows(dev_, id, 1, code.data(), &corr, sq8_.alpha_2) != RXGPU_OK) throwDevice("SQ8 code upload failed");
 	}
-	if (n > syncedCodes_) {
+	if (n > syncedCodes_ && !sq8QuantizeOnHost()) {   // the appended rows: their floats went up as one run at this sync
+		const size_t add = n - syncedCodes_;
+		if (rxgpu_hnsw_quantize_sq8(dev_, syncedCodes_, add, sq8_.minQ, sq8_.alpha, sq8_.delta, sq8_.alpha_2) != RXGPU_OK) throwDevice("SQ8 coding on the device failed");
+		deviceCodedRows_ += add;
+	} else if (n > syncedCodes_) {
 		const size_t add = n - syncedCodes_;
 		std::vector<uint8_t> codes(add * dim);
 		std::vector<float> corr(add);
@@ -717,6 +736,14 @@ SearchResultQueue GpuHnswMap::SearchKnn(const float* queryDataRaw, std::optional
 	ReserveQueue(result, count);
 	for (uint32_t i = 0; i < count; ++i) result.emplace(dist[i], graph_.Label(row[i]));
 	return result;
+}
+
+size_t GpuHnswMap::DeviceCodedRows() const noexcept {
+	size_t n = deviceCodedRows_.load();
+	if (sh_) {
+		for (const auto& m : sh_->maps) n += m->DeviceCodedRows();
+	}
+	return n;
 }
 
 uint64_t GpuHnswMap::TieReruns() const {

@@ -133,6 +133,9 @@ public:
 	bool IsQuantized() const noexcept { return quantized_; }
 	bool QuantizationAvailable() const noexcept { return !quantized_ && !pendingSq8_; }
 	const Sq8Params& QuantizingParams() const noexcept { return sq8_; }
+	// rows whose codes the DEVICE computed from its float rows so far (rxgpu_hnsw_quantize_sq8: whole tables and appended tails; the
+	// individually changed rows of an upsert are coded on the host); over a device list the sum over the shards.  Stays 0 under RXGPU_SQ8_QUANTIZE=host.
+	size_t DeviceCodedRows() const noexcept;
 
 	VectorMetric Metric() const noexcept { return graph_.Metric(); }
 	size_t Dim() const noexcept { return graph_.Dim(); }
@@ -192,6 +195,7 @@ private:
 	mutable size_t syncedCodes_ = 0;                // rows whose codes are on the device
 	mutable std::vector<tableint> codesDirtyRows_;  // what the graph's change tracker named at this sync (when it could)
 	mutable bool codesIncremental_ = false;
+	mutable std::atomic<size_t> deviceCodedRows_{0};
 	void attachCodes() const;
 	void patchCodes(const std::vector<tableint>& dirty, size_t n) const;   // codes of the changed / new rows only
 	float quantizeQuery(const float* queryDataRaw, std::optional<float> queryDataNorm, std::vector<uint8_t>& qcodes, float& normCoef) const;

@@ -489,6 +489,8 @@ long rxhost_hnsw_tie_reruns(void* h) {
 }
 // one-shot searches of this Map that the index's resident search kernel answered (GpuHnswMap::PostedQueries)
 long rxhost_hnsw_posted_queries(void* h) { return long(static_cast<const GpuHnswMap*>(h)->PostedQueries()); }
+// rows of this Map whose SQ8 codes the device computed from its float rows (GpuHnswMap::DeviceCodedRows)
+long rxhost_hnsw_device_coded_rows(void* h) { return long(static_cast<const GpuHnswMap*>(h)->DeviceCodedRows()); }
 long rxhost_hnsw_lds_reruns(void* h) {
 	long n = -1;
 	guarded([&] { n = long(static_cast<const GpuHnswMap*>(h)->LdsReruns()); });

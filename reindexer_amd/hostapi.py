@@ -526,6 +526,8 @@ class GpuHnswMap:
             L.rxhost_hnsw_select.argtypes = [_vp, _vp, _sz, _l, _sz, _i, _f, _i, _i, _vp, _vp, _sz]
             L.rxhost_hnsw_posted_queries.restype = _l
             L.rxhost_hnsw_posted_queries.argtypes = [_vp]
+            L.rxhost_hnsw_device_coded_rows.restype = _l
+            L.rxhost_hnsw_device_coded_rows.argtypes = [_vp]
             L.rxhost_hnsw_tie_reruns.restype = _l
             L.rxhost_hnsw_tie_reruns.argtypes = [_vp]
             L.rxhost_hnsw_lds_reruns.restype = _l
@@ -628,6 +630,10 @@ class GpuHnswMap:
         if n < 0:
             _raise()
         return n
+
+    def device_coded_rows(self) -> int:
+        """Rows whose SQ8 codes the device computed from its float rows so far (rxgpu_hnsw_quantize_sq8); 0 under RXGPU_SQ8_QUANTIZE=host."""
+        return int(lib().rxhost_hnsw_device_coded_rows(self.h))
 
     def posted_queries(self) -> int:
         """One-shot searches answered through the index's resident search kernel so far (rxgpu_hnsw_search_knn_posted)."""
