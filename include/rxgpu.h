@@ -258,6 +258,31 @@ int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* que
 int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, float radius, int inclusive, float* out_dist,
 							 uint32_t* out_row, uint64_t cap, uint64_t* out_total, uint64_t* out_scanned);
 
+/* ---- IVF training from resident rows: the device half of IndexIVF::train / add_with_ids as IvfIndex drives them (ivf_index.cc:96-108,
+ * 143-160; Level1Quantizer::train_q1 IndexIVF.cpp:43-88 -> Clustering::train_encoded Clustering.cpp:330-560) -------------------------
+ * `coarse` = the flat index of the current centroids (nlist = its row count; same dimension, same device: else RXGPU_ERR_PARAMS, as the
+ * list search answers).  No inverted lists are needed.  A row takes part as its PREPARED vector: row[j], on a cosine index
+ * row[j] * (1 / |row|) with the stored reciprocal norm — one correctly rounded f32 multiply (IndexIVFFlat.cpp:54-75 through the engine's
+ * normalisation).  The rows are read where they are (owned or adopted storage, any admitted stride, the first dim floats of a row only).
+ * Row ids are checked on the host before anything is launched: an id >= count is RXGPU_ERR_PARAMS.  n == 0 is RXGPU_OK; a sharded handle
+ * (either one) is RXGPU_ERR_LOGIC.  Both calls synchronise.  Rows with a NaN or an infinite component are outside the contract.
+ * rxgpu_ivf_assign: out_list[i] = the nearest centroid of row_ids[i] (row_ids == NULL: of row first_row + i; with a list first_row is
+ *   ignored; the list may be in any order and repeat rows) — the result of rxgpu_search_knn(coarse, prepared vector, k = 1), bit for
+ *   bit and with its (dist, centroid) tie order: the same chain answers, over queries gathered on the device in chunks of a bounded
+ *   scratch (64 MiB of prepared vectors; RXGPU_IVF_TRAIN_SCRATCH_BYTES, read per call, moves it).
+ * rxgpu_ivf_kmeans_step: one iteration's assignment of the n listed rows (row_ids == NULL: rows 0 .. n - 1) and compute_centroids
+ *   (Clustering.cpp:153-230) over it: per centroid c and component j ONE f32 chain  sum = +0; sum += p_i[j]  over the LIST POSITIONS i
+ *   with assign[i] == c in ascending order (the position in the list, not the row number), then sum * (1 / float(count_c)), every
+ *   operation a correctly rounded f32 one and nothing contracted; count_c == 0: the centroid's row is all zeros (split_clusters, the
+ *   caller's, fills it).  out_centroids [nlist][dim], out_hassign [nlist] = float(count_c), out_assign [n] or NULL.  The reference counts
+ *   with += 1.0f, which agrees with the integer count below 2^24 points: n >= 2^24 is RXGPU_ERR_PARAMS.
+ * rxgpu_ivf_read_train_stats: rows assigned by the two calls, k-means steps, the device time of the calls' launches between two events
+ *   and the part of it the sums kernel took, since the last call (any may be NULL). */
+int rxgpu_ivf_assign(rxgpu_index* h, rxgpu_index* coarse, const uint32_t* row_ids, uint64_t first_row, uint64_t n, uint32_t* out_list);
+int rxgpu_ivf_kmeans_step(rxgpu_index* h, rxgpu_index* coarse, const uint32_t* row_ids, uint64_t n, float* out_centroids, float* out_hassign,
+						  uint32_t* out_assign);
+int rxgpu_ivf_read_train_stats(rxgpu_index* h, uint64_t* rows_assigned, uint64_t* steps, double* kernel_ms, double* sums_ms);
+
 /* Device-resident variant on `stream` (no synchronisation): d_row_ids = device [n_ids] uint32, 1 <= n_ids <= count,
  * kk in [1, 128]; d_out_count may be NULL.  The list is TRUSTED (strictly increasing, below count): an id beyond the
  * index would fault the device.  rxgpu_check_row_list_device() verifies a device list (synchronises `stream`).

@@ -150,6 +150,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "knn_emit_plan.h"]):
             _run(["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # the decisions of IVF training on the device compiled for the host (CPU check of the chunks, segments, tiles and scratch ivf_train.hip uses)
+    src = tdir / "ivf_train_plan_cpu.cc"
+    if src.exists():
+        out = tdir / "libivf_train_plan_cpu.so"
+        if force or _stale(out, [src, CSRC / "ivf_train_plan.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     return outs
 
 

@@ -74,6 +74,9 @@ _SIGNATURES = {
     "rxgpu_index_set_lists": (_i, [_vp, _u32, _vp, _vp]),
     "rxgpu_search_knn_lists": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_search_range_lists": (_i, [_vp, _vp, _vp, _u32, C.c_float, _i, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "rxgpu_ivf_assign": (_i, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "rxgpu_ivf_kmeans_step": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "rxgpu_ivf_read_train_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rxgpu_search_knn_subset_device": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "rxgpu_check_row_list_device": (_i, [_vp, _vp, _u64, _vp, C.POINTER(C.c_int32)]),
     "rxgpu_search_range_subset": (_i, [_vp, _vp, _f, _i, _vp, _u64, _vp, _vp, _u64, C.POINTER(_u64)]),
@@ -425,6 +428,34 @@ class VectorIndex:
             _check(rc)
             n = int(total.value)
             return dist[:n].copy(), row[:n].copy(), int(scanned.value)
+
+    # ---- IVF training from resident rows
+    def ivf_assign(self, coarse: "VectorIndex", row_ids=None, first_row: int = 0, n: int | None = None) -> np.ndarray:
+        """Nearest centroid (a row of `coarse`) of the listed rows, or of rows [first_row, first_row + n) (rxgpu_ivf_assign)."""
+        ids = None if row_ids is None else np.ascontiguousarray(row_ids, np.uint32).reshape(-1)
+        n = ids.shape[0] if ids is not None else int(n)
+        out = np.empty(n, np.uint32)
+        _check(lib().rxgpu_ivf_assign(self._h, coarse._h, ids.ctypes.data if ids is not None else None, first_row, n, out.ctypes.data))
+        return out
+
+    def ivf_kmeans_step(self, coarse: "VectorIndex", row_ids=None, n: int | None = None):
+        """One k-means iteration's device half over the listed rows (or the first n): (centroids [nlist][dim], hassign [nlist], assign [n]) —
+        the assignment and compute_centroids' ordered single-precision sums (rxgpu_ivf_kmeans_step)."""
+        ids = None if row_ids is None else np.ascontiguousarray(row_ids, np.uint32).reshape(-1)
+        n = ids.shape[0] if ids is not None else int(n)
+        nlist = coarse.count
+        cent = np.empty((nlist, self.dim), np.float32)
+        hassign = np.empty(nlist, np.float32)
+        assign = np.empty(n, np.uint32)
+        _check(lib().rxgpu_ivf_kmeans_step(self._h, coarse._h, ids.ctypes.data if ids is not None else None, n, cent.ctypes.data, hassign.ctypes.data,
+                                           assign.ctypes.data))
+        return cent, hassign, assign
+
+    def ivf_read_train_stats(self):
+        """(rows assigned on the device, k-means steps, device milliseconds, of which the sums kernel) since the last call."""
+        rows, steps, ms, sums = _u64(0), _u64(0), C.c_double(0.0), C.c_double(0.0)
+        _check(lib().rxgpu_ivf_read_train_stats(self._h, C.byref(rows), C.byref(steps), C.byref(ms), C.byref(sums)))
+        return int(rows.value), int(steps.value), float(ms.value), float(sums.value)
 
     def hnsw_attach_graph(self, g: dict) -> None:
         """g: flat graph dict (links0, upper_off, upper, deleted, M, maxM0, maxlevel, entry, num_deleted)."""

@@ -83,6 +83,14 @@ void launch_ivf_mark_lists(const uint32_t* probe, const uint32_t* probe_cnt, uin
 void launch_gather_u32(const uint32_t* src, const uint32_t* idx, uint32_t n, uint32_t* out, hipStream_t s);
 void launch_check_row_list(const uint32_t* ids, uint64_t n, uint64_t limit, uint32_t* bad, int cus, hipStream_t s);
 
+// IVF training on the device (ivf_train.hip; layout: ivf_train_plan.h).  ids: list positions -> rows in HBM, or null: position i is row first_row + i
+void launch_ivf_gather(int metric, const float* rows, const float* inv_norms, const uint32_t* ids, uint64_t first_row, uint64_t n, uint32_t stride, uint32_t dim,
+					   float* out, int cus, hipStream_t s);   // prepared vectors [n][dim]: row[j], cosine row[j] * inv_norms[row]
+void launch_ivf_place(const uint32_t* assign, const uint32_t* ids, uint32_t n, uint32_t nlist, uint32_t* table, uint32_t* seg_off, uint32_t* seg_rows, float* hassign,
+					  uint32_t* flag, hipStream_t s);   // stable per-centroid segments of the members' rows; table and flag zeroed by the caller
+void launch_ivf_centroid_sums(int metric, const float* rows, const float* inv_norms, uint32_t stride, uint32_t dim, uint32_t nlist, const uint32_t* seg_off,
+							  const uint32_t* seg_rows, float* centroids, hipStream_t s);   // compute_centroids' ordered sums x 1 / count
+
 // Large-k path (k+1 > 64): distance pass + radix select (knn_select.hip).
 void launch_all_distances(int metric, const float* rows, const float* inv_norms, const float* query, uint64_t n, uint32_t stride,
 						  uint32_t dim, float* out_dist, uint32_t gridx, hipStream_t s);
@@ -603,6 +611,10 @@ struct rxgpu_index {
 	uint64_t sq8_n = 0, sq8_cap = 0;   // rows with codes / rows the tables are allocated for
 	uint64_t sq8_dev_rows = 0, sq8_dev_launches = 0;   // rxgpu_hnsw_quantize_sq8 since rxgpu_hnsw_read_sq8_quantize_stats: rows coded, launches,
 	double sq8_dev_ms = 0.0;                           // and the kernel's time between two events
+	// rxgpu_ivf_assign / rxgpu_ivf_kmeans_step since rxgpu_ivf_read_train_stats: rows assigned, steps, device time of the calls between two events,
+	// and the part of it the sums kernel took
+	uint64_t ivf_dev_rows = 0, ivf_dev_steps = 0;
+	double ivf_dev_ms = 0.0, ivf_sums_ms = 0.0;
 	uint64_t graph_n = 0, graph_deleted = 0;
 	uint64_t graph_rows_cap = 0, graph_upper_cap = 0, graph_upper_used = 0;   // allocated level-0 rows / upper blocks (rxgpu_hnsw_patch_graph grows in place)
 	uint32_t graph_M = 0, graph_maxM0 = 0;

@@ -3,9 +3,11 @@
 // lifetime and the mutations are rxgpu_capi.hip; the chains these calls enqueue are rxgpu_knn_chains.hip.  Host-side plumbing only — all
 // arithmetic is in the kernels.
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 
 #include "../../include/rxgpu.h"
+#include "ivf_train_plan.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
 #include "shard_plan.h"   // check_row_list
@@ -409,6 +411,75 @@ int ivf_check(rxgpu_index* h, rxgpu_index* coarse, const char* who) {
 			 std::string(who) + ": the coarse index must hold one centroid per list, same dimension, same device");
 	return RXGPU_OK;
 }
+// ... and of the training calls, which run before there are lists: nlist is the coarse index's row count
+int ivf_train_check(rxgpu_index* h, rxgpu_index* coarse, const char* who) {
+	if (h->shard_set || coarse->shard_set) {
+		set_error(std::string(who) + ": not available on a sharded index");
+		return RXGPU_ERR_LOGIC;
+	}
+	RX_CHECK(coarse->count > 0 && coarse->count < 0xFFFFFFFFull && coarse->dim == h->dim && coarse->device == h->device, RXGPU_ERR_PARAMS,
+			 std::string(who) + ": the coarse index must hold the centroids, same dimension, same device");
+	return RXGPU_OK;
+}
+
+// An event pair on a stream: the device time of what a call enqueues between begin() and end() (read after the stream is idle).
+struct IvfTimer {
+	hipEvent_t a = nullptr, b = nullptr;
+	~IvfTimer() {
+		if (a) (void)hipEventDestroy(a);
+		if (b) (void)hipEventDestroy(b);
+	}
+	hipError_t begin(hipStream_t s) {
+		if (hipError_t e = hipEventCreate(&a); e != hipSuccess) return e;
+		if (hipError_t e = hipEventCreate(&b); e != hipSuccess) return e;
+		return hipEventRecord(a, s);
+	}
+	hipError_t end(hipStream_t s) { return hipEventRecord(b, s); }
+	double ms() const {
+		float v = 0.f;
+		return hipEventElapsedTime(&v, a, b) == hipSuccess ? double(v) : 0.0;
+	}
+};
+
+uint64_t ivf_gather_budget() {   // read per call (tests cut a small list into several chunks with it)
+	const char* e = getenv("RXGPU_IVF_TRAIN_SCRATCH_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : rxgpu::kIvfGatherBudgetBytes;
+}
+
+// The row list of a training call on the host, before anything is launched: any order, repeats allowed, every id below the row count.
+int ivf_check_ids(const rxgpu_index* h, const uint32_t* row_ids, uint64_t n, const char* who) {
+	for (uint64_t i = 0; i < n; ++i) RX_CHECK(row_ids[i] < h->count, RXGPU_ERR_PARAMS, std::string(who) + ": row id out of range");
+	return RXGPU_OK;
+}
+
+// Nearest centroid of n resident rows into c->d_out_row [n], all on c->stream: the rows listed in c->d_subset (listed) or rows [first_row,
+// first_row + n).  The prepared vectors are gathered chunk by chunk (ivf_train_plan.h) into c->d_queries and searched by the chain that
+// answers rxgpu_search_knn on the coarse index: the same bits, the same (dist, centroid) tie order.
+int ivf_assign_enqueue(rxgpu_index* h, rxgpu_index* coarse, rxgpu_search_ctx* c, bool listed, uint64_t first_row, uint64_t n) {
+	const uint64_t chunk_rows = rxgpu::ivf_gather_chunk_rows(n, h->dim, ivf_gather_budget());
+	if (int rc = c->d_queries.ensure(chunk_rows * h->dim * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(n * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_dist.ensure(chunk_rows * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_count.ensure(chunk_rows * sizeof(uint32_t)); rc) return rc;
+	rxgpu_search_ctx* cc = stream_ctx(coarse, c->stream);
+	const uint32_t* d_ids = listed ? static_cast<const uint32_t*>(c->d_subset.ptr) : nullptr;
+	float* block = static_cast<float*>(c->d_queries.ptr);
+	const uint64_t chunks = rxgpu::ivf_gather_chunks(n, chunk_rows);
+	for (uint64_t i = 0; i < chunks; ++i) {
+		const rxgpu::IvfChunk ch = rxgpu::ivf_gather_chunk(n, chunk_rows, i);
+		{
+			ProfileScope ps(h, "ivf_gather", c->stream);
+			rxgpu::launch_ivf_gather(h->metric, h->d_rows, h->d_inv_norms, d_ids ? d_ids + ch.first : nullptr, first_row + ch.first, ch.rows, h->stride, h->dim, block,
+									 h->cus, c->stream);
+		}
+		RX_HIP(hipGetLastError());
+		if (int rc = enqueue_knn(coarse, cc, block, uint32_t(ch.rows), 1, static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr) + ch.first,
+								 static_cast<uint32_t*>(c->d_out_count.ptr));
+			rc)
+			return rc;
+	}
+	return RXGPU_OK;
+}
 }  // namespace
 
 int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, uint32_t kk, float* out_dist,
@@ -447,6 +518,122 @@ int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* q
 	if (out_scanned) *out_scanned = total;
 	if (total == 0) return RXGPU_OK;
 	return range_on_device(h, c, true, total, radius, inclusive, out_dist, out_row, cap, out_total, "rxgpu_search_range_lists");
+}
+
+// add_with_ids' list assignment (and the closing one of train) for rows the index holds: gather + the coarse quantiser's k = 1 search, the
+// answer back in one copy.
+int rxgpu_ivf_assign(rxgpu_index* h, rxgpu_index* coarse, const uint32_t* row_ids, uint64_t first_row, uint64_t n, uint32_t* out_list) {
+	RX_CHECK(h && coarse, RXGPU_ERR_PARAMS, "rxgpu_ivf_assign: null argument");
+	if (int rc = ivf_train_check(h, coarse, "rxgpu_ivf_assign"); rc) return rc;
+	if (n == 0) return RXGPU_OK;
+	RX_CHECK(out_list, RXGPU_ERR_PARAMS, "rxgpu_ivf_assign: null argument");
+	RX_CHECK(n < 0xFFFFFFFFull, RXGPU_ERR_PARAMS, "rxgpu_ivf_assign: too many rows");
+	if (row_ids) {
+		if (int rc = ivf_check_ids(h, row_ids, n, "rxgpu_ivf_assign"); rc) return rc;
+	} else {
+		RX_CHECK(first_row <= h->count && n <= h->count - first_row, RXGPU_ERR_PARAMS, "rxgpu_ivf_assign: the row range must stay below the row count");
+	}
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	if (row_ids) {
+		if (int rc = c->d_subset.ensure(n * sizeof(uint32_t)); rc) return rc;
+		RX_HIP(hipMemcpyAsync(c->d_subset.ptr, row_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	}
+	IvfTimer timer;
+	RX_HIP(timer.begin(c->stream));
+	if (int rc = ivf_assign_enqueue(h, coarse, c, row_ids != nullptr, row_ids ? 0 : first_row, n); rc) return rc;
+	RX_HIP(timer.end(c->stream));
+	RX_HIP(hipMemcpyAsync(out_list, c->d_out_row.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	std::lock_guard<std::mutex> lk(h->mtx);
+	h->ivf_dev_rows += n;
+	h->ivf_dev_ms += timer.ms();
+	return RXGPU_OK;
+}
+
+// One k-means iteration's device half (Clustering.cpp:153-230 behind the assignment): the listed rows (or the first n) -> nearest centroid
+// -> per-centroid segments in list order -> ordered sums x 1 / count.  split_clusters and the spherical renormalisation stay with the caller.
+int rxgpu_ivf_kmeans_step(rxgpu_index* h, rxgpu_index* coarse, const uint32_t* row_ids, uint64_t n, float* out_centroids, float* out_hassign, uint32_t* out_assign) {
+	RX_CHECK(h && coarse && out_centroids && out_hassign, RXGPU_ERR_PARAMS, "rxgpu_ivf_kmeans_step: null argument");
+	if (int rc = ivf_train_check(h, coarse, "rxgpu_ivf_kmeans_step"); rc) return rc;
+	RX_CHECK(rxgpu::ivf_train_points_ok(n), RXGPU_ERR_PARAMS, "rxgpu_ivf_kmeans_step: a step takes fewer than 2^24 points");
+	const uint32_t nlist = uint32_t(coarse->count);
+	if (n == 0) {
+		std::fill(out_centroids, out_centroids + size_t(nlist) * h->dim, 0.f);
+		std::fill(out_hassign, out_hassign + nlist, 0.f);
+		return RXGPU_OK;
+	}
+	if (row_ids) {
+		if (int rc = ivf_check_ids(h, row_ids, n, "rxgpu_ivf_kmeans_step"); rc) return rc;
+	} else {
+		RX_CHECK(n <= h->count, RXGPU_ERR_PARAMS, "rxgpu_ivf_kmeans_step: more points than the index holds rows");
+	}
+	DeviceGuard dg(h->device);
+	rxgpu_search_ctx* c = acquire_ctx(h);
+	if (!c) return RXGPU_ERR_DEVICE;
+	CtxLease lease{h, c};
+	const rxgpu::IvfTrainScratch sc = rxgpu::ivf_train_scratch(n, nlist, h->dim);
+	if (int rc = c->d_misc.ensure(sc.bytes); rc) return rc;
+	char* base = static_cast<char*>(c->d_misc.ptr);
+	uint32_t* table = reinterpret_cast<uint32_t*>(base + sc.o_table);
+	uint32_t* seg_off = reinterpret_cast<uint32_t*>(base + sc.o_seg_off);
+	uint32_t* seg_rows = reinterpret_cast<uint32_t*>(base + sc.o_seg_rows);
+	float* centroids = reinterpret_cast<float*>(base + sc.o_centroids);
+	float* hassign = reinterpret_cast<float*>(base + sc.o_hassign);
+	uint32_t* flag = reinterpret_cast<uint32_t*>(base + sc.o_flag);
+	if (row_ids) {
+		if (int rc = c->d_subset.ensure(n * sizeof(uint32_t)); rc) return rc;
+		RX_HIP(hipMemcpyAsync(c->d_subset.ptr, row_ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	}
+	const uint32_t* d_ids = row_ids ? static_cast<const uint32_t*>(c->d_subset.ptr) : nullptr;
+	IvfTimer timer, sums;
+	RX_HIP(timer.begin(c->stream));
+	if (int rc = ivf_assign_enqueue(h, coarse, c, row_ids != nullptr, 0, n); rc) return rc;
+	const uint32_t* assign = static_cast<const uint32_t*>(c->d_out_row.ptr);
+	RX_HIP(hipMemsetAsync(table, 0, sc.o_seg_off - sc.o_table, c->stream));
+	RX_HIP(hipMemsetAsync(flag, 0, sizeof(uint32_t), c->stream));
+	{
+		ProfileScope ps(h, "ivf_place", c->stream);
+		rxgpu::launch_ivf_place(assign, d_ids, uint32_t(n), nlist, table, seg_off, seg_rows, hassign, flag, c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	RX_HIP(sums.begin(c->stream));
+	{
+		ProfileScope ps(h, "ivf_sums", c->stream);
+		rxgpu::launch_ivf_centroid_sums(h->metric, h->d_rows, h->d_inv_norms, h->stride, h->dim, nlist, seg_off, seg_rows, centroids, c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	RX_HIP(sums.end(c->stream));
+	RX_HIP(timer.end(c->stream));
+	uint32_t bad = 0;
+	RX_HIP(hipMemcpyAsync(out_centroids, centroids, size_t(nlist) * h->dim * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipMemcpyAsync(out_hassign, hassign, size_t(nlist) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	if (out_assign) RX_HIP(hipMemcpyAsync(out_assign, assign, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipMemcpyAsync(&bad, flag, sizeof(bad), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	RX_CHECK(bad == 0, RXGPU_ERR_LOGIC, "rxgpu_ivf_kmeans_step: a point found no centroid (non-finite rows are outside the contract)");
+	std::lock_guard<std::mutex> lk(h->mtx);
+	h->ivf_dev_rows += n;
+	h->ivf_dev_steps += 1;
+	h->ivf_dev_ms += timer.ms();
+	h->ivf_sums_ms += sums.ms();
+	return RXGPU_OK;
+}
+
+int rxgpu_ivf_read_train_stats(rxgpu_index* h, uint64_t* rows_assigned, uint64_t* steps, double* kernel_ms, double* sums_ms) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (rows_assigned) *rows_assigned = h->ivf_dev_rows;
+	if (steps) *steps = h->ivf_dev_steps;
+	if (kernel_ms) *kernel_ms = h->ivf_dev_ms;
+	if (sums_ms) *sums_ms = h->ivf_sums_ms;
+	h->ivf_dev_rows = 0;
+	h->ivf_dev_steps = 0;
+	h->ivf_dev_ms = 0.0;
+	h->ivf_sums_ms = 0.0;
+	return RXGPU_OK;
 }
 
 int rxgpu_search_knn_subset_device(rxgpu_index* h, const void* d_queries, uint32_t nq, uint32_t kk, const void* d_row_ids, uint64_t n_ids,

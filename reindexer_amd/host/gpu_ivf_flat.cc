@@ -6,6 +6,7 @@
 #include <mutex>
 #include <thread>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <numeric>
@@ -25,6 +26,14 @@ constexpr size_t kAssignBatch = 256;          // queries per coarse-quantiser ca
 constexpr size_t kMaxPointsPerCentroid = 256; // Clustering.h:45
 constexpr int kIterations = 10;               // Level1Quantizer: cp.niter = 10 (IndexIVF.cpp:48)
 constexpr float kSplitEps = 1.0f / 1024.0f;   // Clustering.cpp: EPS of split_clusters
+constexpr size_t kDeviceStepMaxPoints = size_t(1) << 24;   // rxgpu_ivf_kmeans_step counts in integers: equal to the reference's float counts below 2^24
+
+// RXGPU_IVF_TRAIN=host (read per call): the k-means assignment, compute_centroids and the list assignment of stored rows go through the host
+// again — points copied out of the master copy, uploaded as queries 256 at a time, summed in a scalar loop.  For A/B runs; same bits.
+bool trainOnHost() {
+	const char* e = std::getenv("RXGPU_IVF_TRAIN");
+	return e && std::strcmp(e, "host") == 0;
+}
 
 }  // namespace
 
@@ -202,17 +211,27 @@ void GpuIvfFlat::Train(int seed) {
 		ns = nlist_ * kMaxPointsPerCentroid;
 		pick.resize(ns);
 	}
-	std::vector<float> pts(ns * dim_);
-	for (size_t i = 0; i < ns; ++i) {
+	// Where the arithmetic over the points runs.  On the device (the default) the training list goes up as row numbers and every iteration is
+	// one rxgpu_ivf_kmeans_step over the rows the index already holds: the same k = 1 search, the same ordered single-precision sums.
+	const bool onDevice = !trainOnHost() && ns < kDeviceStepMaxPoints;
+	// training point i as the reference sees it
+	auto preparedPoint = [&](size_t i, float* dst) {
 		const size_t srcRow = pick.empty() ? i : size_t(pick[i]);
 		const float* src = rows_.data() + srcRow * dim_;
-		float* dst = pts.data() + i * dim_;
 		if (metric_ == VectorMetric::Cosine) {
 			const float k = invNorms_[srcRow];
 			for (size_t j = 0; j < dim_; ++j) dst[j] = src[j] * k;
 		} else {
 			std::memcpy(dst, src, dim_ * sizeof(float));
 		}
+	};
+	std::vector<float> pts;            // host path: every prepared point
+	std::vector<uint32_t> trainRows;   // device path: the subsample as row numbers (empty: the first ns rows)
+	if (!onDevice) {
+		pts.resize(ns * dim_);
+		for (size_t i = 0; i < ns; ++i) preparedPoint(i, pts.data() + i * dim_);
+	} else if (!pick.empty()) {
+		trainRows.assign(pick.begin(), pick.end());
 	}
 	const bool spherical = metric_ != VectorMetric::L2;   // IndexIVF.cpp:179-182 (cosine is METRIC_INNER_PRODUCT + is_cosine)
 	// fvec_renorm_L2 (utils/distances.cpp:77-86) over fvec_norm_L2sqr (utils/distances_simd.cpp:216-235): in the AVX-512 build (the SIMD level
@@ -227,12 +246,10 @@ void GpuIvfFlat::Train(int seed) {
 	};
 	centroids_.assign(nlist_ * dim_, 0.f);
 	if (ns == nlist_) {   // corner case: the training set is the centroid table (no post-processing, Clustering.cpp:365-383)
-		std::memcpy(centroids_.data(), pts.data(), nlist_ * dim_ * sizeof(float));
+		for (size_t c = 0; c < nlist_; ++c) preparedPoint(c, centroids_.data() + c * dim_);
 	} else {
 		const std::vector<int> perm = faissRandPerm(ns, int64_t(seed) + 1);
-		for (size_t c = 0; c < nlist_; ++c) {
-			std::memcpy(centroids_.data() + c * dim_, pts.data() + size_t(perm[c]) * dim_, dim_ * sizeof(float));
-		}
+		for (size_t c = 0; c < nlist_; ++c) preparedPoint(size_t(perm[c]), centroids_.data() + c * dim_);   // from the host copy on both paths
 		if (spherical) {
 			for (size_t c = 0; c < nlist_; ++c) renorm(centroids_.data() + c * dim_);
 		}
@@ -240,21 +257,29 @@ void GpuIvfFlat::Train(int seed) {
 		std::vector<float> hassign(nlist_);
 		for (int it = 0; it < kIterations; ++it) {
 			uploadCentroids();
-			assign(pts.data(), ns, a);
-			// compute_centroids (Clustering.cpp:153-230)
-			std::fill(centroids_.begin(), centroids_.end(), 0.f);
-			std::fill(hassign.begin(), hassign.end(), 0.f);
-			for (size_t i = 0; i < ns; ++i) {
-				const float* x = pts.data() + i * dim_;
-				float* c = centroids_.data() + size_t(a[i]) * dim_;
-				hassign[a[i]] += 1.0f;
-				for (size_t j = 0; j < dim_; ++j) c[j] += x[j];
-			}
-			for (size_t ci = 0; ci < nlist_; ++ci) {
-				if (hassign[ci] == 0) continue;
-				const float norm = 1 / hassign[ci];
-				float* c = centroids_.data() + ci * dim_;
-				for (size_t j = 0; j < dim_; ++j) c[j] *= norm;
+			if (onDevice) {
+				// assignment + compute_centroids (Clustering.cpp:153-230) where the rows are: centroids_ and hassign come back, 3 MB at nlist 1024 x 768
+				if (rxgpu_ivf_kmeans_step(dev_, devCentroids_, trainRows.empty() ? nullptr : trainRows.data(), ns, centroids_.data(), hassign.data(), nullptr) !=
+					RXGPU_OK) {
+					throwDevice("GpuIvfFlat: k-means step failed");
+				}
+			} else {
+				assign(pts.data(), ns, a);
+				// compute_centroids (Clustering.cpp:153-230)
+				std::fill(centroids_.begin(), centroids_.end(), 0.f);
+				std::fill(hassign.begin(), hassign.end(), 0.f);
+				for (size_t i = 0; i < ns; ++i) {
+					const float* x = pts.data() + i * dim_;
+					float* c = centroids_.data() + size_t(a[i]) * dim_;
+					hassign[a[i]] += 1.0f;
+					for (size_t j = 0; j < dim_; ++j) c[j] += x[j];
+				}
+				for (size_t ci = 0; ci < nlist_; ++ci) {
+					if (hassign[ci] == 0) continue;
+					const float norm = 1 / hassign[ci];
+					float* c = centroids_.data() + ci * dim_;
+					for (size_t j = 0; j < dim_; ++j) c[j] *= norm;
+				}
 			}
 			// split_clusters (Clustering.cpp:243-290): an empty cluster takes half of a big one, both nudged apart by +-1/1024
 			FaissRng rng(1234);
@@ -294,24 +319,44 @@ void GpuIvfFlat::Train(int seed) {
 	for (auto& l : scan_) l.clear();
 	scanPos_.assign(count_, 0u);
 	listOf_.assign(count_, 0u);
+	std::vector<uint32_t> all;
+	assignStored(0, count_, rows_.data(), all);
+	for (size_t i = 0; i < count_; ++i) {
+		listOf_[i] = all[i];
+		lists_[all[i]].push_back(uint32_t(i));   // rows ascend: every list stays sorted
+		scanAppend(all[i], uint32_t(i));
+	}
+}
+
+// The list of rows [first, first + n), which the device index holds already (x = their raw vectors in the master copy): one
+// rxgpu_ivf_assign over the resident rows; under RXGPU_IVF_TRAIN=host the vectors are prepared here and go up again as queries.
+void GpuIvfFlat::assignStored(size_t first, size_t n, const float* x, std::vector<uint32_t>& out) const {
+	out.resize(n);
+	if (n == 0) return;
+	if (!trainOnHost()) {
+		if (rxgpu_ivf_assign(dev_, devCentroids_, nullptr, first, n, out.data()) != RXGPU_OK) throwDevice("GpuIvfFlat: list assignment failed");
+		return;
+	}
 	std::vector<float> prepared;
 	std::vector<uint32_t> chunkAssign;
 	constexpr size_t kChunk = 1 << 15;
-	for (size_t first = 0; first < count_; first += kChunk) {
-		const size_t n = std::min(kChunk, count_ - first);
-		const float* src = rows_.data() + first * dim_;
+	for (size_t c0 = 0; c0 < n; c0 += kChunk) {
+		const size_t cn = std::min(kChunk, n - c0);
+		const float* src = x + c0 * dim_;
 		if (metric_ == VectorMetric::Cosine) {
-			prepared.resize(n * dim_);
-			for (size_t i = 0; i < n; ++i) NormalizeCopyVector(src + i * dim_, int32_t(dim_), prepared.data() + i * dim_);
+			prepared.resize(cn * dim_);
+			for (size_t i = 0; i < cn; ++i) NormalizeCopyVector(src + i * dim_, int32_t(dim_), prepared.data() + i * dim_);
 			src = prepared.data();
 		}
-		assign(src, n, chunkAssign);
-		for (size_t i = 0; i < n; ++i) {
-			listOf_[first + i] = chunkAssign[i];
-			lists_[chunkAssign[i]].push_back(uint32_t(first + i));   // rows ascend: every list stays sorted
-			scanAppend(chunkAssign[i], uint32_t(first + i));
-		}
+		assign(src, cn, chunkAssign);
+		std::copy(chunkAssign.begin(), chunkAssign.end(), out.begin() + c0);
 	}
+}
+
+GpuIvfFlat::TrainStatsData GpuIvfFlat::TrainStats() const {
+	TrainStatsData st;
+	if (rxgpu_ivf_read_train_stats(dev_, &st.rowsAssigned, &st.steps, &st.kernelMs, &st.sumsMs) != RXGPU_OK) throwDevice("GpuIvfFlat::TrainStats");
+	return st;
 }
 
 void GpuIvfFlat::AddWithIds(size_t n, const float* x, const idx_t* ids) {
@@ -339,15 +384,8 @@ void GpuIvfFlat::AddWithIds(size_t n, const float* x, const idx_t* ids) {
 		throwDevice("GpuIvfFlat: row upload failed");
 	}
 	if (trained_) {
-		std::vector<float> prepared;
-		const float* src = x;
-		if (metric_ == VectorMetric::Cosine) {
-			prepared.resize(n * dim_);
-			for (size_t i = 0; i < n; ++i) NormalizeCopyVector(x + i * dim_, int32_t(dim_), prepared.data() + i * dim_);
-			src = prepared.data();
-		}
 		std::vector<uint32_t> a;
-		assign(src, n, a);
+		assignStored(count_, n, x, a);   // the rows went up just above
 		listOf_.resize(count_ + n);
 		for (size_t i = 0; i < n; ++i) {
 			listOf_[count_ + i] = a[i];

@@ -25,8 +25,9 @@
 //     whose rounding depends on the BLAS library the reference finds at run time — the pin is against FAISS with that shortcut off
 //     (faiss::distance_compute_blas_threshold = INT_MAX), the form that is a function of the reference's code alone.
 //
-// MI355X mapping: both halves are the brute-force engine.  The coarse quantiser is a KNN over the nlist centroids (training assigns 256
-// points per call: the matrix-core batch path); the list scan is knn_scan_subset / knn_range_subset over the row list of the probed
+// MI355X mapping: both halves are the brute-force engine.  The coarse quantiser is a KNN over the nlist centroids (training gathers the
+// prepared points from the resident rows on the device and assigns them in tiles of 256: the matrix-core batch path; the centroid sums are
+// ordered per-centroid chains on the device, ivf_train.hip); the list scan is knn_scan_subset / knn_range_subset over the row list of the probed
 // inverted lists, so a query reads nprobe / nlist of the corpus.  The lists are mirrored into HBM as CSR (rebuilt after a mutation) and a
 // search with nprobe <= 64 is ONE C-ABI call (rxgpu_search_knn_lists): coarse search, list union (bitmap), row list and scan all on the
 // device; the host copy of the lists serves mutations, range search and wider probes.
@@ -77,7 +78,16 @@ public:
 
 	// IndexIVF::train over the vectors ALREADY added (the reference trains on space_'s content, ivf_index.cc:96-108) and moves every
 	// vector into its list.  seed: Clustering::seed (1234).
+	// The arithmetic over the points — the assignment of every iteration, compute_centroids, the closing list assignment — runs on the device
+	// over the rows the index holds (rxgpu_ivf_kmeans_step / rxgpu_ivf_assign; same bits); the RNG, split_clusters and the renormalisation stay
+	// here.  RXGPU_IVF_TRAIN=host in the environment (read per call) or 2^24 training points and more: the host path.
 	void Train(int seed = 1234);
+	// what the device did for Train / AddWithIds since the last call: rows assigned, k-means steps, device milliseconds (of which the sums kernel)
+	struct TrainStatsData {
+		uint64_t rowsAssigned = 0, steps = 0;
+		double kernelMs = 0.0, sumsMs = 0.0;
+	};
+	TrainStatsData TrainStats() const;
 	// add_with_ids: before training the vectors only join the flat storage (the reference's `space_` phase); ids must be unique
 	void AddWithIds(size_t n, const float* x, const idx_t* ids);
 	// remove_ids(IDSelectorArray): returns how many were present
@@ -99,6 +109,7 @@ private:
 	void prepareQuery(const float* x, std::vector<float>& q) const;
 	void coarse(const float* q, size_t nprobe, std::vector<uint32_t>& lists) const;
 	void assign(const float* xPrepared, size_t n, std::vector<uint32_t>& out) const;   // nearest centroid per (prepared) vector, GPU
+	void assignStored(size_t first, size_t n, const float* x, std::vector<uint32_t>& out) const;   // ... of rows the device index already holds
 	void uploadCentroids() const;
 	void reserveRows(size_t need);
 	void listInsert(uint32_t list, uint32_t row);

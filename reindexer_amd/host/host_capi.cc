@@ -1408,6 +1408,17 @@ int rxhost_ivf_list_sizes(void* h, uint32_t* out) {
 int rxhost_ivf_list_ids(void* h, size_t list, int64_t* out) {
 	return guarded([&] { static_cast<const GpuIvfFlat*>(h)->ListIds(list, out); });
 }
+// GpuIvfFlat::TrainStats: counts = {rows assigned on the device, k-means steps run there}, ms = {device time of those calls, of which the
+// sums kernel} since the last call — all zero when RXGPU_IVF_TRAIN=host kept the work on the host
+int rxhost_ivf_train_stats(void* h, uint64_t* counts, double* ms) {
+	return guarded([&] {
+		const auto st = static_cast<const GpuIvfFlat*>(h)->TrainStats();
+		counts[0] = st.rowsAssigned;
+		counts[1] = st.steps;
+		ms[0] = st.kernelMs;
+		ms[1] = st.sumsMs;
+	});
+}
 int rxhost_ivf_centroids(void* h, float* out) {
 	return guarded([&] {
 		const auto& c = static_cast<const GpuIvfFlat*>(h)->Centroids();

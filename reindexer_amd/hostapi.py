@@ -1351,6 +1351,7 @@ class GpuIvfFlat:
             L.rxhost_ivf_info.argtypes = [_vp, _vp]
             L.rxhost_ivf_list_sizes.argtypes = [_vp, _vp]
             L.rxhost_ivf_centroids.argtypes = [_vp, _vp]
+            L.rxhost_ivf_train_stats.argtypes = [_vp, _vp, _vp]
             L._ivf_bound = True
         self.dim, self.metric, self.nlist = dim, metric, nlist
         self.h = L.rxhost_ivf_create(metric, dim, nlist, device)
@@ -1385,9 +1386,21 @@ class GpuIvfFlat:
             _raise(rc)
 
     def train(self, seed: int = 1234):
+        """IndexIVF::train over the vectors already added.  The assignment of every k-means iteration, the centroid sums and the closing list
+        assignment run on the device over the rows it holds (rxgpu_ivf_kmeans_step / rxgpu_ivf_assign) with the host path's bits;
+        RXGPU_IVF_TRAIN=host in the environment (read per call) keeps them on the host."""
         rc = lib().rxhost_ivf_train(self.h, seed)
         if rc:
             _raise(rc)
+
+    def train_stats(self) -> dict:
+        """What the device did for train() / add_with_ids() since the last call: rows_assigned, steps (k-means iterations), kernel_ms (device
+        time of those calls) and sums_ms (the centroid sums' part).  All zero where RXGPU_IVF_TRAIN=host kept the work on the host."""
+        counts, ms = np.zeros(2, np.uint64), np.zeros(2, np.float64)
+        rc = lib().rxhost_ivf_train_stats(self.h, counts.ctypes.data, ms.ctypes.data)
+        if rc:
+            _raise(rc)
+        return {"rows_assigned": int(counts[0]), "steps": int(counts[1]), "kernel_ms": float(ms[0]), "sums_ms": float(ms[1])}
 
     def remove_ids(self, ids) -> int:
         ids = np.ascontiguousarray(ids, np.int64).reshape(-1)

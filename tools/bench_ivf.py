@@ -2,22 +2,142 @@
 """IVF-Flat on the GPU engines (first cut): build (k-means on the matrix-core batch path) and search at several nprobe.
 
     python tools/bench_ivf.py --rows 1000000 --dim 768 --nlist 1024 --queries 200 [--out profiles/r1_ivf_1m.json]
+    python tools/bench_ivf.py --train-ab --rows 1000000 --dim 768 --nlist 1024 [--metric l2] [--parent-root DIR] [--out FILE]
+        train() on the device path against RXGPU_IVF_TRAIN=host (and a checkout of the parent commit), every leg in a fresh child process
 
 Per query: coarse quantiser (KNN over the centroids) -> host merge of the probed lists' rows -> row-list scan (knn_scan_subset).  Recall@k is
 measured against the exact result (the same index with every list probed, which the tests pin to the brute-force oracle).  There is no CPU
 line: the reference's IVF backend is FAISS, which cannot be built in this image (BLAS)."""
 import argparse
 import json
+import os
+import shutil
+import statistics
+import subprocess
 import sys
+import tempfile
 import time
+import zlib
 from pathlib import Path
 
 import numpy as np
 
 ROOT = Path(__file__).resolve().parents[1]
+if "--root" in sys.argv:   # a training leg over another checkout of the package (the parent commit, built in place)
+    ROOT = Path(sys.argv[sys.argv.index("--root") + 1]).resolve()
 sys.path.insert(0, str(ROOT))
 
 from reindexer_amd import capi, hostapi  # noqa: E402
+
+HBM_SPEC_BYTES_PER_S = 8.0e12   # MI355X HBM3E specification
+
+
+def make_rows(rows, dim, clusters, seed=20260924):
+    """the bench's clustered corpus, in float32 from the start (3 GB at 1M x 768: one generation serves every leg)"""
+    rng = np.random.default_rng(seed)
+    centres = rng.standard_normal((clusters, dim), dtype=np.float32) * np.float32(0.25)
+    out = np.empty((rows, dim), np.float32)
+    step = 65536
+    for a in range(0, rows, step):
+        b = min(rows, a + step)
+        out[a:b] = centres[rng.integers(0, clusters, b - a)] + rng.standard_normal((b - a, dim), dtype=np.float32) * np.float32(0.08)
+    return out
+
+
+def train_leg(args):
+    """One timed train() in this process: rows from --rows-file, one small warm-up index first (it loads the kernels every leg uses), then
+    add_with_ids + train() on the clock (train() ends in device synchronisation).  Prints one JSON line."""
+    metric = capi.METRICS[args.metric]
+    rows = np.load(args.rows_file, mmap_mode="r")
+    n, dim = rows.shape
+    warm = hostapi.GpuIvfFlat(metric, dim, 16)
+    warm.add_with_ids(np.ascontiguousarray(rows[:8192]), np.arange(8192, dtype=np.int64))
+    warm.train()
+    warm.close()
+    ivf = hostapi.GpuIvfFlat(metric, dim, args.nlist)
+    t0 = time.perf_counter()
+    step = 100_000
+    for a in range(0, n, step):
+        ivf.add_with_ids(np.ascontiguousarray(rows[a:a + step]), np.arange(a, min(n, a + step), dtype=np.int64))
+    add_s = time.perf_counter() - t0
+    if hasattr(ivf, "train_stats"):
+        ivf.train_stats()
+    t0 = time.perf_counter()
+    ivf.train()
+    train_s = time.perf_counter() - t0
+    stats = ivf.train_stats() if hasattr(ivf, "train_stats") else None
+    sizes = ivf.list_sizes()
+    out = {"leg": args.train_leg, "train_seconds": train_s, "add_seconds": add_s, "stats": stats,
+           "centroids_crc32": zlib.crc32(np.ascontiguousarray(ivf.centroids()).tobytes()), "list_sizes_crc32": zlib.crc32(sizes.tobytes()),
+           "RXGPU_IVF_TRAIN": os.environ.get("RXGPU_IVF_TRAIN")}
+    ivf.close()
+    print("LEG " + json.dumps(out), flush=True)
+
+
+def train_ab(args):
+    """train() under the default (device) path, under RXGPU_IVF_TRAIN=host and, with --parent-root, in a checkout of the parent commit: the
+    same rows, every leg in a fresh child process, the legs alternating, --repeat of each; medians.  kernel_ms / sums_ms are the device
+    path's own event pairs (GpuIvfFlat.train_stats); the sums kernel's bytes are counted from the shapes (10 iterations over
+    min(rows, 256 nlist) points: every point's row once per iteration, its row number and 1 / |x| per 64-column tile, the table once)."""
+    tmp = Path(tempfile.mkdtemp(prefix="bench_ivf_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None))
+    try:
+        rows_file = tmp / "rows.npy"
+        np.save(rows_file, make_rows(args.rows, args.dim, args.clusters))
+        legs = [("device", None, None), ("host", "host", None)]
+        if args.parent_root:
+            legs.append(("parent", None, args.parent_root))
+        runs = {name: [] for name, _, _ in legs}
+        for rep in range(args.repeat):
+            for name, env_value, root in legs:
+                env = dict(os.environ)
+                env.pop("RXGPU_IVF_TRAIN", None)
+                if env_value:
+                    env["RXGPU_IVF_TRAIN"] = env_value
+                cmd = [sys.executable, str(Path(__file__).resolve()), "--train-leg", name, "--rows-file", str(rows_file), "--nlist", str(args.nlist),
+                       "--metric", args.metric]
+                if root:
+                    cmd += ["--root", root]
+                res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=args.leg_timeout)
+                line = [l for l in res.stdout.splitlines() if l.startswith("LEG ")]
+                if res.returncode != 0 or not line:
+                    raise RuntimeError(f"leg {name} failed (rc {res.returncode}): {res.stderr[-2000:]}")
+                runs[name].append(json.loads(line[-1][4:]))
+                print(f"# rep {rep} {name}: train {runs[name][-1]['train_seconds']:.3f} s", file=sys.stderr, flush=True)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+    def summary(name):
+        t = [r["train_seconds"] for r in runs[name]]
+        out = {"train_seconds_median": statistics.median(t), "train_seconds_min": min(t), "train_seconds_max": max(t), "train_seconds": t,
+               "add_seconds_median": statistics.median(r["add_seconds"] for r in runs[name])}
+        st = [r["stats"] for r in runs[name] if r["stats"]]
+        if st:
+            out["stats_median"] = {k: statistics.median(s[k] for s in st) for k in st[0]}
+        return out
+
+    ns = min(args.rows, 256 * args.nlist)
+    tiles = -(-args.dim // 64)
+    cosine = args.metric == "cosine"
+    sums_bytes = 10 * (ns * (args.dim * 4 + 4 * tiles * (2 if cosine else 1)) + args.nlist * args.dim * 4)
+    out = {"workload": f"IVF-Flat train(), {args.metric}, {args.rows} x {args.dim}, nlist={args.nlist}, {args.clusters} gaussian clusters; "
+                       f"k-means 10 iterations over {ns} points + list assignment of every row",
+           "arch": capi.device_arch(0), "repeat": args.repeat, "protocol": "every leg a fresh child process over the same rows (one warm-up index of 8192 rows "
+           "first), legs alternating; host clock around train(), which ends in a device synchronisation",
+           "legs": {name: summary(name) for name in runs}}
+    crcs = {(r["centroids_crc32"], r["list_sizes_crc32"]) for name in runs for r in runs[name]}
+    out["every_leg_same_centroid_bits_and_list_sizes"] = len(crcs) == 1
+    dev = out["legs"]["device"]
+    out["device_over_host"] = dev["train_seconds_median"] / out["legs"]["host"]["train_seconds_median"]
+    if "parent" in out["legs"]:
+        out["device_over_parent"] = dev["train_seconds_median"] / out["legs"]["parent"]["train_seconds_median"]
+    if "stats_median" in dev and dev["stats_median"]["sums_ms"] > 0:
+        sums_s = dev["stats_median"]["sums_ms"] * 1e-3
+        out["sums_kernel"] = {"bytes_10_iterations": sums_bytes, "ms_10_iterations": dev["stats_median"]["sums_ms"], "bytes_per_second": sums_bytes / sums_s,
+                              "fraction_of_hbm_spec_8TBps": sums_bytes / sums_s / HBM_SPEC_BYTES_PER_S}
+    text = json.dumps(out)
+    print(text)
+    if args.out:
+        Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
 
 
 def main():
@@ -31,7 +151,18 @@ def main():
     ap.add_argument("--metric", default="cosine")
     ap.add_argument("--nprobe", default="1,4,16,64,128,256")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--train-ab", action="store_true", help="time train() on the device path, under RXGPU_IVF_TRAIN=host (and in --parent-root), fresh processes")
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit (its reindexer_amd package) for a third leg")
+    ap.add_argument("--leg-timeout", type=int, default=300)
+    ap.add_argument("--train-leg", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--rows-file", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.train_leg:
+        return train_leg(args)
+    if args.train_ab:
+        return train_ab(args)
     metric = capi.METRICS[args.metric]
     rng = np.random.default_rng(20260924)
     centres = rng.normal(0, 0.25, (args.clusters, args.dim)).astype(np.float32)
@@ -52,7 +183,7 @@ def main():
     exact = [ivf.search(q, args.k, nprobe=args.nlist)[1] for q in queries]
     out = {"workload": f"IVF-Flat {args.metric}, {args.rows} x {args.dim}, nlist={args.nlist}, k={args.k}, {args.clusters} gaussian clusters",
            "arch": capi.device_arch(0), "add_seconds": add_s,
-           "train_seconds": train_s, "train": "k-means 10 iterations over min(rows, 256 * nlist) points + assignment of every row, 256 points per device call",
+           "train_seconds": train_s, "train": "k-means 10 iterations over min(rows, 256 * nlist) points + assignment of every row, on the device from the resident rows (RXGPU_IVF_TRAIN=host: through host queries, 256 points per device call)",
            "list_sizes": {"min": int(sizes.min()), "median": float(np.median(sizes)), "max": int(sizes.max()), "empty": int((sizes == 0).sum())},
            "nprobe": []}
     for nprobe in [int(x) for x in args.nprobe.split(",")]:
