@@ -361,6 +361,29 @@ int rxgpu_hnsw_patch_graph(rxgpu_index* h, uint32_t n_dirty, const uint32_t* dir
 /* MarkDelete mirror (hnswalg.h:1303-1339): refresh only the flags. */
 int rxgpu_hnsw_update_deleted(rxgpu_index* h, const uint8_t* deleted, uint64_t num_deleted);
 
+/* The level-0 graph built on the device in batches (addPoint's level-0 half, hnswalg.h:1694-1852, 977-1024, 1042-1180, for many rows at
+ * once against the graph as it was before them — the form the reference accepts from its concurrent build).  Rows [first_row, first_row + n)
+ * are uploaded (rxgpu_index_upload_rows) but not linked; first_row must equal the attached node count (>= 1).  Per row i: SearchKnn as
+ * rxgpu_hnsw_search_knn defines it with k = ef = ef_construction over the nodes < first_row, the stored row as the query (cosine: the raw
+ * row); the distances HnswGraph::distIds gives for i and the rows found; getNeighborsByHeuristic2 (M kept at most); the list of i in the
+ * order mutuallyConnectNewElement writes it.  Per node t that received links: the new rows appended in ascending order while the list has
+ * room, else ONE getNeighborsByHeuristic2 over its list and all the incoming rows (the reference: one per incoming link).  Afterwards the
+ * attached node count is first_row + n; the upper lists of the new nodes follow through rxgpu_hnsw_patch_upper, before the next batch or
+ * search.  Graphs without deleted nodes, M <= 64, ef_construction <= 256: RXGPU_ERR_PARAMS otherwise.  RXGPU_ERR_OVERFLOW: the level-0
+ * array allocated by the last attach cannot take the rows — attach the graph again.  Synchronises. */
+int rxgpu_hnsw_link_batch(rxgpu_index* h, uint64_t first_row, uint64_t n, uint32_t ef_construction);
+/* The upper lists only (addPoint's levels >= 1, hnswalg.h:1694-1852, built on the host): rxgpu_hnsw_patch_graph without level 0 and
+ * delete flags.  ids [n_nodes]: every node whose upper lists changed; the nodes rxgpu_hnsw_link_batch added all listed, ascending (level 0
+ * nodes too: levels[j] = 0); levels / upper_rows as for rxgpu_hnsw_patch_graph.  RXGPU_ERR_OVERFLOW: attach the graph again. */
+int rxgpu_hnsw_patch_upper(rxgpu_index* h, uint32_t n_nodes, const uint32_t* ids, const int32_t* levels, const uint32_t* upper_rows, int32_t maxlevel,
+						   uint32_t entry);
+/* Level-0 lists [first_row, first_row + n) of the mirror, out [n][1 + max_m0] (mutuallyConnectNewElement's result, hnswalg.h:1042-1180). */
+int rxgpu_hnsw_read_links0(rxgpu_index* h, uint64_t first_row, uint64_t n, uint32_t* out);
+/* rxgpu_hnsw_link_batch since the last call (hnswalg.h:1694-1852, 977-1024, 1042-1180 on the device): rows linked, batches, nodes whose
+ * list was re-selected, nodes with more than 256 entries (finished by a second launch), and phase_ms [3] = search, select + pair grouping,
+ * back-links (the search: wall clock of the call, which drains its stream; the others between events).  Any may be NULL. */
+int rxgpu_hnsw_read_build_stats(rxgpu_index* h, uint64_t* rows, uint64_t* batches, uint64_t* reselected, uint64_t* past_cap, double* phase_ms);
+
 /* SearchKnn for nq queries (host in/out).  ef == 0 means k*3/2 like the engine (hnswalg.h:1995); ef <= 4096
  * (RXGPU_ERR_PARAMS above that; from ef = 1025 on the candidate heap lives in global scratch instead of LDS).
  * Writes, per query, the members of the reference's top_candidates after trimming to k (UNORDERED: the Map pushes them into the

@@ -93,6 +93,10 @@ _SIGNATURES = {
     "rxgpu_hnsw_read_stats4": (_i, [_vp, _vp]),
     "rxgpu_hnsw_attach_sq8": (_i, [_vp, _vp, _vp, _u64, _f]),
     "rxgpu_hnsw_upload_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp, _f]),
+    "rxgpu_hnsw_link_batch": (_i, [_vp, _u64, _u64, _u32]),
+    "rxgpu_hnsw_patch_upper": (_i, [_vp, _u32, _vp, _vp, _vp, C.c_int32, _u32]),
+    "rxgpu_hnsw_read_links0": (_i, [_vp, _u64, _u64, _vp]),
+    "rxgpu_hnsw_read_build_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
     "rxgpu_hnsw_quantize_sq8": (_i, [_vp, _u64, _u64, _f, _f, _f, _f]),
     "rxgpu_hnsw_read_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp]),
     "rxgpu_hnsw_read_sq8_quantize_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
@@ -466,6 +470,36 @@ class VectorIndex:
         blocks = int(upper_off[-1])
         _check(lib().rxgpu_hnsw_attach_graph(self._h, links0.ctypes.data, upper_off.ctypes.data, upper.ctypes.data, blocks, deleted.ctypes.data,
                                              g["M"], g["maxM0"], g["maxlevel"], g["entry"], g["num_deleted"]))
+
+    def hnsw_link_batch(self, first_row: int, n: int, ef_construction: int) -> None:
+        """Rows [first_row, first_row + n) — uploaded, first_row = the attached node count — searched against the graph before them, given
+        their level-0 lists and linked back, on the device (rxgpu_hnsw_link_batch)."""
+        _check(lib().rxgpu_hnsw_link_batch(self._h, first_row, n, ef_construction))
+
+    def hnsw_patch_upper(self, ids, levels, upper_rows, maxlevel: int, entry: int) -> None:
+        """The upper lists of the listed nodes (every node of the last batch among them, ascending) into the mirror; upper_rows = their
+        blocks of 1 + M words concatenated in that order (rxgpu_hnsw_patch_upper)."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        levels = np.ascontiguousarray(levels, np.int32).reshape(-1)
+        upper_rows = np.ascontiguousarray(upper_rows, np.uint32).reshape(-1)
+        if ids.shape[0] != levels.shape[0]:
+            raise ValueError("one level per node")
+        _check(lib().rxgpu_hnsw_patch_upper(self._h, ids.shape[0], ids.ctypes.data, levels.ctypes.data, upper_rows.ctypes.data if upper_rows.size else None,
+                                            maxlevel, entry))
+
+    def hnsw_read_links0(self, first_row: int, n: int, max_m0: int):
+        """Level-0 lists [n][1 + max_m0] of the mirror (rxgpu_hnsw_read_links0)."""
+        out = np.empty((n, 1 + max_m0), np.uint32)
+        _check(lib().rxgpu_hnsw_read_links0(self._h, first_row, n, out.ctypes.data))
+        return out
+
+    def hnsw_read_build_stats(self) -> dict:
+        """rxgpu_hnsw_link_batch since the last call: rows, batches, nodes re-selected, nodes past the kernel's cap, milliseconds per phase."""
+        rows, batches, resel, over = _u64(0), _u64(0), _u64(0), _u64(0)
+        ms = (C.c_double * 3)()
+        _check(lib().rxgpu_hnsw_read_build_stats(self._h, C.byref(rows), C.byref(batches), C.byref(resel), C.byref(over), ms))
+        return dict(rows=int(rows.value), batches=int(batches.value), reselected=int(resel.value), past_cap=int(over.value),
+                    search_ms=float(ms[0]), select_ms=float(ms[1]), backlink_ms=float(ms[2]))
 
     def hnsw_update_deleted(self, deleted, num_deleted: int) -> None:
         deleted = np.ascontiguousarray(deleted, np.uint8)

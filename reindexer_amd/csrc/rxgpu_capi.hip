@@ -368,6 +368,8 @@ void rxgpu_index_destroy(rxgpu_index* h) {
 	if (h->d_list_rows) (void)hipFree(h->d_list_rows);
 	if (h->d_corr) (void)hipFree(h->d_corr);
 	if (h->d_hnsw_stats) (void)hipFree(h->d_hnsw_stats);
+	h->build_scratch.release();
+	h->build_nodes.release();
 	delete h;
 }
 

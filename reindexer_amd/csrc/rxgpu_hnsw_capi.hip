@@ -158,6 +158,7 @@ struct HnswCall {
 	uint32_t* out_row;
 	uint32_t* out_count;
 	const rxgpu::HnswSink* sink;
+	bool dev_q = false;          // the queries are float rows in HBM already ([nq][dim]): read where they are, nothing is uploaded
 	size_t row_bytes = 0;        // of one query
 	rxgpu::HnswParams p{};       // what every launch of the call shares
 	const void* d_q = nullptr;   // where the kernels read the queries
@@ -168,7 +169,9 @@ struct HnswCall {
 	// Output and query buffers, the early zeroing, the staging buffer, the first upload, and the parameters every launch shares.
 	int stage_and_upload(const float* qcorr, const float* qnorm, uint32_t ef) {
 		row_bytes = size_t(h->dim) * (sq8 ? sizeof(uint8_t) : sizeof(float));
-		if (int rc = c->d_queries.ensure(sq8 ? pl.o_qnorm + size_t(nq) * 4 : size_t(nq) * row_bytes); rc) return rc;
+		if (!dev_q) {   // (queries in HBM are read where they are)
+			if (int rc = c->d_queries.ensure(sq8 ? pl.o_qnorm + size_t(nq) * 4 : size_t(nq) * row_bytes); rc) return rc;
+		}
 		if (int rc = c->d_out_dist.ensure(size_t(nq) * k * sizeof(float)); rc) return rc;
 		if (int rc = c->d_out_row.ensure(size_t(nq) * k * sizeof(uint32_t)); rc) return rc;
 		if (int rc = c->d_out_count.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
@@ -195,8 +198,10 @@ struct HnswCall {
 				RX_HIP(hipHostGetDevicePointer(&dv, hp, 0));
 				zc_dev = static_cast<char*>(dv);
 			}
-			std::memcpy(hp, queries, size_t(nq) * row_bytes);
-			up_queries = hp;
+			if (!dev_q) {
+				std::memcpy(hp, queries, size_t(nq) * row_bytes);
+				up_queries = hp;
+			}
 			if (sq8) {
 				std::memcpy(hp + pl.st_corr, qcorr, size_t(nq) * 4);
 				std::memcpy(hp + pl.st_norm, qnorm, size_t(nq) * 4);
@@ -207,8 +212,8 @@ struct HnswCall {
 			dl_dist = reinterpret_cast<float*>(hp + pl.st_dist);
 			dl_row = reinterpret_cast<uint32_t*>(hp + pl.st_row);
 		}
-		d_q = pl.zero_copy ? static_cast<void*>(zc_dev) : c->d_queries.ptr;
-		if (!pl.zero_copy) RX_HIP(hipMemcpyAsync(c->d_queries.ptr, up_queries, size_t(pl.part_q) * row_bytes, hipMemcpyHostToDevice, c->stream));
+		d_q = dev_q ? queries : pl.zero_copy ? static_cast<void*>(zc_dev) : c->d_queries.ptr;
+		if (!pl.zero_copy && !dev_q) RX_HIP(hipMemcpyAsync(c->d_queries.ptr, up_queries, size_t(pl.part_q) * row_bytes, hipMemcpyHostToDevice, c->stream));
 		if (sq8) {
 			char* qb = static_cast<char*>(c->d_queries.ptr);
 			RX_HIP(hipMemcpyAsync(qb + pl.o_qcorr, up_qcorr, size_t(nq) * 4, hipMemcpyHostToDevice, c->stream));
@@ -338,7 +343,7 @@ struct HnswCall {
 					const uint32_t cnt = std::min(pl.part_q, nq - qa);
 					hipStream_t st = (part & 1u) ? sb : c->stream;
 					const size_t off = size_t(qa) * row_bytes;
-					RX_HIP(hipMemcpyAsync(static_cast<char*>(c->d_queries.ptr) + off, static_cast<const char*>(queries) + off, size_t(cnt) * row_bytes, hipMemcpyHostToDevice, st));
+					if (!dev_q) RX_HIP(hipMemcpyAsync(static_cast<char*>(c->d_queries.ptr) + off, static_cast<const char*>(queries) + off, size_t(cnt) * row_bytes, hipMemcpyHostToDevice, st));
 					launch_part(qa, cnt, qa, st, helpers);
 				}
 				RX_HIP(hipEventRecord(c->split_done, sb));
@@ -398,7 +403,7 @@ struct HnswCall {
 // ([nq][kk] distances | [nq][kk] local rows, invalid entries past a query's count) instead of travelling to the host; only the counts
 // come back (the re-run tiers are driven by them).  The stream is drained before the call returns.
 int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef, float* out_dist,
-					 uint32_t* out_row, uint32_t* out_count, const rxgpu::HnswSink* sink = nullptr, bool try_server = true) {
+					 uint32_t* out_row, uint32_t* out_count, const rxgpu::HnswSink* sink = nullptr, bool try_server = true, bool dev_q = false) {
 	// 1. validate and normalise
 	const bool sq8 = qcorr != nullptr;
 	const bool to_host = sink == nullptr;
@@ -432,7 +437,7 @@ int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, co
 	const HnswLaunchPlan pl =
 		rxgpu::plan_hnsw_search(h->count, h->dim, h->graph_deleted == 0, nq, k, ef, sq8, to_host, uint64_t(free_b) + c->d_visited.bytes, knobs);
 	// 5. staging and the first upload
-	HnswCall call{h, c, pl, nq, k, sq8, queries, out_dist, out_row, out_count, sink};
+	HnswCall call{h, c, pl, nq, k, sq8, queries, out_dist, out_row, out_count, sink, dev_q};
 	if (int rc = call.stage_and_upload(qcorr, qnorm, ef); rc) return rc;
 	const uint32_t* const counts = call.dl_count;
 	std::vector<uint32_t> redo;
@@ -690,6 +695,19 @@ int hnsw_search_to_sink(rxgpu_index* shard, const void* queries, const float* qc
 	RX_CHECK(!qcorr || (shard->d_codes && shard->sq8_n == shard->count), RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_knn_sq8: SQ8 codes are not attached / out of date on a shard");
 	return hnsw_search_impl(shard, queries, qcorr, qnorm, nq, k, ef, nullptr, nullptr, counts.data(), &sink);
 }
+// The construction searches of one build batch (rxgpu_hnsw_build.hip): the queries are nq packed float rows in HBM, the graph is the one of
+// the first `nodes` rows — the rows behind them are stored but not linked yet, so for the length of the call the index counts `nodes` rows.
+// The caller holds the index exclusively (a build batch changes the lists the searches read).
+int hnsw_search_rows_to_sink(rxgpu_index* h, const float* d_queries, uint32_t nq, uint32_t k, uint32_t ef, uint64_t nodes, const HnswSink& sink) {
+	struct CountAs {
+		rxgpu_index* h;
+		uint64_t keep;
+		~CountAs() { h->count = keep; }
+	} restore{h, h->count};
+	h->count = nodes;
+	std::vector<uint32_t> counts(nq);
+	return hnsw_search_impl(h, d_queries, nullptr, nullptr, nq, k, ef, nullptr, nullptr, counts.data(), &sink, false, true);
+}
 }  // namespace rxgpu
 
 extern "C" {
@@ -734,6 +752,7 @@ int rxgpu_hnsw_attach_graph(rxgpu_index* h, const uint32_t* links0, const uint64
 		RX_HIP(hipMemset(h->d_hnsw_stats, 0, 8 * sizeof(unsigned long long)));
 	}
 	h->graph_n = n;
+	h->graph_upper_nodes = n;
 	h->graph_M = M;
 	h->graph_maxM0 = max_m0;
 	h->graph_maxlevel = maxlevel;
@@ -816,6 +835,7 @@ int rxgpu_hnsw_patch_graph(rxgpu_index* h, uint32_t n_dirty, const uint32_t* dir
 	}
 	h->graph_upper_used = used;
 	h->graph_n = n_new;
+	h->graph_upper_nodes = n_new;
 	h->graph_maxlevel = maxlevel;
 	h->graph_entry = entry;
 	h->graph_deleted = num_deleted;

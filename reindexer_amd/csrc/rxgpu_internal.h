@@ -508,6 +508,8 @@ struct HnswSink {
 };
 // queries: float rows, or (qcorr != null) SQ8 codes with their corrective offsets and normCoefs — the shard then searches its code table
 int hnsw_search_to_sink(struct ::rxgpu_index* shard, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef, const HnswSink& sink);
+// nq packed float rows in HBM as queries over the graph of the first `nodes` rows (the construction searches of a build batch)
+int hnsw_search_rows_to_sink(struct ::rxgpu_index* h, const float* d_queries, uint32_t nq, uint32_t k, uint32_t ef, uint64_t nodes, const HnswSink& sink);
 int sharded_hnsw_search_knn(struct ::rxgpu_index* h, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef, float* out_dist,
 							uint32_t* out_row, uint32_t* out_count);
 int sharded_hnsw_search_range(struct ::rxgpu_index* h, const float* query, float radius, uint32_t ef, float* out_dist, uint32_t* out_row, uint64_t cap,
@@ -621,6 +623,14 @@ struct rxgpu_index {
 	int graph_maxlevel = -1;
 	uint32_t graph_entry = 0;
 	bool graph_attached = false;
+	// The batched level-0 build (rxgpu_hnsw_build.hip).  graph_upper_nodes: nodes whose upper lists are mirrored — graph_n, except between a
+	// rxgpu_hnsw_link_batch and the rxgpu_hnsw_patch_upper that follows it.  build_nodes: the two per-node words of the pair grouping
+	// (hnsw_build_plan.h), allocated with the first batch for the graph's row capacity and all zero between batches.
+	uint64_t graph_upper_nodes = 0;
+	rxgpu_devbuf build_scratch, build_nodes;
+	uint64_t build_nodes_cap = 0;
+	uint64_t build_rows = 0, build_batches = 0, build_reselected = 0, build_over = 0;   // since rxgpu_hnsw_read_build_stats
+	double build_ms[3] = {0.0, 0.0, 0.0};                                                // search, select, back-link
 	unsigned long long* d_hnsw_stats = nullptr;
 	// the resident search kernels' mailboxes, made at the first single query of the class: [0] floats, ef <= 128; [1] floats, ef <= 256;
 	// [2] / [3] the same two over the SQ8 codes.  Written once under mtx (release), read without it (acquire).

@@ -4,11 +4,14 @@
 #include <cstring>
 
 #include <algorithm>
+#include <chrono>
 #include <queue>
+#include <thread>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../csrc/hnsw_build_plan.h"
 #include "rxgpu.h"
 
 namespace rxgpu::host {
@@ -115,7 +118,7 @@ void GpuHnswMap::rebindDevice(rxgpu_index* external) {
 }
 
 GpuHnswMap::GpuHnswMap(const GpuHnswMap& other, size_t newCapacity)
-	: graph_(other.graph_, other.sh_ ? 1 : newCapacity), device_(other.device_), synchronization_(other.synchronization_), ownsDev_(!other.sh_) {
+	: graph_((other.flushPending(), other.graph_), other.sh_ ? 1 : newCapacity), device_(other.device_), synchronization_(other.synchronization_), ownsDev_(!other.sh_) {
 	if (other.sh_) {   // copy-on-write tx clone of a Map over a device list: every shard cloned, a sharded handle of its own
 		const ShardedState& O = *other.sh_;
 		sh_ = std::make_unique<ShardedState>();
@@ -212,8 +215,65 @@ void GpuHnswMap::shSyncAll() const {
 
 void GpuHnswMap::AddPointNoLock(ConstFloatVectorView vect, FloatVectorId id) {
 	if (sh_) return shRoute(id.AsNumber()).AddPointNoLock(vect, id);
-	graph_.AddPoint(vect.Data(), id.AsNumber());
+	addNoLock(vect.Data(), id.AsNumber());
+}
+
+void GpuHnswMap::addNoLock(const float* data, labeltype label) {
+	flushPending();
+	graph_.AddPoint(data, label);
 	graphDirty_ = true;
+}
+
+namespace {
+bool deviceBuildAsked() noexcept {
+	const char* e = std::getenv("RXGPU_HNSW_BUILD");
+	return e && std::strcmp(e, "device") == 0;
+}
+}  // namespace
+
+// Device mode.  Which builds the device takes is decided here for what never changes (M, efConstruction) and for deleted nodes, whose slots
+// an insertion recycles: such a point goes through the host insertion at once — under deferMtx_, so that stored rows and host insertions
+// never interleave (MarkDelete has flushed: while deleted nodes exist nothing is pending).  A label that exists is an in-place update.
+bool GpuHnswMap::deferInsert(const float* data, labeltype label) {
+	if (sh_ || !ownsDev_ || !deviceBuildAsked()) return false;
+	const int path = rxgpu::hnsw_build_path(0, uint32_t(graph_.M()), uint32_t(graph_.EfConstruction()), false);
+	std::lock_guard<std::mutex> lk(deferMtx_);
+	if (path == rxgpu::kHnswBuildDevice && graph_.DeletedCount() == 0 && !graph_.HasLabelSync(label)) {
+		graph_.AppendUnlinked(data, label);
+		return true;
+	}
+	if (path != rxgpu::kHnswBuildDevice) {   // never eligible: the usual insertion, concurrent as ever
+		build_.hostRows += 1;
+		build_.hostReason = path;
+		return false;
+	}
+	if (graph_.DeletedCount() != 0) {
+		build_.hostRows += 1;
+		build_.hostReason = rxgpu::kHnswBuildHostDeleted;
+	}
+	flushPending();
+	graph_.AddPoint(data, label);
+	graphDirty_ = true;
+	return true;
+}
+
+void GpuHnswMap::AddPoints(const float* vectors, const labeltype* labels, size_t n) {
+	for (size_t i = 0; i < n; ++i) {
+		const float* v = vectors + i * graph_.Dim();
+		if (sh_) {
+			shRoute(labels[i]).addNoLock(v, labels[i]);
+		} else if (!deferInsert(v, labels[i])) {
+			addNoLock(v, labels[i]);
+		}
+	}
+}
+
+GpuHnswMap::BuildStats GpuHnswMap::ReadBuildStats() const {
+	std::lock_guard<std::mutex> defer(deferMtx_);
+	std::lock_guard<std::mutex> lk(syncMtx_);
+	const BuildStats out = build_;
+	build_ = BuildStats{};
+	return out;
 }
 
 void GpuHnswMap::AddPointConcurrent(ConstFloatVectorView vect, FloatVectorId id) {
@@ -221,6 +281,8 @@ void GpuHnswMap::AddPointConcurrent(ConstFloatVectorView vect, FloatVectorId id)
 		throw std::logic_error("This HNSW index does not support concurrent insertions");   // hnswalg.h:1393-1399 (Synchronization::None)
 	}
 	if (sh_) return shRoute(id.AsNumber()).AddPointConcurrent(vect, id);
+	if (deferInsert(vect.Data(), id.AsNumber())) return;
+	flushPending();   // (rows stored while the variable said "device" are linked before a host insertion, whatever it says now)
 	graph_.AddPointConcurrent(vect.Data(), id.AsNumber());
 	graphDirty_ = true;
 }
@@ -237,6 +299,7 @@ void GpuHnswMap::MarkDelete(FloatVectorId id) {
 		}
 		return S.maps[s]->MarkDelete(id);
 	}
+	flushPending();
 	graph_.MarkDelete(id.AsNumber());
 	deletedDirty_ = true;
 }
@@ -253,6 +316,7 @@ void GpuHnswMap::ResizeIndex(size_t newMaxElements) {
 		}
 		return;
 	}
+	flushPending();
 	graph_.Resize(newMaxElements);
 	graphDirty_ = true;
 }
@@ -296,6 +360,7 @@ void GpuHnswMap::SaveIndex(AnnCacheWriter& writer, const std::atomic_int32_t& ca
 		for (const auto& m : S.maps) m->graph_.SaveIndex(writer, cancel);
 		return;
 	}
+	flushPending();
 	graph_.SaveIndex(writer, cancel);
 }
 
@@ -406,8 +471,142 @@ void GpuHnswMap::LoadGraph(AnnCacheReader& reader) {
 
 void GpuHnswMap::syncDevice() const {
 	std::lock_guard<std::mutex> lk(syncMtx_);
-	if (!graphDirty_ && !deletedDirty_) return;
+	flushLocked();
+	syncLocked();
+}
+
+void GpuHnswMap::flushPending() const {
+	if (sh_ || graph_.PendingFrom() == graph_.Count()) return;
+	std::lock_guard<std::mutex> lk(syncMtx_);
+	flushLocked();
+}
+
+// Steps 1 - 7 of the batch rule (csrc/hnsw_build_plan.h) over the pending tail.  The caller holds the Map exclusively, as for
+// every other change of the graph.
+void GpuHnswMap::flushLocked() const {
 	const size_t n = graph_.Count();
+	size_t from = graph_.PendingFrom();
+	if (from == n) return;
+	const auto t0 = std::chrono::steady_clock::now();
+	const rxgpu::HnswBuildKnobs knobs = rxgpu::read_hnsw_build_knobs();
+	const uint32_t efc = uint32_t(graph_.EfConstruction());
+	const int path = rxgpu::hnsw_build_path(graph_.DeletedCount(), uint32_t(graph_.M()), efc, false);
+	auto hostLink = [&](size_t upTo) {
+		for (size_t id = graph_.PendingFrom(); id < upTo; ++id) graph_.LinkStored(tableint(id));
+		graphDirty_ = true;
+	};
+	if (path != rxgpu::kHnswBuildDevice) {   // (deferInsert keeps such rows out; a graph that lost its eligibility since is finished on the host)
+		build_.hostRows += n - from;
+		build_.hostReason = path;
+		hostLink(n);
+		return;
+	}
+	// 1. seed
+	const size_t seed = size_t(rxgpu::hnsw_build_seed_rows(from, n, knobs));
+	if (seed) {
+		hostLink(from + seed);
+		build_.seedRows += seed;
+		from += seed;
+	}
+	if (from == n) return;
+	// the device mirrors the linked part; the pending rows follow it
+	auto mirror = [&] {
+		const size_t linked = graph_.PendingFrom();
+		// (a re-attach: the device counts the pending rows already, and the graph it mirrors is that of its row count)
+		if (rxgpu_index_count(dev_) > linked && rxgpu_index_truncate(dev_, linked) != RXGPU_OK) throwDevice("truncating the device index failed");
+		graphDirty_ = true;
+		syncLocked();
+		const float* norms = graph_.InvNorms();
+		if (rxgpu_index_upload_rows(dev_, linked, n - linked, graph_.Vectors() + linked * graph_.Dim(), norms ? norms + linked : nullptr) != RXGPU_OK) {
+			throwDevice("row upload failed");
+		}
+		syncedRows_ = n;
+	};
+	const size_t stride0 = 1 + graph_.MaxM0();
+	std::vector<uint32_t> rows0;
+	// level 0 of the nodes [0, upTo) back into the host graph (step 7; also in front of a re-attach)
+	auto readBack = [&](size_t upTo) {
+		rows0.resize(upTo * stride0);
+		if (rxgpu_hnsw_read_links0(dev_, 0, upTo, rows0.data()) != RXGPU_OK) throwDevice("reading the level-0 lists back failed");
+		graph_.SetLinks0(0, upTo, rows0.data());
+	};
+	mirror();
+	std::vector<tableint> touched, ids;
+	std::vector<int32_t> levels;
+	std::vector<uint32_t> upperRows;
+	size_t a = from;
+	while (a < n) {
+		const size_t cnt = size_t(rxgpu::hnsw_build_batch_rows(a, n, knobs));
+		// 6. the upper levels of the batch on the host, beside the device
+		touched.clear();
+		std::string upperError;
+		double upperSeconds = 0;
+		std::thread upper([&] {
+			const auto u0 = std::chrono::steady_clock::now();
+			try {
+				graph_.SetTouchLog(&touched);
+				for (size_t id = a; id < a + cnt; ++id) graph_.LinkUpper(tableint(id));
+			} catch (const std::exception& e) {
+				upperError = e.what();
+			}
+			graph_.SetTouchLog(nullptr);
+			upperSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - u0).count();
+		});
+		// 3 - 5. candidates, lists, back-links on the device
+		const int rc = rxgpu_hnsw_link_batch(dev_, a, cnt, efc);
+		upper.join();
+		build_.upperSeconds += upperSeconds;
+		if (!upperError.empty()) throw std::runtime_error(upperError);
+		// (the Map reserves the device index for MaxElements before it attaches, and the level-0 array is allocated for that capacity: a
+		// batch always fits — RXGPU_ERR_OVERFLOW here would be a broken invariant, not a state to recover from)
+		if (rc != RXGPU_OK) throwDevice("linking a batch on the device failed");
+		ids.clear();
+		levels.clear();
+		upperRows.clear();
+		std::sort(touched.begin(), touched.end());
+		touched.erase(std::unique(touched.begin(), touched.end()), touched.end());
+		for (const tableint id : touched) {
+			if (id < a) ids.push_back(id);
+		}
+		for (size_t id = a; id < a + cnt; ++id) ids.push_back(tableint(id));
+		for (const tableint id : ids) {
+			levels.push_back(graph_.Levels()[id]);
+			graph_.AppendUpper(id, upperRows);
+		}
+		const int rp = rxgpu_hnsw_patch_upper(dev_, uint32_t(ids.size()), ids.data(), levels.data(), upperRows.empty() ? nullptr : upperRows.data(),
+											  graph_.MaxLevel(), graph_.EntryPoint());
+		if (rp == RXGPU_ERR_OVERFLOW) {
+			// The upper blocks allocated by the last attach (twice the expected number) are used up.  Level 0 of the a + cnt nodes is on the
+			// device and their upper levels are linked on the host: level 0 comes home and the graph of a + cnt nodes is attached again, with
+			// new headroom — host and device agree on every node, the next batch goes on from there.
+			readBack(a + cnt);
+			graphOnDevice_ = false;
+			mirror();
+		} else if (rp != RXGPU_OK) {
+			throwDevice("patching the upper lists failed");
+		}
+		a += cnt;
+	}
+	// 7. host and device mirrors are equal: nothing is marked dirty
+	readBack(n);
+	uint64_t rows = 0, batches = 0, resel = 0, over = 0;
+	double ms[3] = {0, 0, 0};
+	if (rxgpu_hnsw_read_build_stats(dev_, &rows, &batches, &resel, &over, ms) == RXGPU_OK) {
+		build_.deviceRows += rows;
+		build_.batches += batches;
+		build_.reselected += resel;
+		build_.pastCap += over;
+		build_.searchMs += ms[0];
+		build_.selectMs += ms[1];
+		build_.backlinkMs += ms[2];
+	}
+	if (quantized_) graphDirty_ = true;   // the new rows get their codes at the sync that follows (on the device, from the rows it holds)
+	build_.flushSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+void GpuHnswMap::syncLocked() const {
+	if (!graphDirty_ && !deletedDirty_) return;
+	const size_t n = graph_.PendingFrom();   // the linked part (everything, outside a flush)
 	if (graphDirty_) {
 		if (rxgpu_index_capacity(dev_) < graph_.MaxElements()) {
 			if (rxgpu_index_reserve(dev_, graph_.MaxElements()) != RXGPU_OK) throwDevice("Not enough memory: resizeIndex failed to allocate base layer");
@@ -501,7 +700,9 @@ static bool sq8QuantizeOnHost() noexcept {
 }
 
 void GpuHnswMap::attachCodes() const {
-	const size_t n = graph_.Count(), dim = graph_.Dim();
+	// the rows that are on the device: everything, except inside a flush, where the pending tail is uploaded behind this sync and coded at
+	// the sync that follows the flush (patchCodes)
+	const size_t n = graph_.PendingFrom(), dim = graph_.Dim();
 	if (n && !sq8QuantizeOnHost()) {
 		if (rxgpu_hnsw_quantize_sq8(dev_, 0, n, sq8_.minQ, sq8_.alpha, sq8_.delta, sq8_.alpha_2) != RXGPU_OK) throwDevice("SQ8 coding on the device failed");
 		deviceCodedRows_ += n;
@@ -541,6 +742,7 @@ void GpuHnswMap::patchCodes(const std::vector<tableint>& dirty, size_t n) const 
 
 void GpuHnswMap::Quantize(float minQ, float maxQ) {
 	if (!(maxQ > minQ)) throw std::runtime_error("Quantize: empty quantisation range");
+	flushPending();
 	if (sh_) {   // ONE quantiser for the whole Map (the reference quantises the index, not its parts): every shard codes its rows with it
 		for (const auto& m : sh_->maps) m->Quantize(minQ, maxQ);
 	}
@@ -552,6 +754,7 @@ void GpuHnswMap::Quantize(float minQ, float maxQ) {
 }
 
 void GpuHnswMap::Quantize(const Sq8QuantizationConfig& config) {
+	flushPending();
 	if (quantized_ || pendingSq8_) throw std::logic_error("Quantize: the Map is quantised already");
 	Sq8Params p;
 	if (sh_) {   // the sample runs over the points of all shards, numbered shard after shard (what internal ids are to a single graph)

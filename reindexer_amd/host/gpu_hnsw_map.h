@@ -1,6 +1,7 @@
 // GpuHnswMap — the GPU `Map` policy for HnswIndexBase<Map> in its HNSW form (hnsw_index.cc:47-58), a drop-in for
 // hnswlib::HierarchicalNSW<Synchronization::None> (cpp_src/core/index/float_vector/hnswlib/hnsw.h:14-126).
-//   build  : host, HnswGraph (hnsw_graph.h) — same graph as the reference builds
+//   build  : host, HnswGraph (hnsw_graph.h) — same graph as the reference builds; opt-in (RXGPU_HNSW_BUILD=device): level 0 on the device
+//            in batches (rxgpu_hnsw_link_batch), the upper levels on the host beside it
 //   search : MI355X, rxgpu_hnsw_search_knn (hnsw_search.hip) — same traversal as the reference, no CPU search path
 #pragma once
 
@@ -95,6 +96,27 @@ public:
 	void MarkDelete(FloatVectorId id);
 	void AddPointNoLock(ConstFloatVectorView vect, FloatVectorId id);
 	void AddPointConcurrent(ConstFloatVectorView vect, FloatVectorId id);   // Synchronization::None: throws, like the reference's ST map
+	// Bulk entry: n vectors of Dim() floats, in row order.  By default n AddPointNoLock calls.
+	//
+	// RXGPU_HNSW_BUILD=device (read per call; default host) on a single-device Map: AddPoints, and AddPointConcurrent of a
+	// Synchronization::OnInsertions Map, only STORE the row (HnswGraph::AppendUnlinked) and return — count, labels and vectors see it at once.
+	// The pending tail is linked in batches on the device (flushPending: the rule of csrc/hnsw_build_plan.h) before anything reads or
+	// changes links: the first search (syncDevice), MarkDelete, AddPointNoLock, SaveIndex, the copy constructor, ResizeIndex, Quantize, Graph().
+	// Built from empty, the levels, every upper list, the entry point and the top level equal the sequential build's; level 0 is the
+	// batched graph (known difference (3)).  Graphs with deleted nodes, M > 64 or efConstruction > 256 insert on the host as
+	// before, and BuildStats says which path ran.
+	void AddPoints(const float* vectors, const labeltype* labels, size_t n);
+	struct BuildStats {
+		uint64_t deviceRows = 0, batches = 0, reselected = 0, pastCap = 0;   // rxgpu_hnsw_read_build_stats, summed over the flushes
+		uint64_t seedRows = 0;          // rows the sequential builder linked in front of the first batch
+		uint64_t hostRows = 0;          // rows of device-mode calls that were inserted on the host after all
+		int hostReason = 0;             // ... and why (rxgpu::HnswBuildPath), 0: none were
+		double searchMs = 0, selectMs = 0, backlinkMs = 0;
+		double upperSeconds = 0;        // host: LinkUpper over the batches (runs beside the device)
+		double flushSeconds = 0;        // wall clock of the flushes
+	};
+	BuildStats ReadBuildStats() const;       // since the last call
+	size_t PendingRows() const noexcept { return graph_.Count() - graph_.PendingFrom(); }
 	void ResizeIndex(size_t newMaxElements);
 
 	SearchResultQueue SearchKnn(const float* queryDataRaw, std::optional<float> queryDataNorm, size_t k, size_t ef = 0) const;
@@ -139,10 +161,20 @@ public:
 
 	VectorMetric Metric() const noexcept { return graph_.Metric(); }
 	size_t Dim() const noexcept { return graph_.Dim(); }
-	const HnswGraph& Graph() const noexcept { return graph_; }
+	const HnswGraph& Graph() const {
+		flushPending();
+		return graph_;
+	}
 
 private:
 	void syncDevice() const;
+	void syncLocked() const;            // under syncMtx_; mirrors the LINKED part of the graph
+	void flushPending() const;          // links the pending tail (steps 1 - 7 of the batch rule)
+	void flushLocked() const;
+	void addNoLock(const float* data, labeltype label);     // AddPointNoLock of a single-device Map
+	bool deferInsert(const float* data, labeltype label);   // device mode: true = stored (or inserted on the host under deferMtx_)
+	mutable BuildStats build_;
+	mutable std::mutex deferMtx_;       // device mode: stored rows and host insertions never interleave; guards build_.hostRows / hostReason
 	// ---- the Map over a device list
 	struct ShardedState;
 	GpuHnswMap(VectorMetric metric, size_t dim, size_t maxElements, size_t M, size_t efConstruction, int device, Synchronization synchronization,

@@ -84,6 +84,7 @@ HnswGraph::HnswGraph(const HnswGraph& o, size_t newMaxElements)
 	  mult_(o.mult_),
 	  count_(o.count_),
 	  numDeleted_(o.numDeleted_),
+	  pending_(o.pending_),
 	  maxLevel_(o.maxLevel_),
 	  entryPoint_(o.entryPoint_),
 	  vectors_(o.vectors_),
@@ -129,6 +130,10 @@ void HnswGraph::Resize(size_t newMaxElements) {
 }
 
 void HnswGraph::markDirty(tableint id) {
+	if (touchLog_) {
+		touchLog_->push_back(id);
+		return;
+	}
 	if (dirtyAll_.load(std::memory_order_relaxed)) return;
 	std::lock_guard<std::mutex> lk(dirtyMtx_);
 	if (dirty_.size() > std::max<size_t>(count_ / 4, 4096)) {
@@ -479,6 +484,7 @@ tableint HnswGraph::addPoint(const float* data, labeltype label) {
 
 // addPoint<LockerT>(data_point, label), hnswalg.h:1401-1470 (allow_replace_deleted_ is always on: hnsw.h:72): a vacated slot is recycled first
 tableint HnswGraph::AddPoint(const float* data, labeltype label) {
+	requireNoPending("AddPoint");
 	if (deletedElements_.empty()) return addPoint<false>(data, label);
 	const tableint id = deletedElements_.pop_front();
 	numDeleted_ -= 1;
@@ -486,6 +492,102 @@ tableint HnswGraph::AddPoint(const float* data, labeltype label) {
 	labelLookup_[label] = id;
 	updatePoint(data, id);
 	return id;
+}
+
+// ---------------------------------------------------------------------------------------------------- stored-but-unlinked rows
+void HnswGraph::requireNoPending(const char* who) const {
+	if (pending_) throw std::logic_error(std::string("HnswGraph::") + who + ": the graph holds stored rows that are not linked yet");
+}
+
+tableint HnswGraph::AppendUnlinked(const float* data, labeltype label) {
+	std::lock_guard<std::mutex> lk(labelMtx_);
+	if (labelLookup_.count(label)) throw std::logic_error("HnswGraph::AppendUnlinked: the label exists (an in-place update is an insertion of its own)");
+	if (!deletedElements_.empty()) throw std::logic_error("HnswGraph::AppendUnlinked: a deleted slot is waiting to be recycled");
+	if (count_ >= maxElements_) throw std::runtime_error("The number of elements exceeds the specified limit");
+	const tableint cur = tableint(count_);
+	labelLookup_[label] = cur;
+	if (metric_ == VectorMetric::Cosine) invNorms_[cur] = CalculateL2Module(data, int32_t(dim_));
+	const int curLevel = randomLevel();   // under the same mutex as the id: levels are drawn in row order
+	levels_[cur] = curLevel;
+	std::memset(list(cur, 0), 0, (1 + maxM0_) * sizeof(uint32_t));
+	labels_[cur] = label;
+	deleted_[cur] = 0;
+	std::memcpy(vectors_.data() + size_t(cur) * dim_, data, dim_ * sizeof(float));
+	upper_[cur].assign(size_t(curLevel) * (1 + M_), 0u);
+	count_++;
+	pending_++;
+	return cur;
+}
+
+// addPoint :1762-1852 for a row that is stored already (sequential form): the descent through the levels above the row's own, then
+// searchBaseLayer + connect from min(its level, the top level) down to minLevel, then the entry point / top level update.
+void HnswGraph::linkLevels(tableint cur, int minLevel) {
+	const int curLevel = levels_[cur];
+	const int maxLevelCopy = maxLevel_;
+	const tableint enterCopy = entryPoint_;
+	tableint currObj = enterCopy;
+	if (currObj != kNoEntry) {
+		if (curLevel < maxLevelCopy) {
+			float curDist = distIds(cur, currObj);
+			for (int level = maxLevelCopy; level > curLevel; --level) {
+				bool changed = true;
+				while (changed) {
+					changed = false;
+					const uint32_t* ll = list(currObj, level);
+					const int size = int(ll[0]);
+					for (int i = 0; i < size; ++i) {
+						const tableint cand = ll[1 + i];
+						if (cand >= maxElements_) throw std::runtime_error("cand error");
+						const float d = distIds(cur, cand);
+						if (d < curDist) {
+							curDist = d;
+							currObj = cand;
+							changed = true;
+						}
+					}
+				}
+			}
+		}
+		for (int level = std::min(curLevel, maxLevelCopy); level >= minLevel; --level) {
+			Heap top = searchBaseLayer<false>(currObj, cur, level, visited_);
+			if (IsDeleted(enterCopy)) {
+				const float d = distIds(cur, enterCopy);
+				if (top.size() < efConstruction_) {
+					top.emplace(d, enterCopy);
+				} else if (top.top().first > d) {
+					top.replace_top(Pair(d, enterCopy));
+				}
+			}
+			currObj = connect<false>(cur, top, level);
+		}
+		if (curLevel > maxLevelCopy) {
+			entryPoint_ = cur;
+			maxLevel_ = curLevel;
+		}
+	} else {
+		maxLevel_ = curLevel;   // first element (hnswalg.h:1839-1848)
+		entryPoint_ = curLevel > maxLevelCopy ? cur : 0;
+	}
+}
+
+void HnswGraph::LinkStored(tableint id) {
+	if (pending_ == 0 || id != count_ - pending_) throw std::logic_error("HnswGraph::LinkStored: not the first pending row");
+	markDirty(id);
+	linkLevels(id, 0);
+	pending_--;
+}
+
+void HnswGraph::LinkUpper(tableint id) {
+	if (id < count_ - pending_ || id >= count_) throw std::logic_error("HnswGraph::LinkUpper: not a pending row");
+	if (entryPoint_ == kNoEntry) throw std::logic_error("HnswGraph::LinkUpper: the first element is linked by LinkStored");
+	if (levels_[id] >= 1) linkLevels(id, 1);
+}
+
+void HnswGraph::SetLinks0(tableint first, size_t n, const uint32_t* rows) {
+	if (size_t(first) + n > count_) throw std::logic_error("HnswGraph::SetLinks0: rows past the element count");
+	if (n) std::memcpy(links0_.data() + size_t(first) * (1 + maxM0_), rows, n * (1 + maxM0_) * sizeof(uint32_t));
+	const size_t from = count_ - pending_;
+	if (first <= from && size_t(first) + n > from) pending_ = count_ - (size_t(first) + n);
 }
 
 void HnswGraph::rebuildDeletedSet() {
@@ -622,6 +724,7 @@ void HnswGraph::releaseVisited(std::unique_ptr<Visited> v) {
 }
 
 tableint HnswGraph::AddPointConcurrent(const float* data, labeltype label) {
+	requireNoPending("AddPointConcurrent");
 	if (!nodeLocks_ || nodeLocksSize_ != maxElements_) EnableConcurrentInserts();
 	// A vacated slot is recycled first, as in the reference (hnswalg.h:1410-1421).  The reference then runs updatePoint next to other inserts
 	// behind per-element data locks (ExpectConcurrentUpdates::Yes); here the recycling insert takes the graph exclusively instead: same
@@ -686,6 +789,7 @@ void HnswGraph::AddPoints(const float* data, const labeltype* labels, size_t n, 
 }
 
 void HnswGraph::MarkDelete(labeltype label) {
+	requireNoPending("MarkDelete");
 	auto it = labelLookup_.find(label);
 	if (it == labelLookup_.end()) throw std::runtime_error("markDelete: Label not found: " + std::to_string(label));
 	const tableint id = it->second;
@@ -836,6 +940,7 @@ void HnswGraph::loadIndex(AnnCacheReader& reader) {
 
 void HnswGraph::Clear() {
 	count_ = 0;
+	pending_ = 0;
 	numDeleted_ = 0;
 	maxLevel_ = -1;
 	entryPoint_ = 0xFFFFFFFFu;

@@ -57,11 +57,31 @@ public:
 	void MarkDelete(labeltype label);
 	void Resize(size_t newMaxElements);
 
+	// The batched build (GpuHnswMap::flushPending; the rule: csrc/hnsw_build_plan.h).  Rows can be STORED without being linked: they form a
+	// tail [PendingFrom(), Count()) whose level-0 lists are empty and which nothing links to.  While such a tail exists only the members
+	// below may change the graph (AddPoint / AddPointConcurrent / MarkDelete throw std::logic_error).
+	//   AppendUnlinked  addPoint's bookkeeping (hnswalg.h:1694-1760): label, vector, 1 / |v|, the level — drawn in row order, so every node's
+	//                   level equals the sequential build's — and an empty level-0 list.  Callable from many threads at once (one mutex);
+	//                   never recycles a deleted slot and never updates an existing label (std::logic_error: the caller inserts those itself)
+	//   LinkStored      the rest of addPoint for the first pending row: afterwards the graph is what AddPoint would have left
+	//   LinkUpper       addPoint's descent, searchBaseLayer and connect for the levels >= 1 of a pending row only (entry point and top level
+	//                   updated as addPoint does); rows in id order.  Levels >= 1 never read level 0, so after LinkUpper over every row the
+	//                   upper lists, the entry point and the top level equal the sequential build's
+	//   SetLinks0       level-0 lists [first, first + n) as built elsewhere (rows [n][1 + maxM0]); rows up to first + n count as linked
+	tableint AppendUnlinked(const float* data, labeltype label);
+	void LinkStored(tableint id);
+	void LinkUpper(tableint id);
+	void SetLinks0(tableint first, size_t n, const uint32_t* rows);
+	size_t PendingFrom() const noexcept { return count_ - pending_; }
+	// While a log is set, the nodes whose lists change are appended to it INSTEAD of the change tracker (the caller mirrors them itself).
+	void SetTouchLog(std::vector<tableint>* log) noexcept { touchLog_ = log; }
+
 	size_t MaxElements() const noexcept { return maxElements_; }
 	size_t Count() const noexcept { return count_; }
 	size_t DeletedCount() const noexcept { return numDeleted_; }
 	size_t Dim() const noexcept { return dim_; }
 	size_t M() const noexcept { return M_; }
+	size_t EfConstruction() const noexcept { return efConstruction_; }
 	size_t MaxM0() const noexcept { return maxM0_; }
 	int MaxLevel() const noexcept { return maxLevel_; }
 	tableint EntryPoint() const noexcept { return entryPoint_; }
@@ -134,6 +154,8 @@ private:
 	void repairConnectionsForUpdate(tableint id, tableint entryPoint, int level, int maxLevel);
 	void rebuildDeletedSet();
 	void markDirty(tableint id);
+	void linkLevels(tableint cur, int minLevel);   // addPoint's linking half, levels min(level(cur), maxLevel_) .. minLevel
+	void requireNoPending(const char* who) const;
 	std::unique_ptr<Visited> acquireVisited();
 	void releaseVisited(std::unique_ptr<Visited> v);
 
@@ -143,6 +165,8 @@ private:
 	const size_t M_, maxM0_, efConstruction_;
 	const double mult_;
 	size_t count_ = 0, numDeleted_ = 0;
+	size_t pending_ = 0;                          // stored rows without links: the tail of the id range
+	std::vector<tableint>* touchLog_ = nullptr;
 	int maxLevel_ = -1;
 	tableint entryPoint_ = 0xFFFFFFFFu;
 

@@ -357,6 +357,45 @@ int rxhost_graph_load_index(void* h, const uint8_t* data, size_t len, const uint
 	});
 }
 void rxhost_graph_clear(void* h) { static_cast<HnswGraph*>(h)->Clear(); }
+// the stored-but-unlinked rows of the batched build (HnswGraph::AppendUnlinked / LinkStored / LinkUpper / SetLinks0)
+int rxhost_graph_append_unlinked(void* h, const float* vecs, size_t n, size_t dim, const uint64_t* labels) {
+	return guarded([&] {
+		auto* g = static_cast<HnswGraph*>(h);
+		for (size_t i = 0; i < n; ++i) g->AppendUnlinked(vecs + i * dim, labels[i]);
+	});
+}
+int rxhost_graph_link_stored(void* h, size_t first, size_t n) {
+	return guarded([&] {
+		auto* g = static_cast<HnswGraph*>(h);
+		for (size_t i = 0; i < n; ++i) g->LinkStored(tableint(first + i));
+	});
+}
+// LinkUpper over rows [first, first + n); the nodes whose upper lists changed (ascending, unique) into touched [cap].  Returns their number
+// (the list is written only when it fits), -1 on error.
+long rxhost_graph_link_upper(void* h, size_t first, size_t n, uint32_t* touched, size_t cap) {
+	long out = -1;
+	guarded([&] {
+		auto* g = static_cast<HnswGraph*>(h);
+		std::vector<tableint> log;
+		g->SetTouchLog(&log);
+		try {
+			for (size_t i = 0; i < n; ++i) g->LinkUpper(tableint(first + i));
+		} catch (...) {
+			g->SetTouchLog(nullptr);
+			throw;
+		}
+		g->SetTouchLog(nullptr);
+		std::sort(log.begin(), log.end());
+		log.erase(std::unique(log.begin(), log.end()), log.end());
+		if (log.size() <= cap && !log.empty()) std::memcpy(touched, log.data(), log.size() * sizeof(uint32_t));
+		out = long(log.size());
+	});
+	return out;
+}
+int rxhost_graph_set_links0(void* h, size_t first, size_t n, const uint32_t* rows) {
+	return guarded([&] { static_cast<HnswGraph*>(h)->SetLinks0(tableint(first), n, rows); });
+}
+size_t rxhost_graph_pending_from(void* h) { return static_cast<HnswGraph*>(h)->PendingFrom(); }
 
 void rxhost_graph_info(void* h, int64_t* info) {
 	auto* g = static_cast<HnswGraph*>(h);
@@ -468,6 +507,33 @@ int rxhost_hnsw_add_many(void* h, const float* vecs, size_t n, size_t dim, const
 		for (size_t i = 0; i < n; ++i) m->AddPointNoLock(ConstFloatVectorView(vecs + i * dim, dim), FloatVectorId::FromNumber(labels[i]));
 	});
 }
+// GpuHnswMap::AddPoints: the bulk entry (deferred to the device build under RXGPU_HNSW_BUILD=device)
+int rxhost_hnsw_add_bulk(void* h, const float* vecs, size_t n, size_t dim, const uint64_t* labels) {
+	return guarded([&] {
+		auto* m = static_cast<GpuHnswMap*>(h);
+		if (dim != m->Dim()) throw std::logic_error("rxhost_hnsw_add_bulk: wrong dimension");
+		m->AddPoints(vecs, labels, n);
+	});
+}
+// FloatPtrByExternalLabel copied out (dim floats)
+int rxhost_hnsw_vector(void* h, uint64_t label, float* out) {
+	return guarded([&] {
+		auto* m = static_cast<GpuHnswMap*>(h);
+		std::memcpy(out, m->FloatPtrByExternalLabel(label), m->Dim() * sizeof(float));
+	});
+}
+size_t rxhost_hnsw_pending_rows(void* h) { return static_cast<GpuHnswMap*>(h)->PendingRows(); }
+// counts [8] = device rows, batches, nodes re-selected, nodes past the kernel's cap, seed rows, host rows, host reason, 0;
+// times [5] = search / select / back-link milliseconds, host upper-level seconds, flush seconds — since the last call
+int rxhost_hnsw_build_stats(void* h, uint64_t* counts, double* times) {
+	return guarded([&] {
+		const GpuHnswMap::BuildStats s = static_cast<GpuHnswMap*>(h)->ReadBuildStats();
+		const uint64_t c[8] = {s.deviceRows, s.batches, s.reselected, s.pastCap, s.seedRows, s.hostRows, uint64_t(s.hostReason), 0};
+		const double t[5] = {s.searchMs, s.selectMs, s.backlinkMs, s.upperSeconds, s.flushSeconds};
+		std::copy(c, c + 8, counts);
+		std::copy(t, t + 5, times);
+	});
+}
 int rxhost_hnsw_add_concurrent(void* h, const float* vec, size_t dim, uint64_t label) {
 	return guarded([&] { static_cast<GpuHnswMap*>(h)->AddPointConcurrent(ConstFloatVectorView(vec, dim), FloatVectorId::FromNumber(label)); });
 }
@@ -496,7 +562,11 @@ long rxhost_hnsw_lds_reruns(void* h) {
 	guarded([&] { n = long(static_cast<const GpuHnswMap*>(h)->LdsReruns()); });
 	return n;
 }
-void* rxhost_hnsw_graph(void* h) { return const_cast<HnswGraph*>(&static_cast<GpuHnswMap*>(h)->Graph()); }
+void* rxhost_hnsw_graph(void* h) {   // (links a pending tail first: null + rxhost_last_error when that fails)
+	void* out = nullptr;
+	guarded([&] { out = const_cast<HnswGraph*>(&static_cast<GpuHnswMap*>(h)->Graph()); });
+	return out;
+}
 // the Map's ANN disk cache through memory (same encoding as rxhost_graph_save_index / _load_index)
 long rxhost_hnsw_save_index(void* h, uint8_t* out, size_t cap) {
 	long n = -1;

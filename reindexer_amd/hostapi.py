@@ -283,6 +283,13 @@ class HnswGraph:
             L.rxhost_graph_save_index.argtypes = [_vp, _vp, _sz]
             L.rxhost_graph_load_index.argtypes = [_vp, _vp, _sz, _vp, _vp, _sz]
             L.rxhost_graph_clear.argtypes = [_vp]
+            L.rxhost_graph_append_unlinked.argtypes = [_vp, _vp, _sz, _sz, _vp]
+            L.rxhost_graph_link_stored.argtypes = [_vp, _sz, _sz]
+            L.rxhost_graph_link_upper.restype = _l
+            L.rxhost_graph_link_upper.argtypes = [_vp, _sz, _sz, _vp, _sz]
+            L.rxhost_graph_set_links0.argtypes = [_vp, _sz, _sz, _vp]
+            L.rxhost_graph_pending_from.restype = _sz
+            L.rxhost_graph_pending_from.argtypes = [_vp]
             L._graph_bound = True
         return L
 
@@ -321,6 +328,41 @@ class HnswGraph:
         rc = lib().rxhost_graph_mark_delete(self.h, int(label))
         if rc:
             _raise(rc)
+
+    # ---- stored-but-unlinked rows (the batched build; HnswGraph::AppendUnlinked / LinkStored / LinkUpper / SetLinks0)
+    def append_unlinked(self, vecs, labels):
+        """Stores the rows — label, vector, 1 / |v|, the level drawn in row order — with empty level-0 lists; nothing links to them yet."""
+        vecs = _f32(vecs).reshape(-1, self.dim)
+        labels = np.ascontiguousarray(labels, np.uint64).reshape(-1)
+        rc = lib().rxhost_graph_append_unlinked(self.h, vecs.ctypes.data, vecs.shape[0], self.dim, labels.ctypes.data)
+        if rc:
+            _raise(rc)
+
+    def link_stored(self, first: int, n: int):
+        """The sequential insertion of the pending rows [first, first + n) (first = pending_from): what add() would have built."""
+        rc = lib().rxhost_graph_link_stored(self.h, first, n)
+        if rc:
+            _raise(rc)
+
+    def link_upper(self, first: int, n: int):
+        """The levels >= 1 of the pending rows [first, first + n), in row order; returns the nodes whose upper lists changed (ascending)."""
+        cap = n * 64 * 8 + 16   # more than the lists of n rows can name: the call links, so it is made once
+        out = np.empty(cap, np.uint32)
+        got = lib().rxhost_graph_link_upper(self.h, first, n, out.ctypes.data, cap)
+        if got < 0:
+            _raise()
+        if got > cap:
+            raise RuntimeError("link_upper: touched list larger than its bound")
+        return out[:got].copy()
+
+    def set_links0(self, first: int, rows):
+        """Level-0 lists [first, first + len(rows)) as built elsewhere; the rows up to there count as linked."""
+        rows = np.ascontiguousarray(rows, np.uint32)
+        rc = lib().rxhost_graph_set_links0(self.h, first, rows.shape[0], rows.ctypes.data)
+        if rc:
+            _raise(rc)
+
+    pending_from = property(lambda self: int(lib().rxhost_graph_pending_from(self.h)))
 
     def export(self) -> dict:
         info = np.zeros(7, np.int64)
@@ -506,6 +548,11 @@ class GpuHnswMap:
             L.rxhost_hnsw_destroy.argtypes = [_vp]
             L.rxhost_hnsw_add_many.argtypes = [_vp, _vp, _sz, _sz, _vp]
             L.rxhost_hnsw_add_concurrent.argtypes = [_vp, _vp, _sz, _u64]
+            L.rxhost_hnsw_add_bulk.argtypes = [_vp, _vp, _sz, _sz, _vp]
+            L.rxhost_hnsw_pending_rows.restype = _sz
+            L.rxhost_hnsw_pending_rows.argtypes = [_vp]
+            L.rxhost_hnsw_build_stats.argtypes = [_vp, _vp, _vp]
+            L.rxhost_hnsw_vector.argtypes = [_vp, _u64, _vp]
             L.rxhost_hnsw_mark_delete.argtypes = [_vp, _u64]
             L.rxhost_hnsw_resize.argtypes = [_vp, _sz]
             L.rxhost_hnsw_count.restype = _sz
@@ -592,6 +639,37 @@ class GpuHnswMap:
         if rc:
             _raise(rc)
 
+    def add_points(self, vecs, labels):
+        """GpuHnswMap::AddPoints, the bulk entry.  Under RXGPU_HNSW_BUILD=device the rows are only stored; the device links them in
+        batches before the first search (or anything else that reads or changes links)."""
+        vecs = _f32(vecs).reshape(-1, self.dim)
+        labels = np.ascontiguousarray(labels, np.uint64).reshape(-1)
+        rc = lib().rxhost_hnsw_add_bulk(self.h, vecs.ctypes.data, vecs.shape[0], self.dim, labels.ctypes.data)
+        if rc:
+            _raise(rc)
+
+    pending_rows = property(lambda self: int(lib().rxhost_hnsw_pending_rows(self.h)))
+
+    def vector(self, label):
+        """FloatPtrByExternalLabel: the stored vector of a label (a copy)."""
+        out = np.empty(self.dim, np.float32)
+        rc = lib().rxhost_hnsw_vector(self.h, int(label), out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return out
+
+    def build_stats(self) -> dict:
+        """The device build since the last call: rows linked on the device, batches, nodes re-selected, nodes past the kernel's cap, seed
+        rows, rows of device-mode calls inserted on the host and why (0 none, 1 deleted nodes, 2 M, 3 efConstruction, 4 device list),
+        milliseconds per device phase, seconds of the host's upper levels and of the flushes."""
+        c, t = np.zeros(8, np.uint64), np.zeros(5, np.float64)
+        rc = lib().rxhost_hnsw_build_stats(self.h, c.ctypes.data, t.ctypes.data)
+        if rc:
+            _raise(rc)
+        return dict(device_rows=int(c[0]), batches=int(c[1]), reselected=int(c[2]), past_cap=int(c[3]), seed_rows=int(c[4]), host_rows=int(c[5]),
+                    host_reason=int(c[6]), search_ms=float(t[0]), select_ms=float(t[1]), backlink_ms=float(t[2]), upper_seconds=float(t[3]),
+                    flush_seconds=float(t[4]))
+
     def add_concurrent(self, vec, label):
         vec = _f32(vec)
         rc = lib().rxhost_hnsw_add_concurrent(self.h, vec.ctypes.data, self.dim, int(label))
@@ -655,6 +733,8 @@ class GpuHnswMap:
         HnswGraph._bind()
         g = HnswGraph.__new__(HnswGraph)
         g.dim, g.metric, g.h = self.dim, self.metric, lib().rxhost_hnsw_graph(self.h)
+        if not g.h:
+            _raise()
         try:
             e = g.export()
             if with_views:

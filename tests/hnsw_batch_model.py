@@ -1,0 +1,190 @@
+"""The batch rule of the device build of HNSW level 0 (reindexer_amd/csrc/hnsw_build_plan.h) restated in Python — the checker of
+hnsw_build.hip, link for link.  Not a test module.
+
+Given the rows in their order:
+  * the host builder (hostapi.HnswGraph) stores every row (levels drawn in row order), links the seed rows sequentially and, batch after
+    batch, the levels >= 1 of the batch's rows (LinkUpper);
+  * step 3 is the oracle's restated SearchKnn (oracle_hnsw_search_knn) with k = ef = efConstruction over the graph of the nodes in front
+    of the batch, the stored row as the query;
+  * distances are HnswGraph::distIds restated over the oracle's ip / l2sqr: 1.0f * s + 0 + 0, negated for inner product / cosine, cosine
+    multiplied by the stored 1 / |v| of the first argument, then of the second (float32 every step);
+  * selectNeighbors and the order connect() writes a list in are restated below (the walk order of a lexicographic heap on (-dist, id);
+    the pop order of a binary max-heap that compares the distance alone).
+"""
+import numpy as np
+
+SEED, RATIO, MIN_BATCH, BATCH_CAP = 1024, 16, 64, 16384
+
+
+def batch_rows(a, n, ratio=RATIO, cap=BATCH_CAP):
+    return min(max(a // ratio, MIN_BATCH), cap, n - a)
+
+
+class _ByFirstHeap:
+    """ResultHeap<pair<float, id>, ByFirst> (host/rx_types.h): a binary max-heap whose comparison reads the distance only."""
+
+    def __init__(self):
+        self.d, self.i = [], []
+
+    def push(self, d, i):
+        self.d.append(d)
+        self.i.append(i)
+        k = len(self.d) - 1
+        while k:
+            up = (k - 1) >> 1
+            if not (self.d[up] < self.d[k]):
+                return
+            self._swap(up, k)
+            k = up
+
+    def pop(self):
+        top = self.i[0]
+        self.d[0], self.i[0] = self.d[-1], self.i[-1]
+        self.d.pop()
+        self.i.pop()
+        n, k = len(self.d), 0
+        while True:
+            big, l, r = k, 2 * k + 1, 2 * k + 2
+            if l < n and self.d[big] < self.d[l]:
+                big = l
+            if r < n and self.d[big] < self.d[r]:
+                big = r
+            if big == k:
+                return top
+            self._swap(big, k)
+            k = big
+
+    def _swap(self, a, b):
+        self.d[a], self.d[b] = self.d[b], self.d[a]
+        self.i[a], self.i[b] = self.i[b], self.i[a]
+
+
+class BatchModel:
+    def __init__(self, orc, metric, rows, inv):
+        self.orc, self.metric, self.rows, self.inv = orc, metric, rows, inv
+
+    def dist_from(self, first, ids):
+        """distIds(first, x) for x in ids."""
+        return self._dist(first, ids, True)
+
+    def dist_to(self, ids, second):
+        """distIds(x, second) for x in ids."""
+        return self._dist(second, ids, False)
+
+    def _dist(self, base, ids, base_first):
+        ids = np.asarray(ids, np.int64)
+        if ids.size == 0:
+            return np.empty(0, np.float32)
+        d = self.orc.dist_many(0 if self.metric == 0 else 1, self.rows[base], self.rows[ids])   # symmetric sums; L2: 1.0f * s + 0 + 0 == s
+        if self.metric == 2:
+            a, b = (self.inv[base], self.inv[ids]) if base_first else (self.inv[ids], self.inv[base])
+            d = (d * a).astype(np.float32)
+            d = (d * b).astype(np.float32)
+        return d.astype(np.float32)
+
+    def select(self, ids, dist, limit):
+        """selectNeighbors(entries, limit) followed by connect()'s write order: the list as it is stored."""
+        order = sorted(range(len(ids)), key=lambda e: (float(dist[e]), -int(ids[e])))   # ascending distance, the larger id first
+        if len(ids) < limit:
+            kept = order
+        else:
+            kept = []
+            for e in order:
+                if len(kept) >= limit:
+                    break
+                c, dc = int(ids[e]), dist[e]
+                if kept:
+                    ds = self.dist_to([int(ids[s]) for s in kept], c)   # distIds(kept, candidate)
+                    if (ds < dc).any():
+                        continue
+                kept.append(e)
+        heap = _ByFirstHeap()
+        for e in kept:
+            heap.push(float(dist[e]), int(ids[e]))
+        return [heap.pop() for _ in range(len(kept))]
+
+
+def search_graph(e, a, rows):
+    """The exported graph cut to its first a nodes, internal ids as labels."""
+    g = dict(e)
+    g.update(n=a, links0=np.ascontiguousarray(e["links0"][:a]), upper_off=np.ascontiguousarray(e["upper_off"][:a + 1]),
+             levels=np.ascontiguousarray(e["levels"][:a]), labels=np.arange(a, dtype=np.uint64), deleted=np.ascontiguousarray(e["deleted"][:a]),
+             vectors=rows)
+    return g
+
+
+def link_batch(model, orc, e, links0, a, cnt, M, max_m0, efc):
+    """Steps 3 - 5 for rows [a, a + cnt) on links0 ([n][1 + maxM0], changed in place); e: the host graph's export in front of the batch's
+    LinkUpper (upper lists, entry point and top level as they were after the batch before).  Returns the number of nodes re-selected."""
+    from oracle.pyoracle import oracle_hnsw_search_knn
+    g = search_graph(e, a, model.rows)
+    g["links0"] = np.ascontiguousarray(links0[:a])
+    inv = np.ascontiguousarray(model.inv[:a]) if model.metric == 2 else None
+    incoming = {}
+    new_lists = []
+    for i in range(a, a + cnt):
+        _, cand = oracle_hnsw_search_knn(orc, g, model.rows[i], min(efc, a), efc, inv)
+        cand = cand.astype(np.int64)
+        chosen = model.select(cand, model.dist_from(i, cand), M)
+        new_lists.append(chosen)
+        for t in chosen:
+            incoming.setdefault(t, []).append(i)
+    for r, chosen in enumerate(new_lists):
+        row = links0[a + r]
+        row[:] = 0
+        row[0] = len(chosen)
+        row[1:1 + len(chosen)] = chosen
+    reselected = 0
+    for t, inc in incoming.items():
+        row = links0[t]
+        cur = [int(x) for x in row[1:1 + int(row[0])]]
+        inc = sorted(inc)
+        if len(cur) + len(inc) <= max_m0:
+            row[1 + len(cur):1 + len(cur) + len(inc)] = inc
+            row[0] = len(cur) + len(inc)
+            continue
+        reselected += 1
+        ids = np.array(cur + inc, np.int64)
+        chosen = model.select(ids, model.dist_to(ids, t), max_m0)
+        row[:] = 0
+        row[0] = len(chosen)
+        row[1:1 + len(chosen)] = chosen
+    return reselected
+
+
+def build(orc, metric, rows, labels, M, efc, seed=SEED, ratio=RATIO, cap=BATCH_CAP, graph=None, on_batch=None):
+    """The whole rule.  graph: a host graph that holds linked nodes already (rows = ALL rows, the first graph.pending_from of them being
+    the graph's); None: built from empty.  on_batch(a, cnt, export_before, touched_upper, export_after) is called per batch.
+    Returns (export of the finished host graph with level 0 set, statistics)."""
+    from reindexer_amd import hostapi
+    n, d = rows.shape
+    g = graph if graph is not None else hostapi.HnswGraph(metric, d, n, M=M, ef_construction=efc)
+    have = g.pending_from
+    g.append_unlinked(rows[have:], labels[have:])
+    L = have
+    if L < seed:
+        s = min(seed, n) - L
+        g.link_stored(L, s)
+        L += s
+    vec, inv = g.vector_views(n)
+    model = BatchModel(orc, metric, rows, inv)
+    e = g.export()
+    links0 = e["links0"].copy()
+    stats = dict(batches=0, reselected=0, seed=L, first_export=e)
+    while L < n:
+        cnt = batch_rows(L, n, ratio, cap)
+        stats["reselected"] += link_batch(model, orc, e, links0, L, cnt, e["M"], e["maxM0"], efc)
+        touched = g.link_upper(L, cnt)
+        after = g.export()
+        if on_batch is not None:
+            on_batch(L, cnt, e, touched, after)
+        e = after
+        stats["batches"] += 1
+        L += cnt
+    g.set_links0(0, links0)
+    out = g.export()
+    out["vectors"] = rows
+    out["inv_norms"] = None if inv is None else np.array(inv)
+    if graph is None:
+        g.close()
+    return out, stats
