@@ -178,8 +178,16 @@ int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_avail
  * element and +8 bytes per row of HBM, built by the first such call; the bf16 shadow is then not built for single queries) under a per-row
  * bound that is proven, not tuned: the same rows and distance bits.  RXGPU_SCAN_I8 (environment, read per call): unset = automatic, 0 = this
  * tier off, 1 = forced for up to 8 queries at any size; RXGPU_SCAN_BF16=0 and =1 both win over it.  shadow_available stands for the shadow of
- * either tier. */
+ * either tier.  Tier 2 names the integer-shadow chain; rxgpu_scan_i6 names the shadow it reads. */
 int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite);
+/* 1 when such a call (whole index, no row list) reads the 6-bit shadow instead of the int8 one (no device is touched): the same chain, the
+ * same bound and the same result bits from 0.75 bytes per element, behind a seed pass over a strided sample of the rows (+0.75 bytes per
+ * element and +8 bytes per row of HBM, built by the first call that takes it; 128 < dim <= 1024).  RXGPU_SCAN_I6 (environment, read per
+ * call): 0 = off, 1 = forced for up to 8 queries at any size, unset = automatic: a call the automatic rules give to tier 2, on an index of at
+ * least 16 GiB of f32 rows (RXGPU_SCAN_I6_MIN_BYTES moves it).  RXGPU_SCAN_BF16 = 0 / 1 and RXGPU_SCAN_I8 = 0 / 1 win over
+ * it: RXGPU_SCAN_I8=1 means the int8 shadow, exactly.  rxgpu_scan_tier does not know the variable and keeps its answers.  i6_available: the
+ * 6-bit shadow fits in HBM (when it does not, the int8 shadow serves the call). */
+int rxgpu_scan_i6(uint64_t rows, uint32_t dim, uint32_t nq, int i6_available, int stats_finite);
 /* Candidates the last pruned single-query search through rxgpu_search_knn (or rxgpu_search_knn_subset / _bitmap / _lists) nominated for the exact re-score, and the capacity of their list
  * (count > cap: the list overflowed, or the query had no finite bound, and the exact scan answered).  A range call the int8 tier served
  * (rxgpu_scan_tier_range) records its candidates and the size of its list the same way.  Recorded only while profiling is enabled
@@ -195,6 +203,8 @@ int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint3
  *   "row_sq"     [count] float |x|^2 (L2 only)
  *   "codes_i8"   [count][dim rounded up to 256] int8 codes          "side_i8"  [count] float pairs {s_r, e_r}
  *   "rows_bf16"  [count][dim rounded up to 64] bf16 words, ROW-MAJOR whatever layout the shadow has on the device
+ *   "codes_i6"   [count][dim rounded up to 256] bytes u = code + 32 (0 in the pad), ROW-MAJOR: de-tiled on the host          "side_i6"  as "side_i8"
+ *   "stats_i6"   3 uint32: bits of max e^2 and of max (e inv_norm)^2 (cosine) of the 6-bit shadow, 1 once a non-finite e was seen
  * The last single-query search a pruned chain answered while profiling was enabled (recorded with rxgpu_index_last_candidates; the
  * snapshot is what that chain left in its buffers and is valid UNTIL THE NEXT CALL ON THE INDEX, which may reuse them):
  *   "pruned_values"     [n] float: the lower bound lo (int8 tier) or the approximate distance (bf16 tier) per row - per LIST POSITION when
@@ -205,7 +215,8 @@ int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint3
  *   "pruned_cand_rows"  [min(candidates, capacity)] uint32 rows the filter nominated, in no particular order
  *   "pruned_emit_cnt"   int8 tier over every row, emitting scan: [4 x workgroups of the scan] uint32, the entries wavefront w emitted
  *   "pruned_emitted"    ... and [n] pairs {float lo, uint32 row}: the wavefronts' segments back to back (knn_emit_plan.h), segment w valid
- *                       up to its count, rows ascending */
+ *                       up to its count, rows ascending
+ *   "pruned_seed"       6-bit front: as "pruned_top", the merged list of the seed pass (its last entry is T_seed) */
 int rxgpu_index_inspect(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
 
 /* ---- Pre-filtered brute force: the caller side of `WHERE cond AND KNN(...)` -------------------

@@ -136,6 +136,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "knn_i8_quant.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-ffp-contract=off", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # the arithmetic and the tile layout of the 6-bit shadow compiled for the host (CPU check of pack / unpack, the integer sum and the bound of knn_scan_i6)
+    src = tdir / "knn_i6_quant_cpu.cc"
+    if src.exists():
+        out = tdir / "libknn_i6_quant_cpu.so"
+        if force or _stale(out, [src, CSRC / "knn_i6_quant.h", CSRC / "knn_i8_quant.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-ffp-contract=off", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     # the range bound of the int8 shadow tier compiled for the host (CPU check of the threshold knn_range_i8 compares against)
     src = tdir / "knn_i8_range_cpu.cc"
     if src.exists():

@@ -65,6 +65,7 @@ _SIGNATURES = {
     "rxgpu_search_knn_device": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "rxgpu_scan_policy": (_i, [_u64, _u32, _u32, _i, _i]),
     "rxgpu_scan_tier": (_i, [_u64, _u32, _u32, _i, _i]),
+    "rxgpu_scan_i6": (_i, [_u64, _u32, _u32, _i, _i]),
     "rxgpu_scan_tier_subset": (_i, [_u64, _u32, _u32, _u32, _i, _i]),
     "rxgpu_scan_tier_range": (_i, [_u64, _u32, _i, _i, _i]),
     "rxgpu_index_last_candidates": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
@@ -214,6 +215,11 @@ def scan_policy(rows: int, dim: int, nq: int = 1, shadow_available: bool = True,
 def scan_tier(rows: int, dim: int, nq: int = 1, shadow_available: bool = True, stats_finite: bool = True) -> int:
     """rxgpu_scan_tier: 0 / 1 / 2 = such a call takes the f32 / bf16-pruned / int8-pruned scan under the current environment.  Touches no device."""
     return int(lib().rxgpu_scan_tier(rows, dim, nq, int(shadow_available), int(stats_finite)))
+
+
+def scan_i6(rows: int, dim: int, nq: int = 1, i6_available: bool = True, stats_finite: bool = True) -> bool:
+    """rxgpu_scan_i6: does such a call (whole index) read the 6-bit shadow instead of the int8 one under the current environment?  Touches no device."""
+    return bool(lib().rxgpu_scan_i6(rows, dim, nq, int(i6_available), int(stats_finite)))
 
 
 def scan_tier_range(rows: int, dim: int, listed: bool = False, shadow_available: bool = True, stats_finite: bool = True) -> int:
@@ -631,6 +637,7 @@ class VectorIndex:
         return int(n.value), int(cap.value)
 
     _INSPECT_DTYPES = {"stats": np.uint32, "row_sq": np.float32, "codes_i8": np.int8, "side_i8": np.float32, "rows_bf16": np.uint16,
+                       "codes_i6": np.uint8, "side_i6": np.float32, "stats_i6": np.uint32, "pruned_seed": np.uint32,
                        "pruned_values": np.float32, "pruned_margin": np.float32, "pruned_q_sq": np.float32, "pruned_qinfo": np.float32,
                        "pruned_qplanes": np.int8, "pruned_top": np.uint32, "pruned_cand_rows": np.uint32,
                        "pruned_emit_cnt": np.uint32, "pruned_emitted": np.uint32}

@@ -293,9 +293,12 @@ __global__ __launch_bounds__(64) void knn_query_prep(const float* src, uint32_t 
 // re-score reads, the query as two int8 planes ([2][ld8] bytes: h, then l), |q|^2 (f32, as knn_query_prep), qinfo = {s_q, |q| rounded up}, the
 // margin of knn_filter_approx, and the candidate counter: 0, or cap + 1 when the query, the margin or the index's statistics are not finite
 // (stats[2]): the exact scan behind the gate answers the query then.  One wavefront per query; the norms and the residual are fp64 sums.
+// estats = {max e^2, max (e inv_norm)^2} of the shadow the scan reads and bad = its non-finite flag (null: none beside stats[2]): the int8
+// shadow's live in stats[3], stats[4], the 6-bit shadow's (knn_scan_i6.hip) in words of their own.
 template <int kMetric>
 __global__ __launch_bounds__(64) void knn_query_prep_i8(const float* src, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
-															 float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap) {
+															 float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap,
+															 const unsigned int* estats, const unsigned int* bad_flag) {
 	const uint32_t qi = blockIdx.x;
 	const int lane = threadIdx.x;
 	const float* q = src + size_t(qi) * dim;
@@ -336,10 +339,10 @@ __global__ __launch_bounds__(64) void knn_query_prep_i8(const float* src, uint32
 	bad = __ballot(bad) != 0;
 	if (lane == 0) {
 		const float qn = i8_norm_up(s64), rq = i8_norm_up(r64);
-		const float mg = i8_margin<kMetric>(s, dim, qn, rq, __uint_as_float(stats[0]), __uint_as_float(stats[1]), __uint_as_float(stats[3]), __uint_as_float(stats[4]));
+		const float mg = i8_margin<kMetric>(s, dim, qn, rq, __uint_as_float(stats[0]), __uint_as_float(stats[1]), __uint_as_float(estats[0]), __uint_as_float(estats[1]));
 		q_sq[qi] = s;
 		qinfo[qi] = make_float2(sq, qn);
-		const bool ok = !bad && stats[2] == 0 && s < __builtin_inff() && qn < __builtin_inff() && mg < __builtin_inff();
+		const bool ok = !bad && stats[2] == 0 && !(bad_flag && *bad_flag != 0) && s < __builtin_inff() && qn < __builtin_inff() && mg < __builtin_inff();
 		margin[qi] = ok ? mg : __builtin_inff();
 		cand_cnt[qi] = ok ? 0u : cap + 1u;
 	}
@@ -491,11 +494,13 @@ void launch_query_prep(int metric, const float* src, uint32_t nq, uint32_t dim, 
 }
 
 void launch_query_prep_i8(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
-						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s) {
+						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s, const unsigned int* estats) {
+	const unsigned int* ew = estats ? estats : stats + 3;
+	const unsigned int* bad = estats ? estats + 2 : nullptr;
 	switch (metric) {
-		case kL2: hipLaunchKernelGGL((knn_query_prep_i8<kL2>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap); break;
-		case kIP: hipLaunchKernelGGL((knn_query_prep_i8<kIP>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap); break;
-		default: hipLaunchKernelGGL((knn_query_prep_i8<kCos>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap); break;
+		case kL2: hipLaunchKernelGGL((knn_query_prep_i8<kL2>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap, ew, bad); break;
+		case kIP: hipLaunchKernelGGL((knn_query_prep_i8<kIP>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap, ew, bad); break;
+		default: hipLaunchKernelGGL((knn_query_prep_i8<kCos>), dim3(nq), dim3(64), 0, s, src, dim, qpad, planes, ld8, stats, q_sq, margin, qinfo, cand_cnt, cap, ew, bad); break;
 	}
 }
 

@@ -93,6 +93,25 @@ struct ScanI8Emit {
 	EmitPlan plan;            // emit_plan(n, gridDim.x)
 };
 
+// The 6-bit front of the same chain (knn_scan_i6.hip, knn_i6_quant.h): the codes come from the tiled 6-bit shadow, the query side, the bound and
+// the emission (ScanI8Emit) are the int8 scan's.  The same kernel also makes the SEED pass: set_step > 1 scans the first set of 16 rows of every
+// set_step sets and emits nothing; its merged list (seed_dist / seed_cnt, as knn_merge_lists leaves them) then tightens the emission of the
+// full pass: a row is emitted when lo <= min(thr of the wavefront, T_seed) + margin.
+struct ScanI6Params {
+	ScanParams sp;            // as ScanI8Params::sp
+	const uint8_t* codes;     // tiles of 4 rows x 3 ld6 bytes (knn_i6_quant.h)
+	const float2* side;       // [n] {s_r, e_r}
+	const int8_t* planes;     // [nq][2][ld6]
+	const float2* qinfo;      // [nq] {s_q, |q| rounded up}
+	const float* row_sq;      // L2
+	const float* q_sq;        // L2: [nq]
+	uint32_t ld6;
+	uint32_t set_step;        // 1: every set
+	float* lower;             // [nq][n] lower bound of every row's distance (the recording form)
+	const float* seed_dist;   // [nq][kk] the seed pass's merged upper bounds, ascending (emitting form)
+	const uint32_t* seed_cnt; // [nq] entries in it: fewer than kk = no seed threshold
+};
+
 // ... and what its range forms (knn_range_i8, knn_range_i8_subset: one query) take instead of the top lists: the radius, and where the rows
 // whose lower bound is within the query's margin of it are compacted
 struct RangeI8Cand {

@@ -144,6 +144,7 @@ void rxgpu_search_ctx::release() {
 	d_qplanes.release();
 	d_emit.release();
 	d_emit_cnt.release();
+	d_seed.release();
 	d_subset.release();
 	d_bitmap.release();
 	d_tiles.release();
@@ -252,6 +253,10 @@ int rxgpu_scan_policy(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_avail
 
 int rxgpu_scan_tier(uint64_t rows, uint32_t dim, uint32_t nq, int shadow_available, int stats_finite) {
 	return int(rxgpu::scan_policy_tier(rows, dim, nq, shadow_available != 0, shadow_available != 0, stats_finite != 0));
+}
+
+int rxgpu_scan_i6(uint64_t rows, uint32_t dim, uint32_t nq, int i6_available, int stats_finite) {
+	return rxgpu::scan_policy_i6(rows, dim, nq, i6_available != 0, stats_finite != 0) ? 1 : 0;
 }
 
 int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, int shadow_available, int stats_finite) {
@@ -491,6 +496,10 @@ int rxgpu_index_truncate(rxgpu_index* h, uint64_t count) {
 	rxgpu::hnsw_server_quiesce(h);   // the resident search kernel reads what changes here
 	// shrinking keeps the statistics (upper bounds stay upper bounds) and the shadow (rows past count are never read)
 	if (count > h->count) rxgpu::derived_invalidate(h);
+	if (count < h->count) {   // (the 6-bit shadow shares tiles between rows: the rows left behind in the last tile go back to zero)
+		DeviceGuard dg(h->device);
+		if (int rc = rxgpu::derived_follow_truncate(h, count); rc) return rc;
+	}
 	h->count = count;
 	return RXGPU_OK;
 }

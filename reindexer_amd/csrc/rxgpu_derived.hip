@@ -1,5 +1,5 @@
-// Data derived from the rows of an index: the row statistics, the bf16 shadow and the int8 shadow.  Built lazily by the search chains
-// (ensure_*), kept in step by the mutations of rxgpu_capi.hip through the four derived_* calls below.  Host-side plumbing only.
+// Data derived from the rows of an index: the row statistics, the bf16 shadow, the int8 shadow and the 6-bit shadow.  Built lazily by the search chains
+// (ensure_*), kept in step by the mutations of rxgpu_capi.hip through the derived_* calls below.  Host-side plumbing only.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/rxgpu.h"
+#include "knn_i6_quant.h"
 #include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
@@ -116,10 +117,62 @@ int ensure_i8_shadow(rxgpu_index* h, hipStream_t s) {
 	return RXGPU_OK;
 }
 
+// 6-bit shadow of the rows for the 6-bit front of the int8-pruned chain (knn_scan_i6.hip): 0.75 bytes per element + 8 bytes per row, in tiles of
+// four rows (knn_i6_quant.h); its residual maxima have three words of their own (kStatsI6Words), so the int8 words keep their meaning.  Built
+// lazily behind the row statistics and kept in step by the mutations like the int8 shadow.  A fresh allocation is zeroed: the rows past the
+// end of the index in the last tile are zero.
+constexpr size_t kStatsI6Words = 3;
+int ensure_i6_shadow(rxgpu_index* h, hipStream_t s) {
+	if (int rc = ensure_row_stats(h, s); rc) return rc;
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (h->i6_valid) return RXGPU_OK;
+	const uint32_t ld6 = i6_ld(h->dim);
+	const uint64_t need = std::max<uint64_t>(h->capacity, h->count);
+	if (h->i6_capacity < need) {
+		if (h->d_codes_i6) (void)hipFree(h->d_codes_i6);
+		if (h->d_side_i6) (void)hipFree(h->d_side_i6);
+		h->d_codes_i6 = nullptr;
+		h->d_side_i6 = nullptr;
+		h->i6_capacity = 0;
+		if (hipMalloc(reinterpret_cast<void**>(&h->d_codes_i6), i6_shadow_bytes(need, ld6)) != hipSuccess ||
+			hipMalloc(reinterpret_cast<void**>(&h->d_side_i6), need * sizeof(float2)) != hipSuccess) {
+			(void)hipGetLastError();   // not an error of the search: the caller takes the int8 front
+			if (h->d_codes_i6) (void)hipFree(h->d_codes_i6);
+			h->d_codes_i6 = nullptr;
+			h->d_side_i6 = nullptr;
+			h->i6_unavailable = true;
+			return RXGPU_ERR_NOMEM;
+		}
+		h->i6_capacity = need;
+		RX_HIP(hipMemsetAsync(h->d_codes_i6, 0, i6_shadow_bytes(need, ld6), s));
+	}
+	if (!h->d_stats_i6) RX_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_stats_i6), kStatsI6Words * sizeof(unsigned int)));
+	RX_HIP(hipMemsetAsync(h->d_stats_i6, 0, kStatsI6Words * sizeof(unsigned int), s));
+	launch_i6_build(h->d_rows, h->d_inv_norms, 0, h->count, h->stride, h->dim, h->d_codes_i6, h->d_side_i6, ld6, h->d_stats_i6, h->cus, s);
+	for (uint64_t row = h->count; row < i6_tiles(h->count) * kI6TileRows; ++row) launch_i6_copy_row(h->d_codes_i6, ld6, ~0ull, row, s);   // (a rebuild over a longer one)
+	RX_HIP(hipGetLastError());
+	RX_HIP(hipStreamSynchronize(s));
+	h->i6_valid = true;
+	return RXGPU_OK;
+}
+
 void derived_invalidate(rxgpu_index* h) {
 	h->stats_valid = false;
 	h->bf16_valid = false;
 	h->i8_valid = false;
+	h->i6_valid = false;
+}
+
+// The index shrinks to `count` rows: the shadows keep their rows (those past the end are never read); the 6-bit shadow's last tile goes back
+// to zero past the end, as a fresh build leaves it.
+int derived_follow_truncate(rxgpu_index* h, uint64_t count) {
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (!h->i6_valid) return RXGPU_OK;
+	const uint64_t end = std::min<uint64_t>(i6_tiles(count) * kI6TileRows, h->i6_capacity);
+	for (uint64_t row = count; row < end; ++row) launch_i6_copy_row(h->d_codes_i6, i6_ld(h->dim), ~0ull, row, nullptr);
+	RX_HIP(hipGetLastError());
+	RX_HIP(hipStreamSynchronize(nullptr));
+	return RXGPU_OK;
 }
 
 // Derived data follows the mutation incrementally (a full recompute streams the whole corpus: 4 ms per 10M x 768 rows).  The row
@@ -153,6 +206,13 @@ int derived_follow_upload(rxgpu_index* h, uint64_t first_row, uint64_t n) {
 			if (int rc = read_stats_finite(h, nullptr); rc) return rc;
 		}
 	}
+	if (h->i6_valid) {
+		if (h->i6_capacity < first_row + n || !h->stats_valid) {
+			h->i6_valid = false;
+		} else {   // re-quantise the range; its residual maxima join the shadow's own statistics words
+			launch_i6_build(h->d_rows, h->d_inv_norms, first_row, n, h->stride, h->dim, h->d_codes_i6, h->d_side_i6, i6_ld(h->dim), h->d_stats_i6, h->cus, nullptr);
+		}
+	}
 	RX_HIP(hipGetLastError());
 	RX_HIP(hipStreamSynchronize(nullptr));
 	return RXGPU_OK;
@@ -173,6 +233,11 @@ int derived_follow_move(rxgpu_index* h, uint64_t from, uint64_t to) {
 		RX_HIP(hipMemcpy(h->d_codes_i8 + to * ld8, h->d_codes_i8 + from * ld8, ld8, hipMemcpyDeviceToDevice));
 		RX_HIP(hipMemcpy(h->d_side_i8 + to, h->d_side_i8 + from, sizeof(float2), hipMemcpyDeviceToDevice));
 	}
+	if (h->i6_valid) {   // (a row's bytes inside its tile are its own)
+		launch_i6_copy_row(h->d_codes_i6, i6_ld(h->dim), from, to, nullptr);
+		RX_HIP(hipGetLastError());
+		RX_HIP(hipMemcpy(h->d_side_i6 + to, h->d_side_i6 + from, sizeof(float2), hipMemcpyDeviceToDevice));
+	}
 	return RXGPU_OK;
 }
 
@@ -188,7 +253,7 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 		uint64_t bytes;
 	};
 	std::vector<Piece> pieces;
-	bool deblock = false;
+	bool deblock = false, detile = false;
 	auto missing = [&](const char* why) {
 		set_error(std::string("rxgpu_index_inspect: ") + what + ": " + why);
 		return RXGPU_ERR_LOGIC;
@@ -207,6 +272,16 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 		} else {
 			pieces.push_back({h->d_side_i8, n * sizeof(float2)});
 		}
+	} else if (name == "codes_i6" || name == "side_i6" || name == "stats_i6") {
+		if (!h->i6_valid) return missing("the 6-bit shadow is not built");
+		if (name == "codes_i6") {   // de-tiled on the host below: [count][ld6] bytes of u
+			detile = true;
+			pieces.push_back({h->d_codes_i6, n * i6_ld(h->dim)});
+		} else if (name == "side_i6") {
+			pieces.push_back({h->d_side_i6, n * sizeof(float2)});
+		} else {
+			pieces.push_back({h->d_stats_i6, kStatsI6Words * sizeof(unsigned int)});
+		}
 	} else if (name == "rows_bf16") {
 		if (!h->bf16_valid) return missing("the bf16 shadow is not built");
 		deblock = h->bf16_blocked;
@@ -218,7 +293,7 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 		const float* qstats = c ? static_cast<const float*>(c->d_qstats.ptr) : nullptr;   // one query: [{s_q, |q|^}] |q|^2, margin
 		const float* q_sq = qstats ? qstats + (i8 ? 2 : 0) : nullptr;
 		const char* known[] = {"pruned_values", "pruned_margin", "pruned_q_sq", "pruned_qinfo", "pruned_qplanes", "pruned_top", "pruned_cand_rows",
-								   "pruned_emit_cnt", "pruned_emitted"};
+								   "pruned_emit_cnt", "pruned_emitted", "pruned_seed"};
 		if (std::find_if(std::begin(known), std::end(known), [&](const char* k) { return name == k; }) == std::end(known)) {
 			set_error(std::string("rxgpu_index_inspect: unknown buffer ") + what);
 			return RXGPU_ERR_PARAMS;
@@ -243,6 +318,11 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 			} else {   // [n] {lo, row} pairs: the segments back to back, each valid up to its count
 				pieces.push_back({c->d_emit.ptr, emit_buffer_bytes(h->last_pruned_n, 1)});
 			}
+		} else if (name == "pruned_seed") {   // d_seed of one query, as "pruned_top": [kk] values and the count of the seed pass's merged list
+			if (!h->last_pruned_i6) return missing("the recorded call did not take the 6-bit front");
+			const float* seed = static_cast<const float*>(c->d_seed.ptr);
+			pieces.push_back({seed, kk * sizeof(float)});
+			pieces.push_back({seed + 2 * size_t(kk), sizeof(uint32_t)});
 		} else if (name == "pruned_top") {   // d_top of one query: [kk] values, [kk] rows, the count
 			const float* top = static_cast<const float*>(c->d_top.ptr);
 			pieces.push_back({top, kk * sizeof(float)});
@@ -262,6 +342,13 @@ int inspect_index(rxgpu_index* h, const char* what, void* out, uint64_t cap_byte
 		return RXGPU_ERR_OVERFLOW;
 	}
 	if (!need) return RXGPU_OK;
+	if (detile) {   // whole tiles to the host, then row by row (knn_i6_quant.h)
+		const uint32_t ld6 = i6_ld(h->dim);
+		std::vector<uint8_t> raw(i6_shadow_bytes(n, ld6));
+		RX_HIP(hipMemcpy(raw.data(), h->d_codes_i6, raw.size(), hipMemcpyDeviceToHost));
+		for (uint64_t r = 0; r < n; ++r) i6_load_row(raw.data(), r, ld6, static_cast<uint8_t*>(out) + r * ld6);
+		return RXGPU_OK;
+	}
 	if (deblock) {   // the tile-blocked shadow ([tile of 256 rows][32-element k-block][row][32]) back to [count][ld]: whole tiles to the host, then a loop
 		const uint32_t ld = bf16_ld(h);
 		const uint64_t tiles = (n + kShadowTileRows - 1) / kShadowTileRows;
@@ -287,6 +374,9 @@ void derived_free(rxgpu_index* h) {
 	if (h->d_rows_bf16) (void)hipFree(h->d_rows_bf16);
 	if (h->d_codes_i8) (void)hipFree(h->d_codes_i8);
 	if (h->d_side_i8) (void)hipFree(h->d_side_i8);
+	if (h->d_codes_i6) (void)hipFree(h->d_codes_i6);
+	if (h->d_side_i6) (void)hipFree(h->d_side_i6);
+	if (h->d_stats_i6) (void)hipFree(h->d_stats_i6);
 	if (h->d_stats) (void)hipFree(h->d_stats);
 }
 

@@ -32,8 +32,17 @@ uint32_t scan_i8_subset_grid_x(uint64_t n_ids, int cus);
 void launch_scan_i8_subset(int metric, const ScanI8Params& p, const uint32_t* ids, uint32_t nq, uint32_t gridx, int cus, hipStream_t s);
 void launch_i8_build(const float* rows, const float* inv_norms, uint64_t n, uint32_t stride, uint32_t dim, int8_t* codes, float2* side, uint32_t ld8,
 					 unsigned int* stats, int cus, hipStream_t s);   // every pointer at the first row of the range
+// estats: the residual maxima the margin takes, {max e^2, max (e inv_norm)^2, non-finite flag}; null = the int8 shadow's (stats[3], stats[4]; its flag is stats[2])
 void launch_query_prep_i8(int metric, const float* src, uint32_t nq, uint32_t dim, float* qpad, int8_t* planes, uint32_t ld8, const unsigned int* stats,
-						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s);
+						  float* q_sq, float* margin, float2* qinfo, uint32_t* cand_cnt, uint32_t cap, hipStream_t s, const unsigned int* estats = nullptr);
+// the 6-bit front of the int8-pruned chain (knn_scan_i6.hip, knn_i6_quant.h): seed pass (emit null) and full pass of one kernel
+struct ScanI6Params;
+uint32_t scan_i6_seed_step(uint64_t n);
+uint32_t scan_i6_grid_x(uint64_t n, uint32_t set_step, int cus);
+void launch_scan_i6(int metric, const ScanI6Params& p, uint32_t nq, uint32_t gridx, hipStream_t s, const ScanI8Emit* emit, bool keep);
+void launch_i6_build(const float* rows, const float* inv_norms, uint64_t first_row, uint64_t n, uint32_t stride, uint32_t dim, uint8_t* codes, float2* side,
+					 uint32_t ld6, unsigned int* stats6, int cus, hipStream_t s);   // every pointer at row 0 of the index
+void launch_i6_copy_row(uint8_t* codes, uint32_t ld6, uint64_t from, uint64_t to, hipStream_t s);   // from == ~0: zeros over row `to`
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
 						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s,
 						  const uint32_t* ids = nullptr);   // ids: approx is indexed by list position and the candidates are ids[position]
@@ -42,6 +51,9 @@ struct EmitPlan;
 void launch_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count, uint32_t kk,
 						   const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus,
 						   hipStream_t s);   // launch_filter_approx over what knn_scan_i8 emitted
+void launch_filter_emitted_wide(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count,
+								uint32_t kk, const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus,
+								hipStream_t s);   // the same candidate set with one atomic per workgroup (knn_scan_i6.hip): for thousands of candidates
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s);
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
@@ -458,6 +470,7 @@ struct rxgpu_search_ctx {
 	rxgpu_devbuf d_top;                                                            // bf16- / int8-pruned scan: approximate top lists
 	rxgpu_devbuf d_qplanes;                                                        // int8-pruned scan: the query's two int8 planes
 	rxgpu_devbuf d_emit, d_emit_cnt;                                               // int8-pruned scan: the rows it emitted and their count per wavefront (knn_emit_plan.h)
+	rxgpu_devbuf d_seed;                                                           // 6-bit front: the seed pass's merged list, laid out like d_top
 	rxgpu_devbuf d_ivf;                                                            // IVF: the coarse search's lists, distances, count
 	rxgpu_devbuf d_subset, d_bitmap, d_tiles;                                      // pre-filtered search: row list, allowed-rows bitmap, tile sums
 	uint32_t pruned_cap = 0;   // candidate capacity of the pruned chain the current call enqueued (0: none) — rxgpu_index_last_candidates
@@ -466,7 +479,8 @@ struct rxgpu_search_ctx {
 	uint64_t pruned_n = 0;
 	uint32_t pruned_kk = 0, pruned_ld = 0;
 	bool pruned_i8 = false;
-	uint32_t pruned_emit_gridx = 0;   // the grid of the int8 scan when it emitted (0: it stored a value per row and emitted nothing)
+	bool pruned_i6 = false;           // the 6-bit front ran: d_seed holds the seed pass's merged list
+	uint32_t pruned_emit_gridx = 0;  // the grid of the int8 scan when it emitted (0: it stored a value per row and emitted nothing)
 	// Set by a host entry point that ends in copy_back_knn, in front of the enqueue, when the call will be recorded for rxgpu_index_inspect
 	// (profiling, one query); cleared by copy_back_knn.  The emitting int8 scan then keeps its value per row as well ("pruned_values").
 	bool keep_values = false;
@@ -587,6 +601,14 @@ struct rxgpu_index {
 	uint64_t i8_capacity = 0;
 	bool i8_valid = false;
 	bool i8_unavailable = false;       // it did not fit in HBM: the call takes the bf16 tier
+	// 6-bit shadow for the 6-bit front of the same chain (knn_scan_i6.hip): tiles of 4 rows (knn_i6_quant.h), its own side pairs and its own
+	// statistics words {max e^2, max (e inv_norm)^2, non-finite}; built lazily and kept in step like the int8 shadow
+	uint8_t* d_codes_i6 = nullptr;     // [i6_tiles(i6_capacity)] tiles
+	float2* d_side_i6 = nullptr;       // [i6_capacity]
+	unsigned int* d_stats_i6 = nullptr;
+	uint64_t i6_capacity = 0;
+	bool i6_valid = false;
+	bool i6_unavailable = false;       // it did not fit in HBM: the call takes the int8 front
 	std::atomic<uint32_t> last_cand_count{0}, last_cand_cap{0};   // rxgpu_index_last_candidates
 	// rxgpu_index_inspect: the context the last profiled single-query pruned call ran in (idle in the pool since, so its buffers hold what the
 	// chain left until the next call on the index takes it), with that call's sizes.  Guarded by mtx; null: none recorded.
@@ -594,6 +616,7 @@ struct rxgpu_index {
 	uint64_t last_pruned_n = 0;
 	uint32_t last_pruned_kk = 0, last_pruned_ld = 0;
 	bool last_pruned_i8 = false;
+	bool last_pruned_i6 = false;
 	uint32_t last_pruned_emit_gridx = 0;
 
 	// HNSW graph mirror (rxgpu_hnsw_attach_graph)
@@ -681,8 +704,10 @@ struct ProfileScope {
 int ensure_row_stats(rxgpu_index* h, hipStream_t s);
 int ensure_bf16_shadow(rxgpu_index* h, hipStream_t s);   // RXGPU_ERR_NOMEM + h->bf16_unavailable: it does not fit, the caller takes the f32 rows
 int ensure_i8_shadow(rxgpu_index* h, hipStream_t s);     // (the row statistics first)  RXGPU_ERR_NOMEM + h->i8_unavailable: the caller takes the bf16 tier
+int ensure_i6_shadow(rxgpu_index* h, hipStream_t s);     // (the row statistics first)  RXGPU_ERR_NOMEM + h->i6_unavailable: the caller takes the int8 front
 // ... and the mutations keep them in step
-void derived_invalidate(rxgpu_index* h);                                        // the rows changed wholesale: everything is rebuilt at its next use
+int derived_follow_truncate(rxgpu_index* h, uint64_t count);                    // the index shrinks to `count` rows (before h->count changes)
+void derived_invalidate(rxgpu_index* h);                                       // the rows changed wholesale: everything is rebuilt at its next use
 int derived_follow_upload(rxgpu_index* h, uint64_t first_row, uint64_t n);      // rows [first_row, first_row + n) were written
 int derived_follow_move(rxgpu_index* h, uint64_t from, uint64_t to);            // row `from` was copied over row `to`
 void derived_free(rxgpu_index* h);                                              // the index is being destroyed
@@ -704,6 +729,8 @@ void sort_dist_row(const std::vector<float>& hd, const std::vector<uint32_t>& hr
 enum ScanTier { kTierF32 = 0, kTierBf16 = 1, kTierI8 = 2 };
 bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite);
 ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool bf16_available, bool i8_available, bool stats_finite);
+// does a whole-index call of nq queries read the 6-bit shadow (the 6-bit front of the kTierI8 chain)?  rxgpu_scan_i6
+bool scan_policy_i6(uint64_t rows, uint32_t dim, uint32_t nq, bool i6_available, bool stats_finite);
 ScanTier scan_policy_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t kk, bool i8_available, bool stats_finite);
 ScanTier scan_policy_tier_range(uint64_t rows, uint32_t dim, bool list, bool i8_available, bool stats_finite);   // rxgpu_scan_tier_range
 // The int8 front of a range call whose query lies in c->d_queries (d_ids null: every row, else n list entries in HBM) and whose counter

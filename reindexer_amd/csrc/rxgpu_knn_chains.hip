@@ -1,11 +1,12 @@
 // The host-side chains of brute-force KNN: which scan a call takes (the policy), and the launches of each chain — fused f32 scan, batched
-// nomination (f32 / bf16 GEMM) with its exact tail, the pruned chains (bf16 / int8 / int8 over a row list) with theirs, the pre-filtered
+// nomination (f32 / bf16 GEMM) with its exact tail, the pruned chains (bf16 / int8 / int8 over a row list / 6-bit) with theirs, the pre-filtered
 // scan.  Called by the entry points of rxgpu_knn_search.hip through rxgpu_internal.h.  Host-side plumbing only — all arithmetic is in the kernels.
 #include <algorithm>
 #include <cstdlib>
 
 #include "../../include/rxgpu.h"
 #include "knn_emit_plan.h"
+#include "knn_i6_quant.h"
 #include "knn_i8_quant.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
@@ -310,6 +311,26 @@ uint64_t pruned_i8_range_auto_min_bytes() {
 	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI8RangeAutoMinBytes;
 }
 
+// The 6-bit front (knn_scan_i6.hip) refines a call of the int8 tier: the same chain reads a 6-bit shadow (0.75 bytes per element) behind a seed
+// pass.  RXGPU_SCAN_I6, read per call: 0 = off, 1 = forced at any size (up to kPrunedMaxQueries queries; for tests and A/B), unset = automatic:
+// a call the automatic rules above give to the int8 tier, on an index of at least kPrunedI6AutoMinBytes of f32 rows.  RXGPU_SCAN_BF16=0 / =1 and
+// RXGPU_SCAN_I8=0 / =1 win over it as documented above: RXGPU_SCAN_I8=1 means the int8 front, exactly.
+// kPrunedI6AutoMinBytes: the measured crossover against the int8 front and every other series (tools/scan_policy_crossover.py, series i6;
+// profiles/scan_i6_crossover.json: at 768 dims the front loses up to 6.1 GB of f32 rows - its seed pass, its merge and a tail over thousands of
+// candidates cost about 65 us - and wins beyond the spread from 12.3 GB on), rounded up to a power of two and never below 1 GiB: 2^34.  The
+// automatic mode is on because the headline A/B shows the gain beyond both spreads (profiles/scan_i6_headline_ab.json).
+// RXGPU_SCAN_I6_MIN_BYTES overrides it.
+constexpr uint64_t kPrunedI6AutoMinBytes = 1ull << 34;
+ScanBf16Mode scan_i6_mode() {
+	const char* e = getenv("RXGPU_SCAN_I6");
+	if (!e || !*e) return kScanBf16Auto;
+	return atoi(e) != 0 ? kScanBf16On : kScanBf16Off;
+}
+uint64_t pruned_i6_auto_min_bytes() {
+	const char* e = getenv("RXGPU_SCAN_I6_MIN_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : kPrunedI6AutoMinBytes;
+}
+
 }  // namespace
 
 // The whole decision, without a device: which scan does a call with nq queries on rows x dim f32 rows take?
@@ -323,6 +344,16 @@ ScanTier scan_policy_tier(uint64_t rows, uint32_t dim, uint32_t nq, bool bf16_av
 	if (mode == kScanBf16On) return nq <= kPrunedMaxQueries ? kTierBf16 : kTierF32;
 	if (!(nq == 1 && stats_finite && rows * dim * sizeof(float) >= pruned_auto_min_bytes())) return kTierF32;
 	return i8_can && rows * dim * sizeof(float) >= pruned_i8_auto_min_bytes() ? kTierI8 : kTierBf16;
+}
+// Does such a call read the 6-bit shadow?  A refinement inside the int8 tier: scan_policy_tier does not know RXGPU_SCAN_I6 and keeps its
+// answers; the forced mode takes a call at any size, as RXGPU_SCAN_I8=1 does.
+bool scan_policy_i6(uint64_t rows, uint32_t dim, uint32_t nq, bool i6_available, bool stats_finite) {
+	const ScanBf16Mode mode = scan_i6_mode();
+	if (mode == kScanBf16Off || !i6_available || !i6_dim_supported(dim)) return false;
+	if (scan_bf16_mode() != kScanBf16Auto || scan_i8_mode() != kScanBf16Auto) return false;
+	if (mode == kScanBf16On) return nq <= kPrunedMaxQueries;
+	if (scan_policy_tier(rows, dim, nq, true, true, stats_finite) != kTierI8) return false;
+	return rows * dim * sizeof(float) >= pruned_i6_auto_min_bytes();
 }
 // ... does it take a pruned scan at all?
 bool scan_policy_pruned(uint64_t rows, uint32_t dim, uint32_t nq, bool shadow_available, bool stats_finite) {
@@ -362,6 +393,7 @@ namespace {
 // rows that can still belong to the result are filtered out of the values, re-scored exactly and merged.  Queries with more such rows than
 // the candidate list holds (massive ties), or without a finite bound, are answered by the exact f32 scan behind a gate on the device.
 constexpr uint32_t kPrunedCap = 4096;
+uint32_t pruned_cap(uint64_t n, uint32_t most = kPrunedCap) { return uint32_t(std::min<uint64_t>(most, std::max<uint64_t>(64, (n + 63) & ~63ull))); }
 // RXGPU_SCAN_I8_EMIT, read per call (A/B runs inside one process): 0 = the int8 scan stores a value per row and knn_filter_approx reads them
 // all back (the sequence before the scan emitted); else / unset = the scan emits, knn_filter_emitted reads what it emitted.
 bool scan_i8_emits() {
@@ -392,11 +424,17 @@ struct PrunedFront {
 	// Which filter form the scan feeds.  false: a value per row in b.values, knn_filter_approx reads all of them.  true: the scan emits the rows
 	// that can still be candidates (knn_emit_plan.h), knn_filter_emitted reads those; b.values is written only for a recording call (b.keep).
 	bool emits;
+	bool many_candidates;     // an emitting front whose filter leaves thousands of rows: knn_filter_emitted_wide
 	uint64_t n;               // rows scanned: the index's, or the entries of ids
 	const uint32_t* ids;      // the row list (null: every row); decides the exact scan behind the gate as well
+	uint32_t cap;             // candidates the list holds per query (a multiple of 64)
 	uint32_t gridx;           // the pruning scan's grid ...
 	uint32_t gridx_exact;     // ... and the gated exact scan's (scan_grid_x, or subset_grid_x over a row list)
 	const char* scan_slot;    // profile slot of the pruning scan
+	// An optional pass in front of the scan, under a profile slot of its own (the 6-bit front's seed pass and its merge).  It may use the part
+	// buffers: the scan overwrites them afterwards.
+	const char* seed_slot;
+	void (*seed)(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, const ScanParams& sp, const PrunedFront& f, const PrunedBufs& b);
 	// The profile slot of the gated exact scan: false = filed for every call.  true = while profiling, the slot counts the calls whose gate
 	// OPENED for one of the queries (the counts are read back first, which synchronises the stream): a call the pruned chain answered
 	// leaves it at 0, like "scan_subset".
@@ -411,7 +449,7 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 							 float* d_out_dist, uint32_t* d_out_row, uint32_t* d_out_count) {
 	if (int rc = f.ensure_shadow(h, c->stream); rc) return rc;
 	const uint32_t grid_max = std::max(f.gridx, f.gridx_exact);
-	const uint32_t cap = uint32_t(std::min<uint64_t>(kPrunedCap, std::max<uint64_t>(64, (f.n + 63) & ~63ull)));
+	const uint32_t cap = f.cap;
 	if (int rc = c->d_qpad.ensure(size_t(nq) * f.ld * sizeof(float)); rc) return rc;
 	if (f.planes) {
 		if (int rc = c->d_qplanes.ensure(size_t(nq) * 2 * f.ld); rc) return rc;
@@ -428,6 +466,9 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	if (int rc = c->d_part_dist.ensure(size_t(nq) * grid_max * kk * sizeof(float)); rc) return rc;
 	if (int rc = c->d_part_row.ensure(size_t(nq) * grid_max * kk * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_top.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
+	if (f.seed) {
+		if (int rc = c->d_seed.ensure(size_t(nq) * (2 * kk + 1) * sizeof(uint32_t)); rc) return rc;
+	}
 	if (int rc = c->d_cand_row.ensure(size_t(nq) * cap * sizeof(uint32_t)); rc) return rc;
 	if (int rc = c->d_cand_dist.ensure(size_t(nq) * cap * sizeof(float)); rc) return rc;
 	if (int rc = c->d_cand_cnt.ensure(size_t(nq) * sizeof(uint32_t)); rc) return rc;
@@ -452,9 +493,14 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	c->pruned_kk = kk;
 	c->pruned_ld = f.ld;
 	c->pruned_i8 = f.planes;
+	c->pruned_i6 = f.seed != nullptr;
 	c->pruned_emit_gridx = f.emits ? f.gridx : 0;
 	f.prep(h, c, d_queries, nq, f, b);
 	const ScanParams e = scan_params(h, c, d_queries, f.n, kk, b.cand_cnt, cap);   // the exact scan behind the gate
+	if (f.seed) {
+		ProfileScope ps(h, f.seed_slot, c->stream);
+		f.seed(h, c, nq, scan_params(h, c, nullptr, f.n, kk), f, b);
+	}
 	{
 		ProfileScope ps(h, f.scan_slot, c->stream);
 		f.scan(h, c, nq, scan_params(h, c, nullptr, f.n, kk), f, b);
@@ -463,7 +509,9 @@ int enqueue_knn_pruned_chain(rxgpu_index* h, rxgpu_search_ctx* c, const float* d
 	launch_merge_lists(e.part_dist, e.part_row, f.gridx, kk, nq, top_dist, top_row, top_cnt, c->stream);
 	{
 		ProfileScope ps(h, "filter_approx", c->stream);
-		if (f.emits) {
+		if (f.emits && f.many_candidates) {
+			launch_filter_emitted_wide(b.emit, b.emit_cnt, emit_plan(f.n, f.gridx), top_dist, top_cnt, kk, b.margin, cand_row, b.cand_cnt, cap, nq, h->cus, c->stream);
+		} else if (f.emits) {
 			launch_filter_emitted(b.emit, b.emit_cnt, emit_plan(f.n, f.gridx), top_dist, top_cnt, kk, b.margin, cand_row, b.cand_cnt, cap, nq, h->cus, c->stream);
 		} else {
 			launch_filter_approx(b.values, f.n, top_dist, top_cnt, kk, b.margin, cand_row, b.cand_cnt, cap, nq, h->cus, c->stream, f.ids);
@@ -512,6 +560,7 @@ int enqueue_knn_pruned(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queri
 	f.ld = (h->dim + 63u) & ~63u;
 	f.qstats_floats = 2;
 	f.n = h->count;
+	f.cap = pruned_cap(f.n);
 	f.gridx = scan_bf16_grid_x(h->count, h->cus);
 	f.gridx_exact = scan_grid_x(h->count, h->cus);
 	f.scan_slot = "scan_bf16";
@@ -546,6 +595,7 @@ int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_qu
 	f.planes = true;
 	f.n = d_ids ? n_ids : h->count;
 	f.ids = d_ids;
+	f.cap = pruned_cap(f.n);
 	f.emits = !d_ids && scan_i8_emits();   // (the gather form keeps a value per list position)
 	f.gridx = d_ids ? scan_i8_subset_grid_x(n_ids, h->cus) : scan_i8_grid_x(h->count, h->cus);
 	f.gridx_exact = d_ids ? subset_grid_x(n_ids, h->dim, kk, h->cus) : scan_grid_x(h->count, h->cus);
@@ -578,6 +628,68 @@ int enqueue_knn_pruned_i8(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_qu
 		} else {
 			launch_scan_i8(h->metric, p, nq, f.gridx, c->stream);
 		}
+	};
+	return enqueue_knn_pruned_chain(h, c, d_queries, nq, kk, f, d_out_dist, d_out_row, d_out_count);
+}
+
+// The 6-bit front of the int8 tier (knn_scan_i6.hip; whole index only): the int8 prep with the 6-bit residual maxima, a seed pass over a strided
+// sample whose merged list gives the scan a tight emission threshold from its first row, and the emitting scan.  The per-row window is four
+// times the int8 one, so the filter leaves thousands of candidates where the int8 front leaves tens: the list holds
+// kPrunedCapI6.  RXGPU_SCAN_I6_CAP lowers it (tests of the overflow gate).
+constexpr uint32_t kPrunedCapI6 = 65536;
+ScanI6Params scan_i6_params(rxgpu_index* h, rxgpu_search_ctx* c, const ScanParams& sp, const PrunedFront& f, const PrunedBufs& b) {
+	ScanI6Params p{};
+	p.sp = sp;
+	p.codes = h->d_codes_i6;
+	p.side = h->d_side_i6;
+	p.planes = static_cast<const int8_t*>(c->d_qplanes.ptr);
+	p.qinfo = reinterpret_cast<const float2*>(b.qstats);
+	p.row_sq = h->d_row_sq;
+	p.q_sq = b.q_sq;
+	p.ld6 = f.ld;
+	p.set_step = 1;
+	p.lower = b.values;
+	return p;
+}
+int enqueue_knn_pruned_i6(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, uint32_t kk, float* d_out_dist, uint32_t* d_out_row,
+						  uint32_t* d_out_count) {
+	PrunedFront f{};
+	f.ensure_shadow = ensure_i6_shadow;   // (the row statistics first)
+	f.ld = i6_ld(h->dim);
+	f.qstats_floats = 4;   // as the int8 front
+	f.planes = true;
+	f.n = h->count;
+	f.cap = pruned_cap(f.n, kPrunedCapI6);
+	if (const char* e = getenv("RXGPU_SCAN_I6_CAP"); e && *e) f.cap = std::min(f.cap, pruned_cap(f.n, uint32_t(std::max(64, atoi(e)) + 63) & ~63u));
+	f.emits = true;
+	f.many_candidates = true;
+	f.gridx = scan_i6_grid_x(h->count, 1, h->cus);
+	f.gridx_exact = scan_grid_x(h->count, h->cus);
+	f.scan_slot = "scan_i6";
+	f.seed_slot = "seed_i6";
+	f.prep = [](rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uint32_t nq, const PrunedFront& f, const PrunedBufs& b) {
+		launch_query_prep_i8(h->metric, d_queries, nq, h->dim, b.qpad, static_cast<int8_t*>(c->d_qplanes.ptr), f.ld, h->d_stats, b.q_sq, b.margin,
+							 reinterpret_cast<float2*>(b.qstats), b.cand_cnt, b.cap, c->stream, h->d_stats_i6);
+	};
+	f.seed = [](rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, const ScanParams& sp, const PrunedFront& f, const PrunedBufs& b) {
+		ScanI6Params p = scan_i6_params(h, c, sp, f, b);
+		p.set_step = scan_i6_seed_step(f.n);
+		const uint32_t gridx = scan_i6_grid_x(f.n, p.set_step, h->cus);   // (<= f.gridx: the part buffers hold it)
+		launch_scan_i6(h->metric, p, nq, gridx, c->stream, nullptr, false);
+		float* seed_dist = static_cast<float*>(c->d_seed.ptr);
+		uint32_t* seed_row = reinterpret_cast<uint32_t*>(seed_dist + size_t(nq) * sp.kk);
+		launch_merge_lists(sp.part_dist, sp.part_row, gridx, sp.kk, nq, seed_dist, seed_row, seed_row + size_t(nq) * sp.kk, c->stream);
+	};
+	f.scan = [](rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, const ScanParams& sp, const PrunedFront& f, const PrunedBufs& b) {
+		ScanI6Params p = scan_i6_params(h, c, sp, f, b);
+		p.seed_dist = static_cast<const float*>(c->d_seed.ptr);
+		p.seed_cnt = reinterpret_cast<const uint32_t*>(p.seed_dist + 2 * size_t(nq) * sp.kk);
+		ScanI8Emit e{};
+		e.margin = b.margin;
+		e.emit = b.emit;
+		e.emit_cnt = b.emit_cnt;
+		e.plan = emit_plan(f.n, f.gridx);
+		launch_scan_i6(h->metric, p, nq, f.gridx, c->stream, &e, b.keep);
 	};
 	return enqueue_knn_pruned_chain(h, c, d_queries, nq, kk, f, d_out_dist, d_out_row, d_out_count);
 }
@@ -696,6 +808,7 @@ int copy_back_knn(rxgpu_index* h, rxgpu_search_ctx* c, uint32_t nq, uint32_t kk,
 		h->last_pruned_kk = c->pruned_kk;
 		h->last_pruned_ld = c->pruned_ld;
 		h->last_pruned_i8 = c->pruned_i8;
+		h->last_pruned_i6 = c->pruned_i6;
 		h->last_pruned_emit_gridx = c->pruned_emit_gridx;
 	} else if (h->profiling) {   // another chain answered: whatever context it ran in may be the recorded one
 		std::lock_guard<std::mutex> lk(h->mtx);
@@ -771,6 +884,18 @@ int enqueue_knn(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_queries, uin
 	// (automatic mode asks whether the row statistics are finite: compute them first where everything else already says yes)
 	if (scan_bf16_mode() == kScanBf16Auto && scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, true) != kTierF32) {
 		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
+	}
+	if (scan_policy_i6(h->count, h->dim, nq, !h->i6_unavailable, true) && h->count) {
+		if (int rc = ensure_row_stats(h, c->stream); rc) return rc;
+		if (scan_policy_i6(h->count, h->dim, nq, !h->i6_unavailable, h->stats_finite)) {
+			int rc = enqueue_knn_pruned_i6(h, c, d_queries, nq, kk, d_out_dist, d_out_row, d_out_count);
+			if (!(rc == RXGPU_ERR_NOMEM && h->i6_unavailable)) return rc;
+			// no room for the 6-bit shadow: the int8 front (which the forced mode takes at any size, like RXGPU_SCAN_I8=1), then the tiers below
+			if (!h->i8_unavailable) {
+				rc = enqueue_knn_pruned_i8(h, c, d_queries, nq, kk, nullptr, 0, d_out_dist, d_out_row, d_out_count);
+				if (!(rc == RXGPU_ERR_NOMEM && h->i8_unavailable)) return rc;
+			}
+		}
 	}
 	if (scan_policy_tier(h->count, h->dim, nq, !h->bf16_unavailable, !h->i8_unavailable, h->stats_finite) == kTierI8) {
 		const int rc = enqueue_knn_pruned_i8(h, c, d_queries, nq, kk, nullptr, 0, d_out_dist, d_out_row, d_out_count);

@@ -5,13 +5,14 @@
     python tools/scan_policy_crossover.py --ab RXGPU_SCAN_BF16_WG_PER_CU=2,3,4 --rows 10000000   # a tuning knob of the bf16 scan, same method
     python tools/scan_policy_crossover.py --ab RXGPU_SCAN_I8_WG_PER_CU=2,3 --rows 10000000       # ... of the int8 scan (a knob named RXGPU_SCAN_I8_*)
 
-One process, one resident corpus per size; per size the three series (RXGPU_SCAN_BF16=0, =1, and RXGPU_SCAN_I8=1 with RXGPU_SCAN_BF16 unset,
-read by the library on every call; the int8 series only at dimensions that tier serves) ALTERNATE,
+One process, one resident corpus per size; per size the four series (RXGPU_SCAN_BF16=0, =1, RXGPU_SCAN_I8=1 with RXGPU_SCAN_BF16 unset, and
+RXGPU_SCAN_I6=1 with both unset: the 6-bit front of the int8 tier; all read by the library on every call; the int8 and 6-bit series only at
+dimensions those serve) ALTERNATE,
 --rounds times each, every round timing --queries single-query searches through rxgpu_search_knn_device with one synchronisation at the end
 (what bench.py calls ms_per_step).  Reported per size and series: median, min, max of the rounds.  The pruned path "wins" at a size when its
 worst round beats the f32 path's best round; the automatic threshold in rxgpu_knn_chains.hip (kPrunedAutoMinBytes) is the smallest such size in
 bytes of f32 rows, rounded up to a power of two, and never below 1 GiB.  The int8 tier's threshold (kPrunedI8AutoMinBytes) follows the same
-rule against the bf16 series.
+rule against the bf16 series, and the 6-bit front's (kPrunedI6AutoMinBytes) against the int8 series and every other one.
 """
 import argparse
 import json
@@ -82,11 +83,16 @@ def main():
         base = {"RXGPU_SCAN_BF16": None, "RXGPU_SCAN_I8": "1"} if knob.startswith("RXGPU_SCAN_I8") else {"RXGPU_SCAN_BF16": "1", "RXGPU_SCAN_I8": None}
         variants = [("%s=%s" % (knob, w), {**base, knob: w}) for w in vals.split(",")]
     else:
-        variants = [("f32", {"RXGPU_SCAN_BF16": "0", "RXGPU_SCAN_I8": None}), ("pruned", {"RXGPU_SCAN_BF16": "1", "RXGPU_SCAN_I8": None})]
+        variants = [("f32", {"RXGPU_SCAN_BF16": "0", "RXGPU_SCAN_I8": None, "RXGPU_SCAN_I6": None}),
+                    ("pruned", {"RXGPU_SCAN_BF16": "1", "RXGPU_SCAN_I8": None, "RXGPU_SCAN_I6": None})]
         os.environ.pop("RXGPU_SCAN_BF16", None)
         os.environ["RXGPU_SCAN_I8"] = "1"
         if capi.scan_tier(1000, args.dim) == 2:
-            variants.append(("int8", {"RXGPU_SCAN_BF16": None, "RXGPU_SCAN_I8": "1"}))
+            variants.append(("int8", {"RXGPU_SCAN_BF16": None, "RXGPU_SCAN_I8": "1", "RXGPU_SCAN_I6": None}))
+        os.environ.pop("RXGPU_SCAN_I8", None)
+        os.environ["RXGPU_SCAN_I6"] = "1"
+        if capi.scan_i6(1000, args.dim):
+            variants.append(("i6", {"RXGPU_SCAN_BF16": None, "RXGPU_SCAN_I8": None, "RXGPU_SCAN_I6": "1"}))
     result = {"dim": args.dim, "metric": args.metric, "k": args.k, "queries_per_round": args.queries, "rounds": args.rounds,
               "arch": capi.device_arch(0), "ab": args.ab, "sizes": []}
     for n in sizes:
@@ -105,9 +111,11 @@ def main():
                 entry["pruned_wins_beyond_spread"] = max(times["pruned"]) < min(times["f32"])
                 if "int8" in times:
                     entry["int8_wins_beyond_spread"] = max(times["int8"]) < min(times["pruned"]) and max(times["int8"]) < min(times["f32"])
+                if "i6" in times:
+                    entry["i6_wins_beyond_spread"] = all(max(times["i6"]) < min(v) for name, v in times.items() if name != "i6")
             result["sizes"].append(entry)
             print(json.dumps(entry), flush=True)
-    for k_ in ["RXGPU_SCAN_BF16", "RXGPU_SCAN_I8"] + ([args.ab.split("=", 1)[0]] if args.ab else []):
+    for k_ in ["RXGPU_SCAN_BF16", "RXGPU_SCAN_I8", "RXGPU_SCAN_I6"] + ([args.ab.split("=", 1)[0]] if args.ab else []):
         os.environ.pop(k_, None)
     if not args.ab:
         wins = [e["f32_bytes"] for e in result["sizes"] if e["pruned_wins_beyond_spread"]]
@@ -125,6 +133,13 @@ def main():
             result["int8_smallest_winning_f32_bytes"] = first
             if first:
                 result["int8_threshold_bytes"] = max(1 << (first - 1).bit_length(), 1 << 30)
+        if any("i6_wins_beyond_spread" in e for e in result["sizes"]):   # the 6-bit front against every other series, same rule
+            wins = [e["f32_bytes"] for e in result["sizes"] if e["i6_wins_beyond_spread"]]
+            losing_above = [e["f32_bytes"] for e in result["sizes"] if not e["i6_wins_beyond_spread"]]
+            first = min((b for b in wins if all(b > l for l in losing_above)), default=None)
+            result["i6_smallest_winning_f32_bytes"] = first
+            if first:
+                result["i6_threshold_bytes"] = max(1 << (first - 1).bit_length(), 1 << 30)
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
