@@ -395,6 +395,39 @@ int rxgpu_hnsw_read_links0(rxgpu_index* h, uint64_t first_row, uint64_t n, uint3
  * back-links (the search: wall clock of the call, which drains its stream; the others between events).  Any may be NULL. */
 int rxgpu_hnsw_read_build_stats(rxgpu_index* h, uint64_t* rows, uint64_t* batches, uint64_t* reselected, uint64_t* past_cap, double* phase_ms);
 
+/* Level 1 of the batch rxgpu_hnsw_link_batch linked last, built on the device under the same batch rule (addPoint's level-1 half for many
+ * rows at once: the descent hnswalg.h:1762-1795, searchBaseLayer + getNeighborsByHeuristic2 977-1024 + mutuallyConnectNewElement 1042-1180
+ * on level 1).  Called between rxgpu_hnsw_link_batch(first_row, n) and the patch of that batch: the attached node count is first_row + n,
+ * the upper lists of the nodes >= first_row are not patched in yet, and the graph in front of the batch has a top level >= 1.  up_rows
+ * [n_up]: EVERY row of the batch whose level is >= 1, ascending.  Per such row i: SearchKnn with k = ef = ef_construction over the nodes
+ * < first_row with level 1 as the base layer — the greedy descent from the entry point through the levels >= 2, then the base-layer search
+ * over the level-1 lists; this holds for rows of level >= 2 too, where addPoint would enter level 1 at the node its level-2 connect hands
+ * down — then getNeighborsByHeuristic2 (M kept at most) and the list in the order mutuallyConnectNewElement writes it.  Per node t that
+ * received links: the new rows appended ascending while its M slots have room, else ONE getNeighborsByHeuristic2 over its list and all the
+ * incoming rows.  The lists of the older nodes are written into the mirror; those of up_rows wait on the device until
+ * rxgpu_hnsw_patch_upper_from(first_level = 2) gives the new nodes their blocks.  Costs a dense level-1 array of (1 + M) * 4 bytes per row
+ * of capacity until rxgpu_hnsw_release_build_view.  Errors — RXGPU_ERR_PARAMS: not the batch linked last, a row outside the batch or out of
+ * order, a graph with deleted nodes, M > 64, ef_construction > 256; RXGPU_ERR_LOGIC: the batch is patched in already, level 1 of it is
+ * linked already, the top level is 0, a sharded index.  Synchronises. */
+int rxgpu_hnsw_link_batch_upper(rxgpu_index* h, uint64_t first_row, uint64_t n, uint32_t n_up, const uint32_t* up_rows, uint32_t ef_construction);
+/* rxgpu_hnsw_patch_upper with a first level (addPoint's levels >= first_level, hnswalg.h:1694-1852, built on the host).  first_level 1:
+ * rxgpu_hnsw_patch_upper.  first_level 2: upper_rows holds the blocks of the levels >= 2 only (levels[j] - 1 blocks of a node of level
+ * levels[j] >= 2, none otherwise); the new nodes get their levels[j] blocks as ever, their level-1 block is filled with what
+ * rxgpu_hnsw_link_batch_upper built (RXGPU_ERR_LOGIC where it did not run over every new node of level >= 1), and the level 1 of the older
+ * nodes is left as it is.  RXGPU_ERR_OVERFLOW: attach the graph again — rxgpu_hnsw_read_level still reads what the device built. */
+int rxgpu_hnsw_patch_upper_from(rxgpu_index* h, int32_t first_level, uint32_t n_nodes, const uint32_t* ids, const int32_t* levels, const uint32_t* upper_rows,
+								int32_t maxlevel, uint32_t entry);
+/* The lists of one level >= 1 of the mirror (mutuallyConnectNewElement's result, hnswalg.h:1042-1180): out [n_ids][1 + M], an empty list
+ * for a node that does not reach the level.  Between rxgpu_hnsw_link_batch_upper and the patch, level 1 of that batch's rows of level >= 1
+ * is read from where it waits.  RXGPU_ERR_PARAMS: a node whose upper lists are not mirrored. */
+int rxgpu_hnsw_read_level(rxgpu_index* h, int32_t level, uint64_t n_ids, const uint32_t* ids, uint32_t* out);
+/* rxgpu_hnsw_link_batch_upper since the last call (hnswalg.h:1762-1852, 977-1024, 1042-1180 on level 1): rows linked, nodes whose list was
+ * re-selected, nodes with more than 256 entries, phase_ms [3] = search, select + pair grouping, back-links.  Any may be NULL. */
+int rxgpu_hnsw_read_build_upper_stats(rxgpu_index* h, uint64_t* rows, uint64_t* reselected, uint64_t* past_cap, double* phase_ms);
+/* Frees the dense level-1 array of rxgpu_hnsw_link_batch_upper (the end of a build; the next call allocates it again).  RXGPU_ERR_LOGIC
+ * while a batch's level-1 lists wait there for their patch (hnswalg.h:1042-1180 has no counterpart: the reference keeps lists in place). */
+int rxgpu_hnsw_release_build_view(rxgpu_index* h);
+
 /* SearchKnn for nq queries (host in/out).  ef == 0 means k*3/2 like the engine (hnswalg.h:1995); ef <= 4096
  * (RXGPU_ERR_PARAMS above that; from ef = 1025 on the candidate heap lives in global scratch instead of LDS).
  * Writes, per query, the members of the reference's top_candidates after trimming to k (UNORDERED: the Map pushes them into the

@@ -172,6 +172,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "hnsw_build_plan.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # ... and of level 1 of a batch (the device / host decision, RXGPU_HNSW_BUILD_UPPER, the view and the scratch of rxgpu_hnsw_link_batch_upper)
+    src = tdir / "hnsw_build_upper_plan_cpu.cc"
+    if src.exists():
+        out = tdir / "libhnsw_build_upper_plan_cpu.so"
+        if force or _stale(out, [src, CSRC / "hnsw_build_plan.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     return outs
 
 

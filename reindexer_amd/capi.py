@@ -98,6 +98,11 @@ _SIGNATURES = {
     "rxgpu_hnsw_patch_upper": (_i, [_vp, _u32, _vp, _vp, _vp, C.c_int32, _u32]),
     "rxgpu_hnsw_read_links0": (_i, [_vp, _u64, _u64, _vp]),
     "rxgpu_hnsw_read_build_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
+    "rxgpu_hnsw_link_batch_upper": (_i, [_vp, _u64, _u64, _u32, _vp, _u32]),
+    "rxgpu_hnsw_patch_upper_from": (_i, [_vp, C.c_int32, _u32, _vp, _vp, _vp, C.c_int32, _u32]),
+    "rxgpu_hnsw_read_level": (_i, [_vp, C.c_int32, _u64, _vp, _vp]),
+    "rxgpu_hnsw_read_build_upper_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
+    "rxgpu_hnsw_release_build_view": (_i, [_vp]),
     "rxgpu_hnsw_quantize_sq8": (_i, [_vp, _u64, _u64, _f, _f, _f, _f]),
     "rxgpu_hnsw_read_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp]),
     "rxgpu_hnsw_read_sq8_quantize_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
@@ -492,6 +497,41 @@ class VectorIndex:
             raise ValueError("one level per node")
         _check(lib().rxgpu_hnsw_patch_upper(self._h, ids.shape[0], ids.ctypes.data, levels.ctypes.data, upper_rows.ctypes.data if upper_rows.size else None,
                                             maxlevel, entry))
+
+    def hnsw_link_batch_upper(self, first_row: int, n: int, up_rows, ef_construction: int) -> None:
+        """Level 1 of the batch hnsw_link_batch(first_row, n) linked last, on the device: up_rows = every row of the batch whose level is
+        >= 1, ascending (rxgpu_hnsw_link_batch_upper)."""
+        up = np.ascontiguousarray(up_rows, np.uint32).reshape(-1)
+        _check(lib().rxgpu_hnsw_link_batch_upper(self._h, first_row, n, up.shape[0], up.ctypes.data if up.size else None, ef_construction))
+
+    def hnsw_patch_upper_from(self, first_level: int, ids, levels, upper_rows, maxlevel: int, entry: int) -> None:
+        """hnsw_patch_upper with a first level: 2 = upper_rows holds the blocks of the levels >= 2 only, and level 1 of the new nodes is
+        what hnsw_link_batch_upper built (rxgpu_hnsw_patch_upper_from)."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        levels = np.ascontiguousarray(levels, np.int32).reshape(-1)
+        upper_rows = np.ascontiguousarray(upper_rows, np.uint32).reshape(-1)
+        if ids.shape[0] != levels.shape[0]:
+            raise ValueError("one level per node")
+        _check(lib().rxgpu_hnsw_patch_upper_from(self._h, first_level, ids.shape[0], ids.ctypes.data, levels.ctypes.data,
+                                                 upper_rows.ctypes.data if upper_rows.size else None, maxlevel, entry))
+
+    def hnsw_read_level(self, level: int, ids, M: int):
+        """The lists [len(ids)][1 + M] of one level >= 1 of the mirror; an empty list where a node does not reach it (rxgpu_hnsw_read_level)."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        out = np.empty((ids.shape[0], 1 + M), np.uint32)
+        _check(lib().rxgpu_hnsw_read_level(self._h, level, ids.shape[0], ids.ctypes.data, out.ctypes.data))
+        return out
+
+    def hnsw_read_build_upper_stats(self) -> dict:
+        """rxgpu_hnsw_link_batch_upper since the last call: rows, nodes re-selected, nodes past the kernel's cap, milliseconds per phase."""
+        rows, resel, over = _u64(0), _u64(0), _u64(0)
+        ms = (C.c_double * 3)()
+        _check(lib().rxgpu_hnsw_read_build_upper_stats(self._h, C.byref(rows), C.byref(resel), C.byref(over), ms))
+        return dict(rows=int(rows.value), reselected=int(resel.value), past_cap=int(over.value), search_ms=float(ms[0]), select_ms=float(ms[1]),
+                    backlink_ms=float(ms[2]))
+
+    def hnsw_release_build_view(self) -> None:
+        _check(lib().rxgpu_hnsw_release_build_view(self._h))
 
     def hnsw_read_links0(self, first_row: int, n: int, max_m0: int):
         """Level-0 lists [n][1 + max_m0] of the mirror (rxgpu_hnsw_read_links0)."""

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(kBuildThreads) void hnsw_build_select(HnswBuildArgs
 	float* lds_rows = reinterpret_cast<float*>(build_rows4);
 	const int lane = threadIdx.x;
 	const uint32_t r = blockIdx.x;
-	const uint32_t i = a.first + r;
+	const uint32_t i = a.row_ids ? a.row_ids[r] : a.first + r;
 	// the candidates the search left: nodes of the graph before the batch
 	const uint32_t k = min(a.k, kHnswBuildEntries);
 	uint32_t n_c = 0;
@@ -257,7 +257,8 @@ __global__ __launch_bounds__(256) void hnsw_build_scatter(HnswBuildArgs a) {
 	const uint32_t t = a.pair_t[p];
 	if (t == kInvalidRow) return;
 	const uint32_t left = atomicSub(&a.node_cnt[t], 1u);
-	a.inc[a.node_seg[t] + left - 1u] = a.first + uint32_t(p / a.M);
+	const uint32_t r = uint32_t(p / a.M);
+	a.inc[a.node_seg[t] + left - 1u] = a.row_ids ? a.row_ids[r] : a.first + r;
 }
 
 // kBig: the second launch, workgroup o finishes the o-th node the first one queued; its entries are ordered in the big arrays
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(kBuildThreads) void hnsw_build_backlink(HnswBuildAr
 	uint32_t* order = kBig ? a.big_pos + big_off : L.order;
 	// An id past the batch can only come from a corrupt list: it is reported (the call fails) and, so that nothing is read out of bounds
 	// on the way there, replaced by the batch's last row.
-	const uint32_t last = a.first + a.n - 1u;
+	const uint32_t last = a.id_end - 1u;
 	for (uint32_t e = lane; e < n_e; e += kBuildThreads) {
 		uint32_t id = e < m0 ? row[1 + e] : a.inc[seg + e - m0];
 		if (id > last) {
@@ -341,8 +342,9 @@ __global__ __launch_bounds__(64) void hnsw_build_patch_upper(HnswUpperPatch p) {
 	} else if (lane == 0) {
 		p.upper_off[id] = at;
 	}
-	const uint32_t words = uint32_t(p.levels[j]) * stride;
-	for (uint32_t w = lane; w < words; w += 64) p.upper[at * stride + w] = p.src_upper[uint64_t(p.upper_src[j]) * stride + w];
+	const uint32_t lv = uint32_t(p.levels[j]);
+	const uint32_t words = lv > p.skip ? (lv - p.skip) * stride : 0u;   // the staged blocks are the levels past `skip`
+	for (uint32_t w = lane; w < words; w += 64) p.upper[(at + p.skip) * stride + w] = p.src_upper[uint64_t(p.upper_src[j]) * stride + w];
 }
 
 template <bool kLdsRows>

@@ -6,7 +6,8 @@
 // The batch rule (known difference (3)): nodes [0, L) are linked; a batch [a, b) with a = L and
 //   b - a = min(max(a / ratio, kHnswBuildMinBatch), cap, n - a)
 // is searched against the graph of the nodes < a, so the rows of one batch do not see each other.  While L < seed the rows go in one by
-// one through the sequential builder.
+// one through the sequential builder.  Level 1 of a batch follows the same rule one level up where RXGPU_HNSW_BUILD_UPPER=device says so
+// (the second half of this file).
 #pragma once
 
 #include <stddef.h>
@@ -14,6 +15,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <string_view>
 
 namespace rxgpu {
 
@@ -137,6 +139,44 @@ inline HnswBuildScratch hnsw_build_scratch(uint64_t rows, uint32_t M, uint32_t m
 	s.o_counters = take(8 * 4);
 	s.bytes = at;
 	s.node_bytes = nodes_cap * 8;
+	return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- level 1 of a batch
+// The same rule one level up: U, the rows of the batch with level >= 1, are searched over the level-1 lists of the graph in
+// front of the batch — reached by the greedy descent from its entry point through its levels >= 2 — given lists of M links at most and
+// linked back with limit M.  Levels >= 2, the entry point and the top level stay on the host.
+
+// RXGPU_HNSW_BUILD_UPPER, read per call: "device" moves level 1 of a batch to the device, "host" / unset / anything else keeps it on the
+// host.  It only means something under RXGPU_HNSW_BUILD=device.
+inline bool read_hnsw_build_upper_device() {
+	const char* e = std::getenv("RXGPU_HNSW_BUILD_UPPER");
+	return e && std::string_view(e) == "device";
+}
+
+// Whether level 1 of a batch goes to the device: the batch's level 0 does (path), the graph in front of it has a level-1 node to start
+// from (its top level is >= 1; the top level only grows, so within a flush a "no" can only come in front of the first "yes"), and the
+// batch holds a row of level >= 1.
+inline bool hnsw_build_upper_on_device(bool upper_device, int path, int top_level_before, uint64_t upper_rows) {
+	return upper_device && path == kHnswBuildDevice && top_level_before >= 1 && upper_rows > 0;
+}
+
+// Bytes of the dense level-1 view [nodes_cap][1 + M]: the level-1 lists as a level-0 array, so that the search, selection and back-link
+// kernels run on level 1 as they are.
+inline uint64_t hnsw_build_upper_view_bytes(uint64_t nodes_cap, uint32_t M) { return nodes_cap * (1 + uint64_t(M)) * 4; }
+
+// Scratch of the level-1 step of one batch with `up_rows` rows in U: the batch scratch for up_rows rows whose lists hold M entries, and
+// behind it (256-byte aligned like every area) the ids of U.  The queries are always packed: U is not contiguous.
+struct HnswBuildUpperScratch {
+	HnswBuildScratch batch;   // hnsw_build_scratch(up_rows, M, M, k, dim, true, nodes_cap)
+	uint64_t o_row_ids;       // [up_rows]
+	uint64_t bytes;
+};
+inline HnswBuildUpperScratch hnsw_build_upper_scratch(uint64_t up_rows, uint32_t M, uint32_t k, uint32_t dim, uint64_t nodes_cap) {
+	HnswBuildUpperScratch s{};
+	s.batch = hnsw_build_scratch(up_rows, M, M, k, dim, true, nodes_cap);
+	s.o_row_ids = s.batch.bytes;
+	s.bytes = (s.o_row_ids + up_rows * 4 + 255) & ~uint64_t(255);
 	return s;
 }
 

@@ -375,6 +375,7 @@ void rxgpu_index_destroy(rxgpu_index* h) {
 	if (h->d_hnsw_stats) (void)hipFree(h->d_hnsw_stats);
 	h->build_scratch.release();
 	h->build_nodes.release();
+	h->build_view.release();
 	delete h;
 }
 

@@ -738,7 +738,14 @@ int rxgpu_hnsw_attach_graph(rxgpu_index* h, const uint32_t* links0, const uint64
 	h->graph_attached = false;
 	const uint64_t rows_cap = std::max<uint64_t>(std::max<uint64_t>(h->capacity, n), 1);
 	// expected upper blocks of a full index: sum over levels of cap / M^level = cap / (M - 1); twice that (and at least what is there) as headroom
-	const uint64_t upper_cap = std::max<uint64_t>(2 * upper_blocks + 64, 2 * rows_cap / std::max<uint32_t>(M - 1, 1) + 64);
+	uint64_t upper_cap = std::max<uint64_t>(2 * upper_blocks + 64, 2 * rows_cap / std::max<uint32_t>(M - 1, 1) + 64);
+	// RXGPU_HNSW_UPPER_HEADROOM=<blocks> (read per attach; tests): that many blocks beyond the attached ones instead — the way to meet
+	// RXGPU_ERR_OVERFLOW of the patch entry points, which the default headroom keeps out of reach
+	if (const char* e = std::getenv("RXGPU_HNSW_UPPER_HEADROOM"); e && *e) {
+		char* end = nullptr;
+		const unsigned long long x = std::strtoull(e, &end, 10);
+		if (end != e && *end == 0 && x > 0) upper_cap = upper_blocks + x;
+	}
 	const size_t row_bytes = (1 + size_t(max_m0)) * sizeof(uint32_t), blk_bytes = (1 + size_t(M)) * sizeof(uint32_t);
 	if (int rc = replace(h->d_links0, links0, n * row_bytes, rows_cap * row_bytes); rc) return rc;
 	if (int rc = replace(h->d_upper_off, upper_off, n ? (n + 1) * sizeof(uint64_t) : 0, (rows_cap + 1) * sizeof(uint64_t)); rc) return rc;
@@ -753,6 +760,7 @@ int rxgpu_hnsw_attach_graph(rxgpu_index* h, const uint32_t* links0, const uint64
 	}
 	h->graph_n = n;
 	h->graph_upper_nodes = n;
+	h->build_upper_end = 0;   // level-1 lists of a build batch that were not patched in are gone with the arrays
 	h->graph_M = M;
 	h->graph_maxM0 = max_m0;
 	h->graph_maxlevel = maxlevel;
@@ -836,6 +844,7 @@ int rxgpu_hnsw_patch_graph(rxgpu_index* h, uint32_t n_dirty, const uint32_t* dir
 	h->graph_upper_used = used;
 	h->graph_n = n_new;
 	h->graph_upper_nodes = n_new;
+	h->build_upper_end = 0;
 	h->graph_maxlevel = maxlevel;
 	h->graph_entry = entry;
 	h->graph_deleted = num_deleted;

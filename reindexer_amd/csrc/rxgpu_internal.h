@@ -654,6 +654,13 @@ struct rxgpu_index {
 	uint64_t build_nodes_cap = 0;
 	uint64_t build_rows = 0, build_batches = 0, build_reselected = 0, build_over = 0;   // since rxgpu_hnsw_read_build_stats
 	double build_ms[3] = {0.0, 0.0, 0.0};                                                // search, select, back-link
+	// Level 1 of a batch (rxgpu_hnsw_link_batch_upper).  build_view: the level-1 lists as a dense array [graph_rows_cap][1 + M], gathered
+	// from the blocks for every batch; the rows of the batch's own nodes stay there until rxgpu_hnsw_patch_upper_from has given them
+	// blocks.  build_upper_end: the end of the batch whose level 1 was linked last (0: none pending), build_upper_last: its rows.
+	rxgpu_devbuf build_view;
+	uint64_t build_upper_end = 0, build_upper_last = 0;
+	uint64_t build_upper_rows = 0, build_upper_reselected = 0, build_upper_over = 0;     // since rxgpu_hnsw_read_build_upper_stats
+	double build_upper_ms[3] = {0.0, 0.0, 0.0};
 	unsigned long long* d_hnsw_stats = nullptr;
 	// the resident search kernels' mailboxes, made at the first single query of the class: [0] floats, ef <= 128; [1] floats, ef <= 256;
 	// [2] / [3] the same two over the SQ8 codes.  Written once under mtx (release), read without it (acquire).

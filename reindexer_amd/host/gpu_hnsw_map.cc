@@ -530,13 +530,37 @@ void GpuHnswMap::flushLocked() const {
 		if (rxgpu_hnsw_read_links0(dev_, 0, upTo, rows0.data()) != RXGPU_OK) throwDevice("reading the level-0 lists back failed");
 		graph_.SetLinks0(0, upTo, rows0.data());
 	};
+	// level 1 of the nodes [0, upTo) back into the host graph, where the device linked some of it (step 7; also in front of a re-attach:
+	// the lists of a batch that was not patched in yet are read from where they wait on the device)
+	const bool upperDevice = rxgpu::read_hnsw_build_upper_device();
+	bool upperOnDeviceSeen = false;
+	std::vector<tableint> upperIds;
+	std::vector<uint32_t> rows1;
+	auto readBackLevel1 = [&](size_t upTo) {
+		if (!upperOnDeviceSeen) return;
+		upperIds.clear();
+		for (size_t id = 0; id < upTo; ++id) {
+			if (graph_.Levels()[id] >= 1) upperIds.push_back(tableint(id));
+		}
+		rows1.resize(upperIds.size() * (1 + graph_.M()));
+		if (rxgpu_hnsw_read_level(dev_, 1, upperIds.size(), upperIds.data(), rows1.data()) != RXGPU_OK) throwDevice("reading the level-1 lists back failed");
+		graph_.SetLevelLists(1, upperIds.data(), upperIds.size(), rows1.data());
+	};
 	mirror();
-	std::vector<tableint> touched, ids;
+	std::vector<tableint> touched, ids, upRows;
 	std::vector<int32_t> levels;
 	std::vector<uint32_t> upperRows;
 	size_t a = from;
 	while (a < n) {
 		const size_t cnt = size_t(rxgpu::hnsw_build_batch_rows(a, n, knobs));
+		// U: the rows of the batch with level >= 1.  Where the graph in front of the batch has a level-1 node to start from (and the
+		// variable says so) the device links their level 1 under the batch rule and the host only the levels >= 2
+		upRows.clear();
+		for (size_t id = a; id < a + cnt; ++id) {
+			if (graph_.Levels()[id] >= 1) upRows.push_back(tableint(id));
+		}
+		const bool upperOnDevice = rxgpu::hnsw_build_upper_on_device(upperDevice, path, graph_.MaxLevel(), upRows.size());
+		const int hostFrom = upperOnDevice ? 2 : 1;
 		// 6. the upper levels of the batch on the host, beside the device
 		touched.clear();
 		std::string upperError;
@@ -545,21 +569,27 @@ void GpuHnswMap::flushLocked() const {
 			const auto u0 = std::chrono::steady_clock::now();
 			try {
 				graph_.SetTouchLog(&touched);
-				for (size_t id = a; id < a + cnt; ++id) graph_.LinkUpper(tableint(id));
+				for (size_t id = a; id < a + cnt; ++id) graph_.LinkUpper(tableint(id), hostFrom);
 			} catch (const std::exception& e) {
 				upperError = e.what();
 			}
 			graph_.SetTouchLog(nullptr);
 			upperSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - u0).count();
 		});
-		// 3 - 5. candidates, lists, back-links on the device
-		const int rc = rxgpu_hnsw_link_batch(dev_, a, cnt, efc);
+		// 3 - 5. candidates, lists, back-links on the device: level 0, then — over the same graph in front of the batch — level 1
+		int rc = rxgpu_hnsw_link_batch(dev_, a, cnt, efc);
+		if (rc == RXGPU_OK && upperOnDevice) rc = rxgpu_hnsw_link_batch_upper(dev_, a, cnt, uint32_t(upRows.size()), upRows.data(), efc);
 		upper.join();
 		build_.upperSeconds += upperSeconds;
 		if (!upperError.empty()) throw std::runtime_error(upperError);
 		// (the Map reserves the device index for MaxElements before it attaches, and the level-0 array is allocated for that capacity: a
 		// batch always fits — RXGPU_ERR_OVERFLOW here would be a broken invariant, not a state to recover from)
 		if (rc != RXGPU_OK) throwDevice("linking a batch on the device failed");
+		if (upperOnDevice) {
+			upperOnDeviceSeen = true;
+		} else {
+			build_.upperHostRows += upRows.size();
+		}
 		ids.clear();
 		levels.clear();
 		upperRows.clear();
@@ -571,15 +601,19 @@ void GpuHnswMap::flushLocked() const {
 		for (size_t id = a; id < a + cnt; ++id) ids.push_back(tableint(id));
 		for (const tableint id : ids) {
 			levels.push_back(graph_.Levels()[id]);
-			graph_.AppendUpper(id, upperRows);
+			graph_.AppendUpper(id, hostFrom, upperRows);
 		}
-		const int rp = rxgpu_hnsw_patch_upper(dev_, uint32_t(ids.size()), ids.data(), levels.data(), upperRows.empty() ? nullptr : upperRows.data(),
-											  graph_.MaxLevel(), graph_.EntryPoint());
+		const int rp = upperOnDevice ? rxgpu_hnsw_patch_upper_from(dev_, 2, uint32_t(ids.size()), ids.data(), levels.data(), upperRows.empty() ? nullptr : upperRows.data(),
+																   graph_.MaxLevel(), graph_.EntryPoint())
+									 : rxgpu_hnsw_patch_upper(dev_, uint32_t(ids.size()), ids.data(), levels.data(), upperRows.empty() ? nullptr : upperRows.data(),
+															  graph_.MaxLevel(), graph_.EntryPoint());
 		if (rp == RXGPU_ERR_OVERFLOW) {
 			// The upper blocks allocated by the last attach (twice the expected number) are used up.  Level 0 of the a + cnt nodes is on the
-			// device and their upper levels are linked on the host: level 0 comes home and the graph of a + cnt nodes is attached again, with
-			// new headroom — host and device agree on every node, the next batch goes on from there.
+			// device and their upper levels are linked on the host — or, level 1, on the device: level 0 and that level 1 come home and the
+			// graph of a + cnt nodes is attached again, with new headroom — host and device agree on every node, the next batch goes on
+			// from there.
 			readBack(a + cnt);
+			readBackLevel1(a + cnt);
 			graphOnDevice_ = false;
 			mirror();
 		} else if (rp != RXGPU_OK) {
@@ -589,6 +623,20 @@ void GpuHnswMap::flushLocked() const {
 	}
 	// 7. host and device mirrors are equal: nothing is marked dirty
 	readBack(n);
+	readBackLevel1(n);
+	if (upperOnDeviceSeen) {
+		(void)rxgpu_hnsw_release_build_view(dev_);
+		uint64_t rows = 0, resel = 0, over = 0;
+		double ms[3] = {0, 0, 0};
+		if (rxgpu_hnsw_read_build_upper_stats(dev_, &rows, &resel, &over, ms) == RXGPU_OK) {
+			build_.upperDeviceRows += rows;
+			build_.upperReselected += resel;
+			build_.upperPastCap += over;
+			build_.upperSearchMs += ms[0];
+			build_.upperSelectMs += ms[1];
+			build_.upperBacklinkMs += ms[2];
+		}
+	}
 	uint64_t rows = 0, batches = 0, resel = 0, over = 0;
 	double ms[3] = {0, 0, 0};
 	if (rxgpu_hnsw_read_build_stats(dev_, &rows, &batches, &resel, &over, ms) == RXGPU_OK) {

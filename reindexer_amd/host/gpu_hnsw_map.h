@@ -1,7 +1,9 @@
 // GpuHnswMap — the GPU `Map` policy for HnswIndexBase<Map> in its HNSW form (hnsw_index.cc:47-58), a drop-in for
 // hnswlib::HierarchicalNSW<Synchronization::None> (cpp_src/core/index/float_vector/hnswlib/hnsw.h:14-126).
 //   build  : host, HnswGraph (hnsw_graph.h) — same graph as the reference builds; opt-in (RXGPU_HNSW_BUILD=device): level 0 on the device
-//            in batches (rxgpu_hnsw_link_batch), the upper levels on the host beside it
+//            in batches (rxgpu_hnsw_link_batch), the upper levels on the host beside it; with RXGPU_HNSW_BUILD_UPPER=device on top of
+//            that, level 1 of a batch on the device too (rxgpu_hnsw_link_batch_upper, the same batch rule one level up) and only the
+//            levels >= 2 — 1 / M^2 of the rows — on the host
 //   search : MI355X, rxgpu_hnsw_search_knn (hnsw_search.hip) — same traversal as the reference, no CPU search path
 #pragma once
 
@@ -105,6 +107,9 @@ public:
 	// Built from empty, the levels, every upper list, the entry point and the top level equal the sequential build's; level 0 is the
 	// batched graph (known difference (3)).  Graphs with deleted nodes, M > 64 or efConstruction > 256 insert on the host as
 	// before, and BuildStats says which path ran.
+	// RXGPU_HNSW_BUILD_UPPER=device (read per flush; default host; only under RXGPU_HNSW_BUILD=device): level 1 of every batch whose graph
+	// has a top level >= 1 is linked on the device under the same rule; the levels >= 2, the entry point and the top level stay the
+	// sequential build's, level 1 becomes a batched level too.  The level-1 lists come home with level 0 when the flush ends.
 	void AddPoints(const float* vectors, const labeltype* labels, size_t n);
 	struct BuildStats {
 		uint64_t deviceRows = 0, batches = 0, reselected = 0, pastCap = 0;   // rxgpu_hnsw_read_build_stats, summed over the flushes
@@ -114,6 +119,10 @@ public:
 		double searchMs = 0, selectMs = 0, backlinkMs = 0;
 		double upperSeconds = 0;        // host: LinkUpper over the batches (runs beside the device)
 		double flushSeconds = 0;        // wall clock of the flushes
+		// level 1 of the batches (RXGPU_HNSW_BUILD_UPPER=device): rows of level >= 1 whose level 1 the device linked
+		// (rxgpu_hnsw_read_build_upper_stats) / the host linked, nodes re-selected and past the cap on level 1, milliseconds per device phase
+		uint64_t upperDeviceRows = 0, upperHostRows = 0, upperReselected = 0, upperPastCap = 0;
+		double upperSearchMs = 0, upperSelectMs = 0, upperBacklinkMs = 0;
 	};
 	BuildStats ReadBuildStats() const;       // since the last call
 	size_t PendingRows() const noexcept { return graph_.Count() - graph_.PendingFrom(); }

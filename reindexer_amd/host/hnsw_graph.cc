@@ -577,10 +577,13 @@ void HnswGraph::LinkStored(tableint id) {
 	pending_--;
 }
 
-void HnswGraph::LinkUpper(tableint id) {
+void HnswGraph::LinkUpper(tableint id, int minLevel) {
 	if (id < count_ - pending_ || id >= count_) throw std::logic_error("HnswGraph::LinkUpper: not a pending row");
 	if (entryPoint_ == kNoEntry) throw std::logic_error("HnswGraph::LinkUpper: the first element is linked by LinkStored");
-	if (levels_[id] >= 1) linkLevels(id, 1);
+	if (minLevel < 1) throw std::logic_error("HnswGraph::LinkUpper: level 0 is not an upper level");
+	// (a row below minLevel changes neither the entry point nor the top level unless the top level is below minLevel - 1, which the caller rules out)
+	if (minLevel > 1 && maxLevel_ < minLevel - 1) throw std::logic_error("HnswGraph::LinkUpper: the graph does not reach the level below minLevel");
+	if (levels_[id] >= minLevel) linkLevels(id, minLevel);
 }
 
 void HnswGraph::SetLinks0(tableint first, size_t n, const uint32_t* rows) {
@@ -588,6 +591,15 @@ void HnswGraph::SetLinks0(tableint first, size_t n, const uint32_t* rows) {
 	if (n) std::memcpy(links0_.data() + size_t(first) * (1 + maxM0_), rows, n * (1 + maxM0_) * sizeof(uint32_t));
 	const size_t from = count_ - pending_;
 	if (first <= from && size_t(first) + n > from) pending_ = count_ - (size_t(first) + n);
+}
+
+void HnswGraph::SetLevelLists(int level, const tableint* ids, size_t n, const uint32_t* rows) {
+	if (level < 1) throw std::logic_error("HnswGraph::SetLevelLists: levels >= 1 (level 0: SetLinks0)");
+	for (size_t j = 0; j < n; ++j) {
+		if (ids[j] >= count_ || levels_[ids[j]] < level) throw std::logic_error("HnswGraph::SetLevelLists: a node that does not reach the level");
+		if (rows[j * (1 + M_)] > M_) throw std::logic_error("HnswGraph::SetLevelLists: a list longer than M");
+	}
+	for (size_t j = 0; j < n; ++j) std::memcpy(list(ids[j], level), rows + j * (1 + M_), (1 + M_) * sizeof(uint32_t));
 }
 
 void HnswGraph::rebuildDeletedSet() {

@@ -67,11 +67,15 @@ public:
 	//   LinkUpper       addPoint's descent, searchBaseLayer and connect for the levels >= 1 of a pending row only (entry point and top level
 	//                   updated as addPoint does); rows in id order.  Levels >= 1 never read level 0, so after LinkUpper over every row the
 	//                   upper lists, the entry point and the top level equal the sequential build's
+	//                   (minLevel 2: the levels >= 2 only — level 1 is built elsewhere under the batch rule; they read no level-1 list)
 	//   SetLinks0       level-0 lists [first, first + n) as built elsewhere (rows [n][1 + maxM0]); rows up to first + n count as linked
+	//   SetLevelLists   the lists of the listed nodes on one level >= 1 as built elsewhere (rows [n][1 + M]); every node reaches the level
 	tableint AppendUnlinked(const float* data, labeltype label);
 	void LinkStored(tableint id);
-	void LinkUpper(tableint id);
+	void LinkUpper(tableint id) { LinkUpper(id, 1); }
+	void LinkUpper(tableint id, int minLevel);
 	void SetLinks0(tableint first, size_t n, const uint32_t* rows);
+	void SetLevelLists(int level, const tableint* ids, size_t n, const uint32_t* rows);
 	size_t PendingFrom() const noexcept { return count_ - pending_; }
 	// While a log is set, the nodes whose lists change are appended to it INSTEAD of the change tracker (the caller mirrors them itself).
 	void SetTouchLog(std::vector<tableint>* log) noexcept { touchLog_ = log; }
@@ -108,6 +112,11 @@ public:
 	// upper levels as CSR blocks of (1 + M) u32: node i owns levels[i] consecutive blocks starting at off[i]
 	void ExportUpper(std::vector<uint64_t>& off, std::vector<uint32_t>& blocks) const;
 	void AppendUpper(tableint id, std::vector<uint32_t>& blocks) const { blocks.insert(blocks.end(), upper_[id].begin(), upper_[id].end()); }
+	// ... from a first level >= 1 on: nothing for a node that does not reach it
+	void AppendUpper(tableint id, int firstLevel, std::vector<uint32_t>& blocks) const {
+		const size_t skip = size_t(firstLevel - 1) * (1 + M_);
+		if (skip < upper_[id].size()) blocks.insert(blocks.end(), upper_[id].begin() + std::ptrdiff_t(skip), upper_[id].end());
+	}
 
 	size_t AllocatedMemSize() const noexcept;
 

@@ -392,6 +392,30 @@ long rxhost_graph_link_upper(void* h, size_t first, size_t n, uint32_t* touched,
 	});
 	return out;
 }
+// LinkUpper(id, minLevel) over rows [first, first + n): rxhost_graph_link_upper for the levels >= minLevel only
+long rxhost_graph_link_upper_from(void* h, size_t first, size_t n, int minLevel, uint32_t* touched, size_t cap) {
+	long out = -1;
+	guarded([&] {
+		auto* g = static_cast<HnswGraph*>(h);
+		std::vector<tableint> log;
+		g->SetTouchLog(&log);
+		try {
+			for (size_t i = 0; i < n; ++i) g->LinkUpper(tableint(first + i), minLevel);
+		} catch (...) {
+			g->SetTouchLog(nullptr);
+			throw;
+		}
+		g->SetTouchLog(nullptr);
+		std::sort(log.begin(), log.end());
+		log.erase(std::unique(log.begin(), log.end()), log.end());
+		if (log.size() <= cap && !log.empty()) std::memcpy(touched, log.data(), log.size() * sizeof(uint32_t));
+		out = long(log.size());
+	});
+	return out;
+}
+int rxhost_graph_set_level_lists(void* h, int level, const uint32_t* ids, size_t n, const uint32_t* rows) {
+	return guarded([&] { static_cast<HnswGraph*>(h)->SetLevelLists(level, ids, n, rows); });
+}
 int rxhost_graph_set_links0(void* h, size_t first, size_t n, const uint32_t* rows) {
 	return guarded([&] { static_cast<HnswGraph*>(h)->SetLinks0(tableint(first), n, rows); });
 }
@@ -532,6 +556,19 @@ int rxhost_hnsw_build_stats(void* h, uint64_t* counts, double* times) {
 		const double t[5] = {s.searchMs, s.selectMs, s.backlinkMs, s.upperSeconds, s.flushSeconds};
 		std::copy(c, c + 8, counts);
 		std::copy(t, t + 5, times);
+	});
+}
+// ... with level 1 of the batches behind them: counts [12] = the 8 above, then rows whose level 1 the device linked, rows whose level 1 the
+// host linked, level-1 nodes re-selected, level-1 nodes past the cap; times [8] = the 5 above, then the level-1 search / select / back-link
+// milliseconds.  One call or the other: both take the counters.
+int rxhost_hnsw_build_stats_upper(void* h, uint64_t* counts, double* times) {
+	return guarded([&] {
+		const GpuHnswMap::BuildStats s = static_cast<GpuHnswMap*>(h)->ReadBuildStats();
+		const uint64_t c[12] = {s.deviceRows, s.batches,		 s.reselected,	  s.pastCap,		 s.seedRows,	 s.hostRows, uint64_t(s.hostReason), 0,
+								s.upperDeviceRows, s.upperHostRows, s.upperReselected, s.upperPastCap};
+		const double t[8] = {s.searchMs, s.selectMs, s.backlinkMs, s.upperSeconds, s.flushSeconds, s.upperSearchMs, s.upperSelectMs, s.upperBacklinkMs};
+		std::copy(c, c + 12, counts);
+		std::copy(t, t + 8, times);
 	});
 }
 int rxhost_hnsw_add_concurrent(void* h, const float* vec, size_t dim, uint64_t label) {

@@ -288,6 +288,9 @@ class HnswGraph:
             L.rxhost_graph_link_upper.restype = _l
             L.rxhost_graph_link_upper.argtypes = [_vp, _sz, _sz, _vp, _sz]
             L.rxhost_graph_set_links0.argtypes = [_vp, _sz, _sz, _vp]
+            L.rxhost_graph_link_upper_from.restype = _l
+            L.rxhost_graph_link_upper_from.argtypes = [_vp, _sz, _sz, C.c_int, _vp, _sz]
+            L.rxhost_graph_set_level_lists.argtypes = [_vp, C.c_int, _vp, _sz, _vp]
             L.rxhost_graph_pending_from.restype = _sz
             L.rxhost_graph_pending_from.argtypes = [_vp]
             L._graph_bound = True
@@ -344,11 +347,15 @@ class HnswGraph:
         if rc:
             _raise(rc)
 
-    def link_upper(self, first: int, n: int):
-        """The levels >= 1 of the pending rows [first, first + n), in row order; returns the nodes whose upper lists changed (ascending)."""
+    def link_upper(self, first: int, n: int, min_level: int = 1):
+        """The levels >= min_level (>= 1) of the pending rows [first, first + n), in row order; returns the nodes whose upper lists changed
+        (ascending)."""
         cap = n * 64 * 8 + 16   # more than the lists of n rows can name: the call links, so it is made once
         out = np.empty(cap, np.uint32)
-        got = lib().rxhost_graph_link_upper(self.h, first, n, out.ctypes.data, cap)
+        if min_level == 1:
+            got = lib().rxhost_graph_link_upper(self.h, first, n, out.ctypes.data, cap)
+        else:
+            got = lib().rxhost_graph_link_upper_from(self.h, first, n, min_level, out.ctypes.data, cap)
         if got < 0:
             _raise()
         if got > cap:
@@ -359,6 +366,14 @@ class HnswGraph:
         """Level-0 lists [first, first + len(rows)) as built elsewhere; the rows up to there count as linked."""
         rows = np.ascontiguousarray(rows, np.uint32)
         rc = lib().rxhost_graph_set_links0(self.h, first, rows.shape[0], rows.ctypes.data)
+        if rc:
+            _raise(rc)
+
+    def set_level_lists(self, level: int, ids, rows):
+        """The lists [len(ids)][1 + M] of the listed nodes on one level >= 1 as built elsewhere."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        rows = np.ascontiguousarray(rows, np.uint32).reshape(ids.shape[0], -1)
+        rc = lib().rxhost_graph_set_level_lists(self.h, level, ids.ctypes.data, ids.shape[0], rows.ctypes.data)
         if rc:
             _raise(rc)
 
@@ -555,6 +570,7 @@ class GpuHnswMap:
             L.rxhost_hnsw_vector.argtypes = [_vp, _u64, _vp]
             L.rxhost_hnsw_mark_delete.argtypes = [_vp, _u64]
             L.rxhost_hnsw_resize.argtypes = [_vp, _sz]
+            L.rxhost_hnsw_build_stats_upper.argtypes = [_vp, _vp, _vp]
             L.rxhost_hnsw_count.restype = _sz
             L.rxhost_hnsw_count.argtypes = [_vp]
             L.rxhost_hnsw_deleted_count.restype = _sz
@@ -661,14 +677,17 @@ class GpuHnswMap:
     def build_stats(self) -> dict:
         """The device build since the last call: rows linked on the device, batches, nodes re-selected, nodes past the kernel's cap, seed
         rows, rows of device-mode calls inserted on the host and why (0 none, 1 deleted nodes, 2 M, 3 efConstruction, 4 device list),
-        milliseconds per device phase, seconds of the host's upper levels and of the flushes."""
-        c, t = np.zeros(8, np.uint64), np.zeros(5, np.float64)
-        rc = lib().rxhost_hnsw_build_stats(self.h, c.ctypes.data, t.ctypes.data)
+        milliseconds per device phase, seconds of the host's upper levels and of the flushes.  Level 1 of the batches
+        (RXGPU_HNSW_BUILD_UPPER=device): rows of level >= 1 whose level 1 the device / the host linked, level-1 nodes re-selected and past
+        the cap, milliseconds per level-1 device phase."""
+        c, t = np.zeros(12, np.uint64), np.zeros(8, np.float64)
+        rc = lib().rxhost_hnsw_build_stats_upper(self.h, c.ctypes.data, t.ctypes.data)
         if rc:
             _raise(rc)
         return dict(device_rows=int(c[0]), batches=int(c[1]), reselected=int(c[2]), past_cap=int(c[3]), seed_rows=int(c[4]), host_rows=int(c[5]),
                     host_reason=int(c[6]), search_ms=float(t[0]), select_ms=float(t[1]), backlink_ms=float(t[2]), upper_seconds=float(t[3]),
-                    flush_seconds=float(t[4]))
+                    flush_seconds=float(t[4]), upper_device_rows=int(c[8]), upper_host_rows=int(c[9]), upper_reselected=int(c[10]),
+                    upper_past_cap=int(c[11]), upper_search_ms=float(t[5]), upper_select_ms=float(t[6]), upper_backlink_ms=float(t[7]))
 
     def add_concurrent(self, vec, label):
         vec = _f32(vec)

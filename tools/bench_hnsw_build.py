@@ -3,6 +3,11 @@
 (RXGPU_HNSW_BUILD=host, --threads inserting threads), same corpus, same session.
 
     python tools/bench_hnsw_build.py --ab [--rows 1000000] [--out profiles/hnsw_build_ab.json]
+    python tools/bench_hnsw_build.py --upper [--parent-json FILE] [--out profiles/hnsw_build_upper_ab.json]
+
+--upper adds a third leg beside the two: RXGPU_HNSW_BUILD=device with RXGPU_HNSW_BUILD_UPPER=device (level 1 of every batch on the device
+too, the host keeps the levels >= 2).  --parent-json: the output of the same tool at the parent commit, run in the same session — its two
+legs are quoted in the file as the yardsticks.
 
 The corpus is the clustered one of bench.py's HNSW leg (tools/bench_hnsw.py: make_clustered), cosine, M = 16, efConstruction = 200.
 Per leg: build seconds (the adds and, for the device leg, the flush the first search triggers), the device's milliseconds per phase
@@ -26,8 +31,11 @@ os.environ.setdefault("RX_TARGET_INSTRUCTIONS", "avx512")
 from reindexer_amd import capi, hostapi  # noqa: E402
 
 
-def leg(mode: str, o, rows, labels, queries, truth) -> dict:
+def leg(name: str, o, rows, labels, queries, truth) -> dict:
+    mode = "device" if name == "device_upper" else name
     os.environ["RXGPU_HNSW_BUILD"] = mode
+    os.environ["RXGPU_HNSW_BUILD_UPPER"] = "device" if name == "device_upper" else "host"
+    print(f"leg {name} ...", file=sys.stderr, flush=True)
     m = hostapi.GpuHnswMap(2, o.dim, o.rows, M=o.M, ef_construction=o.efc, multithread=True, device=o.device)
     t0 = time.perf_counter()
     if mode == "device":
@@ -44,7 +52,8 @@ def leg(mode: str, o, rows, labels, queries, truth) -> dict:
         _, got = m.search_knn(q, o.k, o.ef)
         hit += len(set(int(x) >> 32 for x in got) & set(int(x) for x in want))
     e = m.export_graph()
-    out = {"mode": mode, "build_seconds": build_s, "add_seconds": add_s, "first_search_seconds": first_search_s,
+    print(f"leg {name}: build {build_s:.1f} s", file=sys.stderr, flush=True)
+    out = {"mode": name, "build_seconds": build_s, "add_seconds": add_s, "first_search_seconds": first_search_s,
            "inserts_per_sec": o.rows / build_s, "recall_at_10": hit / (o.k * len(queries)), "mean_level0_degree": float(e["links0"][:, 0].mean()),
            "threads": o.threads if mode == "host" else 1, "stats": st}
     m.close()
@@ -54,6 +63,8 @@ def leg(mode: str, o, rows, labels, queries, truth) -> dict:
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ab", action="store_true", help="both legs in this session: the device build, then the host build; without it the device leg alone")
+    ap.add_argument("--upper", action="store_true", help="three legs: the device build, the device build with level 1 on the device, the host build")
+    ap.add_argument("--parent-json", default=None, help="this tool's output at the parent commit, same session: quoted as the yardsticks")
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--M", type=int, default=16)
@@ -66,9 +77,10 @@ def main():
     ap.add_argument("--seed", type=int, default=20260924)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--legs", default=None, help="comma-separated legs in the order they run (overrides --ab)")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "hnsw_build_ab.json"))
+    ap.add_argument("--out", default=None)
     o = ap.parse_args()
-    o.legs = o.legs or ("device,host" if o.ab else "device")
+    o.legs = o.legs or ("device,device_upper,host" if o.upper else "device,host" if o.ab else "device")
+    o.out = o.out or str(ROOT / "profiles" / ("hnsw_build_upper_ab.json" if o.upper else "hnsw_build_ab.json"))
     from bench_hnsw import make_clustered
     corpus = make_clustered(o.rows + o.recall_queries, o.dim, o.clusters, o.seed, o.device)
     rows, raw_q = corpus[:o.rows], corpus[o.rows:]
@@ -89,6 +101,24 @@ def main():
                   "host upper levels": st["upper_seconds"]}
         out["device_leg_largest_phase"] = max(phases, key=phases.get)
         out["device_leg_phase_seconds"] = phases
+    if "device_upper" in legs:
+        st = legs["device_upper"]["stats"]
+        up = {"build_seconds": legs["device_upper"]["build_seconds"], "upperSeconds": st["upper_seconds"],
+              "level0_device_ms": st["search_ms"] + st["select_ms"] + st["backlink_ms"],
+              "level1_device_ms": st["upper_search_ms"] + st["upper_select_ms"] + st["upper_backlink_ms"],
+              "recall_at_10": {name: l["recall_at_10"] for name, l in legs.items()}}
+        if "device" in legs:
+            up["device_over_device_upper_build_time"] = legs["device"]["build_seconds"] / legs["device_upper"]["build_seconds"]
+        if "host" in legs:
+            up["host_over_device_upper_build_time"] = legs["host"]["build_seconds"] / legs["device_upper"]["build_seconds"]
+        phases = {"device level 0": up["level0_device_ms"] / 1e3, "device level 1": up["level1_device_ms"] / 1e3, "host levels >= 2": st["upper_seconds"]}
+        up["largest_phase"] = max(phases, key=phases.get)
+        up["phase_seconds"] = phases
+        out["device_upper"] = up
+    if o.parent_json:
+        parent = json.loads(Path(o.parent_json).read_text())
+        out["parent_commit"] = {name: {k: l[k] for k in ("build_seconds", "recall_at_10", "threads")} | {"upper_seconds": l["stats"]["upper_seconds"]}
+                                for name, l in parent["legs"].items()}
     Path(o.out).parent.mkdir(parents=True, exist_ok=True)
     Path(o.out).write_text(json.dumps(out, indent=1) + "\n")
     print(json.dumps(out))
