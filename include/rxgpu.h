@@ -218,6 +218,15 @@ int rxgpu_index_last_candidates(const rxgpu_index* h, uint32_t* out_count, uint3
  *                       up to its count, rows ascending
  *   "pruned_seed"       6-bit front: as "pruned_top", the merged list of the seed pass (its last entry is T_seed) */
 int rxgpu_index_inspect(rxgpu_index* h, const char* what, void* out, uint64_t cap_bytes, uint64_t* out_bytes);
+/* Test instrumentation: runs one merge kernel of the single-query KNN chains for one query over host arrays (copied to the device, the result
+ * copied back; nothing is kept).  dist / row: the pairs; a row of 0xFFFFFFFF is an empty slot.  what =
+ *   0  knn_merge_lists over n SORTED lists of kk entries each (dist, row: [n][kk], lists padded with empty slots); kk <= 128
+ *   1  the candidate branch of knn_merge_final over n pairs in any order; kk <= 64
+ *   2  the insertion fold (knn_merge) over the same n pairs; kk <= 64
+ * out_dist / out_row: [kk], ascending by (distance, row) and padded with +inf / 0xFFFFFFFF; *out_count: the entries found.  *out_path: 1 when
+ * a selection answered, 0 when an insertion merge did (always 0 for what = 2). */
+int rxgpu_knn_merge_probe(int device, int what, const float* dist, const uint32_t* row, uint32_t n, uint32_t kk, float* out_dist, uint32_t* out_row,
+						  uint32_t* out_count, int* out_path);
 
 /* ---- Pre-filtered brute force: the caller side of `WHERE cond AND KNN(...)` -------------------
  * The reference evaluates such a query by taking the KNN result and filtering it on the host (selectLoop,

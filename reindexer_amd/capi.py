@@ -70,6 +70,7 @@ _SIGNATURES = {
     "rxgpu_scan_tier_range": (_i, [_u64, _u32, _i, _i, _i]),
     "rxgpu_index_last_candidates": (_i, [_vp, C.POINTER(_u32), C.POINTER(_u32)]),
     "rxgpu_index_inspect": (_i, [_vp, C.c_char_p, _vp, _u64, C.POINTER(_u64)]),
+    "rxgpu_knn_merge_probe": (_i, [_i, _i, _vp, _vp, _u32, _u32, _vp, _vp, C.POINTER(_u32), C.POINTER(_i)]),
     "rxgpu_search_knn_subset": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "rxgpu_search_knn_bitmap": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_index_set_lists": (_i, [_vp, _u32, _vp, _vp]),
@@ -225,6 +226,24 @@ def scan_tier(rows: int, dim: int, nq: int = 1, shadow_available: bool = True, s
 def scan_i6(rows: int, dim: int, nq: int = 1, i6_available: bool = True, stats_finite: bool = True) -> bool:
     """rxgpu_scan_i6: does such a call (whole index) read the 6-bit shadow instead of the int8 one under the current environment?  Touches no device."""
     return bool(lib().rxgpu_scan_i6(rows, dim, nq, int(i6_available), int(stats_finite)))
+
+
+MERGE_LISTS, MERGE_CANDIDATES, MERGE_FOLD = 0, 1, 2
+
+
+def knn_merge_probe(what: int, dist: np.ndarray, row: np.ndarray, kk: int, device: int = 0):
+    """rxgpu_knn_merge_probe (test instrumentation): one merge kernel over host arrays.  MERGE_LISTS: dist / row are [nlists][kk] sorted lists;
+    MERGE_CANDIDATES / MERGE_FOLD: [n] pairs.  Returns (dist[kk], row[kk], count, fast)."""
+    dist = np.ascontiguousarray(dist, np.float32)
+    row = np.ascontiguousarray(row, np.uint32)
+    assert dist.shape == row.shape
+    n = dist.shape[0] if what == MERGE_LISTS else dist.size
+    assert what != MERGE_LISTS or dist.shape == (n, kk)
+    out_d, out_r = np.empty(kk, np.float32), np.empty(kk, np.uint32)
+    cnt, path = _u32(0), _i(0)
+    _check(lib().rxgpu_knn_merge_probe(device, what, dist.ctypes.data, row.ctypes.data, n, kk, out_d.ctypes.data, out_r.ctypes.data, C.byref(cnt),
+                                       C.byref(path)))
+    return out_d, out_r, int(cnt.value), bool(path.value)
 
 
 def scan_tier_range(rows: int, dim: int, listed: bool = False, shadow_available: bool = True, stats_finite: bool = True) -> int:

@@ -308,8 +308,7 @@ __global__ __launch_bounds__(64) void knn_query_prep_i8(const float* src, uint32
 	float s = 0.f, mx = 0.f;
 	double s64 = 0.0;
 	bool bad = false;
-	for (uint32_t i = lane; i < ld8; i += 64) {
-		const float v = i < dim ? q[i] : 0.f;
+	auto measure = [&](uint32_t i, float v) {   // element i of the padded query, in increasing i per lane
 		o[i] = v;
 		if (i < dim) {
 			s = __builtin_fmaf(v, v, s);
@@ -317,16 +316,10 @@ __global__ __launch_bounds__(64) void knn_query_prep_i8(const float* src, uint32
 			mx = fmaxf(mx, fabsf(v));
 			bad |= !(fabsf(v) < __builtin_inff());
 		}
-	}
-	for (int off = 32; off; off >>= 1) {
-		s += __shfl_xor(s, off);
-		s64 += __shfl_xor(s64, off);
-		mx = fmaxf(mx, __shfl_xor(mx, off));
-	}
-	const float sq = i8_scale(mx, kI8QueryMax);
+	};
+	float sq = 0.f;
 	double r64 = 0.0;
-	for (uint32_t i = lane; i < ld8; i += 64) {
-		const float v = i < dim ? q[i] : 0.f;
+	auto quantise = [&](uint32_t i, float v) {
 		const int t = i8_quantize(v, sq, kI8QueryMax);
 		int hh, ll;
 		i8_split(t, hh, ll);
@@ -334,6 +327,40 @@ __global__ __launch_bounds__(64) void knn_query_prep_i8(const float* src, uint32
 		pl[i] = int8_t(ll);
 		const double r = i8_residual(v, sq, t);
 		r64 += r * r;
+	};
+	auto fold = [&] {
+		for (int off = 32; off; off >>= 1) {
+			s += __shfl_xor(s, off);
+			s64 += __shfl_xor(s64, off);
+			mx = fmaxf(mx, __shfl_xor(mx, off));
+		}
+		sq = i8_scale(mx, kI8QueryMax);
+	};
+	// A lane's elements are loaded once, all loads in flight together, and both passes run from registers: a loop with a run-time bound puts
+	// every element behind its own round trip, twice.  (ld8 above kPrepRegs * 64: the loops, same arithmetic in the same order.)
+	constexpr uint32_t kPrepRegs = 16;
+	if (ld8 <= kPrepRegs * 64) {   // uniform
+		float v[kPrepRegs];
+#pragma unroll
+		for (uint32_t u = 0; u < kPrepRegs; ++u) {
+			const uint32_t i = u * 64 + lane;
+			v[u] = i < dim ? q[i] : 0.f;
+		}
+#pragma unroll
+		for (uint32_t u = 0; u < kPrepRegs; ++u) {
+			const uint32_t i = u * 64 + lane;
+			if (i < ld8) measure(i, v[u]);
+		}
+		fold();
+#pragma unroll
+		for (uint32_t u = 0; u < kPrepRegs; ++u) {
+			const uint32_t i = u * 64 + lane;
+			if (i < ld8) quantise(i, v[u]);
+		}
+	} else {
+		for (uint32_t i = lane; i < ld8; i += 64) measure(i, i < dim ? q[i] : 0.f);
+		fold();
+		for (uint32_t i = lane; i < ld8; i += 64) quantise(i, i < dim ? q[i] : 0.f);
 	}
 	for (int off = 32; off; off >>= 1) r64 += __shfl_xor(r64, off);
 	bad = __ballot(bad) != 0;

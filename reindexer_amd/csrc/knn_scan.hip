@@ -691,48 +691,152 @@ __device__ __forceinline__ void merge_bitonic(unsigned long long* key, float* va
 		}
 	}
 }
+// The bound of both selections below is the kk-th smallest of a few hundred group heads, and sorting them all in LDS to read one entry costs 45
+// barrier stages at 512 heads.  Instead every wavefront sorts its 64 heads in registers (no LDS, no barrier) and leaves the first min(kk, 64):
+// the kk-th smallest overall is among those.  For kk = 11 and 512 heads that is 88 keys, and the one of rank kk - 1 is found by counting.
+constexpr uint32_t kMergeRankMax = 256;   // up to this many keys are ranked by counting over LDS (n reads per thread, one barrier); more: bitonic
+// ascending sort of one key per lane across the wavefront: lane i ends with the i-th smallest
+__device__ __forceinline__ unsigned long long merge_wave_sort(unsigned long long k, int lane) {
+	for (int size = 2; size <= kWave; size <<= 1) {
+		for (int j = size >> 1; j > 0; j >>= 1) {
+			const unsigned long long o = __shfl_xor(k, j);
+			const bool take_min = ((lane & size) == 0) == ((lane & j) == 0);
+			k = (k < o) == take_min ? k : o;
+		}
+	}
+	return k;
+}
+// rank of entry i among key[0 .. n): the number of smaller keys, equal keys (pads; the same row handed in twice) in index order
+__device__ __forceinline__ uint32_t merge_rank(const unsigned long long* key, uint32_t n, uint32_t i) {
+	const unsigned long long mine = key[i];
+	uint32_t rank = 0;
+	for (uint32_t j = 0; j < n; ++j) {
+		const unsigned long long k = key[j];
+		rank += (k < mine || (k == mine && j < i)) ? 1u : 0u;
+	}
+	return rank;
+}
+// *bound = the key of rank kk - 1 among key[0 .. m) (m <= kMergeRankMax, kk <= m; pads are ~0, so ~0 when fewer than kk keys are real).
+// `bound` is a word of LDS outside key[0 .. m); ends with a barrier.
+__device__ __forceinline__ void merge_kth_key(const unsigned long long* key, uint32_t m, uint32_t kk, unsigned long long* bound) {
+	__syncthreads();
+	if (threadIdx.x < m && merge_rank(key, m, threadIdx.x) == kk - 1) *bound = key[threadIdx.x];
+	__syncthreads();
+}
+// The n <= kMergeCandMax collected (key, distance) pairs in LDS, unique keys -> the first kk in key order, padded with +inf / kInvalidRow, and
+// the count.  Every thread has passed a barrier since the pairs were written.
+__device__ __forceinline__ void merge_write_sorted(unsigned long long* s_key, float* s_val, uint32_t n, uint32_t kk, float* out_dist, uint32_t* out_row,
+												   uint32_t* out_count) {
+	const uint32_t tid = threadIdx.x, cnt = n < kk ? n : kk;
+	const size_t o = size_t(blockIdx.x) * kk;
+	if (tid == 0 && out_count) out_count[blockIdx.x] = cnt;
+	if (n <= kMergeRankMax) {   // an entry's place is the number of smaller keys
+		if (tid < n) {
+			const uint32_t rank = merge_rank(s_key, n, tid);
+			if (rank < kk) {
+				out_dist[o + rank] = s_val[tid];
+				out_row[o + rank] = uint32_t(s_key[tid]);
+			}
+		}
+		for (uint32_t q = cnt + tid; q < kk; q += kMergeThreads) {
+			out_dist[o + q] = __builtin_inff();
+			out_row[o + q] = kInvalidRow;
+		}
+		return;
+	}
+	uint32_t n2 = 64;
+	while (n2 < n) n2 <<= 1;
+	for (uint32_t q = n + tid; q < n2; q += kMergeThreads) {
+		s_key[q] = ~0ull;
+		s_val[q] = 0.f;
+	}
+	__syncthreads();
+	merge_bitonic(s_key, s_val, n2);
+	for (uint32_t q = tid; q < kk; q += kMergeThreads) {
+		out_dist[o + q] = q < cnt ? s_val[q] : __builtin_inff();
+		out_row[o + q] = q < cnt ? uint32_t(s_key[q]) : kInvalidRow;
+	}
+}
+
 template <typename TK>
 __device__ void merge_by_insertion(const float* part_dist, const uint32_t* part_row, size_t base, uint32_t total, uint32_t kk, float* out_dist,
 								   uint32_t* out_row, uint32_t* out_count, float* s_d, uint32_t* s_i);
 
-// the merge of query blockIdx.x; s_key / s_val: [kMergeHeadsMax], s_n: one word of LDS
+constexpr uint32_t kMergeWalkAhead = 4;   // entries of a list whose loads the walk issues together, ahead of the comparison
+// the merge of query blockIdx.x; s_key / s_val: [kMergeHeadsMax], s_n: one word of LDS.  Returns true when the selection answered, false when
+// the insertion merge did (workgroup-uniform).
 template <typename TK>
-__device__ __forceinline__ void merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, float* out_dist, uint32_t* out_row,
+__device__ __forceinline__ bool merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, float* out_dist, uint32_t* out_row,
 											uint32_t* out_count, unsigned long long* s_key, float* s_val, uint32_t* s_np) {
 	uint32_t& s_n = *s_np;
 	const uint32_t tid = threadIdx.x, total = nlists * kk;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const size_t base = size_t(blockIdx.x) * total;
 	bool serial = nlists < kk || nlists > kMergeHeadsMax;
 	if (!serial) {
-		uint32_t n1 = 64;
-		while (n1 < nlists) n1 <<= 1;
-		for (uint32_t l = tid; l < n1; l += kMergeThreads) {
+		// a head: row and distance loaded together (the slot exists whether or not the list holds an entry)
+		auto head = [&](uint32_t l) {
 			unsigned long long k = ~0ull;
 			if (l < nlists) {
 				const uint32_t r = part_row[base + size_t(l) * kk];
-				if (r != kInvalidRow) k = merge_pair_key(part_dist[base + size_t(l) * kk], r);
+				const float d = part_dist[base + size_t(l) * kk];
+				if (r != kInvalidRow) k = merge_pair_key(d, r);
 			}
-			s_key[l] = k;
-			s_val[l] = 0.f;
-		}
+			return k;
+		};
+		const uint32_t runs = (nlists + kWave - 1) / kWave, per_run = kk < uint32_t(kWave) ? kk : uint32_t(kWave);
+		unsigned long long bound;
 		if (tid == 0) s_n = 0;
-		__syncthreads();
-		merge_bitonic(s_key, s_val, n1);
-		const unsigned long long bound = s_key[kk - 1];   // ~0: fewer than kk non-empty lists — everything valid is a candidate
+		if (nlists <= 2 * kMergeThreads && runs * per_run <= kMergeRankMax) {   // workgroup-uniform
+			unsigned long long h0 = head(tid), h1 = head(kMergeThreads + tid);
+			h0 = merge_wave_sort(h0, lane);
+			if (runs > uint32_t(kMergeWaves)) h1 = merge_wave_sort(h1, lane);
+			if (uint32_t(lane) < per_run) {
+				if (uint32_t(wave) < runs) s_key[wave * per_run + lane] = h0;
+				if (uint32_t(kMergeWaves + wave) < runs) s_key[(kMergeWaves + wave) * per_run + lane] = h1;
+			}
+			merge_kth_key(s_key, runs * per_run, kk, &s_key[kMergeRankMax]);
+			bound = s_key[kMergeRankMax];
+		} else {
+			uint32_t n1 = 64;
+			while (n1 < nlists) n1 <<= 1;
+			for (uint32_t l = tid; l < n1; l += kMergeThreads) {
+				s_key[l] = head(l);
+				s_val[l] = 0.f;
+			}
+			__syncthreads();
+			merge_bitonic(s_key, s_val, n1);
+			bound = s_key[kk - 1];
+		}
+		// bound = ~0: fewer than kk non-empty lists — everything valid is a candidate
 		__syncthreads();
 		// (the candidates overwrite the heads: every thread has read the bound)
 		for (uint32_t l = tid; l < nlists; l += kMergeThreads) {
 			const size_t at = base + size_t(l) * kk;
-			for (uint32_t e = 0; e < kk; ++e) {
-				const uint32_t r = part_row[at + e];
-				if (r == kInvalidRow) break;
-				const float d = part_dist[at + e];
-				const unsigned long long k = merge_pair_key(d, r);
-				if (k > bound) break;
-				const uint32_t pos = atomicAdd(&s_n, 1u);
-				if (pos < kMergeCandMax) {
-					s_key[pos] = k;
-					s_val[pos] = d;
+			bool more = true;
+			for (uint32_t e0 = 0; e0 < kk && more; e0 += kMergeWalkAhead) {
+				uint32_t r[kMergeWalkAhead];
+				float d[kMergeWalkAhead];
+#pragma unroll
+				for (uint32_t u = 0; u < kMergeWalkAhead; ++u) {
+					r[u] = kInvalidRow;
+					d[u] = __builtin_inff();
+					if (e0 + u < kk) {
+						r[u] = part_row[at + e0 + u];
+						d[u] = part_dist[at + e0 + u];
+					}
+				}
+#pragma unroll
+				for (uint32_t u = 0; u < kMergeWalkAhead; ++u) {
+					const unsigned long long k = merge_pair_key(d[u], r[u]);
+					more = more && r[u] != kInvalidRow && k <= bound;
+					if (more) {
+						const uint32_t pos = atomicAdd(&s_n, 1u);
+						if (pos < kMergeCandMax) {
+							s_key[pos] = k;
+							s_val[pos] = d[u];
+						}
+					}
 				}
 			}
 		}
@@ -740,54 +844,137 @@ __device__ __forceinline__ void merge_lists(const float* part_dist, const uint32
 		const uint32_t n = s_n;
 		serial = n > kMergeCandMax;
 		if (!serial) {
-			uint32_t n2 = 64;
-			while (n2 < n) n2 <<= 1;
-			for (uint32_t q = n + tid; q < n2; q += kMergeThreads) {
-				s_key[q] = ~0ull;
-				s_val[q] = 0.f;
-			}
-			__syncthreads();
-			merge_bitonic(s_key, s_val, n2);
-			const uint32_t cnt = n < kk ? n : kk;
-			for (uint32_t q = tid; q < kk; q += kMergeThreads) {
-				out_dist[size_t(blockIdx.x) * kk + q] = q < cnt ? s_val[q] : __builtin_inff();
-				out_row[size_t(blockIdx.x) * kk + q] = q < cnt ? uint32_t(s_key[q]) : kInvalidRow;
-			}
-			if (tid == 0 && out_count) out_count[blockIdx.x] = cnt;
-			return;
+			merge_write_sorted(s_key, s_val, n, kk, out_dist, out_row, out_count);
+			return true;
 		}
 		__syncthreads();
 	}
 	// the insertion merge over the same lists (LDS reused for the wavefronts' lists)
 	merge_by_insertion<TK>(part_dist, part_row, base, total, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
+	return false;
 }
 
+// path (optional, test instrumentation): [query] 1 = the selection answered, 0 = the insertion merge
 template <typename TK>
 __global__ __launch_bounds__(kMergeThreads) void knn_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
 																  float* out_dist, uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt,
-																  uint32_t gate_cap) {
+																  uint32_t gate_cap, uint32_t* path) {
 	__shared__ unsigned long long s_key[kMergeHeadsMax];
 	__shared__ float s_val[kMergeHeadsMax];
 	__shared__ uint32_t s_n;
 	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;   // workgroup-uniform (knn_merge's gate)
-	merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
+	const bool fast = merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
+	if (path && threadIdx.x == 0) path[blockIdx.x] = fast ? 1u : 0u;
+}
+
+// The re-scored candidates of a pruned chain -> the exact top-kk without serial insertions: the rule of merge_lists for UNSORTED groups.  Thread
+// t owns candidates t, t + kMergeThreads, ...; its smallest key is the head of that group, the kk-th smallest head bounds the kk-th best
+// overall, and a second walk (the candidates are in L2 by then) collects every key at or below the bound: for candidates in list order little
+// more than kk.  Up to kMergeThreads candidates need no heads: all of them are collected.  Returns false, workgroup-uniform and with nothing
+// written, when merge_fold has to answer: a NaN distance (pair_lt is no order over NaN, so the fold's answer is the definition), fewer than kk
+// non-empty groups (no bound), more than kMergeCandMax entries collected (masses of equal distances).  kk <= 64.
+__device__ __forceinline__ bool merge_select(const float* cand_dist, const uint32_t* cand_row, size_t base, uint32_t cnt, uint32_t kk, float* out_dist,
+											 uint32_t* out_row, uint32_t* out_count, unsigned long long* s_key, float* s_val, uint32_t* s_np) {
+	uint32_t& s_n = *s_np;
+	const uint32_t tid = threadIdx.x;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	// one trip of a walk: kMergeAhead candidates of this thread, their loads issued together
+	auto walk = [&](auto&& each) {
+		for (uint32_t c0 = tid; c0 < cnt; c0 += kMergeThreads * kMergeAhead) {
+			float cd[kMergeAhead];
+			uint32_t ci[kMergeAhead];
+#pragma unroll
+			for (int u = 0; u < kMergeAhead; ++u) {
+				const uint32_t c = c0 + uint32_t(u) * kMergeThreads;
+				cd[u] = __builtin_inff();
+				ci[u] = kInvalidRow;
+				if (c < cnt) {
+					cd[u] = cand_dist[base + c];
+					ci[u] = cand_row[base + c];
+				}
+			}
+#pragma unroll
+			for (int u = 0; u < kMergeAhead; ++u) {
+				if (ci[u] != kInvalidRow) each(cd[u], ci[u]);
+			}
+		}
+	};
+	uint32_t& s_nan = *reinterpret_cast<uint32_t*>(&s_val[kMergeHeadsMax - 1]);   // (a word neither the heads nor the collected entries reach)
+	if (tid == 0) {
+		s_n = 0;
+		s_nan = 0;
+	}
+	__syncthreads();
+	unsigned long long bound = ~0ull;
+	bool nan = false;
+	if (cnt > uint32_t(kMergeThreads)) {   // workgroup-uniform
+		unsigned long long h = ~0ull;
+		walk([&](float d, uint32_t r) {
+			nan |= d != d;
+			const unsigned long long k = merge_pair_key(d, r);
+			h = k < h ? k : h;
+		});
+		h = merge_wave_sort(h, lane);
+		if (uint32_t(lane) < kk) s_key[uint32_t(wave) * kk + lane] = h;
+		if (nan) s_nan = 1;
+		__syncthreads();
+		if (s_nan) return false;
+		const uint32_t m = uint32_t(kMergeWaves) * kk;   // <= 512 keys
+		if (m <= kMergeRankMax) {
+			merge_kth_key(s_key, m, kk, &s_key[kMergeRankMax]);
+			bound = s_key[kMergeRankMax];
+		} else {
+			if (tid >= m) s_key[tid] = ~0ull;   // kk = 33 .. 64: 264 .. 512 keys, padded to the 512 the sort takes
+			s_val[tid] = 0.f;
+			__syncthreads();
+			merge_bitonic(s_key, s_val, kMergeThreads);
+			bound = s_key[kk - 1];
+		}
+		if (bound == ~0ull) return false;
+		__syncthreads();   // (the candidates overwrite the heads: every thread has read the bound)
+	}
+	walk([&](float d, uint32_t r) {
+		nan |= d != d;
+		const unsigned long long k = merge_pair_key(d, r);
+		if (k <= bound) {
+			const uint32_t pos = atomicAdd(&s_n, 1u);
+			if (pos < kMergeCandMax) {
+				s_key[pos] = k;
+				s_val[pos] = d;
+			}
+		}
+	});
+	if (nan) s_nan = 1;
+	__syncthreads();
+	if (s_nan) return false;
+	const uint32_t n = s_n;
+	if (n > kMergeCandMax) return false;
+	merge_write_sorted(s_key, s_val, n, kk, out_dist, out_row, out_count);
+	return true;
 }
 
 // The one merge at the end of a pruned chain (rxgpu_knn_chains.hip), one workgroup per query.  Gate closed (cand_cnt <= cap): the pruned chain
-// answers — merge_fold over the cand_cnt re-scored candidates.  Gate open: the exact scan behind the gate has run — merge_lists over its lists.
+// answers — merge_select over the cand_cnt re-scored candidates, merge_fold where that declines.  Gate open: the exact scan behind the gate has
+// run — merge_lists over its lists.  path (optional, test instrumentation): [query] 1 = a selection answered, 0 = an insertion merge.
 template <typename TK>
 __global__ __launch_bounds__(kMergeThreads) void knn_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap,
 																  const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
-																  float* out_dist, uint32_t* out_row, uint32_t* out_count) {
+																  float* out_dist, uint32_t* out_row, uint32_t* out_count, uint32_t* path) {
 	__shared__ unsigned long long s_key[kMergeHeadsMax];
 	__shared__ float s_val[kMergeHeadsMax];
 	__shared__ uint32_t s_n;
 	const uint32_t cnt = cand_cnt[blockIdx.x];   // workgroup-uniform
+	bool fast;
 	if (cnt <= cap) {
-		merge_fold(cand_dist, cand_row, size_t(blockIdx.x) * cap, cnt, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
+		fast = merge_select(cand_dist, cand_row, size_t(blockIdx.x) * cap, cnt, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
+		if (!fast) {
+			__syncthreads();   // (the fold's lists reuse the LDS of the selection)
+			merge_fold(cand_dist, cand_row, size_t(blockIdx.x) * cap, cnt, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
+		}
 	} else {
-		merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
+		fast = merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
 	}
+	if (path && threadIdx.x == 0) path[blockIdx.x] = fast ? 1u : 0u;
 }
 
 __device__ __forceinline__ void merge_store_list(const WaveTopK& t, float* d, uint32_t* i, int lane) {
@@ -1243,26 +1430,26 @@ void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t tot
 
 // the partial results are SORTED lists of kk entries (nlists per query): knn_merge_lists
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
-						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt, uint32_t gate_cap) {
+						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt, uint32_t gate_cap, uint32_t* path) {
 	if (kk > uint32_t(kMaxFusedK)) {
 		hipLaunchKernelGGL((knn_merge_lists<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
-						   gate_cnt, gate_cap);
+						   gate_cnt, gate_cap, path);
 	} else {
 		hipLaunchKernelGGL((knn_merge_lists<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
-						   gate_cnt, gate_cap);
+						   gate_cnt, gate_cap, path);
 	}
 }
 
 // the end of a pruned chain: the candidates (cand_cnt <= cap) or the exact scan's nlists sorted lists (knn_merge_final)
 void launch_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap, const float* part_dist,
 						const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-						hipStream_t s) {
-	if (kk > uint32_t(kMaxFusedK)) {   // (the pruned chains keep kk <= 64: the candidate fold holds one entry per lane)
+						hipStream_t s, uint32_t* path) {
+	if (kk > uint32_t(kMaxFusedK)) {   // (the pruned chains keep kk <= 64: the candidate branch holds one entry per lane)
 		hipLaunchKernelGGL((knn_merge_final<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, cand_dist, cand_row, cand_cnt, cap, part_dist, part_row, nlists, kk,
-						   out_dist, out_row, out_count);
+						   out_dist, out_row, out_count, path);
 	} else {
 		hipLaunchKernelGGL((knn_merge_final<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, cand_dist, cand_row, cand_cnt, cap, part_dist, part_row, nlists, kk,
-						   out_dist, out_row, out_count);
+						   out_dist, out_row, out_count, path);
 	}
 }
 

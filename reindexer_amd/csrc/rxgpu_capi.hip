@@ -282,6 +282,50 @@ int rxgpu_index_inspect(rxgpu_index* h, const char* what, void* out, uint64_t ca
 	return rxgpu::inspect_index(h, what, out, cap_bytes, out_bytes);
 }
 
+int rxgpu_knn_merge_probe(int device, int what, const float* dist, const uint32_t* row, uint32_t n, uint32_t kk, float* out_dist, uint32_t* out_row,
+						  uint32_t* out_count, int* out_path) {
+	RX_CHECK(out_dist && out_row && out_count && out_path && (n == 0 || (dist && row)), RXGPU_ERR_PARAMS, "rxgpu_knn_merge_probe: null argument");
+	RX_CHECK(what >= 0 && what <= 2, RXGPU_ERR_PARAMS, "rxgpu_knn_merge_probe: unknown kernel");
+	RX_CHECK(kk >= 1 && kk <= uint32_t(what == 0 ? rxgpu::kMaxFusedK2 : rxgpu::kMaxFusedK), RXGPU_ERR_PARAMS, "rxgpu_knn_merge_probe: kk out of range");
+	const uint64_t pairs = what == 0 ? uint64_t(n) * kk : n;
+	RX_CHECK(pairs <= (1u << 24), RXGPU_ERR_PARAMS, "rxgpu_knn_merge_probe: too many pairs");
+	DeviceGuard dg(device);
+	RX_CHECK(dg.ok, RXGPU_ERR_DEVICE, "rxgpu_knn_merge_probe: no such device");
+	// one allocation: the pairs, the result, {count, path, candidate count}
+	const size_t in_words = size_t(std::max<uint64_t>(pairs, 1));
+	uint32_t* d = nullptr;
+	RX_HIP(hipMalloc(reinterpret_cast<void**>(&d), (2 * in_words + 2 * kk + 3) * sizeof(uint32_t)));
+	float* d_dist = reinterpret_cast<float*>(d);
+	uint32_t* d_row = d + in_words;
+	float* d_od = reinterpret_cast<float*>(d_row + in_words);
+	uint32_t* d_or = d_row + in_words + kk;
+	uint32_t* d_tail = d_or + kk;   // [0] count, [1] path, [2] n
+	const uint32_t tail[3] = {0, 0, n};
+	hipError_t e = hipMemcpy(d_tail, tail, sizeof(tail), hipMemcpyHostToDevice);
+	if (e == hipSuccess && pairs) e = hipMemcpy(d_dist, dist, pairs * sizeof(float), hipMemcpyHostToDevice);
+	if (e == hipSuccess && pairs) e = hipMemcpy(d_row, row, pairs * sizeof(uint32_t), hipMemcpyHostToDevice);
+	if (e == hipSuccess) {
+		if (what == 0) {
+			rxgpu::launch_merge_lists(d_dist, d_row, n, kk, 1, d_od, d_or, d_tail, nullptr, nullptr, 0, d_tail + 1);
+		} else if (what == 1) {   // cand_cnt = cap = n: the candidate branch
+			rxgpu::launch_merge_final(d_dist, d_row, d_tail + 2, n, nullptr, nullptr, 0, kk, 1, d_od, d_or, d_tail, nullptr, d_tail + 1);
+		} else {
+			rxgpu::launch_merge(d_dist, d_row, n, kk, 1, d_od, d_or, d_tail, nullptr, 0, nullptr);
+		}
+		e = hipGetLastError();
+	}
+	if (e == hipSuccess) e = hipDeviceSynchronize();
+	uint32_t back[2] = {0, 0};
+	if (e == hipSuccess) e = hipMemcpy(out_dist, d_od, kk * sizeof(float), hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(out_row, d_or, kk * sizeof(uint32_t), hipMemcpyDeviceToHost);
+	if (e == hipSuccess) e = hipMemcpy(back, d_tail, sizeof(back), hipMemcpyDeviceToHost);
+	(void)hipFree(d);
+	RX_HIP(e);
+	*out_count = back[0];
+	*out_path = int(back[1]);
+	return RXGPU_OK;
+}
+
 int rxgpu_device_count(void) {
 	int n = 0;
 	if (hipGetDeviceCount(&n) != hipSuccess) {

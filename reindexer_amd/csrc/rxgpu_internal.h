@@ -57,12 +57,13 @@ void launch_filter_emitted_wide(const EmitEntry* emit, const uint32_t* emit_cnt,
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s);
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
-						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt = nullptr,
-						uint32_t gate_cap = 0);   // the partial results are sorted lists of kk entries: no serial insertions; gated like launch_merge
+						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt = nullptr, uint32_t gate_cap = 0,
+						uint32_t* path = nullptr);   // the partial results are sorted lists of kk entries: no serial insertions; gated like launch_merge
 // the one merge at the end of a pruned chain: per query the cand_cnt re-scored candidates (cand_cnt <= cap), else the exact scan's sorted lists
+// path (both; rxgpu_knn_merge_probe): [nq] words, 1 where a selection answered the query, 0 where an insertion merge did
 void launch_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap, const float* part_dist,
 						const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-						hipStream_t s);
+						hipStream_t s, uint32_t* path = nullptr);
 void launch_merge_shards(const uint32_t* gathered, uint32_t world, uint32_t nq, uint32_t kk, uint32_t shard_rows, float* out_dist,
 						 uint32_t* out_row, uint32_t* out_count, hipStream_t s, const uint32_t* slot_base = nullptr, bool sorted = true);
 // one shard's HNSW result (unordered, counts <= k) into its [nq][kk] | [nq][kk] slot of the exchange's send buffer, padded with invalid entries
