@@ -2,7 +2,7 @@
 // wavefronts; wavefront w owns the sets w, w + nwaves, ... of kEmitRowsPerSet consecutive rows.  While it scans, a wavefront appends an 8-byte
 // {lo, row} entry for every row whose lower bound can still matter, into a segment of its own: segments lie back to back in wavefront order,
 // each exactly as large as the rows its wavefront scans, so emission can never overflow and needs no overflow path.  knn_filter_emitted
-// (knn_scan.hip) then reads emit_cnt[w] entries of every segment.  Arithmetic on counts only — tests/test_knn_emit_plan.py pins it on the
+// (knn_filter.hip) then reads emit_cnt[w] entries of every segment.  Arithmetic on counts only — tests/test_knn_emit_plan.py pins it on the
 // CPU (tests/cpp/knn_emit_plan_cpu.cc); the kernels take an EmitPlan by value, so nothing divides on the device.
 #pragma once
 

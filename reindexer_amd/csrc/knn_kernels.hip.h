@@ -60,7 +60,7 @@ struct ScanParams {
 	uint32_t gate_cap;
 };
 
-// bf16-pruned scan (knn_scan.hip: knn_scan_bf16 + knn_filter_approx): approximate distances from the bf16 shadow, exact tail
+// bf16-pruned scan (knn_scan.hip: knn_scan_bf16; knn_filter.hip: knn_filter_approx): approximate distances from the bf16 shadow, exact tail
 struct ScanBf16Params {
 	ScanParams sp;            // kk, part_dist / part_row ([nq][gridDim.x][kk]); rows / stride / dim / queries unused here
 	const uint16_t* rows16;   // bf16 shadow: [n][ld], or tile-blocked (shadow_elem_base)

@@ -1,7 +1,7 @@
-// Streaming brute-force scan + fused wavefront top-k, merge, range and re-score kernels (gfx950).
+// Streaming brute-force scans with a fused wavefront top-k (gfx950): f32 over every row or a row list, bf16 over the shadow.  What follows a
+// scan is in knn_merge.hip (top-k merges), knn_filter.hip (candidate filters of the pruned chains) and knn_range.hip (range, distances).
 // See knn_kernels.hip.h for the arithmetic contract.  Reference being replaced:
 // cpp_src/core/index/float_vector/hnswlib/bruteforce.cc:103-143.
-#include <algorithm>
 #include <type_traits>
 
 #include "knn_kernels.hip.h"
@@ -13,39 +13,6 @@
 namespace rxgpu {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kMergeThreads = 512;
-constexpr int kMergeWaves = kMergeThreads / kWave;
-constexpr int kMergeAhead = 8;                       // candidate chunks whose loads a merge wavefront keeps in flight
-
-// block_merge_and_store (knn_scan_common.hip.h) for the two-entries-per-lane list (64 < kk <= 128)
-__device__ __forceinline__ void block_merge_and_store(WaveTopK2& top, const ScanParams& p, int lane, int wave) {
-	__shared__ float s_d[kScanWaves][kMaxFusedK2];
-	__shared__ uint32_t s_i[kScanWaves][kMaxFusedK2];
-	s_d[wave][lane] = top.d0;
-	s_i[wave][lane] = top.i0;
-	s_d[wave][64 + lane] = top.d1;
-	s_i[wave][64 + lane] = top.i1;
-	__syncthreads();
-	if (wave != 0) return;
-	for (int w = 1; w < kScanWaves; ++w) {
-		for (uint32_t e = 0; e < top.kk; ++e) {   // sorted: once one entry is rejected the rest of that list is too
-			const float d = s_d[w][e];
-			const uint32_t i = s_i[w][e];
-			if (i == kInvalidRow || !top.admits(d, i)) break;
-			top.insert(d, i, lane);
-		}
-	}
-	const size_t o = (size_t(blockIdx.y) * gridDim.x + blockIdx.x) * top.kk;
-	if (lane < int(top.kk)) {
-		p.part_dist[o + lane] = top.d0;
-		p.part_row[o + lane] = top.i0;
-	}
-	if (64 + lane < int(top.kk)) {
-		p.part_dist[o + 64 + lane] = top.d1;
-		p.part_row[o + 64 + lane] = top.i1;
-	}
-}
 
 // Rows of this wave's step -> candidate insertion.  `dist` is replicated over each 16-lane group.
 template <typename TK>
@@ -267,8 +234,8 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_subset_generic(ScanPara
 //                         finite bound, which steps 3-4 then leave to the gated exact scan
 //   1. knn_scan_bf16      approximate distance d~ of every row from the bf16 shadow (2 bytes per element), stored ([n] floats) and folded
 //                         into the per-wave top-kk exactly like the f32 scan
-//   2. knn_merge_lists    -> d~_(kk), the kk-th best approximate distance (the scan leaves sorted per-workgroup lists)
-//   3. knn_filter_approx  rows with d~ <= d~_(kk) + 2 eps  (eps = the rigorous bf16 bound of knn_query_stats<.., true>)
+//   2. knn_merge_lists    (knn_merge.hip) -> d~_(kk), the kk-th best approximate distance (the scan leaves sorted per-workgroup lists)
+//   3. knn_filter_approx  (knn_filter.hip) rows with d~ <= d~_(kk) + 2 eps  (eps = the rigorous bf16 bound of knn_query_stats<.., true>)
 //   4. knn_rescore, the gated exact scan, knn_merge_final   EXACT distances of those few dozen rows, exact top-kk by (dist, row)
 // Soundness: a row r of the true top-kk has d~_r <= d_r + eps <= D_kk + eps, and D_kk <= kk-th smallest of (d~ + eps) = d~_(kk) + eps.
 // One 16-lane group owns a row: lane m loads the 16-byte chunks m, m + 16, ... (8 bf16 each; 256 contiguous bytes per group per load),
@@ -468,758 +435,6 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_bf16_blk(ScanBf16Params
 	block_merge_and_store(top, p.sp, lane, wave);
 }
 
-// rows whose approximate distance is within the bound of the kk-th best approximate distance -> candidate list of the query
-__global__ __launch_bounds__(256) void knn_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk,
-														 const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap,
-														 const uint32_t* __restrict__ ids) {
-	const uint32_t qi = blockIdx.y;
-	const int lane = threadIdx.x & 63;
-	if (!(margin[qi] < __builtin_inff())) return;   // no bound for this query (knn_query_prep has set cand_cnt = cap + 1): the exact scan answers it
-	const float thr = (top_count[qi] >= kk ? top_dist[size_t(qi) * kk + kk - 1] : __builtin_inff()) + margin[qi];
-	const float* a = approx + size_t(qi) * n;
-	const uint64_t span = uint64_t(gridDim.x) * blockDim.x;
-	for (uint64_t base = uint64_t(blockIdx.x) * blockDim.x; base < n; base += span) {   // wave-uniform trip count
-		const uint64_t row = base + threadIdx.x;
-		const bool pass = row < n && a[row] <= thr;
-		const uint64_t pm = __ballot(pass);
-		if (!pm) continue;
-		uint32_t pos0 = 0;
-		if (lane == __builtin_ctzll(pm)) pos0 = atomicAdd(&cand_cnt[qi], uint32_t(__popcll(pm)));
-		pos0 = __shfl(pos0, __builtin_ctzll(pm));
-		const uint32_t pos = pos0 + uint32_t(__popcll(pm & ((1ull << lane) - 1)));
-		if (pass && pos < cap) cand_row[size_t(qi) * cap + pos] = ids ? ids[row] : uint32_t(row);   // a row list: position -> row
-	}
-}
-
-// knn_filter_approx over what knn_scan_i8 emitted (knn_emit_plan.h) instead of a value per row: the same early return, the same threshold, the
-// same append.  Workgroups stride over the wavefronts' segments and read emit_cnt[w] entries of each; an entry stays when lo <= thr.  The
-// emitted rows are a superset of {lo <= thr} (knn_scan_i8), so the candidate set is the one knn_filter_approx finds over all rows.
-__global__ __launch_bounds__(256) void knn_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, EmitPlan plan, const float* top_dist,
-														  const uint32_t* top_count, uint32_t kk, const float* margin, uint32_t* cand_row,
-														  uint32_t* cand_cnt, uint32_t cap) {
-	const uint32_t qi = blockIdx.y;
-	const int lane = threadIdx.x & 63;
-	if (!(margin[qi] < __builtin_inff())) return;   // no bound for this query: nothing was emitted, the exact scan answers it
-	const float thr = (top_count[qi] >= kk ? top_dist[size_t(qi) * kk + kk - 1] : __builtin_inff()) + margin[qi];
-	const EmitEntry* all = emit + size_t(qi) * plan.n;
-	const uint32_t* counts = emit_cnt + size_t(qi) * plan.nwaves;
-	for (uint64_t w = blockIdx.x; w < plan.nwaves; w += gridDim.x) {
-		const uint64_t room = emit_rows_of(plan, w);
-		uint64_t cnt = counts[w];
-		cnt = cnt < room ? cnt : room;   // (a count is never above its segment; nothing may read past it whatever the buffer holds)
-		const EmitEntry* seg = all + emit_segment_offset(plan, w);
-		for (uint64_t base = 0; base < cnt; base += blockDim.x) {   // workgroup-uniform trip count
-			const uint64_t at = base + threadIdx.x;
-			EmitEntry ent;
-			ent.lo = __builtin_inff();
-			ent.row = kInvalidRow;
-			if (at < cnt) ent = seg[at];
-			const bool pass = at < cnt && ent.lo <= thr;
-			const uint64_t pm = __ballot(pass);
-			if (!pm) continue;
-			uint32_t pos0 = 0;
-			if (lane == __builtin_ctzll(pm)) pos0 = atomicAdd(&cand_cnt[qi], uint32_t(__popcll(pm)));
-			pos0 = __shfl(pos0, __builtin_ctzll(pm));
-			const uint32_t pos = pos0 + uint32_t(__popcll(pm & ((1ull << lane) - 1)));
-			if (pass && pos < cap) cand_row[size_t(qi) * cap + pos] = ent.row;
-		}
-	}
-}
-
-// Fold `total` candidate (dist,row) pairs at part_*[base ..] (invalid rows skipped) into the sorted top-kk of query blockIdx.x, by all
-// kMergeThreads threads.  s_d / s_i: [kMergeWaves][kMaxFusedK] words of LDS each.
-__device__ __forceinline__ void merge_fold(const float* part_dist, const uint32_t* part_row, size_t base, uint32_t total, uint32_t kk, float* out_dist,
-										   uint32_t* out_row, uint32_t* out_count, float* s_d, uint32_t* s_i) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	WaveTopK top;
-	top.init(kk);
-	// kMergeAhead chunks of 64 candidates per trip, all their loads issued together: one chunk per trip left every trip behind its own
-	// memory round trip (~2 us each: 0.27 ms for the 512 x 101 partial entries of a k = 100 search, against 0.03 ms of list work)
-	for (uint32_t c0 = wave * kWave; c0 < total; c0 += kMergeThreads * kMergeAhead) {
-		float cd[kMergeAhead];
-		uint32_t ci[kMergeAhead];
-#pragma unroll
-		for (int u = 0; u < kMergeAhead; ++u) {
-			const uint32_t c = c0 + uint32_t(u) * kMergeThreads + lane;
-			cd[u] = __builtin_inff();
-			ci[u] = kInvalidRow;
-			if (c < total) {
-				cd[u] = part_dist[base + c];
-				ci[u] = part_row[base + c];
-			}
-		}
-#pragma unroll
-		for (int u = 0; u < kMergeAhead; ++u) {
-			uint64_t pm = __ballot(ci[u] != kInvalidRow && top.admits(cd[u], ci[u]));
-			while (pm) {
-				const int src = __builtin_ctzll(pm);
-				pm &= pm - 1;
-				const float d = __shfl(cd[u], src);
-				const uint32_t i = __shfl(ci[u], src);
-				if (top.admits(d, i)) top.insert(d, i, lane);
-			}
-		}
-	}
-	s_d[wave * kMaxFusedK + lane] = top.bd;
-	s_i[wave * kMaxFusedK + lane] = top.bi;
-	__syncthreads();
-	if (wave != 0) return;
-	for (int w = 1; w < kMergeWaves; ++w) {
-		const float cd = s_d[w * kMaxFusedK + lane];
-		const uint32_t ci = s_i[w * kMaxFusedK + lane];
-		uint64_t pm = __ballot(ci != kInvalidRow && lane < int(kk));
-		while (pm) {
-			const int src = __builtin_ctzll(pm);
-			pm &= pm - 1;
-			const float d = __shfl(cd, src);
-			const uint32_t i = __shfl(ci, src);
-			if (!top.admits(d, i)) break;
-			top.insert(d, i, lane);
-		}
-	}
-	if (lane < int(kk)) {
-		out_dist[size_t(blockIdx.x) * kk + lane] = top.bd;
-		out_row[size_t(blockIdx.x) * kk + lane] = top.bi;
-	}
-	if (lane == 0 && out_count) out_count[blockIdx.x] = top.filled;
-}
-
-// One workgroup per query: merge_fold over the query's `total` pairs.
-__global__ __launch_bounds__(kMergeThreads) void knn_merge(const float* part_dist, const uint32_t* part_row, uint32_t total,
-															uint32_t kk, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-															const uint32_t* gate_cnt, uint32_t gate_cap) {
-	__shared__ float s_d[kMergeWaves * kMaxFusedK];
-	__shared__ uint32_t s_i[kMergeWaves * kMaxFusedK];
-	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;
-	merge_fold(part_dist, part_row, size_t(blockIdx.x) * total, total, kk, out_dist, out_row, out_count, s_d, s_i);
-}
-
-// knn_merge for 64 < kk <= 128 (two entries per lane)
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_wide(const float* part_dist, const uint32_t* part_row, uint32_t total, uint32_t kk,
-																 float* out_dist, uint32_t* out_row, uint32_t* out_count) {
-	__shared__ float s_d[kMergeWaves][kMaxFusedK2];
-	__shared__ uint32_t s_i[kMergeWaves][kMaxFusedK2];
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const size_t base = size_t(blockIdx.x) * total;
-	WaveTopK2 top;
-	top.init(kk);
-	// kMergeAhead chunks of 64 candidates per trip, all their loads issued together: one chunk per trip left every trip behind its own
-	// memory round trip (~2 us each: 0.27 ms for the 512 x 101 partial entries of a k = 100 search, against 0.03 ms of list work)
-	for (uint32_t c0 = wave * kWave; c0 < total; c0 += kMergeThreads * kMergeAhead) {
-		float cd[kMergeAhead];
-		uint32_t ci[kMergeAhead];
-#pragma unroll
-		for (int u = 0; u < kMergeAhead; ++u) {
-			const uint32_t c = c0 + uint32_t(u) * kMergeThreads + lane;
-			cd[u] = __builtin_inff();
-			ci[u] = kInvalidRow;
-			if (c < total) {
-				cd[u] = part_dist[base + c];
-				ci[u] = part_row[base + c];
-			}
-		}
-#pragma unroll
-		for (int u = 0; u < kMergeAhead; ++u) {
-			uint64_t pm = __ballot(ci[u] != kInvalidRow && top.admits(cd[u], ci[u]));
-			while (pm) {
-				const int src = __builtin_ctzll(pm);
-				pm &= pm - 1;
-				const float d = __shfl(cd[u], src);
-				const uint32_t i = __shfl(ci[u], src);
-				if (top.admits(d, i)) top.insert(d, i, lane);
-			}
-		}
-	}
-	s_d[wave][lane] = top.d0;
-	s_i[wave][lane] = top.i0;
-	s_d[wave][64 + lane] = top.d1;
-	s_i[wave][64 + lane] = top.i1;
-	__syncthreads();
-	if (wave != 0) return;
-	for (int w = 1; w < kMergeWaves; ++w) {
-		for (uint32_t e = 0; e < kk; ++e) {
-			const float d = s_d[w][e];
-			const uint32_t i = s_i[w][e];
-			if (i == kInvalidRow || !top.admits(d, i)) break;
-			top.insert(d, i, lane);
-		}
-	}
-	const size_t o = size_t(blockIdx.x) * kk;
-	if (lane < int(kk)) {
-		out_dist[o + lane] = top.d0;
-		out_row[o + lane] = top.i0;
-	}
-	if (64 + lane < int(kk)) {
-		out_dist[o + 64 + lane] = top.d1;
-		out_row[o + 64 + lane] = top.i1;
-	}
-	if (lane == 0 && out_count) out_count[blockIdx.x] = top.filled;
-}
-
-// ---- merge of SORTED partial lists (what the scans leave: gridDim.x lists of kk entries per query), without serial insertions.
-// Folding ~500 lists through a wavefront-wide sorted list costs an insertion (a chain of cross-lane operations, ~0.4 us) for every
-// candidate that beats the running kk-th — ~650 of them at k = 100: 0.25 ms behind a 1.5 ms scan.  The lists are sorted, so:
-//   1. the kk-th smallest list HEAD bounds the kk-th best overall (the heads are kk real candidates at or below it);
-//   2. only entries at or below that bound can be in the result: every list is walked from its head while it stays below — for rows
-//      spread evenly over the partitions that is ~1.1 kk entries in total;
-//   3. those candidates are sorted in LDS (bitonic, (distance, row) keys) and the first kk written.
-// Exact for any data; when the bound lets more than kMergeCandMax entries through (masses of equal distances) or there are fewer lists
-// than kk, the insertion merge runs instead (same kernel, workgroup-uniform branch).
-constexpr uint32_t kMergeHeadsMax = 4096, kMergeCandMax = 2048;
-__device__ __forceinline__ unsigned long long merge_pair_key(float d, uint32_t row) {
-	uint32_t b = __float_as_uint(d);
-	if (b == 0x80000000u) b = 0;   // -0.0 == +0.0 for pair_lt: the row decides
-	b ^= (b >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-	return (static_cast<unsigned long long>(b) << 32) | row;
-}
-// ascending bitonic sort of n = 2^m (key, payload) pairs in LDS by all kMergeThreads threads
-__device__ __forceinline__ void merge_bitonic(unsigned long long* key, float* val, uint32_t n) {
-	for (uint32_t k = 2; k <= n; k <<= 1) {
-		for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-			for (uint32_t t = threadIdx.x; t < n / 2; t += kMergeThreads) {
-				const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-				const unsigned long long x = key[i], y = key[l];
-				if ((x > y) == ((i & k) == 0)) {
-					key[i] = y;
-					key[l] = x;
-					const float vx = val[i];
-					val[i] = val[l];
-					val[l] = vx;
-				}
-			}
-			__syncthreads();
-		}
-	}
-}
-// The bound of both selections below is the kk-th smallest of a few hundred group heads, and sorting them all in LDS to read one entry costs 45
-// barrier stages at 512 heads.  Instead every wavefront sorts its 64 heads in registers (no LDS, no barrier) and leaves the first min(kk, 64):
-// the kk-th smallest overall is among those.  For kk = 11 and 512 heads that is 88 keys, and the one of rank kk - 1 is found by counting.
-constexpr uint32_t kMergeRankMax = 256;   // up to this many keys are ranked by counting over LDS (n reads per thread, one barrier); more: bitonic
-// ascending sort of one key per lane across the wavefront: lane i ends with the i-th smallest
-__device__ __forceinline__ unsigned long long merge_wave_sort(unsigned long long k, int lane) {
-	for (int size = 2; size <= kWave; size <<= 1) {
-		for (int j = size >> 1; j > 0; j >>= 1) {
-			const unsigned long long o = __shfl_xor(k, j);
-			const bool take_min = ((lane & size) == 0) == ((lane & j) == 0);
-			k = (k < o) == take_min ? k : o;
-		}
-	}
-	return k;
-}
-// rank of entry i among key[0 .. n): the number of smaller keys, equal keys (pads; the same row handed in twice) in index order
-__device__ __forceinline__ uint32_t merge_rank(const unsigned long long* key, uint32_t n, uint32_t i) {
-	const unsigned long long mine = key[i];
-	uint32_t rank = 0;
-	for (uint32_t j = 0; j < n; ++j) {
-		const unsigned long long k = key[j];
-		rank += (k < mine || (k == mine && j < i)) ? 1u : 0u;
-	}
-	return rank;
-}
-// *bound = the key of rank kk - 1 among key[0 .. m) (m <= kMergeRankMax, kk <= m; pads are ~0, so ~0 when fewer than kk keys are real).
-// `bound` is a word of LDS outside key[0 .. m); ends with a barrier.
-__device__ __forceinline__ void merge_kth_key(const unsigned long long* key, uint32_t m, uint32_t kk, unsigned long long* bound) {
-	__syncthreads();
-	if (threadIdx.x < m && merge_rank(key, m, threadIdx.x) == kk - 1) *bound = key[threadIdx.x];
-	__syncthreads();
-}
-// The n <= kMergeCandMax collected (key, distance) pairs in LDS, unique keys -> the first kk in key order, padded with +inf / kInvalidRow, and
-// the count.  Every thread has passed a barrier since the pairs were written.
-__device__ __forceinline__ void merge_write_sorted(unsigned long long* s_key, float* s_val, uint32_t n, uint32_t kk, float* out_dist, uint32_t* out_row,
-												   uint32_t* out_count) {
-	const uint32_t tid = threadIdx.x, cnt = n < kk ? n : kk;
-	const size_t o = size_t(blockIdx.x) * kk;
-	if (tid == 0 && out_count) out_count[blockIdx.x] = cnt;
-	if (n <= kMergeRankMax) {   // an entry's place is the number of smaller keys
-		if (tid < n) {
-			const uint32_t rank = merge_rank(s_key, n, tid);
-			if (rank < kk) {
-				out_dist[o + rank] = s_val[tid];
-				out_row[o + rank] = uint32_t(s_key[tid]);
-			}
-		}
-		for (uint32_t q = cnt + tid; q < kk; q += kMergeThreads) {
-			out_dist[o + q] = __builtin_inff();
-			out_row[o + q] = kInvalidRow;
-		}
-		return;
-	}
-	uint32_t n2 = 64;
-	while (n2 < n) n2 <<= 1;
-	for (uint32_t q = n + tid; q < n2; q += kMergeThreads) {
-		s_key[q] = ~0ull;
-		s_val[q] = 0.f;
-	}
-	__syncthreads();
-	merge_bitonic(s_key, s_val, n2);
-	for (uint32_t q = tid; q < kk; q += kMergeThreads) {
-		out_dist[o + q] = q < cnt ? s_val[q] : __builtin_inff();
-		out_row[o + q] = q < cnt ? uint32_t(s_key[q]) : kInvalidRow;
-	}
-}
-
-template <typename TK>
-__device__ void merge_by_insertion(const float* part_dist, const uint32_t* part_row, size_t base, uint32_t total, uint32_t kk, float* out_dist,
-								   uint32_t* out_row, uint32_t* out_count, float* s_d, uint32_t* s_i);
-
-constexpr uint32_t kMergeWalkAhead = 4;   // entries of a list whose loads the walk issues together, ahead of the comparison
-// the merge of query blockIdx.x; s_key / s_val: [kMergeHeadsMax], s_n: one word of LDS.  Returns true when the selection answered, false when
-// the insertion merge did (workgroup-uniform).
-template <typename TK>
-__device__ __forceinline__ bool merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, float* out_dist, uint32_t* out_row,
-											uint32_t* out_count, unsigned long long* s_key, float* s_val, uint32_t* s_np) {
-	uint32_t& s_n = *s_np;
-	const uint32_t tid = threadIdx.x, total = nlists * kk;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const size_t base = size_t(blockIdx.x) * total;
-	bool serial = nlists < kk || nlists > kMergeHeadsMax;
-	if (!serial) {
-		// a head: row and distance loaded together (the slot exists whether or not the list holds an entry)
-		auto head = [&](uint32_t l) {
-			unsigned long long k = ~0ull;
-			if (l < nlists) {
-				const uint32_t r = part_row[base + size_t(l) * kk];
-				const float d = part_dist[base + size_t(l) * kk];
-				if (r != kInvalidRow) k = merge_pair_key(d, r);
-			}
-			return k;
-		};
-		const uint32_t runs = (nlists + kWave - 1) / kWave, per_run = kk < uint32_t(kWave) ? kk : uint32_t(kWave);
-		unsigned long long bound;
-		if (tid == 0) s_n = 0;
-		if (nlists <= 2 * kMergeThreads && runs * per_run <= kMergeRankMax) {   // workgroup-uniform
-			unsigned long long h0 = head(tid), h1 = head(kMergeThreads + tid);
-			h0 = merge_wave_sort(h0, lane);
-			if (runs > uint32_t(kMergeWaves)) h1 = merge_wave_sort(h1, lane);
-			if (uint32_t(lane) < per_run) {
-				if (uint32_t(wave) < runs) s_key[wave * per_run + lane] = h0;
-				if (uint32_t(kMergeWaves + wave) < runs) s_key[(kMergeWaves + wave) * per_run + lane] = h1;
-			}
-			merge_kth_key(s_key, runs * per_run, kk, &s_key[kMergeRankMax]);
-			bound = s_key[kMergeRankMax];
-		} else {
-			uint32_t n1 = 64;
-			while (n1 < nlists) n1 <<= 1;
-			for (uint32_t l = tid; l < n1; l += kMergeThreads) {
-				s_key[l] = head(l);
-				s_val[l] = 0.f;
-			}
-			__syncthreads();
-			merge_bitonic(s_key, s_val, n1);
-			bound = s_key[kk - 1];
-		}
-		// bound = ~0: fewer than kk non-empty lists — everything valid is a candidate
-		__syncthreads();
-		// (the candidates overwrite the heads: every thread has read the bound)
-		for (uint32_t l = tid; l < nlists; l += kMergeThreads) {
-			const size_t at = base + size_t(l) * kk;
-			bool more = true;
-			for (uint32_t e0 = 0; e0 < kk && more; e0 += kMergeWalkAhead) {
-				uint32_t r[kMergeWalkAhead];
-				float d[kMergeWalkAhead];
-#pragma unroll
-				for (uint32_t u = 0; u < kMergeWalkAhead; ++u) {
-					r[u] = kInvalidRow;
-					d[u] = __builtin_inff();
-					if (e0 + u < kk) {
-						r[u] = part_row[at + e0 + u];
-						d[u] = part_dist[at + e0 + u];
-					}
-				}
-#pragma unroll
-				for (uint32_t u = 0; u < kMergeWalkAhead; ++u) {
-					const unsigned long long k = merge_pair_key(d[u], r[u]);
-					more = more && r[u] != kInvalidRow && k <= bound;
-					if (more) {
-						const uint32_t pos = atomicAdd(&s_n, 1u);
-						if (pos < kMergeCandMax) {
-							s_key[pos] = k;
-							s_val[pos] = d[u];
-						}
-					}
-				}
-			}
-		}
-		__syncthreads();
-		const uint32_t n = s_n;
-		serial = n > kMergeCandMax;
-		if (!serial) {
-			merge_write_sorted(s_key, s_val, n, kk, out_dist, out_row, out_count);
-			return true;
-		}
-		__syncthreads();
-	}
-	// the insertion merge over the same lists (LDS reused for the wavefronts' lists)
-	merge_by_insertion<TK>(part_dist, part_row, base, total, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
-	return false;
-}
-
-// path (optional, test instrumentation): [query] 1 = the selection answered, 0 = the insertion merge
-template <typename TK>
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
-																  float* out_dist, uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt,
-																  uint32_t gate_cap, uint32_t* path) {
-	__shared__ unsigned long long s_key[kMergeHeadsMax];
-	__shared__ float s_val[kMergeHeadsMax];
-	__shared__ uint32_t s_n;
-	if (gate_cnt && gate_cnt[blockIdx.x] <= gate_cap) return;   // workgroup-uniform (knn_merge's gate)
-	const bool fast = merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
-	if (path && threadIdx.x == 0) path[blockIdx.x] = fast ? 1u : 0u;
-}
-
-// The re-scored candidates of a pruned chain -> the exact top-kk without serial insertions: the rule of merge_lists for UNSORTED groups.  Thread
-// t owns candidates t, t + kMergeThreads, ...; its smallest key is the head of that group, the kk-th smallest head bounds the kk-th best
-// overall, and a second walk (the candidates are in L2 by then) collects every key at or below the bound: for candidates in list order little
-// more than kk.  Up to kMergeThreads candidates need no heads: all of them are collected.  Returns false, workgroup-uniform and with nothing
-// written, when merge_fold has to answer: a NaN distance (pair_lt is no order over NaN, so the fold's answer is the definition), fewer than kk
-// non-empty groups (no bound), more than kMergeCandMax entries collected (masses of equal distances).  kk <= 64.
-__device__ __forceinline__ bool merge_select(const float* cand_dist, const uint32_t* cand_row, size_t base, uint32_t cnt, uint32_t kk, float* out_dist,
-											 uint32_t* out_row, uint32_t* out_count, unsigned long long* s_key, float* s_val, uint32_t* s_np) {
-	uint32_t& s_n = *s_np;
-	const uint32_t tid = threadIdx.x;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	// one trip of a walk: kMergeAhead candidates of this thread, their loads issued together
-	auto walk = [&](auto&& each) {
-		for (uint32_t c0 = tid; c0 < cnt; c0 += kMergeThreads * kMergeAhead) {
-			float cd[kMergeAhead];
-			uint32_t ci[kMergeAhead];
-#pragma unroll
-			for (int u = 0; u < kMergeAhead; ++u) {
-				const uint32_t c = c0 + uint32_t(u) * kMergeThreads;
-				cd[u] = __builtin_inff();
-				ci[u] = kInvalidRow;
-				if (c < cnt) {
-					cd[u] = cand_dist[base + c];
-					ci[u] = cand_row[base + c];
-				}
-			}
-#pragma unroll
-			for (int u = 0; u < kMergeAhead; ++u) {
-				if (ci[u] != kInvalidRow) each(cd[u], ci[u]);
-			}
-		}
-	};
-	uint32_t& s_nan = *reinterpret_cast<uint32_t*>(&s_val[kMergeHeadsMax - 1]);   // (a word neither the heads nor the collected entries reach)
-	if (tid == 0) {
-		s_n = 0;
-		s_nan = 0;
-	}
-	__syncthreads();
-	unsigned long long bound = ~0ull;
-	bool nan = false;
-	if (cnt > uint32_t(kMergeThreads)) {   // workgroup-uniform
-		unsigned long long h = ~0ull;
-		walk([&](float d, uint32_t r) {
-			nan |= d != d;
-			const unsigned long long k = merge_pair_key(d, r);
-			h = k < h ? k : h;
-		});
-		h = merge_wave_sort(h, lane);
-		if (uint32_t(lane) < kk) s_key[uint32_t(wave) * kk + lane] = h;
-		if (nan) s_nan = 1;
-		__syncthreads();
-		if (s_nan) return false;
-		const uint32_t m = uint32_t(kMergeWaves) * kk;   // <= 512 keys
-		if (m <= kMergeRankMax) {
-			merge_kth_key(s_key, m, kk, &s_key[kMergeRankMax]);
-			bound = s_key[kMergeRankMax];
-		} else {
-			if (tid >= m) s_key[tid] = ~0ull;   // kk = 33 .. 64: 264 .. 512 keys, padded to the 512 the sort takes
-			s_val[tid] = 0.f;
-			__syncthreads();
-			merge_bitonic(s_key, s_val, kMergeThreads);
-			bound = s_key[kk - 1];
-		}
-		if (bound == ~0ull) return false;
-		__syncthreads();   // (the candidates overwrite the heads: every thread has read the bound)
-	}
-	walk([&](float d, uint32_t r) {
-		nan |= d != d;
-		const unsigned long long k = merge_pair_key(d, r);
-		if (k <= bound) {
-			const uint32_t pos = atomicAdd(&s_n, 1u);
-			if (pos < kMergeCandMax) {
-				s_key[pos] = k;
-				s_val[pos] = d;
-			}
-		}
-	});
-	if (nan) s_nan = 1;
-	__syncthreads();
-	if (s_nan) return false;
-	const uint32_t n = s_n;
-	if (n > kMergeCandMax) return false;
-	merge_write_sorted(s_key, s_val, n, kk, out_dist, out_row, out_count);
-	return true;
-}
-
-// The one merge at the end of a pruned chain (rxgpu_knn_chains.hip), one workgroup per query.  Gate closed (cand_cnt <= cap): the pruned chain
-// answers — merge_select over the cand_cnt re-scored candidates, merge_fold where that declines.  Gate open: the exact scan behind the gate has
-// run — merge_lists over its lists.  path (optional, test instrumentation): [query] 1 = a selection answered, 0 = an insertion merge.
-template <typename TK>
-__global__ __launch_bounds__(kMergeThreads) void knn_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap,
-																  const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk,
-																  float* out_dist, uint32_t* out_row, uint32_t* out_count, uint32_t* path) {
-	__shared__ unsigned long long s_key[kMergeHeadsMax];
-	__shared__ float s_val[kMergeHeadsMax];
-	__shared__ uint32_t s_n;
-	const uint32_t cnt = cand_cnt[blockIdx.x];   // workgroup-uniform
-	bool fast;
-	if (cnt <= cap) {
-		fast = merge_select(cand_dist, cand_row, size_t(blockIdx.x) * cap, cnt, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
-		if (!fast) {
-			__syncthreads();   // (the fold's lists reuse the LDS of the selection)
-			merge_fold(cand_dist, cand_row, size_t(blockIdx.x) * cap, cnt, kk, out_dist, out_row, out_count, s_val, reinterpret_cast<uint32_t*>(s_key));
-		}
-	} else {
-		fast = merge_lists<TK>(part_dist, part_row, nlists, kk, out_dist, out_row, out_count, s_key, s_val, &s_n);
-	}
-	if (path && threadIdx.x == 0) path[blockIdx.x] = fast ? 1u : 0u;
-}
-
-__device__ __forceinline__ void merge_store_list(const WaveTopK& t, float* d, uint32_t* i, int lane) {
-	d[lane] = t.bd;
-	i[lane] = t.bi;
-	d[64 + lane] = __builtin_inff();
-	i[64 + lane] = kInvalidRow;
-}
-__device__ __forceinline__ void merge_store_list(const WaveTopK2& t, float* d, uint32_t* i, int lane) {
-	d[lane] = t.d0;
-	i[lane] = t.i0;
-	d[64 + lane] = t.d1;
-	i[64 + lane] = t.i1;
-}
-template <typename TK>
-__device__ void merge_by_insertion(const float* part_dist, const uint32_t* part_row, size_t base, uint32_t total, uint32_t kk, float* out_dist,
-								   uint32_t* out_row, uint32_t* out_count, float* s_d, uint32_t* s_i) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	TK top;
-	top.init(kk);
-	for (uint32_t c0 = wave * kWave; c0 < total; c0 += kMergeThreads * kMergeAhead) {
-		float cd[kMergeAhead];
-		uint32_t ci[kMergeAhead];
-#pragma unroll
-		for (int u = 0; u < kMergeAhead; ++u) {
-			const uint32_t c = c0 + uint32_t(u) * kMergeThreads + lane;
-			cd[u] = __builtin_inff();
-			ci[u] = kInvalidRow;
-			if (c < total) {
-				cd[u] = part_dist[base + c];
-				ci[u] = part_row[base + c];
-			}
-		}
-#pragma unroll
-		for (int u = 0; u < kMergeAhead; ++u) {
-			uint64_t pm = __ballot(ci[u] != kInvalidRow && top.admits(cd[u], ci[u]));
-			while (pm) {
-				const int src = __builtin_ctzll(pm);
-				pm &= pm - 1;
-				const float d = __shfl(cd[u], src);
-				const uint32_t i = __shfl(ci[u], src);
-				if (top.admits(d, i)) top.insert(d, i, lane);
-			}
-		}
-	}
-	merge_store_list(top, s_d + wave * kMaxFusedK2, s_i + wave * kMaxFusedK2, lane);
-	__syncthreads();
-	if (wave != 0) return;
-	for (int w = 1; w < kMergeWaves; ++w) {
-		for (uint32_t e = 0; e < kk; ++e) {   // sorted: once one entry is rejected the rest of that list is too
-			const float d = s_d[w * kMaxFusedK2 + e];
-			const uint32_t i = s_i[w * kMaxFusedK2 + e];
-			if (i == kInvalidRow || !top.admits(d, i)) break;
-			top.insert(d, i, lane);
-		}
-	}
-	merge_store_list(top, s_d, s_i, lane);   // wave 0 only, its own slice
-	const size_t o = size_t(blockIdx.x) * kk;
-	if (lane < int(kk)) {
-		out_dist[o + lane] = s_d[lane];
-		out_row[o + lane] = s_i[lane];
-	}
-	if (64 + lane < int(kk)) {
-		out_dist[o + 64 + lane] = s_d[64 + lane];
-		out_row[o + 64 + lane] = s_i[64 + lane];
-	}
-	if (lane == 0 && out_count) out_count[blockIdx.x] = top.filled;
-}
-
-// Multi-GPU: fold the all-gathered per-shard lists of one query batch into the global top-kk.
-// gathered: [world][2][nq][kk] 32-bit words — per shard the [nq][kk] distances followed by the [nq][kk] shard-local rows (what
-// the scan writes when d_out_row == d_out_dist + nq*kk).  Global row = shard * shard_rows + local row; order = (dist, global row).
-// slot_base (in-process RCCL path, rxgpu_sharded.hip): the global row base of every gathered position (rank-major, several shards per
-// device, padded positions = kInvalidRow and skipped); null: position w is shard w.
-// sorted = 0: the lists are UNORDERED sets (the per-shard HNSW results, members of top_candidates): every entry is offered.
-__global__ __launch_bounds__(64) void knn_merge_shards(const uint32_t* gathered, uint32_t world, uint32_t nq, uint32_t kk, uint32_t shard_rows,
-														const uint32_t* slot_base, float* out_dist, uint32_t* out_row, uint32_t* out_count, uint32_t sorted) {
-	const int lane = threadIdx.x;
-	const uint32_t q = blockIdx.x;
-	WaveTopK top;
-	top.init(kk);
-	for (uint32_t w = 0; w < world; ++w) {
-		const uint32_t* rec = gathered + size_t(w) * 2 * nq * kk + size_t(q) * kk;
-		const uint32_t base = slot_base ? slot_base[w] : w * shard_rows;
-		if (base == kInvalidRow) continue;
-		float cd = __builtin_inff();
-		uint32_t ci = kInvalidRow;
-		if (lane < int(kk)) {
-			cd = __uint_as_float(rec[lane]);
-			const uint32_t local = rec[size_t(nq) * kk + lane];
-			if (local != kInvalidRow) ci = base + local;
-		}
-		uint64_t pm = __ballot(ci != kInvalidRow);
-		while (pm) {
-			const int src = __builtin_ctzll(pm);
-			pm &= pm - 1;
-			const float d = __shfl(cd, src);
-			const uint32_t i = __shfl(ci, src);
-			if (!top.admits(d, i)) {
-				if (sorted) break;   // each shard list is sorted
-				continue;
-			}
-			top.insert(d, i, lane);
-		}
-	}
-	if (lane < int(kk)) {
-		out_dist[size_t(q) * kk + lane] = top.bd;
-		out_row[size_t(q) * kk + lane] = top.bi;
-	}
-	if (lane == 0 && out_count) out_count[q] = top.filled;
-}
-
-// Sharded HNSW: one shard's search result ([nq][k] distances, [nq][k] local rows, [nq] counts <= k) into its slot of the exchange's send
-// buffer — [nq][kk] distances | [nq][kk] rows, entries past a query's count = (+inf, kInvalidRow), which knn_merge_shards skips.
-__global__ __launch_bounds__(256) void knn_pack_lists(const float* dist, const uint32_t* row, const uint32_t* count, uint32_t nq, uint32_t k, uint32_t kk,
-													   uint32_t* dst_dist, uint32_t* dst_row) {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= nq * kk) return;
-	const uint32_t q = i / kk, j = i % kk;
-	const bool have = j < k && j < count[q];
-	dst_dist[i] = have ? __float_as_uint(dist[size_t(q) * k + j]) : 0x7F800000u;
-	dst_row[i] = have ? row[size_t(q) * k + j] : kInvalidRow;
-}
-
-// BruteforceSearch::SearchRange (bruteforce.cc:129-143): compact every row with dist < radius (or <=).
-struct RangeParams {
-	const float* rows;
-	const float* inv_norms;
-	const float* query;
-	uint64_t n;
-	uint32_t stride, dim;
-	float radius;
-	int inclusive;
-	float* out_dist;
-	uint32_t* out_row;
-	uint64_t cap;
-	unsigned long long* counter;
-};
-
-template <int kMetric>
-__global__ __launch_bounds__(kScanThreads) void knn_range(RangeParams p) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
-	const uint64_t nquads = (p.n + kRowsPerWave - 1) / kRowsPerWave;
-	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
-	for (uint64_t quad = uint64_t(blockIdx.x) * kScanWaves + wave; quad < nquads; quad += nwaves) {
-		const uint64_t row = quad * kRowsPerWave + g;
-		const bool valid = row < p.n;
-		const uint64_t rowc = valid ? row : p.n - 1;
-		const float sum = group_distance_generic<kMetric>(p.rows + rowc * p.stride, p.query, p.dim, m);
-		const float dist = metric_epilogue<kMetric>(sum, p.inv_norms, rowc);
-		const bool hit = valid && m == 0 && (p.inclusive ? dist <= p.radius : dist < p.radius);
-		const uint64_t hm = __ballot(hit);
-		if (hm) {
-			unsigned long long basePos = 0;
-			if (lane == 0) basePos = atomicAdd(p.counter, (unsigned long long)__popcll(hm));
-			basePos = __shfl(basePos, 0);
-			if (hit) {
-				const uint64_t pos = basePos + __popcll(hm & ((1ull << lane) - 1));
-				if (pos < p.cap) {
-					p.out_dist[pos] = dist;
-					p.out_row[pos] = uint32_t(row);
-				}
-			}
-		}
-	}
-}
-
-// SearchRange restricted to a row list (the list scan of an IVF range query, ivf_index.cc:212-272; p.n = list entries)
-template <int kMetric>
-__global__ __launch_bounds__(kScanThreads) void knn_range_subset(RangeParams p, const uint32_t* __restrict__ ids) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
-	const uint64_t nquads = (p.n + kRowsPerWave - 1) / kRowsPerWave;
-	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
-	for (uint64_t quad = uint64_t(blockIdx.x) * kScanWaves + wave; quad < nquads; quad += nwaves) {
-		const uint64_t item = quad * kRowsPerWave + g;
-		const bool valid = item < p.n;
-		const uint64_t row = ids[valid ? item : p.n - 1];
-		const float sum = group_distance_generic<kMetric>(p.rows + row * p.stride, p.query, p.dim, m);
-		const float dist = metric_epilogue<kMetric>(sum, p.inv_norms, row);
-		const bool hit = valid && m == 0 && (p.inclusive ? dist <= p.radius : dist < p.radius);
-		const uint64_t hm = __ballot(hit);
-		if (hm) {
-			unsigned long long basePos = 0;
-			if (lane == 0) basePos = atomicAdd(p.counter, (unsigned long long)__popcll(hm));
-			basePos = __shfl(basePos, 0);
-			if (hit) {
-				const uint64_t pos = basePos + __popcll(hm & ((1ull << lane) - 1));
-				if (pos < p.cap) {
-					p.out_dist[pos] = dist;
-					p.out_row[pos] = uint32_t(row);
-				}
-			}
-		}
-	}
-}
-
-// The exact tail of the int8 range forms (knn_range_i8 / knn_range_i8_subset in knn_scan_i8.hip): knn_range_subset over the candidate rows,
-// their number read on the device.  More candidates than the list holds (or no finite bound: the query prep left ccap + 1): nothing is done,
-// the host launches the f32 kernel.  The distance is knn_range's (the same two functions over the same query), so are the test and the
-// counter protocol: p.counter counts every hit, the first p.cap are written.
-template <int kMetric>
-__global__ __launch_bounds__(kScanThreads) void knn_range_rescore(RangeParams p, const uint32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ cand_row,
-																   uint32_t ccap) {
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 15, g = lane >> 4;
-	const uint32_t have = *cand_cnt;
-	if (have > ccap || have == 0) return;
-	const uint64_t n = have;
-	const uint64_t nquads = (n + kRowsPerWave - 1) / kRowsPerWave;
-	const uint64_t nwaves = uint64_t(gridDim.x) * kScanWaves;
-	for (uint64_t quad = uint64_t(blockIdx.x) * kScanWaves + wave; quad < nquads; quad += nwaves) {
-		const uint64_t item = quad * kRowsPerWave + g;
-		const bool valid = item < n;
-		const uint64_t row = cand_row[valid ? item : n - 1];
-		const float sum = group_distance_generic<kMetric>(p.rows + row * p.stride, p.query, p.dim, m);
-		const float dist = metric_epilogue<kMetric>(sum, p.inv_norms, row);
-		const bool hit = valid && m == 0 && (p.inclusive ? dist <= p.radius : dist < p.radius);
-		const uint64_t hm = __ballot(hit);
-		if (hm) {
-			unsigned long long basePos = 0;
-			if (lane == 0) basePos = atomicAdd(p.counter, (unsigned long long)__popcll(hm));
-			basePos = __shfl(basePos, 0);
-			if (hit) {
-				const uint64_t pos = basePos + __popcll(hm & ((1ull << lane) - 1));
-				if (pos < p.cap) {
-					p.out_dist[pos] = dist;
-					p.out_row[pos] = uint32_t(row);
-				}
-			}
-		}
-	}
-}
-
-// DistCalculator::operator()(q,row,id) for an explicit row list: one 16-lane group per row.
-template <int kMetric>
-__global__ __launch_bounds__(256) void knn_distances(const float* rows, const float* inv_norms, const float* query, uint32_t stride,
-													uint32_t dim, const uint32_t* ids, uint32_t n, float* out) {
-	const int lane = threadIdx.x & 63, m = lane & 15;
-	const uint32_t item = blockIdx.x * (256u / kGroup) + (threadIdx.x >> 4);   // 16 rows a block: no 32-bit thread-index product (n up to 2^32 - 1)
-	const uint32_t itemc = item < n ? item : n - 1;
-	const uint64_t row = ids[itemc];
-	const float sum = group_distance_generic<kMetric>(rows + row * stride, query, dim, m);
-	const float dist = metric_epilogue<kMetric>(sum, inv_norms, row);
-	if (item < n && m == 0) out[item] = dist;
-}
-
 // ------------------------------------------------------------------------------------------ launchers
 
 // Tuning knobs (read once): RXGPU_SCAN_QLDS, RXGPU_SCAN_PREFETCH, RXGPU_SCAN_NT, RXGPU_SCAN_WG_PER_CU.
@@ -1404,108 +619,6 @@ void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t
 		case kL2: launch_scan_bf16_metric<kL2>(p, grid, s); break;
 		case kIP: launch_scan_bf16_metric<kIP>(p, grid, s); break;
 		default: launch_scan_bf16_metric<kCos>(p, grid, s); break;
-	}
-}
-void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
-						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s, const uint32_t* ids) {
-	const uint32_t gx = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, uint64_t(cus) * 8)));
-	hipLaunchKernelGGL(knn_filter_approx, dim3(gx, nq), dim3(256), 0, s, approx, n, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap, ids);
-}
-
-void launch_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count, uint32_t kk,
-						   const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s) {
-	const uint32_t gx = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(plan.nwaves, uint64_t(cus) * 8)));
-	hipLaunchKernelGGL(knn_filter_emitted, dim3(gx, nq), dim3(256), 0, s, emit, emit_cnt, plan, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap);
-}
-
-void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
-				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s) {
-	if (kk > uint32_t(kMaxFusedK)) {   // 64 < kk <= 128: never gated (the batched / pruned paths keep kk <= 64)
-		hipLaunchKernelGGL(knn_merge_wide, dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, total_per_query, kk, out_dist, out_row, out_count);
-		return;
-	}
-	hipLaunchKernelGGL(knn_merge, dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, total_per_query, kk, out_dist, out_row, out_count,
-					   gate_cnt, gate_cap);
-}
-
-// the partial results are SORTED lists of kk entries (nlists per query): knn_merge_lists
-void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
-						uint32_t* out_count, hipStream_t s, const uint32_t* gate_cnt, uint32_t gate_cap, uint32_t* path) {
-	if (kk > uint32_t(kMaxFusedK)) {
-		hipLaunchKernelGGL((knn_merge_lists<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
-						   gate_cnt, gate_cap, path);
-	} else {
-		hipLaunchKernelGGL((knn_merge_lists<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, part_dist, part_row, nlists, kk, out_dist, out_row, out_count,
-						   gate_cnt, gate_cap, path);
-	}
-}
-
-// the end of a pruned chain: the candidates (cand_cnt <= cap) or the exact scan's nlists sorted lists (knn_merge_final)
-void launch_merge_final(const float* cand_dist, const uint32_t* cand_row, const uint32_t* cand_cnt, uint32_t cap, const float* part_dist,
-						const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row, uint32_t* out_count,
-						hipStream_t s, uint32_t* path) {
-	if (kk > uint32_t(kMaxFusedK)) {   // (the pruned chains keep kk <= 64: the candidate branch holds one entry per lane)
-		hipLaunchKernelGGL((knn_merge_final<WaveTopK2>), dim3(nq), dim3(kMergeThreads), 0, s, cand_dist, cand_row, cand_cnt, cap, part_dist, part_row, nlists, kk,
-						   out_dist, out_row, out_count, path);
-	} else {
-		hipLaunchKernelGGL((knn_merge_final<WaveTopK>), dim3(nq), dim3(kMergeThreads), 0, s, cand_dist, cand_row, cand_cnt, cap, part_dist, part_row, nlists, kk,
-						   out_dist, out_row, out_count, path);
-	}
-}
-
-void launch_merge_shards(const uint32_t* gathered, uint32_t world, uint32_t nq, uint32_t kk, uint32_t shard_rows, float* out_dist,
-						 uint32_t* out_row, uint32_t* out_count, hipStream_t s, const uint32_t* slot_base, bool sorted) {
-	hipLaunchKernelGGL(knn_merge_shards, dim3(nq), dim3(64), 0, s, gathered, world, nq, kk, shard_rows, slot_base, out_dist, out_row, out_count, sorted ? 1u : 0u);
-}
-
-void launch_pack_lists(const float* dist, const uint32_t* row, const uint32_t* count, uint32_t nq, uint32_t k, uint32_t kk, uint32_t* dst_dist, uint32_t* dst_row,
-					   hipStream_t s) {
-	const uint32_t total = nq * kk;
-	if (!total) return;
-	hipLaunchKernelGGL(knn_pack_lists, dim3((total + 255) / 256), dim3(256), 0, s, dist, row, count, nq, k, kk, dst_dist, dst_row);
-}
-
-void launch_range(int metric, const float* rows, const float* inv_norms, const float* query, uint64_t n, uint32_t stride, uint32_t dim,
-				  float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap, unsigned long long* counter,
-				  uint32_t gridx, hipStream_t s) {
-	RangeParams p{rows, inv_norms, query, n, stride, dim, radius, inclusive, out_dist, out_row, cap, counter};
-	switch (metric) {
-		case kL2: hipLaunchKernelGGL((knn_range<kL2>), dim3(gridx), dim3(kScanThreads), 0, s, p); break;
-		case kIP: hipLaunchKernelGGL((knn_range<kIP>), dim3(gridx), dim3(kScanThreads), 0, s, p); break;
-		default: hipLaunchKernelGGL((knn_range<kCos>), dim3(gridx), dim3(kScanThreads), 0, s, p); break;
-	}
-}
-
-void launch_range_subset(int metric, const float* rows, const float* inv_norms, const float* query, const uint32_t* ids, uint64_t n_ids,
-						 uint32_t stride, uint32_t dim, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
-						 unsigned long long* counter, uint32_t gridx, hipStream_t s) {
-	RangeParams p{rows, inv_norms, query, n_ids, stride, dim, radius, inclusive, out_dist, out_row, cap, counter};
-	switch (metric) {
-		case kL2: hipLaunchKernelGGL((knn_range_subset<kL2>), dim3(gridx), dim3(kScanThreads), 0, s, p, ids); break;
-		case kIP: hipLaunchKernelGGL((knn_range_subset<kIP>), dim3(gridx), dim3(kScanThreads), 0, s, p, ids); break;
-		default: hipLaunchKernelGGL((knn_range_subset<kCos>), dim3(gridx), dim3(kScanThreads), 0, s, p, ids); break;
-	}
-}
-
-// cand_cnt / cand_row / ccap: what knn_range_i8 left; the grid covers ccap candidates
-void launch_range_rescore(int metric, const float* rows, const float* inv_norms, const float* query, const uint32_t* cand_cnt, const uint32_t* cand_row,
-						  uint32_t ccap, uint32_t stride, uint32_t dim, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
-						  unsigned long long* counter, uint32_t gridx, hipStream_t s) {
-	RangeParams p{rows, inv_norms, query, 0, stride, dim, radius, inclusive, out_dist, out_row, cap, counter};
-	switch (metric) {
-		case kL2: hipLaunchKernelGGL((knn_range_rescore<kL2>), dim3(gridx), dim3(kScanThreads), 0, s, p, cand_cnt, cand_row, ccap); break;
-		case kIP: hipLaunchKernelGGL((knn_range_rescore<kIP>), dim3(gridx), dim3(kScanThreads), 0, s, p, cand_cnt, cand_row, ccap); break;
-		default: hipLaunchKernelGGL((knn_range_rescore<kCos>), dim3(gridx), dim3(kScanThreads), 0, s, p, cand_cnt, cand_row, ccap); break;
-	}
-}
-
-void launch_distances(int metric, const float* rows, const float* inv_norms, const float* query, uint32_t stride, uint32_t dim,
-					  const uint32_t* ids, uint32_t n, float* out, hipStream_t s) {
-	const uint32_t blocks = uint32_t((uint64_t(n) * kGroup + 255) / 256);   // 64-bit product: n * 16 wraps from 2^28 rows on
-	switch (metric) {
-		case kL2: hipLaunchKernelGGL((knn_distances<kL2>), dim3(blocks), dim3(256), 0, s, rows, inv_norms, query, stride, dim, ids, n, out); break;
-		case kIP: hipLaunchKernelGGL((knn_distances<kIP>), dim3(blocks), dim3(256), 0, s, rows, inv_norms, query, stride, dim, ids, n, out); break;
-		default: hipLaunchKernelGGL((knn_distances<kCos>), dim3(blocks), dim3(256), 0, s, rows, inv_norms, query, stride, dim, ids, n, out); break;
 	}
 }
 

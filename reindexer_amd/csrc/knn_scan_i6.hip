@@ -6,7 +6,7 @@
 //   2. knn_merge_lists     -> T_seed, the kk-th smallest up_r of the sample (+inf with fewer than kk sampled rows)
 //   3. knn_scan_i6         every row: S_r from the 6-bit shadow, the window [lo_r, up_r] of i8_bounds, up_r into the per-wave top-kk; {lo_r, r}
 //                          is emitted when lo_r <= min(thr of the wavefront, T_seed) + margin
-//   4. knn_merge_lists -> T, knn_filter_emitted_wide (below: knn_filter_emitted's test with one atomic per workgroup), knn_rescore, the gated
+//   4. knn_merge_lists -> T, knn_filter_emitted_wide (knn_filter.hip: knn_filter_emitted's test with one atomic per workgroup), knn_rescore, the gated
 //      exact scan, knn_merge_final: as behind knn_scan_i8
 // Why the seed: with 6-bit codes the per-row window is four times as wide as the int8 one, and a wavefront's own running threshold stays loose
 // for so long that it would emit in nearly every step; a store per step costs the scan its bandwidth.  T_seed is tight from the first row.
@@ -193,61 +193,6 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i6(ScanI6Params p, Scan
 	block_merge_and_store(top, p.sp, lane, wave);
 }
 
-// knn_filter_emitted (knn_scan.hip) for a front that leaves thousands of candidates: the same early return, threshold and test, so the same
-// candidate SET (their order in the list differs; nothing reads it as ordered).  That kernel reserves list positions with one atomic per
-// wavefront and chunk of 64 entries that has a candidate; with 4 % of the emitted entries passing nearly every chunk has one, and 6 000
-// atomics on one word are 60 us at 10M rows.  Here a workgroup strides over the segments twice: it counts what passes, reserves its positions
-// with ONE atomic, and writes on the second walk (the entries are in the cache by then).  A wavefront takes the same 64 entries of every
-// chunk in both walks, so its positions follow from the four wavefront counts alone.
-__global__ __launch_bounds__(256) void knn_filter_emitted_wide(const EmitEntry* emit, const uint32_t* emit_cnt, EmitPlan plan, const float* top_dist,
-																const uint32_t* top_count, uint32_t kk, const float* margin, uint32_t* cand_row,
-																uint32_t* cand_cnt, uint32_t cap) {
-	__shared__ uint32_t s_cnt[4];
-	__shared__ uint32_t s_base;
-	const uint32_t qi = blockIdx.y;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	if (!(margin[qi] < __builtin_inff())) return;   // no bound for this query: nothing was emitted, the exact scan answers it
-	const float thr = (top_count[qi] >= kk ? top_dist[size_t(qi) * kk + kk - 1] : __builtin_inff()) + margin[qi];
-	const EmitEntry* all = emit + size_t(qi) * plan.n;
-	const uint32_t* counts = emit_cnt + size_t(qi) * plan.nwaves;
-	uint32_t mine = 0, at0 = 0;   // wave-uniform: what this wavefront's entries pass; the list position of its next candidate
-	for (int walk = 0; walk < 2; ++walk) {
-		for (uint64_t w = blockIdx.x; w < plan.nwaves; w += gridDim.x) {
-			const uint64_t room = emit_rows_of(plan, w);
-			uint64_t cnt = counts[w];
-			cnt = cnt < room ? cnt : room;   // (a count is never above its segment; nothing may read past it whatever the buffer holds)
-			const EmitEntry* seg = all + emit_segment_offset(plan, w);
-			for (uint64_t base = uint64_t(wave) * 64; base < cnt; base += 256) {
-				const uint64_t at = base + lane;
-				EmitEntry ent;
-				ent.lo = __builtin_inff();
-				ent.row = kInvalidRow;
-				if (at < cnt) ent = seg[at];
-				const bool pass = at < cnt && ent.lo <= thr;
-				const uint64_t pm = __ballot(pass);
-				if (walk == 0) {
-					mine += uint32_t(__popcll(pm));
-				} else {
-					const uint32_t pos = at0 + uint32_t(__popcll(pm & ((1ull << lane) - 1)));
-					if (pass && pos < cap) cand_row[size_t(qi) * cap + pos] = ent.row;
-					at0 += uint32_t(__popcll(pm));
-				}
-			}
-		}
-		if (walk == 0) {
-			if (lane == 0) s_cnt[wave] = mine;
-			__syncthreads();
-			if (threadIdx.x == 0) {
-				const uint32_t total = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-				s_base = total ? atomicAdd(&cand_cnt[qi], total) : 0u;
-			}
-			__syncthreads();
-			at0 = s_base;
-			for (int v = 0; v < wave; ++v) at0 += s_cnt[v];
-		}
-	}
-}
-
 // ---- the shadow: tiles (knn_i6_quant.h) and the side pair {s_r, e_r} per row, from the f32 rows.  knn_i8_build's shape: one 16-lane group per
 // row, lane m quantises the 16-element chunks m, m + 16, ... (read twice: the scale first) and stores its three words of each; the residual is an
 // fp64 sum over the codes as stored.  Rows first_row ... first_row + n - 1; every pointer at row 0 of the index.  Folds max e^2 into stats6[0], max
@@ -366,12 +311,6 @@ void launch_i6_build(const float* rows, const float* inv_norms, uint64_t first_r
 
 void launch_i6_copy_row(uint8_t* codes, uint32_t ld6, uint64_t from, uint64_t to, hipStream_t s) {
 	hipLaunchKernelGGL(knn_i6_copy_row, dim3(1), dim3(64), 0, s, codes, ld6, from, to);
-}
-
-void launch_filter_emitted_wide(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count,
-								uint32_t kk, const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s) {
-	const uint32_t gx = uint32_t(std::max<uint64_t>(1, std::min<uint64_t>(plan.nwaves, uint64_t(cus))));
-	hipLaunchKernelGGL(knn_filter_emitted_wide, dim3(gx, nq), dim3(256), 0, s, emit, emit_cnt, plan, top_dist, top_count, kk, margin, cand_row, cand_cnt, cap);
 }
 
 // The sample of the seed pass: the first set of every scan_i6_seed_step(n) sets, at most kI6SeedSets of them (65 536 rows).

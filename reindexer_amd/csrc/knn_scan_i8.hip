@@ -313,7 +313,7 @@ __global__ __launch_bounds__(kScanThreads) void knn_scan_i8_subset(ScanI8Params 
 // ---- the range forms (BruteforceSearch::SearchRange from the shadow; enqueue_range_pruned_i8 in rxgpu_knn_chains.hip): one query, no top lists.
 // A row can be a hit of the exact kernels only if lo_r <= i8_range_bound(radius, margin) (knn_i8_quant.h); those rows are compacted into
 // c.cand_row the way knn_range compacts its hits (ballot, one atomicAdd per wavefront step that has any, prefix popcount), and
-// knn_range_rescore (knn_scan.hip) holds them against the radius with the exact distance.  The counter counts past c.ccap: the host then
+// knn_range_rescore (knn_range.hip) holds them against the radius with the exact distance.  The counter counts past c.ccap: the host then
 // hands the call to the f32 kernel.  Lane mapping, loads, double buffer and butterfly are knn_scan_i8's, kept apart from it (that kernel is
 // the headline's and stays as measured); what is gone is everything the top lists needed.
 template <int kMetric, int NC8>

@@ -17,12 +17,18 @@ namespace rxgpu {
 
 struct ScanParams;
 
+// ---- knn_scan.hip: the streaming f32 scans (every row; a row list) and the bf16 scan over the shadow
 uint32_t scan_grid_x(uint64_t n, int cus);
 void launch_scan(int metric, const ScanParams& p, uint32_t nq, uint32_t gridx, hipStream_t s);
 struct ScanBf16Params;
 bool scan_bf16_supported(uint32_t ld);
 uint32_t scan_bf16_grid_x(uint64_t n, int cus);
 void launch_scan_bf16(int metric, const ScanBf16Params& p, uint32_t nq, uint32_t gridx, hipStream_t s);
+// pre-filtered search: knn_scan_subset over a strictly increasing row list (knn_subset.hip below makes one from a bitmap)
+uint32_t subset_grid_x(uint64_t n_ids, uint32_t dim, uint32_t kk, int cus);
+void launch_scan_subset(int metric, const ScanParams& p, const uint32_t* ids, uint32_t nq, uint32_t gridx, int cus, hipStream_t s);
+
+// ---- knn_scan_i8.hip, knn_scan_i6.hip: the pruning scans over the int8 and 6-bit shadows
 struct ScanI8Params;   // int8-pruned scan (knn_scan_i8.hip; the query side: knn_query_prep_i8 in knn_batched.hip)
 uint32_t scan_i8_grid_x(uint64_t n, int cus);
 struct ScanI8Emit;     // its emitting form (knn_emit_plan.h): null = lo of every row into p.lower and nothing emitted; keep: p.lower is written as well
@@ -43,6 +49,12 @@ void launch_scan_i6(int metric, const ScanI6Params& p, uint32_t nq, uint32_t gri
 void launch_i6_build(const float* rows, const float* inv_norms, uint64_t first_row, uint64_t n, uint32_t stride, uint32_t dim, uint8_t* codes, float2* side,
 					 uint32_t ld6, unsigned int* stats6, int cus, hipStream_t s);   // every pointer at row 0 of the index
 void launch_i6_copy_row(uint8_t* codes, uint32_t ld6, uint64_t from, uint64_t to, hipStream_t s);   // from == ~0: zeros over row `to`
+// range search from the int8 shadow, one query: the pruning scan (ids null = every row, else p.sp.n list entries); its exact tail over the
+// candidates it left is launch_range_rescore (knn_range.hip)
+struct RangeI8Cand;
+void launch_range_i8(int metric, const ScanI8Params& p, const RangeI8Cand& c, const uint32_t* ids, int cus, hipStream_t s);
+
+// ---- knn_filter.hip: the candidate filters of the pruned chains, one threshold (top_dist[kk - 1] + margin; a query without a finite margin is left alone)
 void launch_filter_approx(const float* approx, uint64_t n, const float* top_dist, const uint32_t* top_count, uint32_t kk, const float* margin,
 						  uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus, hipStream_t s,
 						  const uint32_t* ids = nullptr);   // ids: approx is indexed by list position and the candidates are ids[position]
@@ -53,7 +65,11 @@ void launch_filter_emitted(const EmitEntry* emit, const uint32_t* emit_cnt, cons
 						   hipStream_t s);   // launch_filter_approx over what knn_scan_i8 emitted
 void launch_filter_emitted_wide(const EmitEntry* emit, const uint32_t* emit_cnt, const EmitPlan& plan, const float* top_dist, const uint32_t* top_count,
 								uint32_t kk, const float* margin, uint32_t* cand_row, uint32_t* cand_cnt, uint32_t cap, uint32_t nq, int cus,
-								hipStream_t s);   // the same candidate set with one atomic per workgroup (knn_scan_i6.hip): for thousands of candidates
+								hipStream_t s);   // the same candidate set with one atomic per workgroup: for the thousands of candidates behind knn_scan_i6
+
+// ---- knn_merge.hip: the top-k merges
+// the insertion merge over total_per_query unsorted pairs.  Precondition: kk <= kMaxFusedK (the batched tail is reached with no more,
+// rxgpu_knn_merge_probe refuses more); sorted lists of any kk <= kMaxFusedK2 go through launch_merge_lists
 void launch_merge(const float* part_dist, const uint32_t* part_row, uint32_t total_per_query, uint32_t kk, uint32_t nq, float* out_dist,
 				  uint32_t* out_row, uint32_t* out_count, const uint32_t* gate_cnt, uint32_t gate_cap, hipStream_t s);
 void launch_merge_lists(const float* part_dist, const uint32_t* part_row, uint32_t nlists, uint32_t kk, uint32_t nq, float* out_dist, uint32_t* out_row,
@@ -69,6 +85,8 @@ void launch_merge_shards(const uint32_t* gathered, uint32_t world, uint32_t nq, 
 // one shard's HNSW result (unordered, counts <= k) into its [nq][kk] | [nq][kk] slot of the exchange's send buffer, padded with invalid entries
 void launch_pack_lists(const float* dist, const uint32_t* row, const uint32_t* count, uint32_t nq, uint32_t k, uint32_t kk, uint32_t* dst_dist, uint32_t* dst_row,
 					   hipStream_t s);
+
+// ---- knn_range.hip: range search and explicit-row distances over the f32 rows (one body for the three range forms)
 void launch_range(int metric, const float* rows, const float* inv_norms, const float* query, uint64_t n, uint32_t stride, uint32_t dim,
 				  float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap, unsigned long long* counter,
 				  uint32_t gridx, hipStream_t s);
@@ -77,17 +95,12 @@ void launch_range_subset(int metric, const float* rows, const float* inv_norms, 
 						 unsigned long long* counter, uint32_t gridx, hipStream_t s);
 void launch_distances(int metric, const float* rows, const float* inv_norms, const float* query, uint32_t stride, uint32_t dim,
 					  const uint32_t* ids, uint32_t n, float* out, hipStream_t s);
-// range search from the int8 shadow, one query: the pruning scan (knn_scan_i8.hip; ids null = every row, else p.sp.n list entries) and its exact
-// tail over the candidates it left (knn_scan.hip), which does nothing when there are more than ccap
-struct RangeI8Cand;
-void launch_range_i8(int metric, const ScanI8Params& p, const RangeI8Cand& c, const uint32_t* ids, int cus, hipStream_t s);
+// the exact tail of launch_range_i8 over the candidates it left: does nothing when there are more than ccap (or none)
 void launch_range_rescore(int metric, const float* rows, const float* inv_norms, const float* query, const uint32_t* cand_cnt, const uint32_t* cand_row,
 						  uint32_t ccap, uint32_t stride, uint32_t dim, float radius, int inclusive, float* out_dist, uint32_t* out_row, uint64_t cap,
 						  unsigned long long* counter, uint32_t gridx, hipStream_t s);
 
-// Pre-filtered search (knn_scan.hip: knn_scan_subset; knn_subset.hip: bitmap -> row list)
-uint32_t subset_grid_x(uint64_t n_ids, uint32_t dim, uint32_t kk, int cus);
-void launch_scan_subset(int metric, const ScanParams& p, const uint32_t* ids, uint32_t nq, uint32_t gridx, int cus, hipStream_t s);
+// ---- knn_subset.hip: pre-filtered search, bitmap -> the row list launch_scan_subset walks
 uint32_t bitmap_tiles(uint64_t n_rows);
 void launch_bitmap_count(const uint32_t* words, uint64_t n_rows, uint32_t* tile_scratch, unsigned long long* total, hipStream_t s);
 void launch_bitmap_expand(const uint32_t* words, uint64_t n_rows, const uint32_t* tile_scratch, uint32_t* out_rows, uint64_t cap, hipStream_t s);

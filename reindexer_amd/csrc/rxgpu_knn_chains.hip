@@ -256,7 +256,7 @@ int enqueue_knn_batched(rxgpu_index* h, rxgpu_search_ctx* c, const float* d_quer
 }
 
 // ---- which scan a call takes ----------------------------------------------------------------------------------------
-// bf16-pruned scan for one .. a few queries: 2 bytes per element from HBM instead of 4, exact result (knn_scan.hip).
+// bf16-pruned scan for one .. a few queries: 2 bytes per element from HBM instead of 4, exact result (the chain: header of knn_scan_bf16 in knn_scan.hip; its filter and merges: knn_filter.hip, knn_merge.hip).
 // RXGPU_SCAN_BF16, read per call (a process can switch it for A/B runs): 1 = forced on (up to kPrunedMaxQueries queries, any size), 0 = forced
 // off (the f32 paths, always), unset = automatic: single queries on indexes of at least kPrunedAutoMinBytes of f32 rows.
 enum ScanBf16Mode { kScanBf16Off = 0, kScanBf16On = 1, kScanBf16Auto = 2 };

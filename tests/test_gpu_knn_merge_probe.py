@@ -1,4 +1,4 @@
-"""-m gpu: the merge kernels of the single-query KNN chains on their own, through rxgpu_knn_merge_probe (reindexer_amd/csrc/knn_scan.hip):
+"""-m gpu: the merge kernels of the single-query KNN chains on their own, through rxgpu_knn_merge_probe (reindexer_amd/csrc/knn_merge.hip):
 knn_merge_lists over sorted lists, the candidate branch of knn_merge_final over unsorted pairs, and the insertion fold over the same pairs.
 
 Expected result, in numpy: the valid pairs ordered by (distance with -0.0 -> +0.0, row), the first kk, padded with +inf / 0xFFFFFFFF; distances

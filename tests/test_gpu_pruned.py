@@ -1,4 +1,4 @@
-"""-m gpu: the opt-in bf16-pruned scan (RXGPU_SCAN_BF16=1; knn_scan_bf16 + knn_filter_approx in knn_scan.hip): approximate distances from the
+"""-m gpu: the opt-in bf16-pruned scan (RXGPU_SCAN_BF16=1; knn_scan_bf16 in knn_scan.hip, knn_filter_approx in knn_filter.hip): approximate distances from the
 bf16 shadow prune the corpus under a rigorous bound, the exact kernels re-score the survivors.  The contract does not move: identical rows
 and distance bits to the exact f32 scan / the reference."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""-m gpu: range searches served from the int8 shadow (knn_range_i8 / knn_range_i8_subset in knn_scan_i8.hip, knn_range_rescore in knn_scan.hip,
+"""-m gpu: range searches served from the int8 shadow (knn_range_i8 / knn_range_i8_subset in knn_scan_i8.hip, knn_range_rescore in knn_range.hip,
 enqueue_range_pruned_i8 / range_on_device on the host; the bound is i8_range_bound in knn_i8_quant.h).
 
 The yardstick of every comparison is THE SAME BUILD with RXGPU_SCAN_BF16=0, the f32 range kernels that test_gpu_bruteforce.py and

@@ -1,5 +1,5 @@
 """-m gpu: the emitting form of the int8-pruned scan (knn_scan_i8<.., kEmit>), knn_filter_emitted behind it and knn_merge_final at the end
-of every pruned chain.
+of every pruned chain (knn_scan_i8.hip, knn_filter.hip, knn_merge.hip).
 
 While it scans, a wavefront emits the rows whose lower bound lo is within the margin of thr_d, the kk-th smallest upper bound it has seen
 so far (+inf until it has seen kk): a superset of what the filter keeps, which is then held against the final T.  The shapes are those of

@@ -1,5 +1,5 @@
 """CPU: build-time resource check of the single-workgroup kernels around the pruned single-query scan: knn_merge_lists and knn_merge_final
-(reindexer_amd/csrc/knn_scan.hip) and knn_query_prep_i8 (knn_batched.hip).
+(reindexer_amd/csrc/knn_merge.hip) and knn_query_prep_i8 (knn_batched.hip); and of the range and distance kernels of knn_range.hip.
 
 As tests/test_range_i8_resources.py: hipcc cross-compiles gfx950 without a GPU and `-Rpass-analysis=kernel-resource-usage` prints what the code
 object header will say.  These kernels are latency chains of one workgroup; a spill would put scratch round trips into them.  Every
@@ -25,7 +25,7 @@ def instantiations(usage: dict, kernel: str) -> dict:
 
 @pytest.mark.skipif(not Path(HIPCC).exists(), reason="needs hipcc")
 def test_merge_kernels_stay_in_registers_and_in_their_lds(tmp_path):
-    usage = resource_usage(CSRC / "knn_scan.hip", tmp_path)
+    usage = resource_usage(CSRC / "knn_merge.hip", tmp_path)
     for kernel in ("knn_merge_lists", "knn_merge_final"):
         found = instantiations(usage, kernel)
         assert len(found) == 2, (kernel, sorted(found))   # WaveTopK, WaveTopK2
@@ -42,3 +42,15 @@ def test_query_prep_i8_stays_in_registers(tmp_path):
     for name, u in found.items():
         print(f"{name}: {u['VGPRs']} VGPRs")
         assert u["VGPRs Spill"] == 0 and u["ScratchSize"] == 0, (name, u)
+
+
+@pytest.mark.skipif(not Path(HIPCC).exists(), reason="needs hipcc")
+def test_range_kernels_stay_in_registers(tmp_path):
+    """The three range kernels are one body (range_body) with the row lookup passed in: no form of it may cost a spill or scratch."""
+    usage = resource_usage(CSRC / "knn_range.hip", tmp_path)
+    for kernel in ("knn_range", "knn_range_subset", "knn_range_rescore", "knn_distances"):
+        found = instantiations(usage, kernel)
+        assert len(found) == 3, (kernel, sorted(found))   # L2, IP, cosine
+        for name, u in found.items():
+            print(f"{name}: {u['VGPRs']} VGPRs")
+            assert u["VGPRs Spill"] == 0 and u["ScratchSize"] == 0, (name, u)
