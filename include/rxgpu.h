@@ -453,10 +453,15 @@ int rxgpu_hnsw_search_knn(rxgpu_index* h, const float* queries, uint32_t nq, uin
  * *served = 1: out_* hold what rxgpu_hnsw_search_knn returns for this query (the same device code runs the search).  *served = 0: this query
  * is not taken — every slot (RXGPU_HNSW_SERVER_SLOTS, 256) is busy, ef > 256 (224 on a graph with deleted nodes; up to 128 / 96 and above
  * that are served by two resident kernels of their own), a dimension other than
- * 128 / 512 / 768, a profiled or sharded index, RXGPU_HNSW_SERVER=0, or the search needs the re-run tiers — and the caller uses
+ * 128 / 512 / 768 / 1024 / 1536 (rxgpu_hnsw_distance_blocks names them), a profiled or sharded index, RXGPU_HNSW_SERVER=0, or the search needs the re-run tiers — and the caller uses
  * rxgpu_hnsw_search_knn, which tries the mailbox itself for nq == 1 and launches otherwise. */
 int rxgpu_hnsw_search_knn_posted(rxgpu_index* h, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count,
 								 int32_t* served);
+/* 64-float blocks of the fixed-dimension distance batch a search over rows of `dim` components takes (0: the generic batch).
+ * sq8: over codes; deleted: the graph has deleted nodes.  *mailbox (may be NULL): 1 when the resident kernel serves that row format.
+ * A pure function (no device is touched).  Floats: 128, 512, 768, 1024, 1536 -> dim / 64, mailbox 1, with or without deleted nodes; every
+ * other size (384 among them) 0 / 0.  Codes: 128, 384, 512, 768, 1024, 1536 on a graph without deleted nodes, 128 and 768 with them. */
+int rxgpu_hnsw_distance_blocks(uint32_t dim, int sq8, int deleted, int* mailbox);
 /* The search kernels' own counters since the last read (reset by the call, like rxgpu_hnsw_read_stats): out4[0] = distance evaluations the
  * traversal used, [1] = hops, [2] = searches that started over on the reference's heaps inside the kernel, [3] = two 32-bit counts of the team
  * searches (small launches and the resident kernel): high half = hops that found their link block in LDS because it had come along with the

@@ -90,6 +90,7 @@ _SIGNATURES = {
     "rxgpu_hnsw_patch_graph": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, C.c_int32, _u32, _u64]),
     "rxgpu_hnsw_search_knn": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "rxgpu_hnsw_search_knn_posted": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
+    "rxgpu_hnsw_distance_blocks": (_i, [_u32, _i, _i, C.POINTER(C.c_int)]),
     "rxgpu_hnsw_server_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rxgpu_hnsw_server_times": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rxgpu_hnsw_read_stats4": (_i, [_vp, _vp]),
@@ -250,6 +251,14 @@ def scan_tier_range(rows: int, dim: int, listed: bool = False, shadow_available:
     """rxgpu_scan_tier_range: 0 / 2 = a range call that scans `rows` rows (the index's, or the entries of a row list when `listed`) takes the
     f32 / int8-pruned range kernel under the current environment.  Touches no device."""
     return int(lib().rxgpu_scan_tier_range(rows, dim, int(listed), int(shadow_available), int(stats_finite)))
+
+
+def hnsw_distance_blocks(dim: int, sq8: bool = False, deleted: bool = False) -> tuple[int, bool]:
+    """rxgpu_hnsw_distance_blocks: (64-float blocks of the fixed-dimension distance batch a search over rows of `dim` components takes, 0 = the
+    generic batch; whether the resident kernel serves that row format).  Touches no device."""
+    mailbox = C.c_int(0)
+    blocks = int(lib().rxgpu_hnsw_distance_blocks(dim, int(sq8), int(deleted), C.byref(mailbox)))
+    return blocks, bool(mailbox.value)
 
 
 def scan_tier_subset(n_ids: int, dim: int, nq: int = 1, kk: int = 10, shadow_available: bool = True, stats_finite: bool = True) -> int:

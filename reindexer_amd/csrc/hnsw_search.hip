@@ -34,8 +34,10 @@ __global__ __launch_bounds__(64 * kTeam) void hnsw_team_kernel(HnswParams p) {
 	}
 }
 
+// (wavefronts per SIMD asked for: five of the D = 768 headline form, four of every throughput form over rows of 1024 and 1536 floats — the
+// chunked distance batch leaves the registers for it, and without the bound the allocation lands a few registers above 128)
 template <int kMetric, bool kGlobalCand, int NB, bool kLatency, bool kSq8 = false, int kSorted = 0, bool kDel = false>
-__global__ __launch_bounds__(64, (kSorted == 2 && !kDel && !kLatency && !kSq8 && NB == 12) ? 5 : 1) void hnsw_search_kernel(HnswParams p) {
+__global__ __launch_bounds__(64, (kSorted == 2 && !kDel && !kLatency && !kSq8 && NB == 12) ? 5 : (!kLatency && !kSq8 && NB > 12) ? 4 : 1) void hnsw_search_kernel(HnswParams p) {
 	const uint32_t slot = blockIdx.x;
 	hnsw_search_one<kMetric, kGlobalCand, NB, kLatency, kSq8, kSorted, kDel>(p, slot, p.only ? p.only[slot] : slot);
 	if (p.helper_n) {   // a batch with helper workgroups: this search has ended, and what it queued for them is visible
@@ -83,7 +85,8 @@ template <bool kGlobalCand, int NB, int kSorted = 0, bool kDel = false>
 static void launch_hnsw_nb(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
 	size_t lds = (size_t(p.ef_cap) + (kGlobalCand ? 0 : p.lds_cand_cap)) * 8 + size_t(NB) * 256;   // heaps + the query fragment (NB*16 float4)
 	constexpr bool kHasLatencyVariant = NB > 8;
-	const bool latency = kHasLatencyVariant && blocks <= 3072;   // no more searches than the chip holds of this form (3 per SIMD): spend registers on fewer round trips
+	// no more searches than the chip holds of this form (3 per SIMD; at 1536 floats the two row sets in flight leave one wavefront per SIMD): spend registers on fewer round trips
+	const bool latency = kHasLatencyVariant && blocks <= (NB > 16 ? 1024u : 3072u);
 	// a handful of searches (the Map's single queries and small coalesced batches): four wavefronts per search (hnsw_team_kernel)
 	if constexpr (!kGlobalCand && NB > 0 && kSorted > 0) {
 		if (p.team > 1 && blocks <= p.team_max) {
@@ -150,20 +153,24 @@ static void launch_hnsw_nb(int metric, const HnswParams& p, uint32_t blocks, hip
 
 template <int kSorted, bool kDel>
 static void launch_hnsw_sorted(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	switch (p.dim) {
-		case 128: launch_hnsw_nb<false, 2, kSorted, kDel>(metric, p, blocks, s); break;
-		case 512: launch_hnsw_nb<false, 8, kSorted, kDel>(metric, p, blocks, s); break;
-		case 768: launch_hnsw_nb<false, 12, kSorted, kDel>(metric, p, blocks, s); break;
+	switch (hnsw_distance_blocks(p.dim, false, kDel)) {   // (hnsw_distance_blocks.h: the one list of sizes)
+		case 2: launch_hnsw_nb<false, 2, kSorted, kDel>(metric, p, blocks, s); break;
+		case 8: launch_hnsw_nb<false, 8, kSorted, kDel>(metric, p, blocks, s); break;
+		case 12: launch_hnsw_nb<false, 12, kSorted, kDel>(metric, p, blocks, s); break;
+		case 16: launch_hnsw_nb<false, 16, kSorted, kDel>(metric, p, blocks, s); break;
+		case 24: launch_hnsw_nb<false, 24, kSorted, kDel>(metric, p, blocks, s); break;
 		default: launch_hnsw_nb<false, 0, kSorted, kDel>(metric, p, blocks, s); break;
 	}
 }
 
 template <bool kGlobalCand>
 static void launch_hnsw_mode(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	switch (p.dim) {
-		case 128: launch_hnsw_nb<kGlobalCand, 2>(metric, p, blocks, s); break;
-		case 512: launch_hnsw_nb<kGlobalCand, 8>(metric, p, blocks, s); break;
-		case 768: launch_hnsw_nb<kGlobalCand, 12>(metric, p, blocks, s); break;
+	switch (hnsw_distance_blocks(p.dim, false, false)) {   // (the heaps handle deleted nodes themselves: one list of sizes)
+		case 2: launch_hnsw_nb<kGlobalCand, 2>(metric, p, blocks, s); break;
+		case 8: launch_hnsw_nb<kGlobalCand, 8>(metric, p, blocks, s); break;
+		case 12: launch_hnsw_nb<kGlobalCand, 12>(metric, p, blocks, s); break;
+		case 16: launch_hnsw_nb<kGlobalCand, 16>(metric, p, blocks, s); break;
+		case 24: launch_hnsw_nb<kGlobalCand, 24>(metric, p, blocks, s); break;
 		default: launch_hnsw_nb<kGlobalCand, 0>(metric, p, blocks, s); break;
 	}
 }
@@ -181,19 +188,19 @@ static void launch_hnsw_sq8_nb(int metric, const HnswParams& p, uint32_t blocks,
 template <int kSorted, bool kDel>
 static void launch_hnsw_sq8_sorted(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
 	if constexpr (kDel) {   // graphs with deleted nodes: two embedding sizes get the 16-byte-load form, the rest the generic one
-		switch (p.dim) {
-			case 128: launch_hnsw_sq8_nb<false, 2, kSorted, true>(metric, p, blocks, s); break;
-			case 768: launch_hnsw_sq8_nb<false, 12, kSorted, true>(metric, p, blocks, s); break;
+		switch (hnsw_distance_blocks(p.dim, true, true)) {
+			case 2: launch_hnsw_sq8_nb<false, 2, kSorted, true>(metric, p, blocks, s); break;
+			case 12: launch_hnsw_sq8_nb<false, 12, kSorted, true>(metric, p, blocks, s); break;
 			default: launch_hnsw_sq8_nb<false, 0, kSorted, true>(metric, p, blocks, s); break;
 		}
 	} else {
-		switch (p.dim) {
-			case 128: launch_hnsw_sq8_nb<false, 2, kSorted>(metric, p, blocks, s); break;
-			case 384: launch_hnsw_sq8_nb<false, 6, kSorted>(metric, p, blocks, s); break;
-			case 512: launch_hnsw_sq8_nb<false, 8, kSorted>(metric, p, blocks, s); break;
-			case 768: launch_hnsw_sq8_nb<false, 12, kSorted>(metric, p, blocks, s); break;
-			case 1024: launch_hnsw_sq8_nb<false, 16, kSorted>(metric, p, blocks, s); break;
-			case 1536: launch_hnsw_sq8_nb<false, 24, kSorted>(metric, p, blocks, s); break;
+		switch (hnsw_distance_blocks(p.dim, true, false)) {
+			case 2: launch_hnsw_sq8_nb<false, 2, kSorted>(metric, p, blocks, s); break;
+			case 6: launch_hnsw_sq8_nb<false, 6, kSorted>(metric, p, blocks, s); break;
+			case 8: launch_hnsw_sq8_nb<false, 8, kSorted>(metric, p, blocks, s); break;
+			case 12: launch_hnsw_sq8_nb<false, 12, kSorted>(metric, p, blocks, s); break;
+			case 16: launch_hnsw_sq8_nb<false, 16, kSorted>(metric, p, blocks, s); break;
+			case 24: launch_hnsw_sq8_nb<false, 24, kSorted>(metric, p, blocks, s); break;
 			default: launch_hnsw_sq8_nb<false, 0, kSorted>(metric, p, blocks, s); break;
 		}
 	}
@@ -201,13 +208,13 @@ static void launch_hnsw_sq8_sorted(int metric, const HnswParams& p, uint32_t blo
 
 template <bool kGlobalCand>
 static void launch_hnsw_sq8(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	switch (p.dim) {   // the embedding sizes in use get the 16-byte-load form; any other dim the generic one
-		case 128: launch_hnsw_sq8_nb<kGlobalCand, 2>(metric, p, blocks, s); break;
-		case 384: launch_hnsw_sq8_nb<kGlobalCand, 6>(metric, p, blocks, s); break;
-		case 512: launch_hnsw_sq8_nb<kGlobalCand, 8>(metric, p, blocks, s); break;
-		case 768: launch_hnsw_sq8_nb<kGlobalCand, 12>(metric, p, blocks, s); break;
-		case 1024: launch_hnsw_sq8_nb<kGlobalCand, 16>(metric, p, blocks, s); break;
-		case 1536: launch_hnsw_sq8_nb<kGlobalCand, 24>(metric, p, blocks, s); break;
+	switch (hnsw_distance_blocks(p.dim, true, false)) {   // the embedding sizes in use get the 16-byte-load form; any other dim the generic one
+		case 2: launch_hnsw_sq8_nb<kGlobalCand, 2>(metric, p, blocks, s); break;
+		case 6: launch_hnsw_sq8_nb<kGlobalCand, 6>(metric, p, blocks, s); break;
+		case 8: launch_hnsw_sq8_nb<kGlobalCand, 8>(metric, p, blocks, s); break;
+		case 12: launch_hnsw_sq8_nb<kGlobalCand, 12>(metric, p, blocks, s); break;
+		case 16: launch_hnsw_sq8_nb<kGlobalCand, 16>(metric, p, blocks, s); break;
+		case 24: launch_hnsw_sq8_nb<kGlobalCand, 24>(metric, p, blocks, s); break;
 		default: launch_hnsw_sq8_nb<kGlobalCand, 0>(metric, p, blocks, s); break;
 	}
 }
@@ -265,16 +272,18 @@ static void launch_hnsw_helper_nb(int metric, const HnswParams& p, const HnswHel
 // heap, no `only` list, no overflow queue of their own
 void launch_hnsw_helper(int metric, const HnswParams& p, const HnswHelper& hq, uint32_t groups, hipStream_t s) {
 	if (p.codes) {
-		switch (p.dim) {
-			case 128: launch_hnsw_helper_nb<2, true>(metric, p, hq, groups, s); break;
-			case 768: launch_hnsw_helper_nb<12, true>(metric, p, hq, groups, s); break;
+		switch (hnsw_distance_blocks(p.dim, true, true)) {   // (the two sizes every SQ8 graph has a fixed form for)
+			case 2: launch_hnsw_helper_nb<2, true>(metric, p, hq, groups, s); break;
+			case 12: launch_hnsw_helper_nb<12, true>(metric, p, hq, groups, s); break;
 			default: launch_hnsw_helper_nb<0, true>(metric, p, hq, groups, s); break;
 		}
 		return;
 	}
-	switch (p.dim) {
-		case 128: launch_hnsw_helper_nb<2, false>(metric, p, hq, groups, s); break;
-		case 768: launch_hnsw_helper_nb<12, false>(metric, p, hq, groups, s); break;
+	switch (hnsw_distance_blocks(p.dim, false, false)) {   // (512 has no helper instantiation of its own: the generic batch, as before)
+		case 2: launch_hnsw_helper_nb<2, false>(metric, p, hq, groups, s); break;
+		case 12: launch_hnsw_helper_nb<12, false>(metric, p, hq, groups, s); break;
+		case 16: launch_hnsw_helper_nb<16, false>(metric, p, hq, groups, s); break;
+		case 24: launch_hnsw_helper_nb<24, false>(metric, p, hq, groups, s); break;
 		default: launch_hnsw_helper_nb<0, false>(metric, p, hq, groups, s); break;
 	}
 }

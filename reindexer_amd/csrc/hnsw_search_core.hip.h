@@ -544,6 +544,66 @@ __device__ __forceinline__ void batch_distances_fixed(const HnswParams& p, const
 	}
 }
 
+// dim == 64*NB, NB > 12 (1024 and 1536 floats): a whole row set of NB float4 a lane (96 VGPRs at NB = 24) does not fit beside the search's
+// own state, so the NB loads of a row are cut into chunks of kChunk and the loads of chunk c + 1 are issued before chunk c is reduced: two
+// chunks of a row set are in flight or in registers at any time.  The ONE accumulator runs through the chunks in block order —
+// acc = chain_step(acc, Q(t), x[t]) for t = 0 .. NB - 1, the sequence batch_distances_fixed and the generic batch compute — and is folded once.
+// The latency, team and resident forms (one or two wavefronts per SIMD anyway) take two row sets in chunks of 8: 128 VGPRs of rows, 2 and 3 chunks.
+// The throughput form takes one set in chunks of 4 (32 VGPRs of rows, 4 and 6 chunks): 87 - 99 VGPRs in all, where chunks of 8 came to
+// 131 - 141 and, held to 128 by __launch_bounds__, spilled.  The query fragment is always read from LDS.
+template <int kMetric, int NB, bool kTwoSets, int kChunk = 8>
+__device__ __forceinline__ void batch_distances_wide(const HnswParams& p, const float4* qlds, const uint32_t* ids, int cnt, float* dists, int lane) {
+	static_assert(NB > kChunk && NB % kChunk == 0, "whole chunks, at least two");
+	constexpr int kChunks = NB / kChunk;
+	const int m = lane & 15, g = lane >> 4;
+	for (int base = 0; base < cnt; base += (kTwoSets ? 2 : 1) * kRowsPerWave) {
+		const int ia = base + g, ib = base + kRowsPerWave + g;
+		const bool oka = ia < cnt, okb = ib < cnt;
+		const uint64_t ra = ids[oka ? ia : base], rb = ids[okb ? ib : base];
+		const float4* pa = reinterpret_cast<const float4*>(p.rows + ra * p.stride) + m;
+		const float4* pb = reinterpret_cast<const float4*>(p.rows + rb * p.stride) + m;
+		const bool second = kTwoSets && base + kRowsPerWave < cnt;   // wave-uniform
+		float4 xa[2][kChunk], xb[2][kChunk];
+#pragma unroll
+		for (int t = 0; t < kChunk; ++t) xa[0][t] = pa[16 * t];
+		if (second) {
+#pragma unroll
+			for (int t = 0; t < kChunk; ++t) xb[0][t] = pb[16 * t];
+		}
+		float inva = 1.0f, invb = 1.0f;   // cosine: 1 / |row| travels with the first chunk (see batch_distances_fixed)
+		if constexpr (kMetric == kCos) {
+			inva = p.inv_norms[ra];
+			if (second) invb = p.inv_norms[rb];
+		}
+		float4 acca = make_float4(0.f, 0.f, 0.f, 0.f), accb = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+		for (int c = 0; c < kChunks; ++c) {
+			if (c + 1 < kChunks) {   // the next chunk's loads go out before this chunk is reduced
+#pragma unroll
+				for (int t = 0; t < kChunk; ++t) xa[(c + 1) & 1][t] = pa[16 * (kChunk * (c + 1) + t)];
+				if (second) {
+#pragma unroll
+					for (int t = 0; t < kChunk; ++t) xb[(c + 1) & 1][t] = pb[16 * (kChunk * (c + 1) + t)];
+				}
+			}
+			__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+			for (int t = 0; t < kChunk; ++t) chain_step<kMetric>(acca, qlds[16 * (kChunk * c + t) + m], xa[c & 1][t]);
+			if (second) {
+#pragma unroll
+				for (int t = 0; t < kChunk; ++t) chain_step<kMetric>(accb, qlds[16 * (kChunk * c + t) + m], xb[c & 1][t]);
+			}
+			__builtin_amdgcn_sched_barrier(0);
+		}
+		const float da = 1.0f * metric_epilogue<kMetric>(fold_chains<false>(acca, nullptr, nullptr, 0, m) + 0.0f, &inva, 0);
+		if (oka && m == 0) dists[ia] = da;
+		if (second) {
+			const float db = 1.0f * metric_epilogue<kMetric>(fold_chains<false>(accb, nullptr, nullptr, 0, m) + 0.0f, &invb, 0);
+			if (okb && m == 0) dists[ib] = db;
+		}
+	}
+}
+
 // The node of the nearest entry that is not expanded yet (what pop() would return next if nothing nearer is inserted before), or
 // 0xFFFFFFFF: the search prefetches that node's link block while the current hop's distances are computed.
 template <typename List, int S>
@@ -765,8 +825,14 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 			__syncthreads();   // the whole team: the batch is posted (and everything the driver wrote to LDS before it is visible)
 			int b0, n0;
 			team_slice<kTeam>(cnt, 0, b0, n0);
-			batch_distances_fixed<kMetric, NB, kQLds, true>(p, qreg, q_s, ids + b0, n0, dists + b0, lane);
+			if constexpr (NB > 12) {
+				batch_distances_wide<kMetric, NB, true>(p, q_s, ids + b0, n0, dists + b0, lane);
+			} else {
+				batch_distances_fixed<kMetric, NB, kQLds, true>(p, qreg, q_s, ids + b0, n0, dists + b0, lane);
+			}
 			__syncthreads();   // ... every slice is written
+		} else if constexpr (NB > 12) {
+			batch_distances_wide<kMetric, NB, kLatency, (kLatency ? 8 : 4)>(p, q_s, ids, cnt, dists, lane);
 		} else if constexpr (NB > 0) {
 			batch_distances_fixed<kMetric, NB, kQLds, (kLatency || NB <= 8)>(p, qreg, q_s, ids, cnt, dists, lane);
 		} else {
@@ -1270,7 +1336,11 @@ __device__ __forceinline__ void hnsw_team_serve(const HnswParams& p, const HnswT
 				__builtin_amdgcn_global_load_lds(src, (hnsw_lds_void*)(nbl + 64 * j), 4, 0, 0);
 			}
 		}
-		if (n0 > 0) batch_distances_fixed<kMetric, NB, true, true>(p, qreg, q_s, box->ids + b0, n0, box->dists + b0, lane);
+		if constexpr (NB > 12) {
+			if (n0 > 0) batch_distances_wide<kMetric, NB, true>(p, q_s, box->ids + b0, n0, box->dists + b0, lane);
+		} else {
+			if (n0 > 0) batch_distances_fixed<kMetric, NB, true, true>(p, qreg, q_s, box->ids + b0, n0, box->dists + b0, lane);
+		}
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (a wavefront without rows of its own still has blocks in flight)
 		__syncthreads();
 	}

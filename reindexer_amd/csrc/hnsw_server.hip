@@ -15,8 +15,9 @@ namespace rxgpu {
 //     poll in device memory.  No wait in here depends on another kernel or on the host making progress;
 //   * the next generation is an ordinary launch on the SAME stream: it starts when this one is gone, so a slot has one server at a time and
 //     a request posted while a generation leaves is simply the next one's first.
-// Two kernels speak this protocol: hnsw_server_kernel (float rows, a team of four wavefronts a slot) and hnsw_server_sq8_kernel (SQ8 codes,
-// one wavefront a slot).
+// Three kernels speak this protocol: hnsw_server_kernel (float rows of 128, 512, 768 components, a team of four wavefronts a slot),
+// hnsw_server_wide_kernel (the same body over rows of 1024 and 1536 floats, read in chunks) and hnsw_server_sq8_kernel (SQ8 codes, one
+// wavefront a slot).
 
 // Lane 0 of a slot waits for the slot's next request or for the kernel's end and leaves the verdict in s_cmd: [0] 1 = a request, 2 = leave;
 // [1] its sequence number; [2] k; [3] ef.  Shared by the two resident kernels below: the protocol is one.
@@ -75,8 +76,9 @@ __device__ __forceinline__ void server_answer(const HnswServer& sv, uint32_t slo
 	__hip_atomic_store(&sv.done[slot], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The body of the resident float kernels (hnsw_server_kernel, and hnsw_server_wide_kernel for the rows served in chunks): one protocol, one code.
 template <int kMetric, int NB, int kSorted, bool kDel, int kTeam>
-__global__ __launch_bounds__(64 * kTeam) void hnsw_server_kernel(HnswParams p, HnswServer sv) {
+__device__ __forceinline__ void hnsw_server_body(const HnswParams& p, const HnswServer& sv) {
 	__shared__ HnswTeamBox box;
 	__shared__ uint32_t s_cmd[4];
 	const uint32_t slot = blockIdx.x;
@@ -108,6 +110,16 @@ __global__ __launch_bounds__(64 * kTeam) void hnsw_server_kernel(HnswParams p, H
 		last = seq;
 		__syncthreads();   // the team leaves hnsw_team_serve
 	}
+}
+template <int kMetric, int NB, int kSorted, bool kDel, int kTeam>
+__global__ __launch_bounds__(64 * kTeam) void hnsw_server_kernel(HnswParams p, HnswServer sv) {
+	hnsw_server_body<kMetric, NB, kSorted, kDel, kTeam>(p, sv);
+}
+// rows of 1024 and 1536 floats (NB = 16, 24: batch_distances_wide)
+template <int kMetric, int NB, int kSorted, bool kDel, int kTeam>
+__global__ __launch_bounds__(64 * kTeam) void hnsw_server_wide_kernel(HnswParams p, HnswServer sv) {
+	static_assert(NB > 12, "the narrower rows are hnsw_server_kernel's");
+	hnsw_server_body<kMetric, NB, kSorted, kDel, kTeam>(p, sv);
 }
 
 // The same mailbox over the SQ8 codes of a quantised graph.  A slot is ONE wavefront (the team form serves float rows only: a 768-byte code row
@@ -169,8 +181,13 @@ static void launch_hnsw_server_nb(int metric, const HnswParams& p, const HnswSer
 #define RX_SERVER(M)                                                                                                                       \
 	do {                                                                                                                                   \
 		static std::atomic<uint64_t> raised{0};                                                                                            \
-		if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_kernel<M, NB, kSorted, kDel, 4>), kServerLdsLimit); \
-		hipLaunchKernelGGL((hnsw_server_kernel<M, NB, kSorted, kDel, 4>), dim3(slots), dim3(256), lds, s, ps, sv);                          \
+		if constexpr (NB > 12) {                                                                                                           \
+			if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_wide_kernel<M, NB, kSorted, kDel, 4>), kServerLdsLimit); \
+			hipLaunchKernelGGL((hnsw_server_wide_kernel<M, NB, kSorted, kDel, 4>), dim3(slots), dim3(256), lds, s, ps, sv);                 \
+		} else {                                                                                                                           \
+			if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_kernel<M, NB, kSorted, kDel, 4>), kServerLdsLimit); \
+			hipLaunchKernelGGL((hnsw_server_kernel<M, NB, kSorted, kDel, 4>), dim3(slots), dim3(256), lds, s, ps, sv);                      \
+		}                                                                                                                                  \
 	} while (0)
 	switch (metric) {
 		case kL2: RX_SERVER(kL2); break;
@@ -209,23 +226,21 @@ template <int NB, bool kDel>
 static void launch_hnsw_server_sq8_dim(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
 	p.ef_cap > 128u ? launch_hnsw_server_sq8_nb<NB, 4, kDel>(metric, p, sv, slots, s) : launch_hnsw_server_sq8_nb<NB, 2, kDel>(metric, p, sv, slots, s);
 }
-// the embedding sizes with a fixed-dimension SQ8 distance batch (launch_hnsw_sq8_sorted, hnsw_search.hip): six for a bare graph, two with deleted nodes
-bool hnsw_server_sq8_serves(uint32_t dim, bool bare) {
-	return dim == 128u || dim == 768u || (bare && (dim == 384u || dim == 512u || dim == 1024u || dim == 1536u));
-}
+// the embedding sizes with a fixed-dimension SQ8 distance batch (hnsw_distance_blocks.h): six for a bare graph, two with deleted nodes
+bool hnsw_server_sq8_serves(uint32_t dim, bool bare) { return hnsw_mailbox_serves(dim, true, !bare); }
 static bool launch_hnsw_server_sq8(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
 	if (!hnsw_server_sq8_serves(p.dim, p.bare != 0) || !p.corr || !p.qcodes || !p.qcorr || !p.qnorm) return false;
 	if (p.bare) {
-		switch (p.dim) {
-			case 128: launch_hnsw_server_sq8_dim<2, false>(metric, p, sv, slots, s); return true;
-			case 384: launch_hnsw_server_sq8_dim<6, false>(metric, p, sv, slots, s); return true;
-			case 512: launch_hnsw_server_sq8_dim<8, false>(metric, p, sv, slots, s); return true;
-			case 768: launch_hnsw_server_sq8_dim<12, false>(metric, p, sv, slots, s); return true;
-			case 1024: launch_hnsw_server_sq8_dim<16, false>(metric, p, sv, slots, s); return true;
+		switch (hnsw_distance_blocks(p.dim, true, false)) {
+			case 2: launch_hnsw_server_sq8_dim<2, false>(metric, p, sv, slots, s); return true;
+			case 6: launch_hnsw_server_sq8_dim<6, false>(metric, p, sv, slots, s); return true;
+			case 8: launch_hnsw_server_sq8_dim<8, false>(metric, p, sv, slots, s); return true;
+			case 12: launch_hnsw_server_sq8_dim<12, false>(metric, p, sv, slots, s); return true;
+			case 16: launch_hnsw_server_sq8_dim<16, false>(metric, p, sv, slots, s); return true;
 			default: launch_hnsw_server_sq8_dim<24, false>(metric, p, sv, slots, s); return true;
 		}
 	}
-	if (p.dim == 128u) {
+	if (hnsw_distance_blocks(p.dim, true, true) == 2) {
 		launch_hnsw_server_sq8_dim<2, true>(metric, p, sv, slots, s);
 	} else {
 		launch_hnsw_server_sq8_dim<12, true>(metric, p, sv, slots, s);
@@ -239,10 +254,12 @@ bool launch_hnsw_server(int metric, const HnswParams& p, const HnswServer& sv, u
 	if (!p.sorted || hnsw_server_lds_bytes(p) > kServerLdsLimit) return false;
 	if (p.ef_cap <= 128u ? (!p.vis_lds || p.vis_lds_log2 > 14) : (p.vis_lds || p.vis_lds_log2 || !p.visited || p.vis_hash_log2 < 14)) return false;
 	if (p.codes) return launch_hnsw_server_sq8(metric, p, sv, slots, s);
-	switch (p.dim) {
-		case 128: launch_hnsw_server_dim<2>(metric, p, sv, slots, s); return true;
-		case 512: launch_hnsw_server_dim<8>(metric, p, sv, slots, s); return true;
-		case 768: launch_hnsw_server_dim<12>(metric, p, sv, slots, s); return true;
+	switch (hnsw_distance_blocks(p.dim, false, p.bare == 0)) {
+		case 2: launch_hnsw_server_dim<2>(metric, p, sv, slots, s); return true;
+		case 8: launch_hnsw_server_dim<8>(metric, p, sv, slots, s); return true;
+		case 12: launch_hnsw_server_dim<12>(metric, p, sv, slots, s); return true;
+		case 16: launch_hnsw_server_dim<16>(metric, p, sv, slots, s); return true;
+		case 24: launch_hnsw_server_dim<24>(metric, p, sv, slots, s); return true;
 		default: return false;
 	}
 }

@@ -22,6 +22,7 @@
 
 #include "knn_emit_plan.h"     // EmitEntry, EmitPlan: where knn_scan_i8 puts the rows it emits
 #include "hnsw_launch_plan.h"   // kHnswMaxEf, kHnswLdsCandEf, kHnswCandLds, kHnswSortedMaxEf, kHnswSortedMaxEfDel: the constants the host-side policy reads too
+#include "hnsw_distance_blocks.h"   // hnsw_distance_blocks: which embedding sizes have a fixed-dimension distance batch
 
 namespace rxgpu {
 

@@ -1019,6 +1019,11 @@ int hnsw_posted_impl(rxgpu_index* h, const void* query, const float* qcorr, cons
 }
 }  // namespace
 
+int rxgpu_hnsw_distance_blocks(uint32_t dim, int sq8, int deleted, int* mailbox) {
+	if (mailbox) *mailbox = rxgpu::hnsw_mailbox_serves(dim, sq8 != 0, deleted != 0) ? 1 : 0;
+	return rxgpu::hnsw_distance_blocks(dim, sq8 != 0, deleted != 0);
+}
+
 int rxgpu_hnsw_search_knn_posted(rxgpu_index* h, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count,
 								 int32_t* served) {
 	RX_CHECK(h && query && out_dist && out_row && out_count && served, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_posted: null argument");

@@ -12,8 +12,8 @@
 // bytes, a corrective offset and a normCoef): hnsw_server_search_sq8.  Slot claim, wait and accounting are the float path's.
 //
 // What is NOT served here (the caller takes the ordinary launches): batches, ef above 256 (224 with deleted nodes; an index has a mailbox per
-// row format and list size: ef <= 128 / 96 and above), embedding sizes without a fixed-dimension distance batch (floats: 128, 512, 768; codes:
-// 128, 384, 512, 768, 1024, 1536, with deleted nodes 128 and 768), a profiled index, the Map over a device list, every RXGPU_HNSW_* A/B hook
+// row format and list size: ef <= 128 / 96 and above), embedding sizes without a fixed-dimension distance batch (hnsw_distance_blocks.h; floats:
+// 128, 512, 768, 1024, 1536; codes: 128, 384, 512, 768, 1024, 1536, with deleted nodes 128 and 768), a profiled index, the Map over a device list, every RXGPU_HNSW_* A/B hook
 // that names a kernel form; codes also with RXGPU_HNSW_SERVER_SQ8=0.  A search that comes back flagged (equal keys that the in-kernel restart
 // could not settle, a visited set half full) is answered by the launches' re-run tiers inside the same call.
 #include <immintrin.h>
@@ -432,7 +432,7 @@ static int server_search(rxgpu_index* h, const HnswServerConfig& cfg, bool sq8, 
 
 int hnsw_server_search(rxgpu_index* h, const HnswServerConfig& cfg, const float* query, uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row,
 					   uint32_t* out_count) {
-	if (h->dim != 128 && h->dim != 512 && h->dim != 768) return 0;
+	if (!hnsw_mailbox_serves(h->dim, false, h->graph_deleted != 0)) return 0;
 	return server_search(h, cfg, false, query, size_t(h->dim) * 4, 0.f, 1.f, k, ef, out_dist, out_row, out_count);
 }
 
