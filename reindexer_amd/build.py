@@ -108,6 +108,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "hnsw_launch_plan.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # which kernel an HNSW search gets compiled for the host (CPU check of the rules the launchers and the kernels' LDS layout follow)
+    src = tdir / "hnsw_kernel_pick_cpu.cc"
+    if src.exists():
+        out = tdir / "libhnsw_kernel_pick_cpu.so"
+        if force or _stale(out, [src, CSRC / "hnsw_kernel_pick.h", CSRC / "hnsw_distance_blocks.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     # the decisions of one BM25 merge compiled for the host (CPU check of the plan the merge entry points execute)
     src = tdir / "ft_merge_plan_cpu.cc"
     if src.exists():

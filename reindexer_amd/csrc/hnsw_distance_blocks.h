@@ -1,5 +1,5 @@
-// Which distance batch an HNSW search over rows of `dim` components takes, as a pure function: the launch switches (hnsw_search.hip), the
-// resident kernels (hnsw_server.hip), the mailbox gates (rxgpu_hnsw_server.hip) and rxgpu_hnsw_distance_blocks (include/rxgpu.h) all ask
+// Which distance batch an HNSW search over rows of `dim` components takes, as a pure function: the kernel choice (hnsw_kernel_pick.h, for
+// hnsw_search.hip and hnsw_server.hip), the mailbox gates (rxgpu_hnsw_server.hip) and rxgpu_hnsw_distance_blocks (include/rxgpu.h) all ask
 // here.  No HIP in here — the file compiles for the host on its own.
 #pragma once
 

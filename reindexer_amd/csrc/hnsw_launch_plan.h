@@ -127,7 +127,7 @@ inline HnswLaunchPlan plan_hnsw_search(uint64_t count, uint32_t dim, bool bare, 
 	while ((1ull << pl.vis_hash_log2) < 64ull * ef && pl.vis_hash_log2 < 18) ++pl.vis_hash_log2;
 	if (knobs.visited_log2 >= 0) pl.vis_hash_log2 = uint32_t(std::min(20, std::max(6, knobs.visited_log2)));   // test hook: force overflows
 	// a handful of searches (the latency form of the kernel, at most two workgroups per CU): the same hash set in LDS, whatever the rule
-	// below picks for batches — the launcher decides (launch_hnsw_nb).  RXGPU_HNSW_VISITED_LDS=0: off (A/B)
+	// below picks for batches — the launcher decides (pick_hnsw_search, hnsw_kernel_pick.h).  RXGPU_HNSW_VISITED_LDS=0: off (A/B)
 	pl.vis_lds_log2 = pl.vis_hash_log2;
 	if (knobs.visited_lds == 0) pl.vis_lds_log2 = 0;
 	if (knobs.visited) pl.vis_lds_log2 = 0;   // an explicit choice of the global form (A/B, tests) stands for every launch

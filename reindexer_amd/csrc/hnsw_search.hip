@@ -13,10 +13,11 @@
 // Per query state: candidate heap + result heap in LDS (heap updates by lane 0 in neighbour order), visited bitset in HBM
 // (one atomicOr per neighbour is both the test and the mark).  A query whose candidate heap outgrows LDS is flagged and
 // re-run with the heap in a global scratch (still on the GPU) — never on the CPU.
-// Graphs without deleted nodes, ef <= 256, start differently: both queues as ONE sorted list in registers (HnswSortedList below), and
+// Graphs without deleted nodes, ef <= 256, start differently: both queues as ONE sorted list in registers (HnswSortedList, hnsw_sorted_list.hip.h), and
 // only a search in which equal distances could change what the reference's heaps do starts over on the heaps, inside the same kernel.
 
 
+#include "hnsw_dispatch.hip.h"
 #include "hnsw_search_core.hip.h"
 
 namespace rxgpu {
@@ -81,212 +82,57 @@ __global__ __launch_bounds__(64) void hnsw_helper_kernel(HnswParams p, HnswHelpe
 	}
 }
 
-template <bool kGlobalCand, int NB, int kSorted = 0, bool kDel = false>
-static void launch_hnsw_nb(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	size_t lds = (size_t(p.ef_cap) + (kGlobalCand ? 0 : p.lds_cand_cap)) * 8 + size_t(NB) * 256;   // heaps + the query fragment (NB*16 float4)
-	constexpr bool kHasLatencyVariant = NB > 8;
-	// no more searches than the chip holds of this form (3 per SIMD; at 1536 floats the two row sets in flight leave one wavefront per SIMD): spend registers on fewer round trips
-	const bool latency = kHasLatencyVariant && blocks <= (NB > 16 ? 1024u : 3072u);
-	// a handful of searches (the Map's single queries and small coalesced batches): four wavefronts per search (hnsw_team_kernel)
-	if constexpr (!kGlobalCand && NB > 0 && kSorted > 0) {
-		if (p.team > 1 && blocks <= p.team_max) {
-			HnswParams pt = p;
-			size_t lds_t = lds;
-			// the visited set in LDS, one size up from what the caller allows where that stays within 64 KB (a handful of workgroups: each may take
-			// a large part of its CU's 160 KB): at 10M x 768, ef = 128, 0.7 % of the searches mark more than the 4096 nodes a 32 KB set holds, and
-			// every one of them costs a re-run launch with a bitset behind the batch
-			if (p.vis_lds_log2) {
-				uint32_t lg = p.vis_lds_log2;
-				if (lg >= 12u && lg < 14u) lg += 1u;   // (smaller sizes are the tests' way of forcing the re-run tiers: left as asked)
-				if ((size_t(4) << lg) <= (64u << 10)) {
-					pt.vis_lds = 1;
-					pt.vis_hash_log2 = lg;
-					lds_t += size_t(4) << lg;
-				}
-			}
-			if (p.nbl && !p.spec && p.maxM0 < 64u && lds_t + kHnswNblBytes <= (150u << 10)) {   // the link blocks of a hop's rows come along with the rows (hnsw_team_serve)
-				pt.nbl_off = uint32_t(lds_t);
-				lds_t += kHnswNblBytes;
-			}
-			if (p.spec && !kDel && p.maxM0 < 64u && lds_t + kHnswSpecBytes <= (150u << 10)) {   // distances of the next candidate's neighbours ride along (hnsw_search_core.hip.h)
-				pt.spec_off = uint32_t(lds_t);
-				lds_t += kHnswSpecBytes;
-			}
-#define RX_TEAM(M)                                                                                                                         \
-	do {                                                                                                                                   \
-		static std::atomic<uint64_t> raised{0};                                                                                            \
-		if (lds_t > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_team_kernel<M, NB, kSorted, kDel, 4>), size_t(150) << 10); \
-		hipLaunchKernelGGL((hnsw_team_kernel<M, NB, kSorted, kDel, 4>), dim3(blocks), dim3(256), lds_t, s, pt);                             \
-	} while (0)
-			switch (metric) {
-				case kL2: RX_TEAM(kL2); break;
-				case kIP: RX_TEAM(kIP); break;
-				default: RX_TEAM(kCos); break;
-			}
-#undef RX_TEAM
-			return;
-		}
-	}
-	// at most two searches per CU and a set of up to 32 KB: the visited set moves into LDS (dynamic LDS stays under the 64 KB a launch gets
-	// without an attribute)
-	HnswParams pl = p;
-	if (latency && !kGlobalCand && p.vis_lds_log2 && blocks <= 512 && (size_t(4) << p.vis_lds_log2) <= (32u << 10) && lds + (size_t(4) << p.vis_lds_log2) <= (60u << 10)) {
-		pl.vis_lds = 1;
-		pl.vis_hash_log2 = p.vis_lds_log2;
-		lds += size_t(4) << p.vis_lds_log2;
-	}
-#define RX_HNSW(M)                                                                                                                         \
-	do {                                                                                                                                   \
-		if (latency) {                                                                                                                     \
-			hipLaunchKernelGGL((hnsw_search_kernel<M, kGlobalCand, NB, kHasLatencyVariant, false, kSorted, kDel>), dim3(blocks), dim3(64), lds, s, pl); \
-		} else {                                                                                                                           \
-			hipLaunchKernelGGL((hnsw_search_kernel<M, kGlobalCand, NB, false, false, kSorted, kDel>), dim3(blocks), dim3(64), lds, s, p);    \
-		}                                                                                                                                  \
-	} while (0)
-	switch (metric) {
-		case kL2: RX_HNSW(kL2); break;
-		case kIP: RX_HNSW(kIP); break;
-		default: RX_HNSW(kCos); break;
-	}
-#undef RX_HNSW
-}
-
-template <int kSorted, bool kDel>
-static void launch_hnsw_sorted(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	switch (hnsw_distance_blocks(p.dim, false, kDel)) {   // (hnsw_distance_blocks.h: the one list of sizes)
-		case 2: launch_hnsw_nb<false, 2, kSorted, kDel>(metric, p, blocks, s); break;
-		case 8: launch_hnsw_nb<false, 8, kSorted, kDel>(metric, p, blocks, s); break;
-		case 12: launch_hnsw_nb<false, 12, kSorted, kDel>(metric, p, blocks, s); break;
-		case 16: launch_hnsw_nb<false, 16, kSorted, kDel>(metric, p, blocks, s); break;
-		case 24: launch_hnsw_nb<false, 24, kSorted, kDel>(metric, p, blocks, s); break;
-		default: launch_hnsw_nb<false, 0, kSorted, kDel>(metric, p, blocks, s); break;
-	}
-}
-
-template <bool kGlobalCand>
-static void launch_hnsw_mode(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	switch (hnsw_distance_blocks(p.dim, false, false)) {   // (the heaps handle deleted nodes themselves: one list of sizes)
-		case 2: launch_hnsw_nb<kGlobalCand, 2>(metric, p, blocks, s); break;
-		case 8: launch_hnsw_nb<kGlobalCand, 8>(metric, p, blocks, s); break;
-		case 12: launch_hnsw_nb<kGlobalCand, 12>(metric, p, blocks, s); break;
-		case 16: launch_hnsw_nb<kGlobalCand, 16>(metric, p, blocks, s); break;
-		case 24: launch_hnsw_nb<kGlobalCand, 24>(metric, p, blocks, s); break;
-		default: launch_hnsw_nb<kGlobalCand, 0>(metric, p, blocks, s); break;
-	}
-}
-
-template <bool kGlobalCand, int NB, int kSorted = 0, bool kDel = false>
-static void launch_hnsw_sq8_nb(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	const size_t lds = (size_t(p.ef_cap) + (kGlobalCand ? 0 : p.lds_cand_cap)) * 8;
-	switch (metric) {
-		case kL2: hipLaunchKernelGGL((hnsw_search_kernel<kL2, kGlobalCand, NB, false, true, kSorted, kDel>), dim3(blocks), dim3(64), lds, s, p); break;
-		case kIP: hipLaunchKernelGGL((hnsw_search_kernel<kIP, kGlobalCand, NB, false, true, kSorted, kDel>), dim3(blocks), dim3(64), lds, s, p); break;
-		default: hipLaunchKernelGGL((hnsw_search_kernel<kCos, kGlobalCand, NB, false, true, kSorted, kDel>), dim3(blocks), dim3(64), lds, s, p); break;
-	}
-}
-
-template <int kSorted, bool kDel>
-static void launch_hnsw_sq8_sorted(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	if constexpr (kDel) {   // graphs with deleted nodes: two embedding sizes get the 16-byte-load form, the rest the generic one
-		switch (hnsw_distance_blocks(p.dim, true, true)) {
-			case 2: launch_hnsw_sq8_nb<false, 2, kSorted, true>(metric, p, blocks, s); break;
-			case 12: launch_hnsw_sq8_nb<false, 12, kSorted, true>(metric, p, blocks, s); break;
-			default: launch_hnsw_sq8_nb<false, 0, kSorted, true>(metric, p, blocks, s); break;
-		}
-	} else {
-		switch (hnsw_distance_blocks(p.dim, true, false)) {
-			case 2: launch_hnsw_sq8_nb<false, 2, kSorted>(metric, p, blocks, s); break;
-			case 6: launch_hnsw_sq8_nb<false, 6, kSorted>(metric, p, blocks, s); break;
-			case 8: launch_hnsw_sq8_nb<false, 8, kSorted>(metric, p, blocks, s); break;
-			case 12: launch_hnsw_sq8_nb<false, 12, kSorted>(metric, p, blocks, s); break;
-			case 16: launch_hnsw_sq8_nb<false, 16, kSorted>(metric, p, blocks, s); break;
-			case 24: launch_hnsw_sq8_nb<false, 24, kSorted>(metric, p, blocks, s); break;
-			default: launch_hnsw_sq8_nb<false, 0, kSorted>(metric, p, blocks, s); break;
-		}
-	}
-}
-
-template <bool kGlobalCand>
-static void launch_hnsw_sq8(int metric, const HnswParams& p, uint32_t blocks, hipStream_t s) {
-	switch (hnsw_distance_blocks(p.dim, true, false)) {   // the embedding sizes in use get the 16-byte-load form; any other dim the generic one
-		case 2: launch_hnsw_sq8_nb<kGlobalCand, 2>(metric, p, blocks, s); break;
-		case 6: launch_hnsw_sq8_nb<kGlobalCand, 6>(metric, p, blocks, s); break;
-		case 8: launch_hnsw_sq8_nb<kGlobalCand, 8>(metric, p, blocks, s); break;
-		case 12: launch_hnsw_sq8_nb<kGlobalCand, 12>(metric, p, blocks, s); break;
-		case 16: launch_hnsw_sq8_nb<kGlobalCand, 16>(metric, p, blocks, s); break;
-		case 24: launch_hnsw_sq8_nb<kGlobalCand, 24>(metric, p, blocks, s); break;
-		default: launch_hnsw_sq8_nb<kGlobalCand, 0>(metric, p, blocks, s); break;
-	}
+// From a pick to the instantiation (hnsw_kernel_pick.h states which ones exist: nothing outside that set is compiled, and a pick outside it
+// launches nothing).
+static bool dispatch_hnsw_search(int metric, const HnswKernelPick& k, const HnswParams& p, uint32_t blocks, hipStream_t s) {
+	return with_metric(metric, [&](auto m) {
+		return with_int<0, 2, 6, 8, 12, 16, 24>(k.nb, [&](auto nb) {
+			return with_int<0, 2, 3, 4>(k.sorted, [&](auto sorted) {
+				return with_bool(k.del, [&](auto del) {
+					constexpr int M = decltype(m)::value, NB = decltype(nb)::value, S = decltype(sorted)::value;
+					constexpr bool D = decltype(del)::value;
+					if (k.family == kHnswTeam) {
+						if constexpr (hnsw_team_kernel_exists(NB, S, D)) return hnsw_launch<&hnsw_team_kernel<M, NB, S, D, 4>>(k, blocks, s, p);
+						return false;
+					}
+					return with_bool(k.global_cand, [&](auto global_cand) {
+						return with_bool(k.latency, [&](auto latency) {
+							return with_bool(k.sq8, [&](auto sq8) {
+								constexpr bool G = decltype(global_cand)::value, L = decltype(latency)::value, Q = decltype(sq8)::value;
+								if constexpr (hnsw_search_kernel_exists(G, NB, L, Q, S, D)) return hnsw_launch<&hnsw_search_kernel<M, G, NB, L, Q, S, D>>(k, blocks, s, p);
+								return false;
+							});
+						});
+					});
+				});
+			});
+		});
+	});
 }
 
 void launch_hnsw_search(int metric, const HnswParams& p, uint32_t blocks, bool global_cand, hipStream_t s) {
-	if (p.sorted && !global_cand) {
-		// both queues as one sorted list in registers.  Without deleted nodes: 2 entries a lane up to ef = 128, 4 up to 256; with deleted
-		// nodes the list also holds the deleted candidates in reach: 2 entries a lane up to ef = 96, 3 up to 160, 4 up to 224 (kHnswSortedMaxEfDel)
-		if (p.bare) {
-			const bool four = p.ef > 128;
-			if (p.codes) {
-				four ? launch_hnsw_sq8_sorted<4, false>(metric, p, blocks, s) : launch_hnsw_sq8_sorted<2, false>(metric, p, blocks, s);
-			} else {
-				four ? launch_hnsw_sorted<4, false>(metric, p, blocks, s) : launch_hnsw_sorted<2, false>(metric, p, blocks, s);
-			}
-		} else {
-			const int slots = p.ef <= 96 ? 2 : p.ef <= 160 ? 3 : 4;
-			if (p.codes) {
-				slots == 2 ? launch_hnsw_sq8_sorted<2, true>(metric, p, blocks, s)
-						   : slots == 3 ? launch_hnsw_sq8_sorted<3, true>(metric, p, blocks, s) : launch_hnsw_sq8_sorted<4, true>(metric, p, blocks, s);
-			} else {
-				slots == 2 ? launch_hnsw_sorted<2, true>(metric, p, blocks, s)
-						   : slots == 3 ? launch_hnsw_sorted<3, true>(metric, p, blocks, s) : launch_hnsw_sorted<4, true>(metric, p, blocks, s);
-			}
-		}
-		return;
-	}
-	if (p.codes) {   // SQ8 graph
-		if (global_cand) {
-			launch_hnsw_sq8<true>(metric, p, blocks, s);
-		} else {
-			launch_hnsw_sq8<false>(metric, p, blocks, s);
-		}
-		return;
-	}
-	if (global_cand) {
-		launch_hnsw_mode<true>(metric, p, blocks, s);
-	} else {
-		launch_hnsw_mode<false>(metric, p, blocks, s);
-	}
-}
-
-
-template <int NB, bool kSq8>
-static void launch_hnsw_helper_nb(int metric, const HnswParams& p, const HnswHelper& hq, uint32_t groups, hipStream_t s) {
-	const size_t lds = (size_t(p.ef_cap) + p.lds_cand_cap) * 8 + (kSq8 ? 0 : size_t(NB) * 256);
-	switch (metric) {
-		case kL2: hipLaunchKernelGGL((hnsw_helper_kernel<kL2, NB, kSq8>), dim3(groups), dim3(64), lds, s, p, hq); break;
-		case kIP: hipLaunchKernelGGL((hnsw_helper_kernel<kIP, NB, kSq8>), dim3(groups), dim3(64), lds, s, p, hq); break;
-		default: hipLaunchKernelGGL((hnsw_helper_kernel<kCos, NB, kSq8>), dim3(groups), dim3(64), lds, s, p, hq); break;
-	}
+	const HnswKernelPick k = pick_hnsw_search(hnsw_pick_input(p, blocks, global_cand));
+	if (!dispatch_hnsw_search(metric, k, hnsw_patched(p, k), blocks, s)) hnsw_no_kernel("search", metric, k);
 }
 
 // the helper workgroups of a batch (hnsw_helper_kernel): p = the batch's parameters with the helpers' own visited bitsets, the largest LDS
 // heap, no `only` list, no overflow queue of their own
 void launch_hnsw_helper(int metric, const HnswParams& p, const HnswHelper& hq, uint32_t groups, hipStream_t s) {
-	if (p.codes) {
-		switch (hnsw_distance_blocks(p.dim, true, true)) {   // (the two sizes every SQ8 graph has a fixed form for)
-			case 2: launch_hnsw_helper_nb<2, true>(metric, p, hq, groups, s); break;
-			case 12: launch_hnsw_helper_nb<12, true>(metric, p, hq, groups, s); break;
-			default: launch_hnsw_helper_nb<0, true>(metric, p, hq, groups, s); break;
-		}
-		return;
-	}
-	switch (hnsw_distance_blocks(p.dim, false, false)) {   // (512 has no helper instantiation of its own: the generic batch, as before)
-		case 2: launch_hnsw_helper_nb<2, false>(metric, p, hq, groups, s); break;
-		case 12: launch_hnsw_helper_nb<12, false>(metric, p, hq, groups, s); break;
-		case 16: launch_hnsw_helper_nb<16, false>(metric, p, hq, groups, s); break;
-		case 24: launch_hnsw_helper_nb<24, false>(metric, p, hq, groups, s); break;
-		default: launch_hnsw_helper_nb<0, false>(metric, p, hq, groups, s); break;
-	}
+	const HnswKernelPick k = pick_hnsw_helper(hnsw_pick_input(p, groups, false));
+	const HnswParams pk = hnsw_patched(p, k);
+	const bool launched = with_metric(metric, [&](auto m) {
+		return with_int<0, 2, 12, 16, 24>(k.nb, [&](auto nb) {
+			return with_bool(k.sq8, [&](auto sq8) {
+				constexpr int M = decltype(m)::value, NB = decltype(nb)::value;
+				constexpr bool Q = decltype(sq8)::value;
+				if constexpr (hnsw_helper_kernel_exists(NB, Q)) return hnsw_launch<&hnsw_helper_kernel<M, NB, Q>>(k, groups, s, pk, hq);
+				return false;
+			});
+		});
+	});
+	if (!launched) hnsw_no_kernel("helper", metric, k);
 }
+
 
 // SearchRange's second half on the device (hnswalg.h:2030-2064): the closure of the ef-search's hits under "neighbour on level 0, not
 // deleted, dist < radius".  The result is a SET (the reference's radius_queue order does not change it), so the expansion runs level by

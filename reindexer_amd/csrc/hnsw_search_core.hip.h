@@ -1,11 +1,15 @@
 // Device code shared by the HNSW search kernels (hnsw_search.hip: the launches; hnsw_server.hip: the resident form): the reference's two
-// heaps, the sorted list, distance batches, visited sets and ONE search by one wavefront / one team (hnsw_search_one).  See hnsw_search.hip
-// for what is replaced and why the results are equal.
+// heaps and ONE search by one wavefront / one team (hnsw_search_one); the sorted list (hnsw_sorted_list.hip.h), the distance
+// batches (hnsw_distances.hip.h) and the visited sets (hnsw_visited.hip.h) are files of their own.  See hnsw_search.hip for what is replaced
+// and why the results are equal.
 #pragma once
 #include <type_traits>
 
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
+#include "hnsw_distances.hip.h"
+#include "hnsw_sorted_list.hip.h"
+#include "hnsw_visited.hip.h"
 
 namespace rxgpu {
 
@@ -59,635 +63,7 @@ __device__ __forceinline__ void hp_replace_top(uint2* h, int n, float vd, uint32
 	hp_sift_down(h, 0, n);
 }
 
-// --- The fast path of a search over a graph without deleted nodes: BOTH queues as one sorted list spread over the lanes ---
-// In a bare-bone search (hnswalg.h:873-876, 932-960) every candidate is pushed into top_candidates together with its push into
-// candidate_set, so the live part of candidate_set is "the members of top_candidates that were not expanded yet": what top_candidates
-// evicted lies at or above lowerBound for good, and popping it ends the search like an empty candidate_set does (at: see below).  One list of <= ef
-// entries sorted by distance plus one "expanded" bit per entry therefore carries the whole Layer0SearchState: entry 64 s + l lives in
-// slot s of lane l, an insertion is one ballot + one lane shift (wave_shr DPP) instead of two binary-heap sifts by one lane, the pop is a
-// scalar find-first-zero.
-// Equal distances.  With CompareByFirst heaps the reference's choice among EQUAL keys is whatever libstdc++'s sift loops leave on top,
-// which a sorted list cannot know.  Where that choice cannot matter the list goes on; where it can, the search is flagged and starts
-// over on the heaps (the code below the list's branch in hnsw_search_kernel; kHnswTie and a launch of its own if the launcher gave the
-// workgroup no heap area):
-//   * the popped candidate's key d equals the next unexpanded one's (which of the two the reference expands first is its heap's
-//     secret) AND lowerBound has come down to d by the time every candidate with a key <= d is expanded.  While lowerBound stays above
-//     d the order is immaterial: each node of key <= d that gets evaluated is admitted (key < lowerBound) and expanded before anything
-//     farther, so both orders expand the same closure — "evaluated nodes of key <= d, and what their lists reach" —, top_candidates
-//     is the ef smallest keys of the same evaluated set, and lowerBound in the other order is never below its value at the end of this
-//     one (fewer keys seen, larger ef-th smallest).  The check is made when the first key > d is popped, or when the list runs dry;
-//   * the popped key, or lowerBound when the list runs dry, equals the key of the last node that went OUTSIDE the list with a key equal
-//     to lowerBound — evicted next to an equal maximum, or refused admission at dist == lowerBound: an evicted entry is still in the
-//     reference's candidate_set, alive (dist > lowerBound is false) and due for expansion, and in another order of equal pops a refused
-//     node is one that got in.  (Keys outside the list never lie below lowerBound, and lowerBound only falls: the last such key is the
-//     only one that can still equal it.)
-//   * entries k - 1 and k of the final list are equal (SearchKnn's trim to k pops one of them);
-//   * a key is not finite.
-// Everything else depends on keys alone: top_candidates is the multiset of the ef smallest keys seen, an eviction among equal maxima
-// changes neither lowerBound nor candidate_set, and an equal key met in the middle of the list has no consequence until one of the
-// events above.  (Flagging every equal key met on insertion re-ran 31 % of the queries of a 1M x 768 corpus: with 128 keys in a narrow
-// band of float32 values a search of ~400 insertions meets one more often than not.)
-__device__ __forceinline__ uint32_t wave_shr1(uint32_t x) {   // lane l <- lane l - 1 (lane 0 keeps its value)
-	return uint32_t(__builtin_amdgcn_update_dpp(int(x), int(x), 0x138 /* wave_shr:1 */, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float lane_value(float v, int l) { return __uint_as_float(uint32_t(__builtin_amdgcn_readlane(int(__float_as_uint(v)), l))); }
-// The per-slot state of a list as VECTOR values, not arrays: an array member keeps the whole struct in scratch memory as soon as a loop
-// over it is not unrolled before LLVM's SROA pass runs (seen for S = 3 and 4: 100 bytes of scratch per lane, every access a memory op).
-template <int S>
-struct HnswVec {
-	typedef float f __attribute__((ext_vector_type(S)));
-	typedef uint32_t u __attribute__((ext_vector_type(S)));
-	typedef uint64_t m __attribute__((ext_vector_type(S)));
-};
-// entries >= pos move up by one (the last one falls off the registers), (nd, nid) lands at pos
-template <int S>
-__device__ __forceinline__ void sorted_shift_in(typename HnswVec<S>::f& d, typename HnswVec<S>::u& id, int pos, float nd, uint32_t nid, bool dpp, int lane) {
-#pragma unroll
-	for (int s = S - 1; s >= 0; --s) {
-		if (pos >= 64 * (s + 1)) continue;   // uniform: the slot lies below the insertion point
-		const int g = 64 * s + lane;
-		float up_d;
-		uint32_t up_i;
-		if (dpp) {
-			up_d = __uint_as_float(wave_shr1(__float_as_uint(d[s])));
-			up_i = wave_shr1(id[s]);
-		} else {   // RXGPU_HNSW_SORTED=2: the same shift through the LDS crossbar (ds_bpermute)
-			up_d = __shfl_up(d[s], 1, 64);
-			up_i = __shfl_up(id[s], 1, 64);
-		}
-		if (s > 0) {
-			const float carry_d = lane_value(d[s > 0 ? s - 1 : 0], 63);
-			const uint32_t carry_i = uint32_t(__builtin_amdgcn_readlane(int(id[s > 0 ? s - 1 : 0]), 63));
-			if (lane == 0) {
-				up_d = carry_d;
-				up_i = carry_i;
-			}
-		}
-		d[s] = g < pos ? d[s] : (g == pos ? nd : up_d);
-		id[s] = g < pos ? id[s] : (g == pos ? nid : up_i);
-	}
-}
-// the same for a wave-uniform bit per entry
-template <int S>
-__device__ __forceinline__ void mask_shift_in(typename HnswVec<S>::m& m, int pos, bool bit) {
-#pragma unroll
-	for (int s = S - 1; s >= 0; --s) {
-		if (pos >= 64 * (s + 1)) continue;
-		if (pos < 64 * s) {
-			m[s] = (m[s] << 1) | (m[s > 0 ? s - 1 : 0] >> 63);
-		} else {
-			const uint64_t below = (1ull << (pos - 64 * s)) - 1ull;
-			m[s] = (m[s] & below) | ((m[s] & ~below) << 1) | (uint64_t(bit) << (pos - 64 * s));
-		}
-	}
-}
-template <int S>
-struct HnswSortedList {
-	typename HnswVec<S>::f d;
-	typename HnswVec<S>::u id;
-	typename HnswVec<S>::m done;   // wave-uniform: bit l of word s = entry 64 s + l is expanded (or empty)
-	int n;
-	float lower;        // lowerBound: the largest key while the list is filling, entry ef - 1 afterwards
-	float outside;      // key of the last node evicted, or refused at dist == lowerBound (NaN before the first: equal to nothing)
-	float pend;         // largest key at which a pop met an equal unexpanded key and the verdict is still open
-	bool pending;
-	bool tie;
-	bool dpp;
-
-	__device__ __forceinline__ void init(bool use_dpp) {
-		dpp = use_dpp;
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			d[s] = __builtin_inff();
-			id[s] = 0u;
-			done[s] = ~0ull;
-		}
-		n = 0;
-		lower = 3.402823466e+38f;
-		outside = __builtin_nanf("");
-		pend = 0.f;
-		pending = false;
-		tie = false;
-	}
-	// every candidate of key <= pend is expanded now: the order among the equal ones was immaterial iff lowerBound is still above pend
-	// (a list that is not full admits everything, whatever lowerBound says)
-	__device__ __forceinline__ void settle(int ef) {
-		if (pending && n == ef && !(lower > pend)) tie = true;
-		pending = false;
-	}
-	// key of entry e (wave-uniform e)
-	__device__ __forceinline__ float key_at(int e) const {
-		float v = d[0];
-#pragma unroll
-		for (int s = 1; s < S; ++s) v = (e >> 6) == s ? d[s] : v;
-		return lane_value(v, e & 63);
-	}
-	// (nd, nid) wave-uniform; the caller has checked n < ef || lower > nd
-	__device__ __forceinline__ void insert(float nd, uint32_t nid, int ef, int lane) {
-		int pos = 0;
-#pragma unroll
-		for (int s = 0; s < S; ++s) pos += __popcll(__ballot(d[s] < nd));
-		tie = tie || !(nd < __builtin_inff());
-		if (n == ef) outside = lower;   // the list is full: its last entry leaves
-		sorted_shift_in<S>(d, id, pos, nd, nid, dpp, lane);
-		mask_shift_in<S>(done, pos, false);   // bit pos: 0 = not expanded
-		if (n < ef) {
-			++n;
-		} else {
-#pragma unroll
-			for (int s = 0; s < S; ++s) {   // the evicted maximum sits at index ef now (if the registers reach that far): an empty entry again
-				const bool here = (ef >> 6) == s;
-				d[s] = (here && lane == (ef & 63)) ? __builtin_inff() : d[s];
-				done[s] |= here ? 1ull << (ef & 63) : 0ull;
-			}
-		}
-		lower = key_at(n - 1);
-	}
-	// the interface the kernel shares with HnswSortedListDel: members of top_candidates held, insertion with a delete mark (none here)
-	__device__ __forceinline__ int held() const { return n; }
-	__device__ __forceinline__ void insert(float nd, uint32_t nid, bool, int ef, int lane) { insert(nd, nid, ef, lane); }
-	// first entry that was not expanded yet, -1 if none (selects over static slot numbers, no early exit: the arrays must stay in registers)
-	__device__ __forceinline__ int first_open() const {
-		int e = -1;
-#pragma unroll
-		for (int s = S - 1; s >= 0; --s) {
-			const uint64_t o = ~done[s];
-			e = o ? 64 * s + __builtin_ctzll(o) : e;
-		}
-		return e;
-	}
-	// the first unexpanded entry behind entry `after`, -1 if none
-	__device__ __forceinline__ int next_open(int after) const {
-		int e = -1;
-#pragma unroll
-		for (int s = S - 1; s >= 0; --s) {
-			uint64_t o = ~done[s];
-			if ((after >> 6) == s) o = (after & 63) == 63 ? 0ull : (o & (~0ull << ((after & 63) + 1)));
-			if ((after >> 6) > s) o = 0ull;
-			e = o ? 64 * s + __builtin_ctzll(o) : e;
-		}
-		return e;
-	}
-	// candidate_set.top() + pop(): the nearest entry that was not expanded yet
-	__device__ __forceinline__ bool pop(uint32_t& node, float& dist, int ef) {
-		const int e = first_open();
-		if (e < 0) {
-			settle(ef);
-			return false;
-		}
-		uint32_t iv = id[0];
-#pragma unroll
-		for (int s = 1; s < S; ++s) iv = (e >> 6) == s ? id[s] : iv;
-		dist = key_at(e);
-		node = uint32_t(__builtin_amdgcn_readlane(int(iv), e & 63));
-		if (pending && dist > pend) settle(ef);
-#pragma unroll
-		for (int s = 0; s < S; ++s) done[s] |= (e >> 6) == s ? 1ull << (e & 63) : 0ull;
-		const int next = first_open();
-		tie = tie || dist == outside;
-		if (next >= 0 && key_at(next) == dist) {
-			pend = pending ? fmaxf(pend, dist) : dist;
-			pending = true;
-		}
-		return true;
-	}
-};
-
-// The same list for a graph WITH deleted nodes (hnswalg.h:882-893, 943-957): a deleted node is a candidate like any other but never a
-// member of top_candidates, lowerBound follows the LIVE entries only, the search stops on a far candidate only once ef live entries are
-// held, and a deleted entry point enters candidate_set at FLT_MAX (initLayer0SearchState :853-856).  The list holds live and deleted
-// entries in one order; `del` marks the deleted ones, `live` counts the others.  Once ef live entries are held everything behind the
-// last of them is dead — deleted entries above lowerBound, the live entry a new one evicts — and leaves the list; `outside` takes the
-// smallest key that leaves.  The equal-key rules are the bare list's, with "full" meaning live == ef; a list that runs out of registers
-// (many deleted nodes in reach) flags the search like an equal key does.  tests/test_hnsw_sorted_model.py holds the Python restatement
-// of both lists and runs it against the two-heap oracle.
-template <int S>
-struct HnswSortedListDel {
-	static constexpr int kCap = 64 * S;
-	typename HnswVec<S>::f d;
-	typename HnswVec<S>::u id;
-	typename HnswVec<S>::m done;   // wave-uniform: expanded (or empty)
-	typename HnswVec<S>::m del;    // wave-uniform: the entry is a deleted node (0 for empty slots)
-	int n, live;
-	float lower, outside, pend;
-	bool pending, tie, dpp;
-
-	__device__ __forceinline__ void init(bool use_dpp) {
-		dpp = use_dpp;
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			d[s] = __builtin_inff();
-			id[s] = 0u;
-			done[s] = ~0ull;
-			del[s] = 0ull;
-		}
-		n = live = 0;
-		lower = 3.402823466e+38f;
-		outside = __builtin_nanf("");
-		pend = 0.f;
-		pending = false;
-		tie = false;
-	}
-	__device__ __forceinline__ float key_at(int e) const {
-		float v = d[0];
-#pragma unroll
-		for (int s = 1; s < S; ++s) v = (e >> 6) == s ? d[s] : v;
-		return lane_value(v, e & 63);
-	}
-	// bits of word s that belong to entries < count
-	static __device__ __forceinline__ uint64_t below_count(int s, int count) {
-		const int c = count - 64 * s;
-		return c <= 0 ? 0ull : (c >= 64 ? ~0ull : ((1ull << c) - 1ull));
-	}
-	__device__ __forceinline__ int last_live() const {
-		int e = -1;
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			const uint64_t m = ~del[s] & below_count(s, n);
-			e = m ? 64 * s + 63 - __builtin_clzll(m) : e;
-		}
-		return e;
-	}
-	__device__ __forceinline__ int held() const { return live; }
-	__device__ __forceinline__ void settle(int ef) {
-		if (pending && live == ef && !(lower > pend)) tie = true;
-		pending = false;
-	}
-	// (nd, nid, isdel) wave-uniform; the caller has checked live < ef || lower > nd
-	__device__ __forceinline__ void insert(float nd, uint32_t nid, bool isdel, int ef, int lane) {
-		tie = tie || !(nd < __builtin_inff());
-		const bool full = live == ef;
-		if (n == kCap && !(full && !isdel)) {   // no register left for one more entry: the heaps take the search over
-			tie = true;
-			return;
-		}
-		int pos = 0;
-#pragma unroll
-		for (int s = 0; s < S; ++s) pos += __popcll(__ballot(d[s] < nd));
-		const float old_lower = lower;
-		sorted_shift_in<S>(d, id, pos, nd, nid, dpp, lane);
-		mask_shift_in<S>(done, pos, false);
-		mask_shift_in<S>(del, pos, isdel);
-		const bool fell_off = n == kCap;   // only with a full top and a live newcomer: the entry that fell off was the largest live one
-		if (!fell_off) ++n;
-		if (!isdel) {
-			if (!full) {
-				++live;
-			} else if (fell_off) {
-				outside = old_lower;
-			} else {   // the largest live entry leaves top_candidates: from here on it is one of the dead behind the last live entry
-				const int gone = last_live();
-				outside = key_at(gone);
-#pragma unroll
-				for (int s = 0; s < S; ++s) del[s] |= (gone >> 6) == s ? 1ull << (gone & 63) : 0ull;
-			}
-			if (live == ef) {   // everything behind the last live entry is dead now
-				const int keep = last_live() + 1;
-				if (keep < n) {
-					outside = key_at(keep);   // the smallest key that leaves
-#pragma unroll
-					for (int s = 0; s < S; ++s) {
-						const uint64_t stay = below_count(s, keep);
-						d[s] = (64 * s + lane) >= keep ? __builtin_inff() : d[s];
-						done[s] |= ~stay;
-						del[s] &= stay;
-					}
-					n = keep;
-				}
-			}
-		}
-		if (live > 0) lower = key_at(last_live());
-	}
-	__device__ __forceinline__ int first_open() const {
-		int e = -1;
-#pragma unroll
-		for (int s = S - 1; s >= 0; --s) {
-			const uint64_t o = ~done[s];
-			e = o ? 64 * s + __builtin_ctzll(o) : e;
-		}
-		return e;
-	}
-	__device__ __forceinline__ bool pop(uint32_t& node, float& dist, int ef) {
-		const int e = first_open();
-		if (e < 0) {
-			settle(ef);
-			return false;
-		}
-		uint32_t iv = id[0];
-#pragma unroll
-		for (int s = 1; s < S; ++s) iv = (e >> 6) == s ? id[s] : iv;
-		dist = key_at(e);
-		node = uint32_t(__builtin_amdgcn_readlane(int(iv), e & 63));
-		if (pending && dist > pend) settle(ef);
-#pragma unroll
-		for (int s = 0; s < S; ++s) done[s] |= (e >> 6) == s ? 1ull << (e & 63) : 0ull;
-		const int next = first_open();
-		tie = tie || dist == outside;
-		if (next >= 0 && key_at(next) == dist) {
-			pend = pending ? fmaxf(pend, dist) : dist;
-			pending = true;
-		}
-		return true;
-	}
-	// index of the r-th live entry (r < live)
-	__device__ __forceinline__ int live_at(int r) const {
-		int e = -1, seen = 0;
-#pragma unroll
-		for (int s = 0; s < S; ++s) {
-			uint64_t m = ~del[s] & below_count(s, n);
-			const int c = __popcll(m);
-			if (e < 0 && r < seen + c) {
-				for (int i = seen; i < r; ++i) m &= m - 1;   // drop the r - seen lowest set bits (wave-uniform loop)
-				e = 64 * s + __builtin_ctzll(m);
-			}
-			seen += c;
-		}
-		return e;
-	}
-};
-
-// Distances of `cnt` rows (ids in LDS) to the query, 4 rows per step; every lane participates in every step.
-template <int kMetric>
-__device__ __forceinline__ void batch_distances(const HnswParams& p, const float* q, const uint32_t* ids, int cnt, float* dists, int lane) {
-	const int m = lane & 15, g = lane >> 4;
-	for (int base = 0; base < cnt; base += kRowsPerWave) {
-		const int idx = base + g;
-		const bool ok = idx < cnt;
-		const uint64_t row = ids[ok ? idx : base];
-		const float sum = group_distance_generic<kMetric>(p.rows + row * p.stride, q, p.dim, m);
-		const float dist = 1.0f * metric_epilogue<kMetric>(sum, p.inv_norms, row);   // normCoef == 1 (hnswalg.h:1855-1863)
-		if (ok && m == 0) dists[idx] = dist;
-	}
-}
-
-// dim == 64*NB, SQ8: 16-byte loads.  Lane m of the row's 16-lane group reads bytes [256 i + 16 m, + 16) of load i: block 4 i + (m >> 2),
-// bytes 16 (m & 3) .. + 16 of it, i.e. the element pairs of reference lanes j = 8 (m & 1) + p, p = 0 .. 7 (pair p = halfword p of the 16
-// bytes) — in the low half of the block for (m & 3) < 2, in the high half above; both halves feed the same reference lane.  Eight integer
-// accumulators a lane, over all blocks (the reference's lanes accumulate over all blocks too); a transpose-reduction over the eight lanes
-// of equal parity (xor 2, 4, 8: 7 exchanges) leaves reference lane j's sum on lane (j >> 3) + 2 ((j >> 2) & 1) + 4 ((j >> 1) & 1) + 8 (j & 1),
-// and the 16 sums are then added as floats in the reference's order j = 0 .. 15.  L2: (a - b)^2 = a^2 - 2ab + b^2 per pair, exact in
-// uint32; the query's b^2 share (qq) is computed once a search.  The query words and qq live in registers for the whole search.
-template <int kMetric, int NB>
-__device__ __forceinline__ void batch_distances_sq8_fixed(const HnswParams& p, const uint4 (&qw)[(NB + 3) / 4], const uint32_t (&qq)[8], float qcorr,
-														  float qnorm, const uint32_t* ids, int cnt, float* dists, int lane) {
-	constexpr int L = (NB + 3) / 4;
-	const int m = lane & 15, g = lane >> 4;
-	const int group_base = lane & ~15;
-	for (int base = 0; base < cnt; base += kRowsPerWave) {
-		const int idx = base + g;
-		const bool ok = idx < cnt;
-		const uint64_t row = ids[ok ? idx : base];
-		const uint4* r = reinterpret_cast<const uint4*>(p.codes + row * uint64_t(64 * NB));
-		uint4 a[L];
-#pragma unroll
-		for (int i = 0; i < L; ++i) {
-			if (256 * i + 256 <= 64 * NB || 256 * i + 16 * m < 64 * NB) {
-				a[i] = r[16 * i + m];
-			} else {
-				a[i] = make_uint4(0u, 0u, 0u, 0u);
-			}
-		}
-		uint32_t ab[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, aa[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-		for (int i = 0; i < L; ++i) {
-			const uint32_t aw[4] = {a[i].x, a[i].y, a[i].z, a[i].w};
-			const uint32_t bw[4] = {qw[i].x, qw[i].y, qw[i].z, qw[i].w};
-#pragma unroll
-			for (int c = 0; c < 4; ++c) {
-				const uint32_t lo = aw[c] & 0x0000FFFFu, hi = aw[c] & 0xFFFF0000u;
-				ab[2 * c] = __builtin_amdgcn_udot4(lo, bw[c], ab[2 * c], false);
-				ab[2 * c + 1] = __builtin_amdgcn_udot4(hi, bw[c], ab[2 * c + 1], false);
-				if constexpr (kMetric == kL2) {
-					aa[2 * c] = __builtin_amdgcn_udot4(lo, aw[c], aa[2 * c], false);
-					aa[2 * c + 1] = __builtin_amdgcn_udot4(hi, aw[c], aa[2 * c + 1], false);
-				}
-			}
-		}
-		uint32_t s8[8];
-#pragma unroll
-		for (int q = 0; q < 8; ++q) s8[q] = kMetric == kL2 ? aa[q] + qq[q] - 2u * ab[q] : ab[q];
-		const bool up1 = (m & 2) != 0, up2 = (m & 4) != 0, up3 = (m & 8) != 0;
-		uint32_t t4[4], t2[2];
-#pragma unroll
-		for (int q = 0; q < 4; ++q) t4[q] = (up1 ? s8[q + 4] : s8[q]) + uint32_t(__shfl_xor(int(up1 ? s8[q] : s8[q + 4]), 2, 64));
-#pragma unroll
-		for (int q = 0; q < 2; ++q) t2[q] = (up2 ? t4[q + 2] : t4[q]) + uint32_t(__shfl_xor(int(up2 ? t4[q] : t4[q + 2]), 4, 64));
-		const uint32_t mine = (up3 ? t2[1] : t2[0]) + uint32_t(__shfl_xor(int(up3 ? t2[0] : t2[1]), 8, 64));
-		float result = 0.f;
-#pragma unroll
-		for (int j = 0; j < 16; ++j) {   // result += (float)lane[j], j = 0 .. 15
-			const int holder = (j >> 3) + 2 * ((j >> 2) & 1) + 4 * ((j >> 1) & 1) + 8 * (j & 1);
-			result += float(uint32_t(__shfl(int(mine), group_base + holder, 64)));
-		}
-		result = result + 0.f;   // + (float)tail, tail == 0: dim is a multiple of 64 (x + 0.f == x for every x the sum can take)
-		float dist;
-		if constexpr (kMetric == kL2) {
-			dist = p.alpha2 * result + qcorr + p.corr[row];
-		} else {
-			dist = -(p.alpha2 * result + qcorr + p.corr[row]);
-			if constexpr (kMetric == kCos) dist *= p.inv_norms[row];
-		}
-		dist = qnorm * dist;
-		if (ok && m == 0) dists[idx] = dist;
-	}
-}
-
-// dim == 64*NB: the query fragment lives in registers and the NB 16-byte loads of EIGHT rows (two per 16-lane group) are
-// issued before the first reduction — one HBM round trip per 8 neighbours instead of three per 4.
-// kQLds: the query fragment is re-read from LDS (ds_read_b128) instead of living in NB*4 VGPRs — 48 fewer registers at D = 768, which is
-// what lets four of these wavefronts (instead of two) share a SIMD: the search is latency-bound, occupancy is throughput.
-template <int kMetric, int NB, bool kQLds, bool kTwoSets>
-__device__ __forceinline__ void batch_distances_fixed(const HnswParams& p, const float4 (&q)[kQLds ? 1 : NB], const float4* qlds, const uint32_t* ids,
-													  int cnt, float* dists, int lane) {
-	const int m = lane & 15, g = lane >> 4;
-	auto Q = [&](int t) -> float4 {
-		if constexpr (kQLds) {
-			return qlds[16 * t + m];
-		} else {
-			return q[t];
-		}
-	};
-	for (int base = 0; base < cnt; base += (kTwoSets ? 2 : 1) * kRowsPerWave) {
-		const int ia = base + g, ib = base + kRowsPerWave + g;
-		const bool oka = ia < cnt, okb = ib < cnt;
-		const uint64_t ra = ids[oka ? ia : base], rb = ids[okb ? ib : base];
-		const float4* pa = reinterpret_cast<const float4*>(p.rows + ra * p.stride) + m;
-		const float4* pb = reinterpret_cast<const float4*>(p.rows + rb * p.stride) + m;
-		float4 xa[NB], xb[NB];
-#pragma unroll
-		for (int t = 0; t < NB; ++t) xa[t] = pa[16 * t];
-		const bool second = kTwoSets && base + kRowsPerWave < cnt;   // wave-uniform; one row set per trip keeps the D = 768 kernel at 4+ waves per SIMD
-		if (second) {
-#pragma unroll
-			for (int t = 0; t < NB; ++t) xb[t] = pb[16 * t];
-		}
-		// cosine: 1 / |row| of the epilogue travels WITH the rows — read behind the scheduling barrier it was a dependent round trip of its
-		// own at the end of every distance trip
-		float inva = 1.0f, invb = 1.0f;
-		if constexpr (kMetric == kCos) {
-			inva = p.inv_norms[ra];
-			if (second) invb = p.inv_norms[rb];
-		}
-		__builtin_amdgcn_sched_barrier(0);
-		float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-		for (int t = 0; t < NB; ++t) chain_step<kMetric>(acc, Q(t), xa[t]);
-		const float da = 1.0f * metric_epilogue<kMetric>(fold_chains<false>(acc, nullptr, nullptr, 0, m) + 0.0f, &inva, 0);
-		if (oka && m == 0) dists[ia] = da;
-		if (second) {
-			acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-			for (int t = 0; t < NB; ++t) chain_step<kMetric>(acc, Q(t), xb[t]);
-			const float db = 1.0f * metric_epilogue<kMetric>(fold_chains<false>(acc, nullptr, nullptr, 0, m) + 0.0f, &invb, 0);
-			if (okb && m == 0) dists[ib] = db;
-		}
-	}
-}
-
-// dim == 64*NB, NB > 12 (1024 and 1536 floats): a whole row set of NB float4 a lane (96 VGPRs at NB = 24) does not fit beside the search's
-// own state, so the NB loads of a row are cut into chunks of kChunk and the loads of chunk c + 1 are issued before chunk c is reduced: two
-// chunks of a row set are in flight or in registers at any time.  The ONE accumulator runs through the chunks in block order —
-// acc = chain_step(acc, Q(t), x[t]) for t = 0 .. NB - 1, the sequence batch_distances_fixed and the generic batch compute — and is folded once.
-// The latency, team and resident forms (one or two wavefronts per SIMD anyway) take two row sets in chunks of 8: 128 VGPRs of rows, 2 and 3 chunks.
-// The throughput form takes one set in chunks of 4 (32 VGPRs of rows, 4 and 6 chunks): 87 - 99 VGPRs in all, where chunks of 8 came to
-// 131 - 141 and, held to 128 by __launch_bounds__, spilled.  The query fragment is always read from LDS.
-template <int kMetric, int NB, bool kTwoSets, int kChunk = 8>
-__device__ __forceinline__ void batch_distances_wide(const HnswParams& p, const float4* qlds, const uint32_t* ids, int cnt, float* dists, int lane) {
-	static_assert(NB > kChunk && NB % kChunk == 0, "whole chunks, at least two");
-	constexpr int kChunks = NB / kChunk;
-	const int m = lane & 15, g = lane >> 4;
-	for (int base = 0; base < cnt; base += (kTwoSets ? 2 : 1) * kRowsPerWave) {
-		const int ia = base + g, ib = base + kRowsPerWave + g;
-		const bool oka = ia < cnt, okb = ib < cnt;
-		const uint64_t ra = ids[oka ? ia : base], rb = ids[okb ? ib : base];
-		const float4* pa = reinterpret_cast<const float4*>(p.rows + ra * p.stride) + m;
-		const float4* pb = reinterpret_cast<const float4*>(p.rows + rb * p.stride) + m;
-		const bool second = kTwoSets && base + kRowsPerWave < cnt;   // wave-uniform
-		float4 xa[2][kChunk], xb[2][kChunk];
-#pragma unroll
-		for (int t = 0; t < kChunk; ++t) xa[0][t] = pa[16 * t];
-		if (second) {
-#pragma unroll
-			for (int t = 0; t < kChunk; ++t) xb[0][t] = pb[16 * t];
-		}
-		float inva = 1.0f, invb = 1.0f;   // cosine: 1 / |row| travels with the first chunk (see batch_distances_fixed)
-		if constexpr (kMetric == kCos) {
-			inva = p.inv_norms[ra];
-			if (second) invb = p.inv_norms[rb];
-		}
-		float4 acca = make_float4(0.f, 0.f, 0.f, 0.f), accb = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-		for (int c = 0; c < kChunks; ++c) {
-			if (c + 1 < kChunks) {   // the next chunk's loads go out before this chunk is reduced
-#pragma unroll
-				for (int t = 0; t < kChunk; ++t) xa[(c + 1) & 1][t] = pa[16 * (kChunk * (c + 1) + t)];
-				if (second) {
-#pragma unroll
-					for (int t = 0; t < kChunk; ++t) xb[(c + 1) & 1][t] = pb[16 * (kChunk * (c + 1) + t)];
-				}
-			}
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for (int t = 0; t < kChunk; ++t) chain_step<kMetric>(acca, qlds[16 * (kChunk * c + t) + m], xa[c & 1][t]);
-			if (second) {
-#pragma unroll
-				for (int t = 0; t < kChunk; ++t) chain_step<kMetric>(accb, qlds[16 * (kChunk * c + t) + m], xb[c & 1][t]);
-			}
-			__builtin_amdgcn_sched_barrier(0);
-		}
-		const float da = 1.0f * metric_epilogue<kMetric>(fold_chains<false>(acca, nullptr, nullptr, 0, m) + 0.0f, &inva, 0);
-		if (oka && m == 0) dists[ia] = da;
-		if (second) {
-			const float db = 1.0f * metric_epilogue<kMetric>(fold_chains<false>(accb, nullptr, nullptr, 0, m) + 0.0f, &invb, 0);
-			if (okb && m == 0) dists[ib] = db;
-		}
-	}
-}
-
-// The node of the nearest entry that is not expanded yet (what pop() would return next if nothing nearer is inserted before), or
-// 0xFFFFFFFF: the search prefetches that node's link block while the current hop's distances are computed.
-template <typename List, int S>
-__device__ __forceinline__ uint32_t hnsw_peek_open(const List& list) {
-	const int e = list.first_open();
-	if (e < 0) return 0xFFFFFFFFu;
-	uint32_t iv = list.id[0];
-#pragma unroll
-	for (int s = 1; s < S; ++s) iv = (e >> 6) == s ? list.id[s] : iv;
-	return uint32_t(__builtin_amdgcn_readlane(int(iv), e & 63));
-}
-
-// the node of list entry e (wave-uniform e >= 0)
-template <typename List, int S>
-__device__ __forceinline__ uint32_t hnsw_node_at(const List& list, int e) {
-	uint32_t iv = list.id[0];
-#pragma unroll
-	for (int s = 1; s < S; ++s) iv = (e >> 6) == s ? list.id[s] : iv;
-	return uint32_t(__builtin_amdgcn_readlane(int(iv), e & 63));
-}
-
 typedef __attribute__((address_space(3))) void hnsw_lds_void;
-// "Seen before?" of the reference's visited list (vl_type tags, hnswalg.h:904-931), as test-and-set.  Bitset: one atomicOr.  Hash set
-// (HnswParams::vis_hash_log2): linear probing with compare-and-swap on node + 1; the neighbours a wavefront tests together are distinct
-// nodes, two lanes can only meet on an EMPTY slot and the CAS settles that.  The table is at most half full (the callers check), so a probe
-// sequence ends.  Its 32 KB stay in the L2 / Infinity Cache for the life of the search, where a bitset over 10M nodes (1.25 MB per
-// search, 6 GB for the searches in flight) sends every test to HBM.
-__device__ __forceinline__ bool hnsw_visit(uint32_t* visited, uint32_t hash_log2, uint32_t id) {
-	if (hash_log2 == 0) {
-		const uint32_t bit = 1u << (id & 31);
-		return !(atomicOr(&visited[id >> 5], bit) & bit);
-	}
-	const uint32_t mask = (1u << hash_log2) - 1u, key = id + 1u;
-	uint32_t h = (id * 2654435761u) >> (32u - hash_log2);
-	for (;;) {
-		const uint32_t old = atomicCAS(&visited[h], 0u, key);
-		if (old == 0u) return true;
-		if (old == key) return false;
-		h = (h + 1u) & mask;
-	}
-}
-
-// the latency form may keep the hash set in LDS (HnswParams::vis_lds): same probing, a ds_cmpst_rtn instead of a global atomic.  (Its own
-// function, without the bitset branch: sharing hnsw_visit let the compiler merge the two bitset paths into ONE flat_atomic_or.)
-__device__ __forceinline__ bool hnsw_visit_lds(uint32_t* table, uint32_t hash_log2, uint32_t id) {
-	const uint32_t mask = (1u << hash_log2) - 1u, key = id + 1u;
-	uint32_t h = (id * 2654435761u) >> (32u - hash_log2);
-	for (;;) {
-		const uint32_t old = atomicCAS(&table[h], 0u, key);
-		if (old == 0u) return true;
-		if (old == key) return false;
-		h = (h + 1u) & mask;
-	}
-}
-// "seen before?" WITHOUT the mark (the speculative distance batch of a team search looks ahead at a candidate's neighbours, but only the
-// expansion itself may mark them)
-__device__ __forceinline__ bool hnsw_seen(const uint32_t* visited, uint32_t hash_log2, uint32_t id) {
-	if (hash_log2 == 0) return ((__hip_atomic_load(&visited[id >> 5], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >> (id & 31)) & 1u) != 0u;
-	const uint32_t mask = (1u << hash_log2) - 1u, key = id + 1u;
-	uint32_t h = (id * 2654435761u) >> (32u - hash_log2);
-	for (;;) {
-		const uint32_t v = __hip_atomic_load(&visited[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (v == key) return true;
-		if (v == 0u) return false;
-		h = (h + 1u) & mask;
-	}
-}
-__device__ __forceinline__ bool hnsw_seen_lds(const uint32_t* table, uint32_t hash_log2, uint32_t id) {
-	const uint32_t mask = (1u << hash_log2) - 1u, key = id + 1u;
-	uint32_t h = (id * 2654435761u) >> (32u - hash_log2);
-	for (;;) {
-		const uint32_t v = table[h];
-		if (v == key) return true;
-		if (v == 0u) return false;
-		h = (h + 1u) & mask;
-	}
-}
-template <bool kLds>
-__device__ __forceinline__ bool hnsw_visit_sel(uint32_t* visited, uint32_t* lds_vis, bool use_lds, uint32_t hash_log2, uint32_t id) {
-	if constexpr (kLds) {
-		if (use_lds) return hnsw_visit_lds(lds_vis, hash_log2, id);
-	}
-	return hnsw_visit(visited, hash_log2, id);
-}
 
 // kLatency: few queries in flight -> two row sets per distance trip (fewer dependent round trips per hop, 172 VGPRs at D = 768);
 // otherwise one set (92 VGPRs: twice the resident searches).  D <= 512 always affords two.
@@ -735,12 +111,19 @@ __device__ __forceinline__ void team_slice(int cnt, int wave, int& begin, int& n
 	if (n < 0) n = 0;
 }
 #define HN_SYNC() hn_sync<kTeam>()
+// (One function on purpose, for now: prologue, descent, layer 0 on the sorted list — with its look-ahead hop —, layer 0 on the heaps, store.
+// Taking the descent, the insertion loop and the two stores out as __forceinline__ functions of their own, with the same statements, changed
+// the machine code of every kernel that runs this — about a thousand lines of each — and so did one shared loop for the three "fetch a link
+// block, test-and-mark, compact" sites; a full split over a shared state struct left one resident kernel spilling 8 VGPRs
+// (tools/compare_kernel_isa.py, tests/test_hnsw_wide_rows_resources.py).  A split has to be measured on the device against this form, not
+// assumed equal.)
 template <int kMetric, bool kGlobalCand, int NB, bool kLatency, bool kSq8 = false, int kSorted = 0, bool kDel = false, int kTeam = 1>
 __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint32_t slot, const uint32_t qi, HnswTeamBox* box = nullptr) {
 	static_assert(kTeam == 1 || (NB > 0 && !kSq8 && !kGlobalCand), "the team form serves the fixed-dimension float search with its heaps in LDS");
 	static_assert(kSorted == 0 || !kGlobalCand, "the sorted-list search starts in LDS; its re-runs with a global heap are heap-kernel launches");
 	// dynamic LDS: [ef_cap] result heap (dist, id) then [lds_cand_cap] candidate heap (dist, id) — sized by the launcher so that
-	// small-ef searches keep more wavefronts resident per CU
+	// small-ef searches keep more wavefronts resident per CU.  (The areas of hnsw_lds_layout, spelled out: asking that function here, as
+	// hnsw_team_serve does, moved the query loads of 45 SQ8 kernels — tools/compare_kernel_isa.py.)
 	extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_lds[];
 	uint2* top = reinterpret_cast<uint2*>(hnsw_lds);   // (dist bits, id) entries
 	uint2* lcand = top + p.ef_cap;
@@ -1313,7 +696,8 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 template <int kMetric, int NB, int kTeam>
 __device__ __forceinline__ void hnsw_team_serve(const HnswParams& p, const HnswTeamBox* box) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char hnsw_lds[];
-	const float4* q_s = reinterpret_cast<const float4*>(reinterpret_cast<uint2*>(hnsw_lds) + p.ef_cap + p.lds_cand_cap);   // as hnsw_search_one lays it out
+	const HnswLdsLayout at = hnsw_lds_layout(p.ef_cap, p.lds_cand_cap, false, NB, false);
+	const float4* q_s = reinterpret_cast<const float4*>(reinterpret_cast<uint2*>(hnsw_lds) + at.top + at.cand);
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	float4 qreg[1];
 	for (;;) {

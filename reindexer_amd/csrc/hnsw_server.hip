@@ -1,4 +1,5 @@
 // The resident HNSW search kernel (protocol: HnswServer, knn_kernels.hip.h; host side: rxgpu_hnsw_server.hip).
+#include "hnsw_dispatch.hip.h"
 #include "hnsw_search_core.hip.h"
 
 namespace rxgpu {
@@ -153,115 +154,49 @@ __global__ __launch_bounds__(64) void hnsw_server_sq8_kernel(HnswParams p, HnswS
 	}
 }
 
-// The resident kernel exists for the embedding sizes with a fixed-dimension distance batch and ef <= 256 (224 with deleted nodes); everything
-// else keeps the launches.  p: ef_cap / lds_cand_cap as for a team launch, vis_lds_log2 = the size of a hash set in LDS (0: the set is in HBM).
-// dynamic LDS of a server workgroup: heaps + query fragment + visited set, then (what fits under 60 KB) the link-block area and the look-ahead area
-constexpr size_t kServerLdsLimit = size_t(150) << 10;   // one workgroup per CU: it may take most of the CU's 160 KB (the launcher raises the kernel's limit)
-static size_t server_layout(const HnswParams& p, uint32_t* nbl_off, uint32_t* spec_off) {
-	size_t at = (size_t(p.ef_cap) + p.lds_cand_cap) * 8 + size_t(p.dim / 64) * 256 + (p.vis_lds_log2 ? (size_t(4) << p.vis_lds_log2) : 0);
-	*nbl_off = *spec_off = 0u;
-	if (p.nbl && !p.spec && p.maxM0 < 64u && at + kHnswNblBytes <= kServerLdsLimit) {   // (the look-ahead experiment keeps link blocks of its own)
-		*nbl_off = uint32_t(at);
-		at += kHnswNblBytes;
-	}
-	if (p.spec && p.bare && p.maxM0 < 64u && at + kHnswSpecBytes <= kServerLdsLimit) {
-		*spec_off = uint32_t(at);
-		at += kHnswSpecBytes;
-	}
-	return at;
-}
+// dynamic LDS of a float server workgroup (pick_hnsw_server: what its first gate measures, whatever the row format)
 size_t hnsw_server_lds_bytes(const HnswParams& p) {
-	uint32_t a, b;
-	return server_layout(p, &a, &b);
-}
-template <int NB, int kSorted, bool kDel>
-static void launch_hnsw_server_nb(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	HnswParams ps = p;
-	const size_t lds = server_layout(p, &ps.nbl_off, &ps.spec_off);
-#define RX_SERVER(M)                                                                                                                       \
-	do {                                                                                                                                   \
-		static std::atomic<uint64_t> raised{0};                                                                                            \
-		if constexpr (NB > 12) {                                                                                                           \
-			if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_wide_kernel<M, NB, kSorted, kDel, 4>), kServerLdsLimit); \
-			hipLaunchKernelGGL((hnsw_server_wide_kernel<M, NB, kSorted, kDel, 4>), dim3(slots), dim3(256), lds, s, ps, sv);                 \
-		} else {                                                                                                                           \
-			if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_kernel<M, NB, kSorted, kDel, 4>), kServerLdsLimit); \
-			hipLaunchKernelGGL((hnsw_server_kernel<M, NB, kSorted, kDel, 4>), dim3(slots), dim3(256), lds, s, ps, sv);                      \
-		}                                                                                                                                  \
-	} while (0)
-	switch (metric) {
-		case kL2: RX_SERVER(kL2); break;
-		case kIP: RX_SERVER(kIP); break;
-		default: RX_SERVER(kCos); break;
-	}
-#undef RX_SERVER
-}
-template <int NB>
-static void launch_hnsw_server_dim(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	const bool wide = p.ef_cap > 128u;   // the second mailbox of an index: lists of four entries a lane
-	if (p.bare) {
-		wide ? launch_hnsw_server_nb<NB, 4, false>(metric, p, sv, slots, s) : launch_hnsw_server_nb<NB, 2, false>(metric, p, sv, slots, s);
-	} else {
-		wide ? launch_hnsw_server_nb<NB, 4, true>(metric, p, sv, slots, s) : launch_hnsw_server_nb<NB, 2, true>(metric, p, sv, slots, s);
-	}
-}
-// The mailbox over codes: one wavefront a slot, heaps (a search that starts over) and — class 0 — the visited set in dynamic LDS.
-template <int NB, int kSorted, bool kDel>
-static void launch_hnsw_server_sq8_nb(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	const size_t lds = (size_t(p.ef_cap) + p.lds_cand_cap) * 8 + (p.vis_lds_log2 ? (size_t(4) << p.vis_lds_log2) : 0);
-#define RX_SERVER(M)                                                                                                                       \
-	do {                                                                                                                                   \
-		static std::atomic<uint64_t> raised{0};                                                                                            \
-		if (lds > (size_t(60) << 10)) (void)raise_dynamic_lds_once(raised, reinterpret_cast<const void*>(&hnsw_server_sq8_kernel<M, NB, kSorted, kDel>), kServerLdsLimit); \
-		hipLaunchKernelGGL((hnsw_server_sq8_kernel<M, NB, kSorted, kDel>), dim3(slots), dim3(64), lds, s, p, sv);                           \
-	} while (0)
-	switch (metric) {
-		case kL2: RX_SERVER(kL2); break;
-		case kIP: RX_SERVER(kIP); break;
-		default: RX_SERVER(kCos); break;
-	}
-#undef RX_SERVER
-}
-template <int NB, bool kDel>
-static void launch_hnsw_server_sq8_dim(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	p.ef_cap > 128u ? launch_hnsw_server_sq8_nb<NB, 4, kDel>(metric, p, sv, slots, s) : launch_hnsw_server_sq8_nb<NB, 2, kDel>(metric, p, sv, slots, s);
+	HnswPickInput in = hnsw_pick_input(p, 0u, false);
+	in.sq8 = false;
+	return pick_hnsw_server(in).lds_bytes;
 }
 // the embedding sizes with a fixed-dimension SQ8 distance batch (hnsw_distance_blocks.h): six for a bare graph, two with deleted nodes
-bool hnsw_server_sq8_serves(uint32_t dim, bool bare) { return hnsw_mailbox_serves(dim, true, !bare); }
-static bool launch_hnsw_server_sq8(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	if (!hnsw_server_sq8_serves(p.dim, p.bare != 0) || !p.corr || !p.qcodes || !p.qcorr || !p.qnorm) return false;
-	if (p.bare) {
-		switch (hnsw_distance_blocks(p.dim, true, false)) {
-			case 2: launch_hnsw_server_sq8_dim<2, false>(metric, p, sv, slots, s); return true;
-			case 6: launch_hnsw_server_sq8_dim<6, false>(metric, p, sv, slots, s); return true;
-			case 8: launch_hnsw_server_sq8_dim<8, false>(metric, p, sv, slots, s); return true;
-			case 12: launch_hnsw_server_sq8_dim<12, false>(metric, p, sv, slots, s); return true;
-			case 16: launch_hnsw_server_sq8_dim<16, false>(metric, p, sv, slots, s); return true;
-			default: launch_hnsw_server_sq8_dim<24, false>(metric, p, sv, slots, s); return true;
-		}
-	}
-	if (hnsw_distance_blocks(p.dim, true, true) == 2) {
-		launch_hnsw_server_sq8_dim<2, true>(metric, p, sv, slots, s);
-	} else {
-		launch_hnsw_server_sq8_dim<12, true>(metric, p, sv, slots, s);
-	}
+bool hnsw_server_sq8_serves(uint32_t dim, bool bare) {
+	HnswPickInput in{};
+	in.dim = dim;
+	in.bare = bare;
+	in.sq8 = true;
+	return pick_hnsw_server(in).nb != 0;
+}
+// The resident kernel of a mailbox (pick_hnsw_server has the classes and the gates); false: this call has no resident form.
+bool launch_hnsw_server(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
+	const HnswKernelPick k = pick_hnsw_server(hnsw_pick_input(p, slots, false));
+	if (!k.served) return false;
+	const HnswParams pk = hnsw_patched(p, k);
+	const bool launched = with_metric(metric, [&](auto m) {
+		return with_int<2, 6, 8, 12, 16, 24>(k.nb, [&](auto nb) {
+			return with_int<2, 4>(k.sorted, [&](auto sorted) {
+				return with_bool(k.del, [&](auto del) {
+					constexpr int M = decltype(m)::value, NB = decltype(nb)::value, S = decltype(sorted)::value;
+					constexpr bool D = decltype(del)::value;
+					if (k.family == kHnswServerSq8) {
+						if constexpr (hnsw_server_kernel_exists(NB, true, S, D)) return hnsw_launch<&hnsw_server_sq8_kernel<M, NB, S, D>>(k, slots, s, pk, sv);
+						return false;
+					}
+					if constexpr (!hnsw_server_kernel_exists(NB, false, S, D)) {
+						return false;
+					} else if constexpr (NB > 12) {
+						return hnsw_launch<&hnsw_server_wide_kernel<M, NB, S, D, 4>>(k, slots, s, pk, sv);
+					} else {
+						return hnsw_launch<&hnsw_server_kernel<M, NB, S, D, 4>>(k, slots, s, pk, sv);
+					}
+				});
+			});
+		});
+	});
+	if (!launched) hnsw_no_kernel("server", metric, k);
 	return true;
 }
-// Two classes of resident kernel (an index may have one of each per row format, serving a mailbox of its own): ef <= 128 (96 with deleted
-// nodes) — lists of two entries a lane, the visited set in LDS — and ef <= 256 (224) — four entries a lane, the visited hash set of a slot in
-// HBM (p.visited: [slots][visited_words], zeroed by the search itself).  p.ef_cap says which: 128 or 256.  p.codes: the mailbox over SQ8 codes.
-bool launch_hnsw_server(int metric, const HnswParams& p, const HnswServer& sv, uint32_t slots, hipStream_t s) {
-	if (!p.sorted || hnsw_server_lds_bytes(p) > kServerLdsLimit) return false;
-	if (p.ef_cap <= 128u ? (!p.vis_lds || p.vis_lds_log2 > 14) : (p.vis_lds || p.vis_lds_log2 || !p.visited || p.vis_hash_log2 < 14)) return false;
-	if (p.codes) return launch_hnsw_server_sq8(metric, p, sv, slots, s);
-	switch (hnsw_distance_blocks(p.dim, false, p.bare == 0)) {
-		case 2: launch_hnsw_server_dim<2>(metric, p, sv, slots, s); return true;
-		case 8: launch_hnsw_server_dim<8>(metric, p, sv, slots, s); return true;
-		case 12: launch_hnsw_server_dim<12>(metric, p, sv, slots, s); return true;
-		case 16: launch_hnsw_server_dim<16>(metric, p, sv, slots, s); return true;
-		case 24: launch_hnsw_server_dim<24>(metric, p, sv, slots, s); return true;
-		default: return false;
-	}
-}
+
 
 }  // namespace rxgpu

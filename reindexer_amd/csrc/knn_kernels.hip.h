@@ -22,7 +22,7 @@
 
 #include "knn_emit_plan.h"     // EmitEntry, EmitPlan: where knn_scan_i8 puts the rows it emits
 #include "hnsw_launch_plan.h"   // kHnswMaxEf, kHnswLdsCandEf, kHnswCandLds, kHnswSortedMaxEf, kHnswSortedMaxEfDel: the constants the host-side policy reads too
-#include "hnsw_distance_blocks.h"   // hnsw_distance_blocks: which embedding sizes have a fixed-dimension distance batch
+#include "hnsw_kernel_pick.h"   // kHnswNblBytes, kHnswSpecBytes, kHnswNblRows, kHnswSpecLog2, hnsw_lds_layout; through it hnsw_distance_blocks.h: which embedding sizes have a fixed-dimension distance batch
 
 namespace rxgpu {
 
@@ -172,10 +172,6 @@ struct GemmBf16Params {
 
 constexpr int kHnswMaxNeighbors = 128;  // 2*M <= 128
 constexpr uint32_t kHnswOverflow = 0xFFFFFFFFu;
-constexpr uint32_t kHnswSpecLog2 = 11;   // speculative team search: 2048-entry direct-mapped table of distances computed ahead of time
-constexpr uint32_t kHnswSpecBytes = (2u << kHnswSpecLog2) * 4 + (128 + 3 * 64) * 4;   // table + two link blocks + the trip's id / distance / destination arrays
-constexpr int kHnswNblRows = 32;             // team searches: link blocks fetched along with a hop's rows (one 64-word slot each)
-constexpr uint32_t kHnswNblBytes = kHnswNblRows * 64 * 4;
 constexpr uint32_t kHnswTie = 0xFFFFFFFEu;        // sorted-list search met equal keys: re-run on the heap kernel
 
 struct HnswParams {

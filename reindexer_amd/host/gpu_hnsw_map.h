@@ -70,8 +70,8 @@ public:
 	// on that shard's GPU (one rxgpu_index_create_sharded handle owns the N device indexes).  SearchKnn runs every shard's search at once and
 	// the per-shard results meet in the same ncclAllGather + (dist, global row) merge as brute force (rxgpu_hnsw_search_knn on the sharded
 	// handle): the k best of the union of the per-shard engine results, recall >= the single graph's at equal ef.  SQ8 (one quantiser for the Map, a
-	// code table per shard) and streaming sessions (a session per shard, merged batch by batch) work over a device list too; the ANN disk
-	// cache does not (it reports "not available").
+	// code table per shard), streaming sessions (a session per shard, merged batch by batch) and the ANN disk cache (a graph per shard in a
+	// stream of its own shape: SaveIndex / LoadIndex below) work over a device list too.
 	GpuHnswMap(VectorMetric metric, size_t dim, size_t maxElements, size_t M, size_t efConstruction, std::vector<int> devices,
 			   Synchronization synchronization = Synchronization::None);
 	GpuHnswMap(const GpuHnswMap& other, size_t newCapacity);

@@ -1,4 +1,4 @@
-"""-m gpu: the sorted-list form of the HNSW search (HnswSortedList in hnsw_search.hip) — graphs without deleted nodes, ef <= 256.
+"""-m gpu: the sorted-list form of the HNSW search (HnswSortedList in reindexer_amd/csrc/hnsw_sorted_list.hip.h) — graphs without deleted nodes, ef <= 256.
 Bar: the same labels and distance bits as the kernel that replays the reference's binary heaps, and as the restated engine; a query that
 meets EQUAL distances is handed to the heap kernel (the reference's order among equal keys is its sift order), which the tie counter shows."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""-m gpu: the visited set of an HNSW search as a HASH SET sized by ef (hnsw_visit in hnsw_search.hip; the reference's visited list is a
+"""-m gpu: the visited set of an HNSW search as a HASH SET sized by ef (hnsw_visit in hnsw_visited.hip.h; the reference's visited list is a
 tag array over all nodes, visited_list_pool.h:13-36 — the semantics are "seen before", hnswalg.h:904-931) instead of a bitset over the
 nodes zeroed by a memset in front of every launch.  Bar: the same answers as the bitset path, bit for bit, the same number of distance
 evaluations and hops (= the same traversal); a search that would fill the set leaves as an overflow and is re-run on the bitset; the

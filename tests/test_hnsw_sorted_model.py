@@ -1,4 +1,4 @@
-"""CPU: the rule set of the sorted-list HNSW search (HnswSortedList in reindexer_amd/csrc/hnsw_search.hip), restated in Python and run
+"""CPU: the rule set of the sorted-list HNSW search (HnswSortedList in reindexer_amd/csrc/hnsw_sorted_list.hip.h), restated in Python and run
 against the C restatement of the reference's two-heap search (oracle/oracle_hnsw.c) on graphs FULL of equal distances.
 
 The device kernel keeps top_candidates + candidate_set as one sorted list and claims: unless it raises its tie flag, pops, evictions and
