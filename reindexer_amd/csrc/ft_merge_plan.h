@@ -16,12 +16,22 @@
 
 #include "rxgpu.h"
 
+#if defined(__HIPCC__)
+#define RX_FT_HD __host__ __device__
+#else
+#define RX_FT_HD
+#endif
+
 namespace rxgpu {
 
 constexpr int kFtPassItems = 4;            // postings per thread in the posting-side kernels
 constexpr uint32_t kFtRangeDocs = 8192;    // documents per workgroup of the document-range kernel (ft_ranges); multiple of 32
 constexpr int kFtBlockPostings = 256 * kFtPassItems;
 inline uint32_t ft_pass_blocks(uint64_t n) { return uint32_t((n + kFtBlockPostings - 1) / kFtBlockPostings); }
+constexpr int kFtApplyWords = 4;           // mask words per thread in ft_preselect_apply
+// workgroups of ft_preselect_apply over `nwords` mask words = the words of its look-back chain (FtCleanLayout::lb_pre, zeroed by ft_adders)
+RX_FT_HD inline uint64_t ft_apply_blocks(uint64_t nwords) { return (nwords + 256 * kFtApplyWords - 1) / (256 * kFtApplyWords); }
+constexpr int kFtRankTiles = 2;            // tiles of kFtBlockPostings postings per workgroup of ft_rank_all
 constexpr uint32_t kFtSparseSubs = 16;     // sub-terms (NOT terms' included) a sparse merge holds bitmaps for
 constexpr uint32_t kFtHistCopies = 8, kFtHistStride = 65536 + 1024;
 constexpr uint32_t kFtSyncWords = 16;      // the kFtSync* words of a merge (rxgpu_internal.h names them)
@@ -389,7 +399,7 @@ inline void ft_plan_layouts(const FtMergeFacts& f, const FtStructSizes& sz, FtMe
 	FtCleanLayout& c = p.clean;
 	FtCarver cc;
 	c.hist = cc.region(size_t(kFtHistCopies) * kFtHistStride * 4);   // copies of (fine + coarse)
-	c.lb_pre = cc.region(((nwords + 1023) / 1024) * 8);
+	c.lb_pre = cc.region(ft_apply_blocks(nwords) * 8);
 	c.bcnt = cc.region(size_t(n_ranges) * 4);
 	c.sync = cc.region(kFtSyncWords * 4);
 	c.dbg = cc.region(64 * 8);
@@ -567,5 +577,103 @@ struct FtNoPhrases {
 };
 
 #undef RX_PLAN_CHECK
+
+// ---------------------------------------------------------------------------------------------------------------------- the dense train
+// The merge slot of the first document of (row, range) = the entries of ft_adders' table in front of it, in row-major order.  Up to
+// kFtFinishRows merged sub-terms (and 8192 entries) the table is small and every workgroup of ft_finish adds up its own bases (one pass, all
+// rows at once); larger queries run ft_slot_bases, which turns the table into its prefix.
+constexpr uint32_t kFtFinishRows = 16;
+constexpr uint32_t kFtSparseRecords = 768;   // buckets up to this size are replayed from an LDS copy of their records
+constexpr uint32_t kFtSparsePostings = 6;    // ... if no document of theirs has more postings than this
+constexpr uint32_t kFtSparseHeads = 512;     // chain heads of that copy (by the low bits of the document)
+constexpr uint32_t kFtBitmapRows = 8;        // up to this many merged sub-terms ft_finish ranks the first postings with per-row bitmaps instead of a sort
+template <typename Plan>
+RX_FT_HD inline bool ft_own_bases(const Plan& p) { return p.n_rows <= kFtFinishRows && uint64_t(p.n_rows) * p.n_ranges <= kFtRangeDocs; }
+// ft_finish's compact layout (16-bit slots, 32 KB of LDS, 4 workgroups per CU): up to kFtBitmapRows merged sub-terms and mergeLimit below 65535
+template <typename Plan>
+RX_FT_HD inline bool ft_finish_compact(const Plan& p) { return p.n_rows <= kFtBitmapRows && p.max_merged < 0xFFFFu; }
+
+// ft_finish's dynamic LDS, in 32-bit words from its start.  One block, carved twice: the sorted layout (document table + key list) and the
+// compact one (slots + per-row bitmaps + their prefixes); the table of ft_adders lies at the start of the key list / of the block while the
+// row bases are summed, and the sparse-bucket replay overlays what the slots leave idle.
+struct FtFinishLds {
+	static constexpr uint32_t kBitmapWords = kFtBitmapRows * (kFtRangeDocs / 32);
+	// sorted layout
+	static constexpr uint32_t tab = 0;                                   // [kFtRangeDocs] halves: first row of every document, then its position in the key list
+	static constexpr uint32_t keys = tab + kFtRangeDocs / 2;             // [kFtRangeDocs] (row << 13 | document) of the first postings, then their slots
+	static constexpr uint32_t words = keys + kFtRangeDocs;
+	// compact layout
+	static constexpr uint32_t slot = 0;                                  // [kFtRangeDocs] halves: first row, then the slot
+	static constexpr uint32_t bits = slot + kFtRangeDocs / 2;            // [kFtBitmapRows][256]
+	static constexpr uint32_t pref = bits + kBitmapWords;                // [kFtBitmapRows][256]
+	static constexpr uint32_t words_few = pref + kBitmapWords;
+	// the table of ft_adders while the bases are summed (ft_own_bases: at most kFtRangeDocs entries)
+	RX_FT_HD static constexpr uint32_t table(bool compact) { return compact ? 0u : keys; }
+	// sparse-bucket overlay: behind the 16-bit slots / inside the idle tail of the key list (its slots are no more than the bucket's records)
+	RX_FT_HD static constexpr uint32_t sparse(bool compact) { return compact ? bits : kFtRangeDocs; }
+	static constexpr uint32_t sparse_rec = 0;                                     // [kFtSparseRecords] uint4
+	static constexpr uint32_t sparse_head = sparse_rec + kFtSparseRecords * 4;    // [kFtSparseHeads]
+	static constexpr uint32_t sparse_todo = sparse_head + kFtSparseHeads;         // [kFtSparseRecords] halves
+	static constexpr uint32_t sparse_words = sparse_todo + kFtSparseRecords / 2;
+	static constexpr size_t bytes = size_t(words) * 4, bytes_few = size_t(words_few) * 4;
+};
+static_assert(FtFinishLds::bytes == 48 * 1024 && FtFinishLds::bytes_few == 32 * 1024, "ft_finish: 48 KB, 32 KB in the compact layout");
+static_assert(FtFinishLds::table(false) + kFtRangeDocs <= FtFinishLds::words && FtFinishLds::table(true) + kFtRangeDocs <= FtFinishLds::words_few,
+			  "the table of ft_adders fits both layouts");
+static_assert(FtFinishLds::keys + kFtSparseRecords <= FtFinishLds::sparse(false), "the slots of a sparse bucket end in front of its overlay");
+static_assert(FtFinishLds::sparse(false) + FtFinishLds::sparse_words <= FtFinishLds::words &&
+				  FtFinishLds::sparse(true) + FtFinishLds::sparse_words <= FtFinishLds::words_few,
+			  "the sparse-bucket overlay fits both layouts");
+static_assert(kFtSparseRecords <= 1023, "a record index and the end marker fit ten bits");
+
+// What the dense train launches for Q merges over one index (grid.y = query): a grid of 0 means the kernel is not launched.
+//   * a document-range shard (range_count != 0, Q == 1) runs its own ranges and mask words only,
+//   * phase < 0 launches the whole train, 0 / 1 / 2 the piece a sharded merge exchanges between,
+//   * one grid serves the batch: the widest query sets ft_rank_all's, any query that needs ft_preselect_apply / ft_slot_bases / ft_finish's
+//     large layout sets it for all (the kernels return at once for the queries that do not).
+struct FtTrainLaunch {
+	uint32_t nq = 0;
+	uint32_t syn_grid = 0;       // ft_syn_masks (a query with multi-word synonyms runs alone: the caller's rule)
+	uint32_t ranges_grid = 0;    // ft_ranges
+	uint32_t apply_blocks = 0;   // ft_preselect_apply
+	uint32_t rank_blocks = 0;    // ft_rank_all
+	uint32_t adders_grid = 0;    // ft_adders
+	uint32_t bases_grid = 0;     // ft_slot_bases (one workgroup per query)
+	uint32_t finish_grid = 0;    // ft_finish ...
+	size_t finish_lds = 0;       // ... and its dynamic LDS
+};
+template <typename Plan>
+inline FtTrainLaunch ft_train_launch(const Plan* host_plans, uint32_t nq, int phase) {
+	FtTrainLaunch t;
+	t.nq = nq;
+	if (!nq) return t;
+	uint32_t rank_blocks = 0;
+	bool any_pre = false, any_bases = false, any_large = false;
+	for (uint32_t q = 0; q < nq; ++q) {
+		const Plan& p = host_plans[q];
+		any_large = any_large || !ft_finish_compact(p);
+		rank_blocks = std::max(rank_blocks, (uint32_t(p.merge_blocks) + kFtRankTiles - 1) / kFtRankTiles);
+		any_pre = any_pre || (!p.simple && p.prescore);
+		any_bases = any_bases || !ft_own_bases(p);
+	}
+	const Plan& p0 = host_plans[0];
+	const uint32_t ranges = p0.range_count ? p0.range_count : p0.n_ranges;
+	const uint64_t words = p0.range_count ? uint64_t(p0.range_count) * (kFtRangeDocs / 32) : p0.nwords;
+	if (phase < 0 || phase == 0) {
+		t.syn_grid = p0.n_syn_jobs ? p0.n_ranges : 0u;
+		t.ranges_grid = ranges;
+	}
+	if (phase < 0 || phase == 1) {
+		t.apply_blocks = any_pre ? uint32_t(ft_apply_blocks(words)) : 0u;
+		t.rank_blocks = rank_blocks;
+		t.adders_grid = ranges;
+	}
+	if (phase < 0 || phase == 2) {
+		t.bases_grid = any_bases ? 1u : 0u;
+		t.finish_grid = ranges;
+		t.finish_lds = any_large ? FtFinishLds::bytes : FtFinishLds::bytes_few;
+	}
+	return t;
+}
 
 }  // namespace rxgpu

@@ -1,6 +1,6 @@
 // Device-side calcTermRankImpl (cpp_src/core/ft/ft_fast/phrasemergerimpl.h:13-81) with the three calculators behind Bm25Calculator<BM>
 // (core/ft/bm25.h:8-68: Bm25Rx, Bm25Classic, TermCount — selected per merge like the selecter does from bm25Config.bm25Type,
-// selecterimpl.h:615-624) and the FTFieldConfig helpers (core/ft/config/ftconfig.h:127-148), used by the merge kernels (ft_merge.hip).
+// selecterimpl.h:615-624) and the FTFieldConfig helpers (core/ft/config/ftconfig.h:127-148), used by the merge kernels (ft_admit.hip, ft_sparse.hip, ft_phrase.hip).
 // P supplies the term / field configuration (FtTermCfg member names), S the posting arrays (FtPosSubterm; s.idf is the calculator's
 // IDF, computed on the host per sub-term).
 #pragma once

@@ -1,4 +1,4 @@
-// Device helpers shared by the two ft_fast merge trains (ft_merge.hip: the dense train; ft_sparse.hip: the train for sparsely hit document
+// Device helpers shared by the two ft_fast merge trains (ft_merge.hip and its kernel units: the dense train; ft_sparse.hip: the train for sparsely hit document
 // ranges): the plan in the constant address space, the pre-score threshold (mergerimpl.h:433-446), the positions distance
 // (mergerimpl.h:20-37) and the per-document replay of mergeTerm / mergeSimple / mergePhrase (mergerimpl.h:39-250).
 #pragma once

@@ -27,7 +27,7 @@
 //    whole-corpus single-term merge ranks its 20 000 merged documents, not its 600 000 postings, and no range is a straggler.
 //
 // Launch train: ft_sp_scan, [ft_sp_threshold, ft_sp_select — queries that may preselect: they come first in the batch], ft_slot_bases
-// (ft_merge.hip), [ft_sp_place — the others], ft_sp_replay.
+// (ft_admit.hip), [ft_sp_place — the others], ft_sp_replay.
 // Results are the dense train's to the bit (same float operations per document, same slots): tests/test_gpu_ft_sparse.py runs both.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -103,8 +103,8 @@ __device__ __forceinline__ void sp_open(FtPlanK& p, uint32_t* unit_lds, uint32_t
 		const auto& s = p.sp_sub[lane];
 		docp = s.doc;
 		c.attr = s.attr;
-		lo = range < s.n_ranges ? s.range_off[range] : s.n;
-		hi = range + 1 < s.n_ranges ? s.range_off[range + 1] : s.n;
+		lo = ft_seg_lo(s, range);
+		hi = ft_seg_hi(s, range);
 	}
 	c.lo = lo;
 #pragma unroll

@@ -214,7 +214,7 @@ struct HybridFuseArgs {
 hipError_t launch_hybrid_prepare(const HybridFuseArgs& a, hipStream_t st);   // FT only: may run while the KNN search is still going
 hipError_t launch_hybrid_join(const HybridFuseArgs& a, hipStream_t st);      // needs both halves
 
-// ft_fast merge (ft_merge.hip): Merger::mergeSimple / mergeTerm + restricting bitmask + preselect, restated ORDER-FREE so that a whole
+// ft_fast merge (ft_merge.hip and the units of its kernels): Merger::mergeSimple / mergeTerm + restricting bitmask + preselect, restated ORDER-FREE so that a whole
 // query is a fixed number of launches (see the header of ft_merge.hip)
 struct FtPosSubterm {
 	uint64_t n;
@@ -314,7 +314,7 @@ struct FtPlan {
 	unsigned long long* dbg;   // RXGPU_FT_STAMPS=<workgroup>: wall-clock stamps of that workgroup's phases (null otherwise)
 	uint32_t dbg_block;
 	uint32_t* sync;            // kFtSync* words; kept zero between merges (the last workgroup of ft_finish clears them)
-	unsigned long long* lookback_pre;     // [ceil(nwords / (256 * 4))]
+	unsigned long long* lookback_pre;     // [ft_apply_blocks(nwords)] (ft_merge_plan.h): one word per workgroup of ft_preselect_apply
 	// packed result: header (4 x u32: numDocs, error flag, preselected, 0) then doc[max_merged] u32, proc[max_merged] f32,
 	// terms_counter[max_merged] u16, field[max_merged] u8 — one D2H copy
 	uint32_t* out_header;
@@ -376,7 +376,15 @@ hipError_t launch_ft_merge_phase(const FtPlan* plans, const FtPlan* host_plans, 
 // the train for sparsely hit ranges (ft_sparse.hip) over nq plans that all have sparse = 1, those with prescore = 1 in front: ft_sp_scan,
 // [ft_sp_threshold, ft_sp_select], ft_slot_bases, [ft_sp_place], ft_sp_replay
 hipError_t launch_ft_merge_sparse(const FtPlan* plans, const FtPlan* host_plans, uint32_t nq, hipStream_t st);
-void launch_ft_slot_bases(const FtPlan* plans, uint32_t nq, hipStream_t st);   // ft_merge.hip
+// The kernels of the dense train, each launched from its own unit (the build has no relocatable device code); grid.y = query.  What the
+// train launches is ft_train_launch's decision (ft_merge_plan.h), ft_merge.hip executes it.
+void launch_ft_syn_masks(const FtPlan* plans, uint32_t ranges, hipStream_t st);                          // ft_ranges.hip
+void launch_ft_ranges(const FtPlan* plans, uint32_t ranges, uint32_t nq, hipStream_t st);
+void launch_ft_preselect_apply(const FtPlan* plans, uint32_t blocks, uint32_t nq, hipStream_t st);
+void launch_ft_rank_all(const FtPlan* plans, uint32_t blocks, uint32_t nq, hipStream_t st);              // ft_admit.hip
+void launch_ft_adders(const FtPlan* plans, uint32_t ranges, uint32_t nq, hipStream_t st);
+void launch_ft_slot_bases(const FtPlan* plans, uint32_t nq, hipStream_t st);
+hipError_t launch_ft_finish(const FtPlan* plans, uint32_t ranges, uint32_t nq, size_t lds_bytes, hipStream_t st);   // ft_finish.hip
 void launch_ft_shard_fold(const FtPlan* plan, uint32_t* dst, hipStream_t st);                                            // hist copies + popcount -> dst [kFtFoldWords]
 void launch_ft_shard_hist_combine(const FtPlan* plan, const uint32_t* gathered, const uint32_t* pos, uint32_t n_shards, hipStream_t st);   // gathered [..][kFtFoldWords]
 void launch_ft_shard_table_sum(uint32_t* table, const uint32_t* gathered, const uint32_t* pos, uint32_t n_shards, uint64_t n, uint64_t stride, hipStream_t st);   // gathered [..][stride]

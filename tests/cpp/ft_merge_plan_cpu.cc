@@ -203,6 +203,44 @@ void ft_out_layout_cpu(uint64_t max_merged, uint64_t* out) {
 	std::memcpy(out, v, sizeof(v));
 }
 
+// What the dense train launches (ft_train_launch) for nq host plans given as rows of nine facts:
+//   n_rows, max_merged, merge_blocks, simple, prescore, n_ranges, range_count, nwords, n_syn_jobs
+// out = {syn_grid, ranges_grid, apply_blocks, rank_blocks, adders_grid, bases_grid, finish_grid, finish_lds}
+void ft_train_launch_cpu(const uint64_t* facts, uint32_t nq, int32_t phase, uint64_t* out) {
+	struct Plan {
+		uint32_t n_rows, max_merged, merge_blocks;
+		uint8_t simple, prescore;
+		uint32_t n_ranges, range_count;
+		uint64_t nwords;
+		uint32_t n_syn_jobs;
+	};
+	std::vector<Plan> plans(nq);
+	for (uint32_t q = 0; q < nq; ++q) {
+		const uint64_t* f = facts + 9 * size_t(q);
+		plans[q] = Plan{uint32_t(f[0]), uint32_t(f[1]), uint32_t(f[2]), uint8_t(f[3]), uint8_t(f[4]), uint32_t(f[5]), uint32_t(f[6]), f[7], uint32_t(f[8])};
+	}
+	const rxgpu::FtTrainLaunch t = rxgpu::ft_train_launch(plans.data(), nq, phase);
+	const uint64_t v[8] = {t.syn_grid, t.ranges_grid, t.apply_blocks, t.rank_blocks, t.adders_grid, t.bases_grid, t.finish_grid, t.finish_lds};
+	std::memcpy(out, v, sizeof(v));
+}
+
+// ft_finish's dynamic LDS as the kernel carves it, in words: the sorted layout, the compact one, the sparse-bucket overlay in both
+void ft_finish_lds_cpu(uint32_t* out) {
+	using L = rxgpu::FtFinishLds;
+	const uint32_t v[14] = {L::tab,           L::keys,          L::words,      L::slot,        L::bits,        L::pref,         L::words_few,
+							L::table(false),  L::table(true),   L::sparse(false), L::sparse(true), L::sparse_head, L::sparse_todo, L::sparse_words};
+	std::memcpy(out, v, sizeof(v));
+}
+
+uint64_t ft_apply_blocks_cpu(uint64_t nwords) { return rxgpu::ft_apply_blocks(nwords); }
+
+// the constants of the dense train's launch rules
+void ft_train_constants(uint32_t* out) {
+	const uint32_t v[7] = {uint32_t(rxgpu::kFtApplyWords), uint32_t(rxgpu::kFtRankTiles), rxgpu::kFtFinishRows,  rxgpu::kFtBitmapRows,
+						   rxgpu::kFtSparseRecords,        rxgpu::kFtSparsePostings,      rxgpu::kFtSparseHeads};
+	std::memcpy(out, v, sizeof(v));
+}
+
 // the constants the decisions share with the kernels
 void ft_plan_constants(uint32_t* out) {
 	const uint32_t v[9] = {uint32_t(rxgpu::kFtBlockPostings), uint32_t(rxgpu::kFtPassItems), rxgpu::kFtRangeDocs, rxgpu::kFtSparseSubs, rxgpu::kFtHistCopies,

@@ -497,3 +497,136 @@ def test_plan_carries_the_packed_layout_and_the_areas_sizes(lib):
     assert (r.out_doc, r.out_proc, r.out_terms_counter, r.out_field, r.out_bytes) == (256, 512, 768, 1024, 1280)
     assert r.area_hdr_bytes == a256(63 * NF * 2 * 4) and r.area_bytes == 63 * NF * 5 * 3 * 4
     assert plan(lib, [T(OR, [W(40)]), T(OR, [W(23)])]).area_bytes == 0
+
+
+# ------------------------------------------------------------------------------------------------------------------------------ the dense train's launches
+LDS_LARGE, LDS_FEW = 48 * 1024, 32 * 1024   # ft_finish: document table + key list / the compact layout
+LAUNCH = ["syn_grid", "ranges_grid", "apply_blocks", "rank_blocks", "adders_grid", "bases_grid", "finish_grid", "finish_lds"]
+
+
+def Q(n_rows, max_merged=100, merge_blocks=1, simple=0, prescore=0, n_ranges=2, range_count=0, nwords=282, n_syn_jobs=0):
+    """One host plan as the nine facts ft_train_launch reads (9000 documents: two ranges, 282 mask words)."""
+    return (n_rows, max_merged, merge_blocks, simple, prescore, n_ranges, range_count, nwords, n_syn_jobs)
+
+
+def train(L, plans, phase=-1):
+    facts = np.ascontiguousarray(plans, dtype=np.uint64).reshape(-1, 9)
+    out = np.full(9, 0xDEAD, np.uint64)
+    L.ft_train_launch_cpu.argtypes = [P, C.c_uint32, C.c_int32, P]
+    L.ft_train_launch_cpu(facts.ctypes.data, len(plans), phase, out.ctypes.data)
+    assert out[8] == 0xDEAD
+    return dict(zip(LAUNCH, (int(x) for x in out)))
+
+
+def launches(syn=0, ranges=0, apply=0, rank=0, adders=0, bases=0, finish=0, lds=0):
+    return dict(zip(LAUNCH, (syn, ranges, apply, rank, adders, bases, finish, lds)))
+
+
+def test_train_constants(lib):
+    c = np.zeros(7, np.uint32)
+    lib.ft_train_constants.argtypes = [P]
+    lib.ft_train_constants(c.ctypes.data)
+    # kFtApplyWords, kFtRankTiles, kFtFinishRows, kFtBitmapRows, kFtSparseRecords, kFtSparsePostings, kFtSparseHeads
+    assert list(c) == [4, 2, 16, 8, 768, 6, 512]
+
+
+def test_train_of_a_simple_query(lib):
+    # ft_ranges (mask only), ft_rank_all over ceil(3 / 2) workgroups of two tiles, ft_adders, ft_finish in the compact layout
+    assert train(lib, [Q(1, merge_blocks=3, simple=1)]) == launches(ranges=2, rank=2, adders=2, finish=2, lds=LDS_FEW)
+    # (the gate never holds for a Simple() query: the flag alone launches nothing)
+    assert train(lib, [Q(1, merge_blocks=3, simple=1, prescore=1)])["apply_blocks"] == 0
+    assert train(lib, []) == launches()
+
+
+def test_train_of_a_two_term_query_with_pre_score(lib):
+    q = Q(2, max_merged=20000, merge_blocks=5, prescore=1, n_ranges=3, nwords=625)
+    assert train(lib, [q]) == launches(ranges=3, apply=1, rank=3, adders=3, finish=3, lds=LDS_FEW)
+    assert train(lib, [Q(2, max_merged=20000, merge_blocks=5, n_ranges=3, nwords=625)])["apply_blocks"] == 0
+    # a query without merged postings (every term a NOT): ft_rank_all is not launched
+    assert train(lib, [Q(0, merge_blocks=0)])["rank_blocks"] == 0
+
+
+@pytest.mark.parametrize("rows,bases,lds", [(8, 0, LDS_FEW), (9, 0, LDS_LARGE), (16, 0, LDS_LARGE), (17, 1, LDS_LARGE)])
+def test_train_by_the_number_of_rows(lib, rows, bases, lds):
+    # up to 8 rows the bitmaps; up to 16 rows (and 8192 entries) ft_finish sums its own bases
+    assert train(lib, [Q(rows, merge_blocks=rows)]) == launches(ranges=2, rank=(rows + 1) // 2, adders=2, bases=bases, finish=2, lds=lds)
+
+
+def test_train_by_the_size_of_the_table(lib):
+    def q(rows, ranges):
+        return Q(rows, n_ranges=ranges, nwords=ranges * 256)
+    assert train(lib, [q(3, 2730)])["bases_grid"] == 0      # 8190 entries
+    assert train(lib, [q(3, 2731)])["bases_grid"] == 1      # 8193
+    assert train(lib, [q(16, 512)])["bases_grid"] == 0      # 8192 exactly
+    assert train(lib, [q(16, 513)])["bases_grid"] == 1
+    assert train(lib, [q(3, 2731)])["finish_lds"] == LDS_FEW   # the layout is a matter of rows and mergeLimit only
+
+
+def test_train_by_merge_limit(lib):
+    # 16-bit slots hold 0 .. 65534 and 0xFFFF for "never merged"
+    assert train(lib, [Q(2, max_merged=65534)])["finish_lds"] == LDS_FEW
+    assert train(lib, [Q(2, max_merged=65535)])["finish_lds"] == LDS_LARGE
+
+
+def test_train_of_a_document_range_shard_phase_by_phase(lib):
+    # 80000 documents: 10 ranges, 2500 mask words; this shard holds 5 ranges = 1280 words = two workgroups of ft_preselect_apply (the whole
+    # index would take three)
+    q = Q(2, max_merged=20000, merge_blocks=4, prescore=1, n_ranges=10, range_count=5, nwords=2500)
+    assert train(lib, [q], 0) == launches(ranges=5)
+    assert train(lib, [q], 1) == launches(apply=2, rank=2, adders=5)
+    assert train(lib, [q], 2) == launches(finish=5, lds=LDS_FEW)
+    assert train(lib, [q], -1) == launches(ranges=5, apply=2, rank=2, adders=5, finish=5, lds=LDS_FEW)
+    whole = Q(2, max_merged=20000, merge_blocks=4, prescore=1, n_ranges=10, nwords=2500)
+    assert train(lib, [whole], 1) == launches(apply=3, rank=2, adders=10)
+    many = Q(17, max_merged=20000, merge_blocks=17, n_ranges=10, range_count=5, nwords=2500)
+    assert train(lib, [many], 2) == launches(bases=1, finish=5, lds=LDS_LARGE)
+    assert train(lib, [many], 1)["bases_grid"] == 0
+
+
+def test_train_with_synonym_masks(lib):
+    q = Q(3, merge_blocks=3, n_syn_jobs=1)
+    assert train(lib, [q]) == launches(syn=2, ranges=2, rank=2, adders=2, finish=2, lds=LDS_FEW)
+    assert train(lib, [q], 0) == launches(syn=2, ranges=2)
+    assert train(lib, [q], 1)["syn_grid"] == 0
+
+
+def test_train_of_a_mixed_batch_takes_the_large_layout_and_the_widest_grid(lib):
+    two, nine = Q(2, merge_blocks=2), Q(9, merge_blocks=12, prescore=1)
+    assert train(lib, [two, two]) == launches(ranges=2, rank=1, adders=2, finish=2, lds=LDS_FEW)
+    for batch in ([two, nine], [nine, two]):
+        assert train(lib, batch) == launches(ranges=2, apply=1, rank=6, adders=2, finish=2, lds=LDS_LARGE)
+    assert train(lib, [two, Q(17, merge_blocks=17)])["bases_grid"] == 1
+
+
+@pytest.mark.parametrize("nwords,blocks", [(1023, 1), (1024, 1), (1025, 2)])
+def test_apply_blocks_size_the_grid_and_the_look_back_chain(lib, nwords, blocks):
+    # 256 threads x 4 mask words per workgroup of ft_preselect_apply; one 8-byte look-back word per workgroup
+    lib.ft_apply_blocks_cpu.restype, lib.ft_apply_blocks_cpu.argtypes = C.c_uint64, [C.c_uint64]
+    assert lib.ft_apply_blocks_cpu(nwords) == blocks
+    ranges = (nwords * 32 + 8191) // 8192
+    assert train(lib, [Q(2, prescore=1, n_ranges=ranges, nwords=nwords)])["apply_blocks"] == blocks
+    r = plan(lib, [T(OR, [W(50)]), T(OR, [W(60)])], N=nwords * 32, limit=100, mode=0)
+    assert r.nwords == nwords and r.prescore and r.clean["lb_pre"][1] == blocks * 8
+
+
+def test_train_of_a_planned_query(lib):
+    terms = [T(OR, [W(2000), W(30, proc=90)]), T(NOT, [W(9)]), T(AND, [W(1025)])]
+    r = plan(lib, terms, N=20000, limit=100, mode=0)
+    q = Q(r.n_rows, r.max_merged, r.merge_blocks, 0, r.prescore, r.n_ranges, 0, r.nwords, r.n_jobs)
+    assert train(lib, [q]) == launches(ranges=3, apply=1, rank=3, adders=3, finish=3, lds=LDS_FEW)   # 5 blocks of postings: 3 workgroups
+
+
+def test_finish_lds_layouts(lib):
+    v = np.zeros(14, np.uint32)
+    lib.ft_finish_lds_cpu.argtypes = [P]
+    lib.ft_finish_lds_cpu(v.ctypes.data)
+    tab, keys, words, slot, bits, pref, words_few, table_large, table_few, sparse_large, sparse_few, sp_head, sp_todo, sp_words = (int(x) for x in v)
+    # sorted layout: 8192 halves of document table, 8192 keys; compact: 8192 halves of slots, 8 x 256 bitmap words, 8 x 256 prefixes
+    assert (tab, keys, words) == (0, 4096, 12288) and words * 4 == LDS_LARGE
+    assert (slot, bits, pref, words_few) == (0, 4096, 6144, 8192) and words_few * 4 == LDS_FEW
+    # the table of ft_adders (up to 8192 entries): over the key list / from the start of the compact block
+    assert (table_large, table_few) == (4096, 0) and table_large + 8192 <= words and table_few + 8192 <= words_few
+    # sparse bucket: 768 records of four words, 512 heads, 768 halves; behind the slots (compact) / behind 768 slots of the key list (sorted)
+    assert (sp_head, sp_todo, sp_words) == (3072, 3584, 3968)
+    assert sparse_few == bits and sparse_few + sp_words <= words_few
+    assert sparse_large >= keys + 768 and sparse_large + sp_words <= words

@@ -1,4 +1,4 @@
-"""-m gpu: ft_fast BM25 merge on the GPU (ft_merge.hip through rxgpu_ft_* and GpuFtMerger) vs the CPU restatement that is pinned
+"""-m gpu: ft_fast BM25 merge on the GPU (the train of ft_merge.hip, kernels in ft_ranges / ft_admit / ft_finish / ft_transfer.hip, through rxgpu_ft_* and GpuFtMerger) vs the CPU restatement that is pinned
 by the reference's golden debug_rank strings.  Bar: id set equal, uint8 rank equal — here the raw float ranks are
 bit-identical as well, because the kernel keeps the reference's fp64/fp32 types operation for operation."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""-m gpu: PHRASES in the ft_fast merge on the GPU (ft_phrase.hip + ft_merge.hip through rxgpu_ft_merge_query_raw and
+"""-m gpu: PHRASES in the ft_fast merge on the GPU (ft_phrase.hip + the dense train of ft_merge.hip through rxgpu_ft_merge_query_raw and
 GpuFtMerger::MergeQuery) against the REAL reference merger — ft::Merger<IdRelVec, MergeData, uint32_t>::Merge with PhraseMerger
 (phrasemergerimpl.h:161-329, mergerimpl.h:39-90, 326-384, 504-510) compiled in place (oracle/_ref/libref_ft.so; the shim groups the terms
 into PhraseResults the way Selector::Process does, selecterimpl.h:482-572).

@@ -1,6 +1,6 @@
 """-m gpu: the launch train for SPARSELY hit document ranges (reindexer_amd/csrc/ft_sparse.hip: one wavefront per (query, range), one bitmap
 per sub-term in LDS, ranking after the merge slots are known) against the restated Merger::Merge (itself pinned to the real ft::Merger,
-tests/test_bm25_oracle.py) AND against the dense train (ft_merge.hip) on the same queries.
+tests/test_bm25_oracle.py) AND against the dense train (ft_merge.hip and its kernel units) on the same queries.
 
 Bar: the merged documents IN MERGE ORDER, raw rank bits, fields, terms counters / uint8 ranks and the preselect flag — for OR / AND / NOT
 terms, Simple() queries with the mergeLimit cut, the preselect phase with ties at the threshold (kept in document order across ranges),

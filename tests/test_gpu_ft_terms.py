@@ -1,4 +1,4 @@
-"""-m gpu: ft_fast MULTI-TERM merge on the GPU (ft_merge.hip through rxgpu_ft_merge_terms_raw and GpuFtMerger::MergeQuery) vs the
+"""-m gpu: ft_fast MULTI-TERM merge on the GPU (the train of ft_merge.hip, kernels in ft_ranges / ft_admit / ft_finish / ft_transfer.hip, through rxgpu_ft_merge_terms_raw and GpuFtMerger::MergeQuery) vs the
 CPU restatement of Merger::Merge, which tests/test_bm25_oracle.py pins bit-exact against the real reference merger.
 Bar: the same documents in the same merge order, the same raw-rank bits, fields and uint8 ranks — for AND / OR / NOT terms, zero field
 boosts, array positions, the mergeLimit cut inside mergeTerm and the preselect phase."""
@@ -104,6 +104,47 @@ def test_gpu_multi_term_sparse_ranges(hostapi, ft, limit, ops, nsub, total, size
     _, words, avg, removed, excluded, terms, store = _multi_case(3000 + limit + total + len(ops), nf, total, limit, ops, False, None, sizes=sizes,
                                                                  nsub_range=nsub)
     _check(hostapi, ft, nf, total, limit, words, avg, removed, excluded, terms, store, variants=((1.0, 0.5), (1.7, 0.8)))
+
+
+@pytest.mark.parametrize("ops,nsub,sizes,rows", [
+    ((1, 1), (8, 9), (150, 900), 16),           # the most rows ft_finish sums its own slot bases for (sorted layout)
+    ((1,) * 17, (1, 2), (150, 900), 17),        # one more: ft_slot_bases
+    ((1, 1), (1025, 1026), (1, 4), 2050),       # more rows than ft_adders counts in LDS: its table is built in global memory
+])
+def test_gpu_multi_term_row_count_boundaries(hostapi, ft, ops, nsub, sizes, rows):
+    """The numbers of merged sub-terms at which the admission kernels change path, over two document ranges."""
+    nf, total, limit = 2, 9_000, 20000
+    _, words, avg, removed, excluded, terms, store = _multi_case(5000 + rows, nf, total, limit, ops, False, None, sizes=sizes, nsub_range=nsub)
+    assert sum(len(t["subs"]) for t in terms) == rows
+    _check(hostapi, ft, nf, total, limit, words, avg, removed, excluded, terms, store, variants=((1.0, 0.5),))
+
+
+def test_gpu_slot_bases_by_table_size(hostapi, ft):
+    """Three merged sub-terms over 2731 document ranges: the table of ft_adders has 8193 entries, one more than a workgroup of ft_finish
+    sums for itself, so ft_slot_bases runs in front of ft_finish's compact layout (which otherwise always has its own bases)."""
+    nf, n_ranges, limit = 1, 2731, 20000
+    total = n_ranges * 8192 - 100
+    rng = np.random.default_rng(6100)
+    words = rng.integers(1, 6, (total, nf)).astype(np.float32)
+    words[0] = 0
+    avg = words[1:].mean(axis=0).astype(np.float32)
+    removed, excluded = np.zeros(total, np.uint8), np.zeros(total, np.uint8)
+    removed[rng.integers(1, total, total // 30)] = 1
+    excluded[rng.integers(1, total, total // 30)] = 1
+    terms, store = [], []
+    for op, procs in ((1, (100.0, 70.5)), (1, (85.0,))):
+        subs = []
+        for proc in procs:
+            n = int(rng.integers(2500, 3500))
+            s = make_pos_postings(rng, 4 * n, nf, n, proc)   # positions of n postings; their documents are spread over the whole index below
+            stride = (total - 1) // n
+            s["doc"] = (1 + np.arange(n) * stride + rng.integers(0, stride, n)).astype(np.uint32)
+            s["word"] = len(store)
+            store.append(s)
+            subs.append(s)
+        terms.append(dict(op=op, opts=dict(boost=1.0, term_len_boost=1.0, field_boost=[1.0] * nf, need_sum_rank=[0] * nf), subs=subs))
+    assert 3 * n_ranges == 8193 and max(int(s["doc"][-1]) for s in store) < total
+    _check(hostapi, ft, nf, total, limit, words, avg, removed, excluded, terms, store, variants=((1.0, 0.5),))
 
 
 def test_gpu_one_merger_many_query_shapes(hostapi, ft):

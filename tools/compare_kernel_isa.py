@@ -23,7 +23,8 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 from reindexer_amd.build import HIP_FLAGS, HIPCC  # noqa: E402
 
-DEFAULT_UNITS = ["knn_scan.hip", "knn_merge.hip", "knn_filter.hip", "knn_range.hip", "knn_scan_i6.hip", "knn_scan_i8.hip"]
+DEFAULT_UNITS = ["knn_scan.hip", "knn_merge.hip", "knn_filter.hip", "knn_range.hip", "knn_scan_i6.hip", "knn_scan_i8.hip",
+                 "ft_merge.hip", "ft_ranges.hip", "ft_admit.hip", "ft_finish.hip", "ft_transfer.hip", "ft_sparse.hip", "ft_phrase.hip"]
 ORDINAL = re.compile(r"(\.L|\b)(BB|func_end|func_begin|tmp)\d+")   # (the loop comments name blocks as BB<n>_<m>, without the .L)
 
 
