@@ -294,6 +294,9 @@ typedef struct {
 	float lower;
 	size_t ef;
 	int bare, empty_graph;
+	/* the last Continue: candidate_set / top_candidates / extras as the call found them, and the largest candidate_set and extras it met in
+	 * front of a pop (what a device call that stages its heaps in a fixed area has to watch) */
+	size_t cand_start, top_start, ext_start, cand_peak, ext_peak;
 } orc_hnsw_stream;
 
 void* orc_hnsw_stream_begin(int metric, size_t n, size_t dim, size_t M, size_t maxM0, int maxlevel, uint32_t entry, size_t num_deleted,
@@ -367,11 +370,16 @@ size_t orc_hnsw_stream_continue(void* h, size_t batch, float* out_dist, uint64_t
 	const orc_hnsw_graph* g = &s->g;
 	const size_t orig_ef = s->ef;
 	if (batch > s->ef) s->ef = batch;
+	s->cand_start = s->cand_peak = s->cand.n;
+	s->top_start = s->top.n;
+	s->ext_start = s->ext_peak = s->extras.n;
 	stream_merge_extras(s);
 	for (;;) {
 		if (s->cand.n == 0) break;
 		const float cdist = -s->cand.c[0].d;
 		if (cdist > s->lower && s->top.n >= s->ef) break;   /* streaming: never the bare-bone shortcut */
+		if (s->cand.n > s->cand_peak) s->cand_peak = s->cand.n;
+		if (s->extras.n > s->ext_peak) s->ext_peak = s->extras.n;
 		const float dist = -s->cand.c[0].d;
 		const uint32_t cur = s->cand.c[0].id;
 		fh_pop(&s->cand);
@@ -413,6 +421,16 @@ size_t orc_hnsw_stream_continue(void* h, size_t batch, float* out_dist, uint64_t
 	free(tc.c);
 	*exhausted = s->cand.n == 0 && s->top.n == 0 && s->extras.n == 0;
 	return n;
+}
+
+/* out5 = candidate_set, top_candidates, extras at the start of the last Continue; the largest candidate_set and extras in front of a pop */
+void orc_hnsw_stream_last_sizes(void* h, size_t* out5) {
+	const orc_hnsw_stream* s = (const orc_hnsw_stream*)h;
+	out5[0] = s->cand_start;
+	out5[1] = s->top_start;
+	out5[2] = s->ext_start;
+	out5[3] = s->cand_peak;
+	out5[4] = s->ext_peak;
 }
 
 void orc_hnsw_stream_end(void* h) {

@@ -502,6 +502,14 @@ class OracleHnswStream:
         n = self.L.orc_hnsw_stream_continue(self.s, batch, od.ctypes.data, ol.ctypes.data, C.byref(ex))
         return od[:n].copy(), ol[:n].copy(), bool(ex.value)
 
+    def last_sizes(self):
+        """(candidate_set, top_candidates, extras at the start of the last next(); the largest candidate_set and extras it met in front of a pop)"""
+        out = (C.c_size_t * 5)()
+        self.L.orc_hnsw_stream_last_sizes.argtypes = [_vp, _vp]
+        self.L.orc_hnsw_stream_last_sizes.restype = None
+        self.L.orc_hnsw_stream_last_sizes(self.s, out)
+        return tuple(int(x) for x in out)
+
     def close(self):
         if self.s:
             self.L.orc_hnsw_stream_end(self.s)

@@ -113,9 +113,10 @@ def search_graph(e, a, rows):
     return g
 
 
-def link_batch(model, orc, e, links0, a, cnt, M, max_m0, efc):
+def link_batch(model, orc, e, links0, a, cnt, M, max_m0, efc, entries=None):
     """Steps 3 - 5 for rows [a, a + cnt) on links0 ([n][1 + maxM0], changed in place); e: the host graph's export in front of the batch's
-    LinkUpper (upper lists, entry point and top level as they were after the batch before).  Returns the number of nodes re-selected."""
+    LinkUpper (upper lists, entry point and top level as they were after the batch before).  Returns the number of nodes re-selected.
+    entries (a dict): the most entries — current links + incoming rows — each re-selected node held at a re-selection."""
     from oracle.pyoracle import oracle_hnsw_search_knn
     g = search_graph(e, a, model.rows)
     g["links0"] = np.ascontiguousarray(links0[:a])
@@ -144,6 +145,8 @@ def link_batch(model, orc, e, links0, a, cnt, M, max_m0, efc):
             row[0] = len(cur) + len(inc)
             continue
         reselected += 1
+        if entries is not None:
+            entries[t] = max(entries.get(t, 0), len(cur) + len(inc))
         ids = np.array(cur + inc, np.int64)
         chosen = model.select(ids, model.dist_to(ids, t), max_m0)
         row[:] = 0
@@ -170,10 +173,10 @@ def build(orc, metric, rows, labels, M, efc, seed=SEED, ratio=RATIO, cap=BATCH_C
     model = BatchModel(orc, metric, rows, inv)
     e = g.export()
     links0 = e["links0"].copy()
-    stats = dict(batches=0, reselected=0, seed=L, first_export=e)
+    stats = dict(batches=0, reselected=0, seed=L, first_export=e, reselected_entries={})
     while L < n:
         cnt = batch_rows(L, n, ratio, cap)
-        stats["reselected"] += link_batch(model, orc, e, links0, L, cnt, e["M"], e["maxM0"], efc)
+        stats["reselected"] += link_batch(model, orc, e, links0, L, cnt, e["M"], e["maxM0"], efc, stats["reselected_entries"])
         touched = g.link_upper(L, cnt)
         after = g.export()
         if on_batch is not None:

@@ -31,12 +31,13 @@ CASES = {
     "general_ip": (1, 3000, 48, 4, 40, 256, 16, 0),
     "general_cos": (2, 3000, 48, 4, 40, 256, 16, 0),
     "cos768": (2, 1500, 768, 16, 200, 1024, 16, 0),
+    "rows1024": (2, 1400, 1024, 16, 100, 1024, 16, 0),
     "padded": (0, 1000, 50, 4, 8, 64, 2, 0),
     "ties_hub": (0, 600, 32, 4, 50, 64, 16, 0),
     "hub_past_cap": (0, 2600, 32, 4, 50, 1300, 1, 0),
     "append": (0, 3000, 40, 6, 60, 1024, 16, 2000),
 }
-CORPUS_SEED = dict(general_l2=177, general_ip=177, general_cos=177, cos768=178, padded=179, ties_hub=181, hub_past_cap=182, append=183)
+CORPUS_SEED = dict(general_l2=177, general_ip=177, general_cos=177, cos768=178, rows1024=184, padded=179, ties_hub=181, hub_past_cap=182, append=183)
 TIES_BATCH = (320, 384)        # ties_hub: the batch [320, 384) (a = 320: 320 // 16 = 20 < 64 rows, so 64) is all copies of one row
 HUB_COPIES = (1300, 2500)      # hub_past_cap: 1200 rows of the one batch [1300, 2600) are copies of one row
 
@@ -94,6 +95,9 @@ def check_conditions(name, hub, want, stats):
         assert stats["reselected_l1"] > 50 and stats["batches_with_level2"] >= 1 and stats["l1_host_rows"] == 0, stats
     elif name == "cos768":
         assert (1 + M) * d * 4 + (3 * 256 + 4 * 128) * 4 <= 64 * 1024      # hnsw_build_select_lds: the kept rows fit in LDS
+        assert stats["l1_rows"] == int((lv[1024:] >= 1).sum()) >= 10, stats
+    elif name == "rows1024":
+        assert (1 + M) * d * 4 + (3 * 256 + 4 * 128) * 4 > 64 * 1024       # hnsw_build_select_lds: the kept rows do not fit in LDS, they are read from L2
         assert stats["l1_rows"] == int((lv[1024:] >= 1).sum()) >= 10, stats
     elif name == "padded":
         assert d % 4 and stats["reselected_l1"] > 30, stats

@@ -140,6 +140,89 @@ def test_appending_to_a_host_built_graph(rxgpu, oracle):
     assert dstats["rows"] == 1000
 
 
+# ------------------------------------------------------------------------------------------------------------------ kept rows in L2; the caps
+FIXED_LDS = (3 * 256 + 4 * 128) * 4   # candidate ids / distances / order; kept and heap ids / distances: the static arrays of the selection kernel
+
+
+def select_lds_plan(d, M):
+    """(static bytes, dynamic bytes, kept rows in LDS) of the selection kernel's launch for rows of d floats, as hnsw_build_plan.h decides it
+    (tests/cpp/hnsw_build_plan_cpu.cc): a case asserts what it claims of its plan, so a changed budget cannot move it to the other kernel
+    unnoticed."""
+    from .test_hnsw_build_plan import LIB
+    if not LIB.exists():
+        from reindexer_amd import build
+        build.build_cpp_tests()
+    L = C.CDLL(str(LIB))
+    L.hnsw_build_plan_lds.restype, L.hnsw_build_plan_lds.argtypes = None, [C.c_uint32, C.c_uint32, C.c_void_p]
+    out = (C.c_uint32 * 3)()
+    L.hnsw_build_plan_lds((d + 3) // 4 * 4, M, out)
+    return tuple(int(x) for x in out)
+
+
+def assert_rows_from_l2(d, M):
+    """the new row and M kept rows do not fit beside the static arrays: hnsw_build_select<kMetric, false> reads the kept rows from L2"""
+    assert (1 + M) * ((d + 3) // 4 * 4) * 4 + FIXED_LDS > 64 * 1024
+    assert select_lds_plan(d, M) == (FIXED_LDS, 0, 0), (d, M, select_lds_plan(d, M))
+
+
+def link_for_link_with_reselection(rxgpu, oracle, metric, rows, M, efc, seed, ratio=16):
+    want, got, stats, dstats = device_against_model(rxgpu, oracle, metric, rows, M, efc, seed, ratio)
+    assert_link_for_link(want, got)
+    assert stats["reselected"] > 0, stats["reselected"]
+    assert dstats["rows"] == rows.shape[0] - seed and dstats["batches"] == stats["batches"] and dstats["reselected"] == stats["reselected"], (
+        dstats, stats["batches"], stats["reselected"])
+    return want, got, stats, dstats
+
+
+@pytest.mark.parametrize("metric", [0, 1, 2])
+def test_1024_float_rows_kept_rows_from_l2(rxgpu, oracle, metric):
+    """1024 floats at M = 16: 17 rows are 69 632 bytes.  The batch search runs over the wide-row kernels, with a sink."""
+    assert_rows_from_l2(1024, 16)
+    link_for_link_with_reselection(rxgpu, oracle, metric, make_corpus(85, 1400, 1024), 16, 100, 1024)
+
+
+def test_1536_float_rows_kept_rows_from_l2(rxgpu, oracle):
+    """the same at three chunks of 512 floats"""
+    assert_rows_from_l2(1536, 16)
+    link_for_link_with_reselection(rxgpu, oracle, 2, make_corpus(86, 1300, 1536), 16, 100, 1024)
+
+
+@pytest.mark.parametrize("metric", [0, 2])
+def test_768_float_rows_at_m_32_kept_rows_from_l2(rxgpu, oracle, metric):
+    """the fixed-dimension size whose kept rows fit at M = 16 (test_768_cosine_kept_rows_in_lds) and not from M = 19 on"""
+    assert select_lds_plan(768, 18)[2] == 1 and select_lds_plan(768, 19)[2] == 0
+    assert_rows_from_l2(768, 32)
+    link_for_link_with_reselection(rxgpu, oracle, metric, make_corpus(87, 1300, 768), 32, 100, 1024)
+
+
+@pytest.mark.parametrize("M,kept", [(58, True), (59, False)])
+def test_launch_on_the_lds_budget_and_one_link_past_it(rxgpu, oracle, M, kept):
+    """256 floats at M = 58: 59 rows are 60 416 bytes, and with the 5120 static bytes the launch takes 65 536 bytes, the whole budget;
+    at M = 59 the kept rows are read from L2."""
+    if kept:
+        assert FIXED_LDS == 5120 and select_lds_plan(256, M) == (5120, 60416, 1) and 5120 + 60416 == 64 * 1024
+    else:
+        assert_rows_from_l2(256, M)
+    link_for_link_with_reselection(rxgpu, oracle, 0, make_corpus(88, 900, 256), M, 120, 512)
+
+
+@pytest.mark.parametrize("copies", [80, 300])
+def test_m_and_ef_construction_at_their_caps(rxgpu, oracle, copies):
+    """M = 64 (maxM0 = 128, the length of the kernel's kept and heap arrays) and efConstruction = 256 (its candidate arrays).  The batch
+    [300, 600) (ratio 1) begins with copies of seed row 7: all of them find it at distance 0, so row 7 holds more than 128 entries and is
+    re-selected at maxM0 = 128; with 300 copies it holds more than 256 and the second launch finishes it."""
+    assert select_lds_plan(32, 64) == (FIXED_LDS, 65 * 32 * 4, 1)
+    rows = make_corpus(89, 900, 32)
+    rows[300:300 + copies] = rows[7]
+    want, got, stats, dstats = link_for_link_with_reselection(rxgpu, oracle, 0, rows, 64, 256, 300, ratio=1)
+    assert want.shape[1] == 1 + 128 and int(want[:, 0].max()) > 64, int(want[:, 0].max())
+    held = stats["reselected_entries"].get(7, 0)   # the model: what row 7 held when it was re-selected
+    if copies == 300:
+        assert held > 256 and dstats["past_cap"] >= 1, (held, dstats)
+    else:
+        assert 128 < held <= 256 and max(stats["reselected_entries"].values()) <= 256 and dstats["past_cap"] == 0, (held, dstats)
+
+
 def test_link_batch_refuses_what_it_does_not_take(rxgpu, oracle):
     rows = make_corpus(84, 400, 16)
     from reindexer_amd import hostapi

@@ -97,6 +97,12 @@ def test_768_cosine_kept_rows_in_lds(rxgpu, oracle):
     device_against_model(rxgpu, oracle, "cos768")
 
 
+def test_1024_float_rows_kept_rows_from_l2(rxgpu, oracle):
+    """17 rows of 1024 floats do not fit in LDS: the level-1 selection reads its kept rows from L2, and the level-1 search runs over the
+    wide-row kernels"""
+    device_against_model(rxgpu, oracle, "rows1024")
+
+
 def test_padded_stride_nearly_everything_reselected(rxgpu, oracle):
     """D = 50: a row stride of 52 floats.  M = 4, efConstruction = 8, batches half the size of the graph they search: nearly every touched
     level-1 node overflows its 4 slots and is re-selected."""

@@ -172,7 +172,8 @@ def test_latency_form_keeps_dynamic_lds_under_60k(lib):
 
 
 @pytest.mark.parametrize("bare", [1, 0])
-@pytest.mark.parametrize("nbl,spec,maxM0", [(0, 0, 32), (1, 0, 32), (1, 0, 64), (0, 1, 32), (0, 1, 64), (1, 1, 32), (1, 1, 64)])
+@pytest.mark.parametrize("nbl,spec,maxM0", [(0, 0, 32), (1, 0, 32), (1, 0, 64), (0, 1, 32), (0, 1, 64), (1, 1, 32), (1, 1, 64), (1, 0, 128), (0, 1, 128),
+                                            (1, 1, 128)])
 def test_team_areas(lib, bare, nbl, spec, maxM0):
     at = 8896 + 65536   # 74432: heaps, query fragment, the 2^14-word set
     want_nbl = at if (nbl and not spec and maxM0 == 32) else 0
