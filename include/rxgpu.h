@@ -271,12 +271,33 @@ int rxgpu_scan_tier_subset(uint64_t n_ids, uint32_t dim, uint32_t nq, uint32_t k
  *   = rows in the probed lists.  Output as rxgpu_search_knn for nq = 1.
  * rxgpu_search_range_lists: IndexIVFFlat::range_search (ivf_index.cc:212-272 drives it) over the same device lists — probed lists ->
  *   row list on the device -> the range kernels of rxgpu_search_range_subset (the int8-pruned one where rxgpu_scan_tier_range says so
- *   for the rows of the probed lists); output, overflow protocol and ordering as rxgpu_search_range_subset. */
+ *   for the rows of the probed lists); output, overflow protocol and ordering as rxgpu_search_range_subset.
+ * rxgpu_search_knn_lists_batch: nq queries (host [nq][dim], prepared for the metric) in one call.  For every i, out_dist / out_row
+ *   [i * kk ..], out_count[i] and out_scanned[i] (optional array) are what rxgpu_search_knn_lists(h, coarse, queries + i * dim, nprobe, kk,
+ *   ...) writes for that query: the same rows, the same distance bits, the same (dist, row) order, out_count[i] = min(kk, rows in the
+ *   probed lists).  The checks and codes are the single call's (a sharded handle, lists unset or stale: RXGPU_ERR_LOGIC); nq == 0, kk == 0
+ *   or an empty index: RXGPU_OK with zero counts; nprobe is clamped to [1, nlist].  With the clamped nprobe <= 128 and kk <= 128 the
+ *   queries go through DEVICE TRAINS on one stream, no host round trip inside a train: one upload, the coarse search for all of them
+ *   (the chain of rxgpu_search_knn over the centroids), per query the running 64-entry chunk counts of its probed lists, one list scan
+ *   (knn_scan_lists: grid (workgroups per query, queries); the lists are disjoint, so a query's candidates are the concatenation of
+ *   its probed lists — no bitmap, no row list) and one merge, then one set of copies back and one wait.  A call is cut into several
+ *   trains only where its device buffers would pass 256 MiB (RXGPU_IVF_BATCH_SCRATCH_BYTES, read per call, moves that); the launches
+ *   this call adds to a train — chunk counts, scan, merge — do not depend on the number of queries.  Outside that envelope every query is
+ *   answered by the single call's chain inside this call.
+ * rxgpu_ivf_read_batch_stats: batch calls, their queries, device trains run and queries answered one by one, since the last call
+ *   (any may be NULL).
+ * rxgpu_ivf_batch_default: 1 where a caller with nq queries at hand should make the batch call (nq >= 2 inside the envelope), 0 where it
+ *   should keep driving single calls — the rule of ivf_batch_plan.h that GpuIvfFlat::SearchBatch follows (no device is touched; nprobe
+ *   = the clamped value). */
 int rxgpu_index_set_lists(rxgpu_index* h, uint32_t nlist, const uint64_t* list_off, const uint32_t* list_rows);
 int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, uint32_t kk, float* out_dist,
 						   uint32_t* out_row, uint32_t* out_count, uint64_t* out_scanned);
 int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, float radius, int inclusive, float* out_dist,
 							 uint32_t* out_row, uint64_t cap, uint64_t* out_total, uint64_t* out_scanned);
+int rxgpu_search_knn_lists_batch(rxgpu_index* h, rxgpu_index* coarse, const float* queries, uint32_t nq, uint32_t nprobe, uint32_t kk, float* out_dist,
+								 uint32_t* out_row, uint32_t* out_count, uint64_t* out_scanned);
+int rxgpu_ivf_read_batch_stats(rxgpu_index* h, uint64_t* calls, uint64_t* queries, uint64_t* trains, uint64_t* queries_one_by_one);
+int rxgpu_ivf_batch_default(uint32_t nq, uint32_t nprobe, uint32_t kk);
 
 /* ---- IVF training from resident rows: the device half of IndexIVF::train / add_with_ids as IvfIndex drives them (ivf_index.cc:96-108,
  * 143-160; Level1Quantizer::train_q1 IndexIVF.cpp:43-88 -> Clustering::train_encoded Clustering.cpp:330-560) -------------------------

@@ -171,6 +171,14 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "ivf_train_plan.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # the decisions of a batched IVF list search compiled for the host (CPU check of the envelope, the trains, gridx, the chunk rule and the scratch
+    # rxgpu_search_knn_lists_batch and knn_scan_lists use)
+    src = tdir / "ivf_batch_plan_cpu.cc"
+    if src.exists():
+        out = tdir / "libivf_batch_plan_cpu.so"
+        if force or _stale(out, [src, CSRC / "ivf_batch_plan.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     # the decisions of the batched HNSW build on the device compiled for the host (CPU check of the schedule, the eligibility rule, the LDS
     # decision and the scratch layout rxgpu_hnsw_build.hip and the Map follow)
     src = tdir / "hnsw_build_plan_cpu.cc"

@@ -76,6 +76,9 @@ _SIGNATURES = {
     "rxgpu_index_set_lists": (_i, [_vp, _u32, _vp, _vp]),
     "rxgpu_search_knn_lists": (_i, [_vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_search_range_lists": (_i, [_vp, _vp, _vp, _u32, C.c_float, _i, _vp, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
+    "rxgpu_search_knn_lists_batch": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "rxgpu_ivf_read_batch_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "rxgpu_ivf_batch_default": (_i, [_u32, _u32, _u32]),
     "rxgpu_ivf_assign": (_i, [_vp, _vp, _vp, _u64, _u64, _vp]),
     "rxgpu_ivf_kmeans_step": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "rxgpu_ivf_read_train_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -456,6 +459,25 @@ class VectorIndex:
                                             C.byref(scanned)))
         c = int(cnt[0])
         return dist[:c], row[:c], int(scanned.value)
+
+    def search_knn_lists_batch(self, coarse: "VectorIndex", queries, nprobe: int, k: int):
+        """rxgpu_search_knn_lists for every row of `queries` in one call: (dist [nq][k], row [nq][k], count [nq], scanned [nq]); entries past
+        a query's count keep +inf / 0xFFFFFFFF."""
+        q = _f32c(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        row = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        cnt = np.zeros(max(nq, 1), np.uint32)
+        scanned = np.zeros(max(nq, 1), np.uint64)
+        _check(lib().rxgpu_search_knn_lists_batch(self._h, coarse._h, q.ctypes.data, nq, nprobe, k, dist.ctypes.data, row.ctypes.data, cnt.ctypes.data,
+                                                  scanned.ctypes.data))
+        return dist[:, :k], row[:, :k], cnt[:nq], scanned[:nq]
+
+    def ivf_read_batch_stats(self):
+        """(batch calls, their queries, device trains, queries answered one by one) since the last call."""
+        calls, queries, trains, single = _u64(0), _u64(0), _u64(0), _u64(0)
+        _check(lib().rxgpu_ivf_read_batch_stats(self._h, C.byref(calls), C.byref(queries), C.byref(trains), C.byref(single)))
+        return int(calls.value), int(queries.value), int(trains.value), int(single.value)
 
     def search_range_lists(self, coarse: "VectorIndex", query, nprobe: int, radius: float, inclusive: bool = False, cap: int = 1 << 14):
         """IndexIVFFlat::range_search over the device lists in one call: (dist[n], row[n], rows scanned), ascending by (dist, row)."""

@@ -109,6 +109,12 @@ void launch_ivf_mark_lists(const uint32_t* probe, const uint32_t* probe_cnt, uin
 void launch_gather_u32(const uint32_t* src, const uint32_t* idx, uint32_t n, uint32_t* out, hipStream_t s);
 void launch_check_row_list(const uint32_t* ids, uint64_t n, uint64_t limit, uint32_t* bad, int cus, hipStream_t s);
 
+// ---- knn_lists.hip: the list scan of a batched IVF search (layout and chunk rule: ivf_batch_plan.h)
+void launch_ivf_batch_offsets(const uint32_t* probe, const uint32_t* probe_cnt, const uint64_t* list_off, uint32_t nprobe, uint32_t nq, uint32_t* cum,
+							  unsigned long long* scanned, hipStream_t s);   // running chunk counts [nq][nprobe + 1] and rows probed [nq]
+void launch_scan_lists(int metric, const ScanParams& p, const uint32_t* probe, const uint32_t* cum, const uint64_t* list_off, const uint32_t* list_rows,
+					   uint32_t nprobe, uint32_t nq, uint32_t gridx, hipStream_t s);   // partial lists [nq][gridx][kk], every slot written
+
 // IVF training on the device (ivf_train.hip; layout: ivf_train_plan.h).  ids: list positions -> rows in HBM, or null: position i is row first_row + i
 void launch_ivf_gather(int metric, const float* rows, const float* inv_norms, const uint32_t* ids, uint64_t first_row, uint64_t n, uint32_t stride, uint32_t dim,
 					   float* out, int cus, hipStream_t s);   // prepared vectors [n][dim]: row[j], cosine row[j] * inv_norms[row]
@@ -651,6 +657,9 @@ struct rxgpu_index {
 	uint32_t* d_list_rows = nullptr;  // [lists_rows]
 	uint32_t nlist = 0;
 	uint64_t lists_rows = 0, lists_count = 0;   // rows listed; the index row count the lists were built for
+	uint64_t lists_longest = 0;                 // rows of the longest list
+	// rxgpu_search_knn_lists_batch since rxgpu_ivf_read_batch_stats: calls, queries, device trains, queries answered one by one (guarded by mtx)
+	uint64_t ivf_batch_calls = 0, ivf_batch_queries = 0, ivf_batch_trains = 0, ivf_batch_one_by_one = 0;
 	// SQ8 copy of the rows (rxgpu_hnsw_attach_sq8): codes [sq8_n][dim], stored corrective offsets, alpha^2
 	uint8_t* d_codes = nullptr;
 	float* d_corr = nullptr;

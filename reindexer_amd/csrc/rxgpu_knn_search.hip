@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "../../include/rxgpu.h"
+#include "ivf_batch_plan.h"
 #include "ivf_train_plan.h"
 #include "knn_kernels.hip.h"
 #include "rxgpu_internal.h"
@@ -363,6 +364,8 @@ int rxgpu_index_set_lists(rxgpu_index* h, uint32_t nlist, const uint64_t* list_o
 	h->nlist = nlist;
 	h->lists_rows = total;
 	h->lists_count = h->count;
+	h->lists_longest = 0;
+	for (uint32_t l = 0; l < nlist; ++l) h->lists_longest = std::max<uint64_t>(h->lists_longest, list_off[l + 1] - list_off[l]);
 	return RXGPU_OK;
 }
 
@@ -499,6 +502,134 @@ int rxgpu_search_knn_lists(rxgpu_index* h, rxgpu_index* coarse, const float* que
 	if (out_scanned) *out_scanned = total;
 	if (total == 0) return RXGPU_OK;
 	return search_subset_host(h, c, query, 1, kk, static_cast<const uint32_t*>(c->d_subset.ptr), total, out_dist, out_row, out_count);
+}
+
+namespace {
+uint64_t ivf_batch_budget() {   // read per call (tests cut a call into several trains with it)
+	const char* e = getenv("RXGPU_IVF_BATCH_SCRATCH_BYTES");
+	return e && *e ? strtoull(e, nullptr, 10) : rxgpu::kIvfBatchScratchBytes;
+}
+
+// One device train over cq queries (host, prepared), all on c->stream: upload, coarse search, running chunk counts, list scan, merge, then one
+// set of copies back through the context's pinned block and one wait.  Layout and gridx: ivf_batch_plan.h.
+int ivf_batch_train(rxgpu_index* h, rxgpu_index* coarse, rxgpu_search_ctx* c, const float* queries, uint32_t cq, uint32_t nprobe, uint32_t kk, uint32_t gridx,
+					float* out_dist, uint32_t* out_row, uint32_t* out_count, uint64_t* out_scanned) {
+	const size_t qbytes = size_t(cq) * h->dim * sizeof(float);
+	if (int rc = c->d_queries.ensure(qbytes); rc) return rc;
+	RX_HIP(hipMemcpyAsync(c->d_queries.ptr, queries, qbytes, hipMemcpyHostToDevice, c->stream));
+	const rxgpu::IvfBatchScratch sc = rxgpu::ivf_batch_scratch(cq, nprobe);
+	if (int rc = c->d_ivf.ensure(sc.bytes); rc) return rc;
+	char* ivf = static_cast<char*>(c->d_ivf.ptr);
+	uint32_t* probe = reinterpret_cast<uint32_t*>(ivf + sc.o_probe);
+	uint32_t* pcnt = reinterpret_cast<uint32_t*>(ivf + sc.o_pcnt);
+	uint32_t* cum = reinterpret_cast<uint32_t*>(ivf + sc.o_cum);
+	unsigned long long* scanned = reinterpret_cast<unsigned long long*>(ivf + sc.o_scanned);
+	const size_t part = size_t(cq) * gridx * kk;
+	if (int rc = c->d_part_dist.ensure(part * sizeof(float)); rc) return rc;
+	if (int rc = c->d_part_row.ensure(part * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_dist.ensure(size_t(cq) * kk * sizeof(float)); rc) return rc;
+	if (int rc = c->d_out_row.ensure(size_t(cq) * kk * sizeof(uint32_t)); rc) return rc;
+	if (int rc = c->d_out_count.ensure(size_t(cq) * sizeof(uint32_t)); rc) return rc;
+	// the result's way back: [cq][kk] distances, [cq][kk] rows, [cq] rows probed, [cq] counts
+	const size_t o_hrow = size_t(cq) * kk * sizeof(float), o_hscan = o_hrow + size_t(cq) * kk * sizeof(uint32_t), o_hcnt = o_hscan + size_t(cq) * sizeof(uint64_t);
+	if (int rc = c->ensure_pinned(o_hcnt + size_t(cq) * sizeof(uint32_t)); rc) return rc;
+	// 1. the coarse search: the chain that answers rxgpu_search_knn on the centroids, whatever nq (the single call's bits)
+	rxgpu_search_ctx* cc = stream_ctx(coarse, c->stream);
+	auto* run = nprobe <= uint32_t(rxgpu::kMaxFusedK) ? enqueue_knn : enqueue_knn_fused;
+	if (int rc = run(coarse, cc, static_cast<const float*>(c->d_queries.ptr), cq, nprobe, reinterpret_cast<float*>(ivf + sc.o_pdist), probe, pcnt); rc) return rc;
+	// 2. running chunk counts and rows probed
+	{
+		ProfileScope ps(h, "ivf_batch_offsets", c->stream);
+		rxgpu::launch_ivf_batch_offsets(probe, pcnt, h->d_list_off, nprobe, cq, cum, scanned, c->stream);
+	}
+	// 3. the list scan, 4. the merge of its sorted partial lists
+	rxgpu::ScanParams p{};
+	p.rows = h->d_rows;
+	p.inv_norms = h->d_inv_norms;
+	p.queries = static_cast<const float*>(c->d_queries.ptr);
+	p.stride = h->stride;
+	p.dim = h->dim;
+	p.kk = kk;
+	p.part_dist = static_cast<float*>(c->d_part_dist.ptr);
+	p.part_row = static_cast<uint32_t*>(c->d_part_row.ptr);
+	{
+		ProfileScope ps(h, "scan_lists", c->stream);
+		rxgpu::launch_scan_lists(h->metric, p, probe, cum, h->d_list_off, h->d_list_rows, nprobe, cq, gridx, c->stream);
+	}
+	{
+		ProfileScope ps(h, "merge", c->stream);
+		rxgpu::launch_merge_lists(p.part_dist, p.part_row, gridx, kk, cq, static_cast<float*>(c->d_out_dist.ptr), static_cast<uint32_t*>(c->d_out_row.ptr),
+								  static_cast<uint32_t*>(c->d_out_count.ptr), c->stream);
+	}
+	RX_HIP(hipGetLastError());
+	char* hp = static_cast<char*>(c->h_pinned);
+	RX_HIP(hipMemcpyAsync(hp, c->d_out_dist.ptr, o_hrow, hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipMemcpyAsync(hp + o_hrow, c->d_out_row.ptr, o_hscan - o_hrow, hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipMemcpyAsync(hp + o_hscan, scanned, o_hcnt - o_hscan, hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipMemcpyAsync(hp + o_hcnt, c->d_out_count.ptr, size_t(cq) * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	RX_HIP(hipStreamSynchronize(c->stream));
+	const float* hd = reinterpret_cast<const float*>(hp);
+	const uint32_t* hr = reinterpret_cast<const uint32_t*>(hp + o_hrow);
+	const uint64_t* hs = reinterpret_cast<const uint64_t*>(hp + o_hscan);
+	const uint32_t* hc = reinterpret_cast<const uint32_t*>(hp + o_hcnt);
+	for (uint32_t q = 0; q < cq; ++q) {   // what the single call writes: the first count entries
+		const uint32_t n = std::min(hc[q], kk);
+		std::memcpy(out_dist + size_t(q) * kk, hd + size_t(q) * kk, size_t(n) * sizeof(float));
+		std::memcpy(out_row + size_t(q) * kk, hr + size_t(q) * kk, size_t(n) * sizeof(uint32_t));
+		out_count[q] = n;
+		if (out_scanned) out_scanned[q] = hs[q];
+	}
+	return RXGPU_OK;
+}
+}  // namespace
+
+int rxgpu_search_knn_lists_batch(rxgpu_index* h, rxgpu_index* coarse, const float* queries, uint32_t nq, uint32_t nprobe, uint32_t kk, float* out_dist,
+								 uint32_t* out_row, uint32_t* out_count, uint64_t* out_scanned) {
+	RX_CHECK(h && coarse && (nq == 0 || (queries && out_dist && out_row && out_count)), RXGPU_ERR_PARAMS, "rxgpu_search_knn_lists_batch: null argument");
+	if (int rc = ivf_check(h, coarse, "rxgpu_search_knn_lists_batch"); rc) return rc;
+	if (nq == 0) return RXGPU_OK;
+	std::fill(out_count, out_count + nq, 0u);
+	if (out_scanned) std::fill(out_scanned, out_scanned + nq, uint64_t(0));
+	if (h->count == 0 || kk == 0) return RXGPU_OK;
+	nprobe = std::max<uint32_t>(1, std::min<uint32_t>(nprobe, h->nlist));
+	uint64_t trains = 0, one_by_one = 0;
+	int rc = RXGPU_OK;
+	if (!rxgpu::ivf_batch_on_device(nprobe, kk)) {   // outside the envelope: the single call's chain per query, inside this call
+		for (uint32_t q = 0; q < nq && rc == RXGPU_OK; ++q, ++one_by_one) {
+			rc = rxgpu_search_knn_lists(h, coarse, queries + size_t(q) * h->dim, nprobe, kk, out_dist + size_t(q) * kk, out_row + size_t(q) * kk, out_count + q,
+										out_scanned ? out_scanned + q : nullptr);
+		}
+	} else {
+		DeviceGuard dg(h->device);
+		rxgpu_search_ctx* c = acquire_ctx(h);
+		if (!c) return RXGPU_ERR_DEVICE;
+		CtxLease lease{h, c};
+		const uint32_t gridx = rxgpu::ivf_batch_grid_x(nq, nprobe, h->nlist, h->lists_rows, h->lists_longest, uint32_t(h->cus));
+		const uint32_t per = rxgpu::ivf_batch_train_queries(nq, h->dim, nprobe, kk, gridx, ivf_batch_budget());
+		for (uint32_t q0 = 0; q0 < nq && rc == RXGPU_OK; q0 += per, ++trains) {
+			rc = ivf_batch_train(h, coarse, c, queries + size_t(q0) * h->dim, std::min(per, nq - q0), nprobe, kk, gridx, out_dist + size_t(q0) * kk,
+								 out_row + size_t(q0) * kk, out_count + q0, out_scanned ? out_scanned + q0 : nullptr);
+		}
+	}
+	std::lock_guard<std::mutex> lk(h->mtx);
+	h->ivf_batch_calls += 1;
+	h->ivf_batch_queries += nq;
+	h->ivf_batch_trains += trains;
+	h->ivf_batch_one_by_one += one_by_one;
+	return rc;
+}
+
+int rxgpu_ivf_batch_default(uint32_t nq, uint32_t nprobe, uint32_t kk) { return rxgpu::ivf_batch_default_on_device(nq, nprobe, kk) ? 1 : 0; }
+
+int rxgpu_ivf_read_batch_stats(rxgpu_index* h, uint64_t* calls, uint64_t* queries, uint64_t* trains, uint64_t* queries_one_by_one) {
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	std::lock_guard<std::mutex> lk(h->mtx);
+	if (calls) *calls = h->ivf_batch_calls;
+	if (queries) *queries = h->ivf_batch_queries;
+	if (trains) *trains = h->ivf_batch_trains;
+	if (queries_one_by_one) *queries_one_by_one = h->ivf_batch_one_by_one;
+	h->ivf_batch_calls = h->ivf_batch_queries = h->ivf_batch_trains = h->ivf_batch_one_by_one = 0;
+	return RXGPU_OK;
 }
 
 int rxgpu_search_range_lists(rxgpu_index* h, rxgpu_index* coarse, const float* query, uint32_t nprobe, float radius, int inclusive, float* out_dist,

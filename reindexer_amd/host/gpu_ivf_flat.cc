@@ -35,6 +35,12 @@ bool trainOnHost() {
 	return e && std::strcmp(e, "host") == 0;
 }
 
+// RXGPU_IVF_BATCH=threads (read per call): SearchBatch drives single searches from four host threads again, whatever the shape.  For A/B runs; same bits.
+bool batchOnThreads() {
+	const char* e = std::getenv("RXGPU_IVF_BATCH");
+	return e && std::strcmp(e, "threads") == 0;
+}
+
 }  // namespace
 
 GpuIvfFlat::GpuIvfFlat(VectorMetric metric, size_t dim, size_t nlist, int device)
@@ -359,6 +365,12 @@ GpuIvfFlat::TrainStatsData GpuIvfFlat::TrainStats() const {
 	return st;
 }
 
+GpuIvfFlat::BatchStatsData GpuIvfFlat::BatchStats() const {
+	BatchStatsData st;
+	if (rxgpu_ivf_read_batch_stats(dev_, &st.calls, &st.queries, &st.trains, &st.queriesOneByOne) != RXGPU_OK) throwDevice("GpuIvfFlat::BatchStats");
+	return st;
+}
+
 void GpuIvfFlat::AddWithIds(size_t n, const float* x, const idx_t* ids) {
 	if (n == 0) return;
 	if (count_ + n > 0xFFFFFFF0ull) throw std::runtime_error("GpuIvfFlat: too many vectors");
@@ -498,15 +510,58 @@ void GpuIvfFlat::Search(const float* x, size_t k, size_t nprobe, float* distance
 	if (trained_) orderTies(n, distances, labels);
 }
 
-// n queries (IndexIVFFlat::search's n; ivf_index.cc:355-372 passes 1, SelectKnn callers with several keys more): the queries are independent
-// launch trains, so a few host threads drive them side by side — every Search checks out its own device scratch and stream.
+// n queries (IndexIVFFlat::search's n; ivf_index.cc:355-372 passes 1, SelectKnn callers with several keys more).  On a trained index they
+// are ONE rxgpu_search_knn_lists_batch call — the coarse search, the list scan and the merge of all of them as one launch train — and the
+// tail of Search per query: where equal distances straddle the k-th place that query alone is replayed.  Where the rule of the batch call
+// says so (rxgpu_ivf_batch_default: nprobe or k + 1 above 128) and under RXGPU_IVF_BATCH=threads, the host threads below drive single searches.
 void GpuIvfFlat::SearchBatch(size_t n, const float* x, size_t k, size_t nprobe, float* distances, idx_t* labels) const {
 	if (n == 0) return;
-	const size_t workers = std::min<size_t>(n, 4);
-	if (workers <= 1) {
+	if (n == 1) {
 		Search(x, k, nprobe, distances, labels);
 		return;
 	}
+	const uint32_t np = uint32_t(std::min(std::max<size_t>(nprobe, 1), nlist_));
+	const bool fits = k > 0 && k < 0xFFFFFFFFull && n <= 0xFFFFFFFFull;
+	if (trained_ && count_ > 0 && fits && !batchOnThreads() && rxgpu_ivf_batch_default(uint32_t(n), np, uint32_t(k + 1)) == 1) {
+		const float pad = metric_ == VectorMetric::L2 ? std::numeric_limits<float>::infinity() : -std::numeric_limits<float>::infinity();
+		std::fill(distances, distances + n * k, pad);
+		std::fill(labels, labels + n * k, idx_t(-1));
+		std::vector<float> q(n * dim_), one;
+		for (size_t i = 0; i < n; ++i) {
+			prepareQuery(x + i * dim_, one);
+			std::memcpy(q.data() + i * dim_, one.data(), dim_ * sizeof(float));
+		}
+		syncLists();
+		const size_t kk = k + 1;   // one candidate more than asked for, as in Search
+		std::vector<float> dist(n * kk);
+		std::vector<uint32_t> row(n * kk), cnt(n);
+		if (rxgpu_search_knn_lists_batch(dev_, devCentroids_, q.data(), uint32_t(n), np, uint32_t(kk), dist.data(), row.data(), cnt.data(), nullptr) != RXGPU_OK) {
+			throwDevice("GpuIvfFlat::SearchBatch");
+		}
+		for (size_t i = 0; i < n; ++i) {
+			const float* d = dist.data() + i * kk;
+			const uint32_t* r = row.data() + i * kk;
+			float* outD = distances + i * k;
+			idx_t* outL = labels + i * k;
+			if (cnt[i] > k && d[k] == d[k - 1]) {
+				replayTies(q.data() + i * dim_, k, nprobe, d[k - 1], outD, outL);
+				continue;
+			}
+			const uint32_t m = uint32_t(std::min<size_t>(cnt[i], k));
+			for (uint32_t j = 0; j < m; ++j) {
+				outD[j] = toFaiss(d[j]);
+				outL[j] = ids_[r[j]];
+			}
+			orderTies(m, outD, outL);
+		}
+		return;
+	}
+	searchBatchThreads(n, x, k, nprobe, distances, labels);
+}
+
+// The queries as independent launch trains: a few host threads drive them side by side — every Search checks out its own device scratch and stream.
+void GpuIvfFlat::searchBatchThreads(size_t n, const float* x, size_t k, size_t nprobe, float* distances, idx_t* labels) const {
+	const size_t workers = std::min<size_t>(n, 4);
 	if (trained_) syncLists();   // once, before the threads (it mutates the cached device lists)
 	std::atomic<size_t> next{0};
 	std::exception_ptr failure;

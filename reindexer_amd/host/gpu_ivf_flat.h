@@ -30,7 +30,9 @@
 // ordered per-centroid chains on the device, ivf_train.hip); the list scan is knn_scan_subset / knn_range_subset over the row list of the probed
 // inverted lists, so a query reads nprobe / nlist of the corpus.  The lists are mirrored into HBM as CSR (rebuilt after a mutation) and a
 // search with nprobe <= 64 is ONE C-ABI call (rxgpu_search_knn_lists): coarse search, list union (bitmap), row list and scan all on the
-// device; the host copy of the lists serves mutations, range search and wider probes.
+// device; the host copy of the lists serves mutations, range search and wider probes.  Several queries are ONE call too
+// (rxgpu_search_knn_lists_batch): the lists are disjoint, so the scan walks each query's probed lists back to back — one coarse search, one
+// list scan and one merge for the whole batch (knn_lists.hip).
 #pragma once
 
 #include <cstdint>
@@ -97,8 +99,15 @@ public:
 	// search(1, x, k, distances, labels, nprobe): best first; L2: squared distance ascending, inner product / cosine: similarity descending;
 	// labels[i] = -1 past the last hit (FAISS convention).  Untrained: exact search over everything (IndexFlat).
 	void Search(const float* x, size_t k, size_t nprobe, float* distances, idx_t* labels) const;
-	// n queries, x [n][dim] -> distances / labels [n][k]: the searches run side by side on a few streams
+	// n queries, x [n][dim] -> distances / labels [n][k], each what Search gives.  Trained, n >= 2, nprobe and k + 1 up to 128: one
+	// rxgpu_search_knn_lists_batch call (one launch train for all queries), then Search's tie handling per query.  Otherwise, and under
+	// RXGPU_IVF_BATCH=threads in the environment (read per call), single searches side by side on a few streams.
 	void SearchBatch(size_t n, const float* x, size_t k, size_t nprobe, float* distances, idx_t* labels) const;
+	// what the batch call did for SearchBatch since the last call: calls, their queries, device trains, queries it answered one by one
+	struct BatchStatsData {
+		uint64_t calls = 0, queries = 0, trains = 0, queriesOneByOne = 0;
+	};
+	BatchStatsData BatchStats() const;
 	// range_search: L2: dist < radius; inner product / cosine: similarity > radius; sorted best first
 	void RangeSearch(const float* x, float radius, size_t nprobe, std::vector<float>& distances, std::vector<idx_t>& labels) const;
 
@@ -119,6 +128,7 @@ private:
 	// faiss tie semantics over the candidates with internal distance <= worst (see Search)
 	void replayTies(const float* q, size_t k, size_t nprobe, float worst, float* distances, idx_t* labels) const;
 	void orderTies(size_t n, float* distances, idx_t* labels) const;
+	void searchBatchThreads(size_t n, const float* x, size_t k, size_t nprobe, float* distances, idx_t* labels) const;
 	float toFaiss(float internal) const noexcept { return metric_ == VectorMetric::L2 ? internal : -internal; }
 
 	const VectorMetric metric_;

@@ -1526,6 +1526,17 @@ int rxhost_ivf_train_stats(void* h, uint64_t* counts, double* ms) {
 		ms[1] = st.sumsMs;
 	});
 }
+// GpuIvfFlat::BatchStats: out = {batch calls, their queries, device trains, queries answered one by one} since the last call — all zero
+// where SearchBatch drove single searches (RXGPU_IVF_BATCH=threads, or a shape outside the batch call's envelope)
+int rxhost_ivf_batch_stats(void* h, uint64_t* out) {
+	return guarded([&] {
+		const auto st = static_cast<const GpuIvfFlat*>(h)->BatchStats();
+		out[0] = st.calls;
+		out[1] = st.queries;
+		out[2] = st.trains;
+		out[3] = st.queriesOneByOne;
+	});
+}
 int rxhost_ivf_centroids(void* h, float* out) {
 	return guarded([&] {
 		const auto& c = static_cast<const GpuIvfFlat*>(h)->Centroids();

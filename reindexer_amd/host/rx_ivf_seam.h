@@ -50,9 +50,13 @@ public:
 	}
 	size_t AllocatedMemSize() const noexcept { return ivf_->NTotal() * (ivf_->Dim() * sizeof(float) + sizeof(idx_t) + 2 * sizeof(uint32_t)); }
 
-	// faiss::Index::search as IvfIndex's helpers call it: n == 1
+	// faiss::Index::search: IvfIndex's helpers call it with n == 1; several queries are one batched list search (GpuIvfFlat::SearchBatch)
 	void search(idx_t n, const float* x, idx_t k, float* distances, idx_t* labels, const faiss::SearchParameters* params = nullptr) const {
-		for (idx_t i = 0; i < n; ++i) ivf_->Search(x + size_t(i) * ivf_->Dim(), size_t(k), nprobeOf(params), distances + size_t(i) * k, labels + size_t(i) * k);
+		if (n > 1) {
+			ivf_->SearchBatch(size_t(n), x, size_t(k), nprobeOf(params), distances, labels);
+		} else if (n == 1) {
+			ivf_->Search(x, size_t(k), nprobeOf(params), distances, labels);
+		}
 	}
 	// faiss::Index::range_search: result->lims is allocated by the caller's RangeSearchResult(nq); labels / distances by do_allocation()
 	void range_search(idx_t n, const float* x, float radius, faiss::RangeSearchResult* result, const faiss::SearchParameters* params = nullptr) const {

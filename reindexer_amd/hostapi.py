@@ -1451,6 +1451,7 @@ class GpuIvfFlat:
             L.rxhost_ivf_list_sizes.argtypes = [_vp, _vp]
             L.rxhost_ivf_centroids.argtypes = [_vp, _vp]
             L.rxhost_ivf_train_stats.argtypes = [_vp, _vp, _vp]
+            L.rxhost_ivf_batch_stats.argtypes = [_vp, _vp]
             L._ivf_bound = True
         self.dim, self.metric, self.nlist = dim, metric, nlist
         self.h = L.rxhost_ivf_create(metric, dim, nlist, device)
@@ -1501,6 +1502,15 @@ class GpuIvfFlat:
             _raise(rc)
         return {"rows_assigned": int(counts[0]), "steps": int(counts[1]), "kernel_ms": float(ms[0]), "sums_ms": float(ms[1])}
 
+    def batch_stats(self) -> dict:
+        """What rxgpu_search_knn_lists_batch did for search_batch() since the last call: calls, queries, trains (device launch trains) and
+        queries_one_by_one.  All zero where search_batch drove single searches (RXGPU_IVF_BATCH=threads, nprobe or k + 1 above 128)."""
+        out = np.zeros(4, np.uint64)
+        rc = lib().rxhost_ivf_batch_stats(self.h, out.ctypes.data)
+        if rc:
+            _raise(rc)
+        return {"calls": int(out[0]), "queries": int(out[1]), "trains": int(out[2]), "queries_one_by_one": int(out[3])}
+
     def remove_ids(self, ids) -> int:
         ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
         n = lib().rxhost_ivf_remove(self.h, ids.ctypes.data, ids.shape[0])
@@ -1522,7 +1532,8 @@ class GpuIvfFlat:
         return d[:k], l[:k]
 
     def search_batch(self, x, k: int, nprobe: int = 1):
-        """x [n][dim] -> (distances [n][k], labels [n][k]): GpuIvfFlat::SearchBatch, the queries side by side on a few streams."""
+        """x [n][dim] -> (distances [n][k], labels [n][k]): GpuIvfFlat::SearchBatch — on a trained index one batched list search for all
+        queries (RXGPU_IVF_BATCH=threads in the environment: single searches side by side on a few streams)."""
         x = _f32(x).reshape(-1, self.dim)
         n = x.shape[0]
         d, l = np.empty((n, max(k, 1)), np.float32), np.empty((n, max(k, 1)), np.int64)

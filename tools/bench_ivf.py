@@ -4,6 +4,8 @@
     python tools/bench_ivf.py --rows 1000000 --dim 768 --nlist 1024 --queries 200 [--out profiles/r1_ivf_1m.json]
     python tools/bench_ivf.py --train-ab --rows 1000000 --dim 768 --nlist 1024 [--metric l2] [--parent-root DIR] [--out FILE]
         train() on the device path against RXGPU_IVF_TRAIN=host (and a checkout of the parent commit), every leg in a fresh child process
+    python tools/bench_ivf.py --batch-ab --rows 1000000 --dim 768 --nlist 1024 [--metric cosine] [--out profiles/ivf_batch_ab.json]
+        search_batch on one index in one session: the batched list search against RXGPU_IVF_BATCH=threads, 256 and 4096 queries at nprobe 1 / 16 / 64
 
 Per query: coarse quantiser (KNN over the centroids) -> host merge of the probed lists' rows -> row-list scan (knn_scan_subset).  Recall@k is
 measured against the exact result (the same index with every list probed, which the tests pin to the brute-force oracle).  There is no CPU
@@ -140,6 +142,105 @@ def train_ab(args):
         Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
 
 
+def batch_ab(args):
+    """search_batch on ONE trained index in one session: the default (rxgpu_search_knn_lists_batch, one launch train for all queries) against
+    RXGPU_IVF_BATCH=threads (four host threads driving single searches), --batch-queries queries at --batch-nprobe, the legs alternating,
+    --repeat timed calls of each behind one warm-up call; medians and ranges.  Labels and distance bits of the two legs are compared.  The
+    scan kernel's own time comes from the C-ABI over the same rows, centroids and lists (event pairs of the "scan_lists" profile slot), its
+    bytes are the rows probed x dim x 4."""
+    metric = capi.METRICS[args.metric]
+    nqs = [int(x) for x in args.batch_queries.split(",")]
+    nprobes = [int(x) for x in args.batch_nprobe.split(",")]
+    rows = make_rows(args.rows, args.dim, args.clusters)
+    rng = np.random.default_rng(20260925)
+    queries = np.ascontiguousarray(rows[rng.integers(0, args.rows, max(nqs))] + rng.standard_normal((max(nqs), args.dim), dtype=np.float32) * np.float32(0.08))
+    ivf = hostapi.GpuIvfFlat(metric, args.dim, args.nlist)
+    step = 100_000
+    for a in range(0, args.rows, step):
+        ivf.add_with_ids(rows[a:a + step], np.arange(a, min(args.rows, a + step), dtype=np.int64))
+    ivf.train()
+    sizes = ivf.list_sizes()
+    out = {"workload": f"IVF-Flat search_batch, {args.metric}, {args.rows} x {args.dim}, nlist={args.nlist}, k={args.k}, {args.clusters} gaussian clusters; "
+                       "queries = stored rows + noise",
+           "arch": capi.device_arch(0), "repeat": args.repeat,
+           "protocol": "one index, one process; per shape one untimed call of each leg, then the legs alternating, host clock around search_batch "
+                       "(which ends in a device synchronisation); median of the timed calls, min and max given",
+           "legs": {"train": "default: one rxgpu_search_knn_lists_batch call", "threads": "RXGPU_IVF_BATCH=threads: four host threads, one rxgpu_search_knn_lists per query"},
+           "list_sizes": {"min": int(sizes.min()), "median": float(np.median(sizes)), "max": int(sizes.max()), "empty": int((sizes == 0).sum())},
+           "shapes": []}
+
+    def set_leg(leg):
+        if leg == "threads":
+            os.environ["RXGPU_IVF_BATCH"] = "threads"
+        else:
+            os.environ.pop("RXGPU_IVF_BATCH", None)
+
+    for nq in nqs:
+        for nprobe in nprobes:
+            q = queries[:nq]
+            times = {"train": [], "threads": []}
+            got, stats = {}, {}
+            for leg in times:
+                set_leg(leg)
+                ivf.search_batch(q, args.k, nprobe=nprobe)
+            ivf.batch_stats()
+            for _ in range(args.repeat):
+                for leg in times:
+                    set_leg(leg)
+                    t0 = time.perf_counter()
+                    d, l = ivf.search_batch(q, args.k, nprobe=nprobe)
+                    times[leg].append(time.perf_counter() - t0)
+                    got[leg] = (np.ascontiguousarray(d).view(np.uint32).copy(), l.copy())
+                    stats[leg] = ivf.batch_stats()
+            set_leg("train")
+            entry = {"queries": nq, "nprobe": nprobe}
+            for leg, t in times.items():
+                med = statistics.median(t)
+                entry[leg] = {"seconds_median": med, "seconds_min": min(t), "seconds_max": max(t), "seconds": t, "queries_per_sec_median": nq / med,
+                              "batch_stats_last_call": stats[leg]}
+            entry["threads_over_train"] = entry["threads"]["seconds_median"] / entry["train"]["seconds_median"]
+            entry["same_labels_and_distance_bits"] = bool(np.array_equal(got["train"][0], got["threads"][0]) and np.array_equal(got["train"][1], got["threads"][1]))
+            out["shapes"].append(entry)
+            print(f"# nq {nq} nprobe {nprobe}: train {entry['train']['seconds_median'] * 1e3:.2f} ms, threads {entry['threads']['seconds_median'] * 1e3:.2f} ms, "
+                  f"same {entry['same_labels_and_distance_bits']}", file=sys.stderr, flush=True)
+    # the scan kernel alone: the same rows, centroids and lists behind the C-ABI, profiling on
+    cents = np.ascontiguousarray(ivf.centroids())
+    lists = [ivf.list_ids(l).astype(np.uint32) for l in range(args.nlist)]   # ids are row numbers here
+    ivf.close()
+    cosine = args.metric == "cosine"
+    qprep = np.stack([hostapi.normalize_copy(v)[0] for v in queries]) if cosine else queries
+    with capi.VectorIndex(metric, args.dim, args.rows) as ix, capi.VectorIndex(metric, args.dim, args.nlist) as cx:
+        for a in range(0, args.rows, step):
+            r = rows[a:a + step]
+            ix.upload_rows(a, r, (1.0 / np.sqrt(np.einsum("ij,ij->i", r.astype(np.float64), r.astype(np.float64)))).astype(np.float32) if cosine else None)
+        cx.upload_rows(0, cents, (1.0 / np.linalg.norm(cents.astype(np.float64), axis=1)).astype(np.float32) if cosine else None)
+        ix.set_lists(lists)
+        ix.profile_enable(True)
+        for entry in out["shapes"]:
+            nq, nprobe = entry["queries"], entry["nprobe"]
+            ix.search_knn_lists_batch(cx, qprep[:nq], nprobe, args.k + 1)
+            n0, ms0 = ix.profile_read("scan_lists")
+            m0 = ix.profile_read("merge")[1]
+            o0 = ix.profile_read("ivf_batch_offsets")[1]
+            for _ in range(args.repeat):
+                _, _, _, scanned = ix.search_knn_lists_batch(cx, qprep[:nq], nprobe, args.k + 1)
+            n1, ms1 = ix.profile_read("scan_lists")
+            launches = n1 - n0
+            ms = (ms1 - ms0) / max(launches, 1)
+            nbytes = int(scanned.sum()) * args.dim * 4
+            entry["scan_lists_kernel"] = {"launches_per_call": launches / args.repeat, "ms_per_launch_mean": ms, "rows_probed": int(scanned.sum()), "bytes": nbytes,
+                                          "bytes_per_second": nbytes / (ms * 1e-3) if ms > 0 else None,
+                                          "fraction_of_hbm_spec_8TBps": nbytes / (ms * 1e-3) / HBM_SPEC_BYTES_PER_S if ms > 0 else None,
+                                          "merge_ms_per_call_mean": (ix.profile_read("merge")[1] - m0) / args.repeat,
+                                          "offsets_ms_per_call_mean": (ix.profile_read("ivf_batch_offsets")[1] - o0) / args.repeat,
+                                          "note": "the norms of this leg's rows are computed in numpy (not the engine's): timing only, no bits are compared here"}
+        ix.profile_enable(False)
+    text = json.dumps(out)
+    print(text)
+    if args.out:
+        Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -155,6 +256,9 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--parent-root", default=None, help="a built checkout of the parent commit (its reindexer_amd package) for a third leg")
     ap.add_argument("--leg-timeout", type=int, default=300)
+    ap.add_argument("--batch-ab", action="store_true", help="time search_batch on one index: the batched list search against RXGPU_IVF_BATCH=threads")
+    ap.add_argument("--batch-queries", default="256,4096")
+    ap.add_argument("--batch-nprobe", default="1,16,64")
     ap.add_argument("--train-leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--rows-file", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--root", default=None, help=argparse.SUPPRESS)
@@ -163,6 +267,8 @@ def main():
         return train_leg(args)
     if args.train_ab:
         return train_ab(args)
+    if args.batch_ab:
+        return batch_ab(args)
     metric = capi.METRICS[args.metric]
     rng = np.random.default_rng(20260924)
     centres = rng.normal(0, 0.25, (args.clusters, args.dim)).astype(np.float32)
