@@ -8,6 +8,9 @@ Corpus of that test (5 docs + the empty sentinel vdoc, one FT field, default FTC
   3 "слово простая фраза что то еще."                            6 words
   4 "слово начало простая фраза конец что то еще простая фраза слово слово."   12 words
   5 "жил пил гулял"                                              3 words          => average 6.4 words
+
+The merger comparisons below draw their documents at random below `total` (3000 nearly everywhere).  Totals ON the kernels' edges (2, 33,
+8191 .. 32769) with documents placed next to every document-range boundary are pinned in tests/test_ft_edge_cases.py.
 """
 from pathlib import Path
 
