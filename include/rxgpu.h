@@ -526,6 +526,23 @@ int rxgpu_hnsw_read_sq8_quantize_stats(rxgpu_index* h, uint64_t* rows, uint64_t*
  * rxgpu_hnsw_search_knn. */
 int rxgpu_hnsw_search_knn_sq8(rxgpu_index* h, const uint8_t* query_codes, const float* query_corr, const float* query_norm_coef, uint32_t nq,
 							  uint32_t k, uint32_t ef, float* out_dist, uint32_t* out_row, uint32_t* out_count);
+/* SearchKnn under an allowed-rows bitmap — `WHERE cond AND KNN(...)` on a graph index in ONE device call.  allowed_words = host
+ * [n_words >= ceil(count / 32)], bit (r % 32) of word r / 32 set = node r may be returned (rxgpu_search_knn_bitmap's layout); bits at and
+ * above the node count are ignored; one bitmap serves all nq queries.  The reference fork has no filter functor: its delete mark is how it
+ * expresses a node that is traversed but not returned (hnswalg.h:1982 picks the branch by num_deleted, runLayer0Step :871-963 keeps a marked
+ * node in candidate_set and out of top_candidates, MarkDelete :1303-1339 sets the mark).  So, per query, the call returns what
+ * rxgpu_hnsw_search_knn (_sq8) returns on the same graph if every node with a clear bit also carried the delete mark, num_deleted counting
+ * the nodes marked either way: ef == 0, the clamp of k and the outputs (unordered (dist, row), out_count[q] <= k) are the unfiltered call's.
+ * *out_allowed (may be NULL) = set bits below the node count.  The kernels read the bitmap itself where they read the delete byte (N / 8
+ * bytes per call in flight, uploaded once per call into the call's own context: concurrent calls bring their own filters).  A graph without
+ * delete marks under a bitmap with every bit below the count set is answered by the unfiltered path (the reference's bare-bone branch).
+ * RXGPU_ERR_PARAMS: allowed_words == NULL, n_words < ceil(count / 32), ef > 4096.  RXGPU_ERR_LOGIC: a sharded handle (its shard handles
+ * take the call), no graph attached (no codes attached for _sq8).  nq == 0 or k == 0: RXGPU_OK, nothing written. */
+int rxgpu_hnsw_search_knn_filtered(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, const uint32_t* allowed_words,
+								   uint64_t n_words, float* out_dist, uint32_t* out_row, uint32_t* out_count, uint64_t* out_allowed);
+int rxgpu_hnsw_search_knn_sq8_filtered(rxgpu_index* h, const uint8_t* query_codes, const float* query_corr, const float* query_norm_coef, uint32_t nq,
+									   uint32_t k, uint32_t ef, const uint32_t* allowed_words, uint64_t n_words, float* out_dist, uint32_t* out_row,
+									   uint32_t* out_count, uint64_t* out_allowed);
 /* ONE quantised query through the index's RESIDENT search kernel over the SQ8 codes — rxgpu_hnsw_search_knn_posted for a quantised graph: the
  * same mailbox protocol, the same lifetime rules (idle / lifetime / every mutating entry point, the uploads of the code table among them, make
  * the kernel leave), one wavefront per slot.  The query travels as for rxgpu_hnsw_search_knn_sq8 with nq == 1: query_codes [dim], its

@@ -115,6 +115,13 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "hnsw_kernel_pick.h", CSRC / "hnsw_distance_blocks.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
+    # ... and which kernel a search under an allowed-rows bitmap gets (the filtered family of the same header)
+    src = tdir / "hnsw_filtered_pick_cpu.cc"
+    if src.exists():
+        out = tdir / "libhnsw_filtered_pick_cpu.so"
+        if force or _stale(out, [src, CSRC / "hnsw_kernel_pick.h", CSRC / "hnsw_distance_blocks.h"]):
+            _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
+        outs.append(out)
     # the decisions of one BM25 merge compiled for the host (CPU check of the plan the merge entry points execute)
     src = tdir / "ft_merge_plan_cpu.cc"
     if src.exists():

@@ -112,6 +112,8 @@ _SIGNATURES = {
     "rxgpu_hnsw_read_sq8_rows": (_i, [_vp, _u64, _u64, _vp, _vp]),
     "rxgpu_hnsw_read_sq8_quantize_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_double)]),
     "rxgpu_hnsw_search_knn_sq8": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "rxgpu_hnsw_search_knn_filtered": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "rxgpu_hnsw_search_knn_sq8_filtered": (_i, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(_u64)]),
     "rxgpu_hnsw_search_knn_sq8_posted": (_i, [_vp, _vp, _f, _f, _u32, _u32, _vp, _vp, _vp, C.POINTER(C.c_int32)]),
     "rxgpu_hnsw_read_stats": (_i, [_vp, C.POINTER(_u64), C.POINTER(_u64)]),
     "rxgpu_hnsw_read_tie_reruns": (_i, [_vp, C.POINTER(_u64)]),
@@ -609,6 +611,37 @@ class VectorIndex:
         cnt = np.zeros(nq, np.uint32)
         _check(lib().rxgpu_hnsw_search_knn(self._h, q.ctypes.data, nq, k, ef, dist.ctypes.data, row.ctypes.data, cnt.ctypes.data))
         return dist[:, :k], row[:, :k], cnt
+
+    def hnsw_search_knn_filtered(self, queries, k: int, ef: int, allowed_words):
+        """SearchKnn under an allowed-rows bitmap (rxgpu_hnsw_search_knn_filtered): bit r % 32 of word r // 32 set = node r may be returned;
+        one bitmap for all queries.  (dist, row, count, set bits below the node count)."""
+        q = _f32c(queries).reshape(-1, self.dim)
+        nq = q.shape[0]
+        words = np.ascontiguousarray(allowed_words, np.uint32).reshape(-1)
+        dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        row = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        cnt = np.zeros(nq, np.uint32)
+        n_allowed = _u64(0)
+        _check(lib().rxgpu_hnsw_search_knn_filtered(self._h, q.ctypes.data, nq, k, ef, words.ctypes.data, words.size, dist.ctypes.data, row.ctypes.data,
+                                                    cnt.ctypes.data, C.byref(n_allowed)))
+        return dist[:, :k], row[:, :k], cnt, int(n_allowed.value)
+
+    def hnsw_search_knn_sq8_filtered(self, qcodes, qcorr, qnorm, k: int, ef: int, allowed_words):
+        """The same over the SQ8 codes (rxgpu_hnsw_search_knn_sq8_filtered); the queries travel as for hnsw_search_knn_sq8."""
+        qc = np.ascontiguousarray(qcodes, np.uint8).reshape(-1, self.dim)
+        nq = qc.shape[0]
+        qcorr = _f32c(qcorr).reshape(-1)
+        qnorm = _f32c(qnorm).reshape(-1)
+        if qcorr.shape[0] != nq or qnorm.shape[0] != nq:
+            raise ValueError("one corrective offset and one normCoef per query")
+        words = np.ascontiguousarray(allowed_words, np.uint32).reshape(-1)
+        dist = np.full((nq, max(k, 1)), np.inf, np.float32)
+        row = np.full((nq, max(k, 1)), 0xFFFFFFFF, np.uint32)
+        cnt = np.zeros(nq, np.uint32)
+        n_allowed = _u64(0)
+        _check(lib().rxgpu_hnsw_search_knn_sq8_filtered(self._h, qc.ctypes.data, qcorr.ctypes.data, qnorm.ctypes.data, nq, k, ef, words.ctypes.data,
+                                                        words.size, dist.ctypes.data, row.ctypes.data, cnt.ctypes.data, C.byref(n_allowed)))
+        return dist[:, :k], row[:, :k], cnt, int(n_allowed.value)
 
     def hnsw_search_knn_posted(self, query, k: int, ef: int = 0):
         """One query through the index's resident search kernel (rxgpu_hnsw_search_knn_posted): (dist, row, count, served)."""

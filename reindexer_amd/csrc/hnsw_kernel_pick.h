@@ -44,9 +44,10 @@ struct HnswPickInput {
 	uint32_t nbl, spec, maxM0;
 	uint32_t blocks;                                 // searches of the launch / groups of helpers / slots of the mailbox
 	bool global_cand;
+	bool filtered = false;                           // the call brings an allowed-rows bitmap (HnswFilteredParams): the kernels of hnsw_filtered.hip
 };
 
-enum HnswKernelFamily : int { kHnswSearch = 0, kHnswTeam, kHnswHelper, kHnswServer, kHnswServerWide, kHnswServerSq8 };
+enum HnswKernelFamily : int { kHnswSearch = 0, kHnswTeam, kHnswHelper, kHnswServer, kHnswServerWide, kHnswServerSq8, kHnswFiltered, kHnswFilteredTeam };
 
 struct HnswKernelPick {
 	HnswKernelFamily family;
@@ -93,8 +94,44 @@ constexpr HnswKernelPick hnsw_pick_end(HnswKernelPick k, size_t lds) {
 	return k;
 }
 
+// launch_hnsw_filtered: a search under an allowed-rows bitmap (hnsw_filtered_kernel, or hnsw_filtered_team_kernel for a handful of floats
+// searches).  Hidden nodes are traversed like deleted ones, so the pick is never bare: the list with deleted nodes up to ef = 224
+// (kHnswSortedMaxEfDel), the heaps above that and in every re-run with global candidates.  The family has the fixed distance batches for
+// 128 and 768 components only (other fixed sizes take the generic batch: same bits), no latency form outside the team, no link-block or
+// look-ahead area, and neither helpers nor a resident form (the launch plan and hnsw_search_impl leave both out).
+constexpr int hnsw_filtered_blocks(uint32_t dim) { return dim == 128u ? 2 : dim == 768u ? 12 : 0; }
+constexpr HnswKernelPick pick_hnsw_filtered(const HnswPickInput& in) {
+	HnswKernelPick k = hnsw_pick_start(in, kHnswFiltered);
+	k.sq8 = in.sq8;
+	k.global_cand = in.global_cand;
+	k.vis_lds = 0;
+	if (in.sorted && !in.global_cand && in.ef <= 224u) {
+		k.sorted = hnsw_sorted_slots(in.ef, false);
+		k.del = true;
+	}
+	k.nb = hnsw_filtered_blocks(in.dim);
+	size_t lds = hnsw_lds_layout(in.ef_cap, in.lds_cand_cap, in.global_cand, k.nb, in.sq8).visited_off();
+	if (!in.sq8 && k.nb > 0 && k.sorted > 0 && in.team > 1u && in.blocks <= in.team_max) {   // the planner's call is one query: four wavefronts per search
+		k.family = kHnswFilteredTeam;
+		k.latency = true;
+		k.team = 4;
+		k.threads = 256;
+		if (in.vis_lds_log2) {   // the visited set in LDS, by the rule of the unfiltered team (pick_hnsw_search)
+			uint32_t lg = in.vis_lds_log2;
+			if (lg >= 12u && lg < 14u) lg += 1u;
+			if ((size_t(4) << lg) <= (64u << 10)) {
+				k.vis_lds = 1;
+				k.vis_hash_log2 = lg;
+				lds += size_t(4) << lg;
+			}
+		}
+	}
+	return hnsw_pick_end(k, lds);
+}
+
 // launch_hnsw_search: hnsw_search_kernel, or hnsw_team_kernel for a handful of searches
 constexpr HnswKernelPick pick_hnsw_search(const HnswPickInput& in) {
+	if (in.filtered) return pick_hnsw_filtered(in);
 	HnswKernelPick k = hnsw_pick_start(in, kHnswSearch);
 	k.sq8 = in.sq8;
 	k.global_cand = in.global_cand;
@@ -191,6 +228,13 @@ constexpr bool hnsw_search_kernel_exists(bool global_cand, int nb, bool latency,
 	return sq8 ? (!latency && hnsw_sq8_nb(nb, del)) : (hnsw_float_nb(nb) && (!latency || nb > 8));
 }
 constexpr bool hnsw_team_kernel_exists(int nb, int sorted, bool del) { return nb > 0 && hnsw_float_nb(nb) && hnsw_sorted_form_exists(sorted, del); }
+// hnsw_filtered.hip: heaps in LDS and with global candidates, the three lists with deleted nodes; floats and codes with the generic batch and
+// the fixed ones for 128 and 768 components; the team for floats at those two sizes on the lists
+constexpr bool hnsw_filtered_kernel_exists(bool team, bool global_cand, int nb, bool sq8, int sorted, bool del) {
+	if (nb != 0 && nb != 2 && nb != 12) return false;
+	if (team) return !sq8 && nb > 0 && !global_cand && del && sorted >= 2 && sorted <= 4;
+	return sorted == 0 ? !del : (del && !global_cand && sorted >= 2 && sorted <= 4);
+}
 constexpr bool hnsw_helper_kernel_exists(int nb, bool sq8) { return sq8 ? hnsw_sq8_nb(nb, true) : (hnsw_float_nb(nb) && nb != 8); }
 constexpr bool hnsw_server_kernel_exists(int nb, bool sq8, int sorted, bool del) {
 	return nb > 0 && (sorted == 2 || sorted == 4) && (sq8 ? hnsw_sq8_nb(nb, del) : hnsw_float_nb(nb));

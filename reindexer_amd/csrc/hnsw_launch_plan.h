@@ -107,8 +107,10 @@ struct HnswLaunchPlan {
 
 // count / dim / bare: the index (rows, floats or codes per row, no deleted nodes); nq / k / ef: the call, k and ef already defaulted and
 // checked; visited_avail_bytes: free HBM + what the context's visited buffer already holds (small calls pass the latter alone).
+// filtered: the call brings an allowed-rows bitmap — never bare (the caller passes bare = false), and no helper workgroups: the filtered
+// family has none.
 inline HnswLaunchPlan plan_hnsw_search(uint64_t count, uint32_t dim, bool bare, uint32_t nq, uint32_t k, uint32_t ef, bool sq8, bool to_host,
-									   uint64_t visited_avail_bytes, const HnswKnobs& knobs) {
+									   uint64_t visited_avail_bytes, const HnswKnobs& knobs, bool filtered = false) {
 	HnswLaunchPlan pl{};
 	// ef > 1024: the result heap alone takes the LDS budget of a search — the candidate heap goes to global scratch from the start
 	const bool big_ef = pl.big_ef = ef > uint32_t(kHnswLdsCandEf);
@@ -214,7 +216,7 @@ inline HnswLaunchPlan plan_hnsw_search(uint64_t count, uint32_t dim, bool bare, 
 	// Round 4: with helper workgroups beside the batch (below) an overflowing restart is no longer a launch behind the batch, and the area
 	// can shrink to what lets a CU hold 20 searches instead of 15 (LDS per workgroup 10.3 -> 7.6 KB): first pass of 16 384 queries at
 	// 1M x 768 11.9 -> 10.5 ms (profiles/rd4k_hnsw_1m_restart_caps.txt; without the helpers the one restart that overflows costs 2.5 ms).
-	const bool helper_wanted = pl.helper_wanted = nq >= 2048 && !big_ef && knobs.helper != 0;
+	const bool helper_wanted = pl.helper_wanted = nq >= 2048 && !big_ef && knobs.helper != 0 && !filtered;
 	// ... where a batch lasts long against one heap search: the overflowing searches now run beside the batch, but one that is queued late
 	// still sticks out by its own length (2.5 ms at 1M x 768, where the whole batch takes 10: 1.29 M q/s with the copies at 600 entries
 	// against 1.16 - 1.22 M at 256 although the first pass alone runs at 1.57 - 1.70 M; at 10M x 768: 495 k -> 586 k q/s,

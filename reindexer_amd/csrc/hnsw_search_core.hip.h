@@ -69,6 +69,10 @@ typedef __attribute__((address_space(3))) void hnsw_lds_void;
 // otherwise one set (92 VGPRs: twice the resident searches).  D <= 512 always affords two.
 // kSorted: 0 = the reference's two heaps, replayed by lane 0; S > 0 = HnswSortedList<S> (ef <= 64 S, no deleted nodes, heaps not in LDS at all)
 // kDel (with kSorted): the graph has deleted nodes — HnswSortedListDel
+// kFilter (hnsw_filtered.hip): the call brings a bitmap of the nodes it may return (HnswFilteredParams::allowed; p is then that struct's
+// base); a node with a clear bit is hidden exactly as a deleted one is — read in the four places that read the delete mark (entry point on
+// the list and on the heaps, the fresh neighbours' nb_del[] on either path), from the bitmap itself: one bit per node, never a byte array
+// per call
 // A search that leaves as kHnswOverflow also goes into the launch's overflow queue when there is one: a few helper workgroups launched
 // beside the batch (hnsw_helper_kernel) pick it up and run it with the largest LDS heap WHILE the batch is still running — after the batch
 // such a search is pure tail (one of 16 384 queries took 5 - 7 ms of a 32 ms batch at 10M x 768).
@@ -111,16 +115,22 @@ __device__ __forceinline__ void team_slice(int cnt, int wave, int& begin, int& n
 	if (n < 0) n = 0;
 }
 #define HN_SYNC() hn_sync<kTeam>()
+// hidden from a filtered call's result: deleted, or not in the call's bitmap (p is the base of the kernel's HnswFilteredParams)
+__device__ __forceinline__ bool hnsw_hidden(const HnswParams& p, uint32_t id) {
+	const uint32_t* allowed = static_cast<const HnswFilteredParams&>(p).allowed;
+	return p.deleted[id] != 0 || !((allowed[id >> 5] >> (id & 31)) & 1);
+}
 // (One function on purpose, for now: prologue, descent, layer 0 on the sorted list — with its look-ahead hop —, layer 0 on the heaps, store.
 // Taking the descent, the insertion loop and the two stores out as __forceinline__ functions of their own, with the same statements, changed
 // the machine code of every kernel that runs this — about a thousand lines of each — and so did one shared loop for the three "fetch a link
 // block, test-and-mark, compact" sites; a full split over a shared state struct left one resident kernel spilling 8 VGPRs
 // (tools/compare_kernel_isa.py, tests/test_hnsw_wide_rows_resources.py).  A split has to be measured on the device against this form, not
 // assumed equal.)
-template <int kMetric, bool kGlobalCand, int NB, bool kLatency, bool kSq8 = false, int kSorted = 0, bool kDel = false, int kTeam = 1>
+template <int kMetric, bool kGlobalCand, int NB, bool kLatency, bool kSq8 = false, int kSorted = 0, bool kDel = false, int kTeam = 1, bool kFilter = false>
 __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint32_t slot, const uint32_t qi, HnswTeamBox* box = nullptr) {
 	static_assert(kTeam == 1 || (NB > 0 && !kSq8 && !kGlobalCand), "the team form serves the fixed-dimension float search with its heaps in LDS");
 	static_assert(kSorted == 0 || !kGlobalCand, "the sorted-list search starts in LDS; its re-runs with a global heap are heap-kernel launches");
+	static_assert(!kFilter || kSorted == 0 || kDel, "a filtered search hides nodes: its list is the one with deleted nodes");
 	// dynamic LDS: [ef_cap] result heap (dist, id) then [lds_cand_cap] candidate heap (dist, id) — sized by the launcher so that
 	// small-ef searches keep more wavefronts resident per CU.  (The areas of hnsw_lds_layout, spelled out: asking that function here, as
 	// hnsw_team_serve does, moved the query loads of 45 SQ8 kernels — tools/compare_kernel_isa.py.)
@@ -272,7 +282,13 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 		List list;
 		list.init(p.sorted == 1);
 		const int ef = int(p.ef);
-		if (!kDel || !p.deleted[cur]) {
+		bool ep_live;
+		if constexpr (kFilter) {
+			ep_live = !hnsw_hidden(p, cur);
+		} else {
+			ep_live = !kDel || !p.deleted[cur];
+		}
+		if (ep_live) {
 			list.insert(curdist, cur, false, ef, lane);
 			ndist += 1;   // the reference recomputes the entry distance here (same value)
 		} else {
@@ -473,7 +489,11 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 				HN_SYNC();
 				HN_PHASE(ph_a);
 				if constexpr (kDel) {   // the delete marks travel while the distances are computed
-					for (int j = lane; j < nfresh; j += 64) nb_del[j] = p.deleted[nb_id[j]];
+					if constexpr (kFilter) {
+						for (int j = lane; j < nfresh; j += 64) nb_del[j] = hnsw_hidden(p, nb_id[j]);
+					} else {
+						for (int j = lane; j < nfresh; j += 64) nb_del[j] = p.deleted[nb_id[j]];
+					}
 				}
 				if constexpr (kTeam > 1) {
 					team_links = (p.nbl_off != 0u && p.maxM0 < 64u) ? 1 : 0;
@@ -585,7 +605,12 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 		HN_SYNC();
 	}
 	{
-		const bool ep_ok = p.bare || !p.deleted[cur];
+		bool ep_ok;
+		if constexpr (kFilter) {
+			ep_ok = !hnsw_hidden(p, cur);
+		} else {
+			ep_ok = p.bare || !p.deleted[cur];
+		}
 		if (lane == 0) {
 			if (ep_ok) {
 				hp_emplace(top, top_n, curdist, cur);
@@ -642,7 +667,9 @@ __device__ __forceinline__ void hnsw_search_one(const HnswParams& p, const uint3
 		}
 		HN_SYNC();
 		distances(nb_id, nfresh, nb_d);
-		if (!p.bare) {
+		if constexpr (kFilter) {
+			for (int j = lane; j < nfresh; j += 64) nb_del[j] = hnsw_hidden(p, nb_id[j]);
+		} else if (!p.bare) {
 			for (int j = lane; j < nfresh; j += 64) nb_del[j] = p.deleted[nb_id[j]];
 		}
 		ndist += nfresh;

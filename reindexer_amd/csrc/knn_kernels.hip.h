@@ -229,6 +229,12 @@ struct HnswParams {
 	const float* qcorr;          // [nq]
 	const float* qnorm;          // [nq]
 };
+// A filtered search (hnsw_filtered.hip): the same parameters and, BESIDE them, the call's allowed-rows bitmap — one bit per node, bit
+// (id & 31) of word id >> 5 set = the node may be returned; a node with a clear bit is traversed like a deleted one (bare = 0 in such a
+// call).  A struct of its own so that HnswParams, and with it the kernel arguments of every other kernel, stay byte for byte what they are.
+struct HnswFilteredParams : HnswParams {
+	const uint32_t* allowed;
+};
 
 // what the helper workgroups of a batch poll (hnsw_helper_kernel)
 struct HnswHelper {

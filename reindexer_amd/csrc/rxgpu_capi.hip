@@ -140,6 +140,7 @@ void rxgpu_search_ctx::release() {
 	d_ivf.release();
 	d_gcand_d.release();
 	d_redo.release();
+	d_allowed.release();
 	d_top.release();
 	d_qplanes.release();
 	d_emit.release();

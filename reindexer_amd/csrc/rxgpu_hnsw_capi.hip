@@ -162,6 +162,7 @@ struct HnswCall {
 	size_t row_bytes = 0;        // of one query
 	rxgpu::HnswParams p{};       // what every launch of the call shares
 	const void* d_q = nullptr;   // where the kernels read the queries
+	const uint32_t* allowed = nullptr;   // a call under an allowed-rows bitmap: the bitmap in this call's context (HBM), beside p in every launch
 	// where counts and lists arrive on the host: the caller's arrays, or the pinned staging buffer
 	uint32_t* dl_count = nullptr;
 	float* dl_dist = nullptr;
@@ -312,7 +313,18 @@ struct HnswCall {
 			pc.lds_cand_cap = pl.sorted_restart_cap;
 			if (pl.sorted_restart_cap == 0) pc.ef_cap = 0;
 		}
-		rxgpu::launch_hnsw_search(h->metric, pc, cnt, false, st);
+		launch(pc, cnt, false, st);
+	}
+	// every launch of the call, first pass and re-run tiers alike: a call under a bitmap takes the filtered family and nothing else
+	void launch(const rxgpu::HnswParams& pc, uint32_t cnt, bool global_cand, hipStream_t st) {
+		if (allowed) {
+			rxgpu::HnswFilteredParams pf{};
+			static_cast<rxgpu::HnswParams&>(pf) = pc;
+			pf.allowed = allowed;
+			rxgpu::launch_hnsw_filtered(h->metric, pf, cnt, global_cand, st);
+		} else {
+			rxgpu::launch_hnsw_search(h->metric, pc, cnt, global_cand, st);
+		}
 	}
 
 	// Every query once, in launches of vis_slots searches; counts (and lists) are on the host when it returns.
@@ -388,7 +400,7 @@ struct HnswCall {
 			pc.only = static_cast<const uint32_t*>(c->d_redo.ptr) + r0;
 			if (global_cand) pc.gcand = static_cast<uint2*>(c->d_gcand_d.ptr);
 			ProfileScope ps(h, profile_name, c->stream);
-			rxgpu::launch_hnsw_search(h->metric, pc, cq, global_cand, c->stream);
+			launch(pc, cq, global_cand, c->stream);
 		}
 		RX_HIP(hipGetLastError());
 		if (int rc = fetch_counts(); rc) return rc;
@@ -403,7 +415,8 @@ struct HnswCall {
 // ([nq][kk] distances | [nq][kk] local rows, invalid entries past a query's count) instead of travelling to the host; only the counts
 // come back (the re-run tiers are driven by them).  The stream is drained before the call returns.
 int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k, uint32_t ef, float* out_dist,
-					 uint32_t* out_row, uint32_t* out_count, const rxgpu::HnswSink* sink = nullptr, bool try_server = true, bool dev_q = false) {
+					 uint32_t* out_row, uint32_t* out_count, const rxgpu::HnswSink* sink = nullptr, bool try_server = true, bool dev_q = false,
+					 const uint32_t* allowed = nullptr) {
 	// 1. validate and normalise
 	const bool sq8 = qcorr != nullptr;
 	const bool to_host = sink == nullptr;
@@ -421,7 +434,7 @@ int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, co
 	RX_CHECK(ef <= uint32_t(rxgpu::kHnswMaxEf), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn: ef must be <= 4096 on the GPU engine");
 	const HnswKnobs knobs = rxgpu::read_hnsw_knobs();
 	// 2. ONE query, the planner's call: through the mailbox of the index's resident kernel (rxgpu_hnsw_server.hip) — no launch on the path
-	if (nq == 1 && to_host && try_server) {
+	if (nq == 1 && to_host && try_server && !allowed) {
 		const int served = hnsw_try_server(h, knobs, queries, qcorr, qnorm, k, ef, out_dist, out_row, out_count);
 		if (served == 1) return RXGPU_OK;
 		if (served != 0 && served != 2) return served;   // (2: the search ran there and came back flagged — the tiers below answer it)
@@ -434,11 +447,18 @@ int hnsw_search_impl(rxgpu_index* h, const void* queries, const float* qcorr, co
 	// 4. the plan (a handful of searches never comes near the visited budget: no driver call on the path of a single-query SearchKnn)
 	size_t free_b = 0, total_b = 0;
 	if (nq > 256 && hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-	const HnswLaunchPlan pl =
-		rxgpu::plan_hnsw_search(h->count, h->dim, h->graph_deleted == 0, nq, k, ef, sq8, to_host, uint64_t(free_b) + c->d_visited.bytes, knobs);
+	const HnswLaunchPlan pl = rxgpu::plan_hnsw_search(h->count, h->dim, h->graph_deleted == 0 && !allowed, nq, k, ef, sq8, to_host,
+													  uint64_t(free_b) + c->d_visited.bytes, knobs, allowed != nullptr);
 	// 5. staging and the first upload
 	HnswCall call{h, c, pl, nq, k, sq8, queries, out_dist, out_row, out_count, sink, dev_q};
 	if (int rc = call.stage_and_upload(qcorr, qnorm, ef); rc) return rc;
+	if (allowed) {   // the bitmap, once, into this call's context: HnswCall::launch hands it to the first pass and every re-run tier
+		const size_t bytes = size_t((h->count + 31) / 32) * sizeof(uint32_t);
+		if (int rc = c->d_allowed.ensure(bytes); rc) return rc;
+		RX_HIP(hipMemcpyAsync(c->d_allowed.ptr, allowed, bytes, hipMemcpyHostToDevice, c->stream));
+		call.allowed = static_cast<const uint32_t*>(c->d_allowed.ptr);
+		call.p.bare = 0;   // hidden nodes are traversed like deleted ones (hnswalg.h:1982: the branch with deleted nodes)
+	}
 	const uint32_t* const counts = call.dl_count;
 	std::vector<uint32_t> redo;
 	if (pl.big_ef) {
@@ -1074,6 +1094,49 @@ int rxgpu_hnsw_search_knn_sq8(rxgpu_index* h, const uint8_t* query_codes, const 
 	RX_CHECK(h->count == 0 || (h->d_codes && h->sq8_n == h->count), RXGPU_ERR_LOGIC,
 			 "rxgpu_hnsw_search_knn_sq8: SQ8 codes are not attached / out of date");
 	return hnsw_search_impl(h, query_codes, query_corr, query_norm_coef, nq, k, ef, out_dist, out_row, out_count);
+}
+
+/* SearchKnn under an allowed-rows bitmap: the reference has no filter functor, so the result is defined through its delete mark — hnswalg.h:1982
+ * (num_deleted picks the branch), :871-963 (runLayer0Step keeps a marked node in candidate_set and out of top_candidates), :1303-1339
+ * (MarkDelete).  One body for floats and codes. */
+static int hnsw_filtered_entry(rxgpu_index* h, const void* queries, const float* qcorr, const float* qnorm, uint32_t nq, uint32_t k,
+							   uint32_t ef, const uint32_t* allowed_words, uint64_t n_words, float* out_dist, uint32_t* out_row, uint32_t* out_count,
+							   uint64_t* out_allowed) {
+	const bool sq8 = qcorr != nullptr;
+	RX_CHECK(h, RXGPU_ERR_PARAMS, "null index");
+	RX_CHECK(!h->shard_set, RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_knn_filtered: not available on a sharded index (its shard handles take the call)");
+	RX_CHECK(queries && (!sq8 || qnorm), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_filtered: null argument");
+	RX_CHECK(allowed_words, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_filtered: null bitmap");
+	const uint64_t words = (h->count + 31) / 32;
+	RX_CHECK(n_words >= words, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_filtered: the bitmap is shorter than ceil(count / 32) words");
+	RX_CHECK(ef <= uint32_t(rxgpu::kHnswMaxEf), RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_filtered: ef must be <= 4096 on the GPU engine");
+	RX_CHECK(h->count == 0 || (h->graph_attached && h->graph_n == h->count), RXGPU_ERR_LOGIC, "rxgpu_hnsw_search_knn_filtered: graph is not attached / out of date");
+	RX_CHECK(!sq8 || h->count == 0 || (h->d_codes && h->sq8_n == h->count), RXGPU_ERR_LOGIC,
+			 "rxgpu_hnsw_search_knn_sq8_filtered: SQ8 codes are not attached / out of date");
+	if (nq == 0 || k == 0) return RXGPU_OK;
+	RX_CHECK(out_count && out_dist && out_row, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_filtered: null argument");
+	uint64_t set = 0;   // bits below the node count
+	for (uint64_t w = 0; w < words; ++w) {
+		uint32_t v = allowed_words[w];
+		if (w == words - 1 && (h->count & 31u)) v &= (1u << (h->count & 31u)) - 1u;
+		set += uint64_t(__builtin_popcount(v));
+	}
+	if (out_allowed) *out_allowed = set;
+	// nothing hidden at all: the reference would take its bare-bone branch — the unfiltered path answers, and nothing else
+	if (h->graph_deleted == 0 && set == h->count) return hnsw_search_impl(h, queries, qcorr, qnorm, nq, k, ef, out_dist, out_row, out_count);
+	return hnsw_search_impl(h, queries, qcorr, qnorm, nq, k, ef, out_dist, out_row, out_count, nullptr, false, false, allowed_words);
+}
+
+int rxgpu_hnsw_search_knn_filtered(rxgpu_index* h, const float* queries, uint32_t nq, uint32_t k, uint32_t ef, const uint32_t* allowed_words,
+								   uint64_t n_words, float* out_dist, uint32_t* out_row, uint32_t* out_count, uint64_t* out_allowed) {
+	return hnsw_filtered_entry(h, queries, nullptr, nullptr, nq, k, ef, allowed_words, n_words, out_dist, out_row, out_count, out_allowed);
+}
+
+int rxgpu_hnsw_search_knn_sq8_filtered(rxgpu_index* h, const uint8_t* query_codes, const float* query_corr, const float* query_norm_coef, uint32_t nq,
+									   uint32_t k, uint32_t ef, const uint32_t* allowed_words, uint64_t n_words, float* out_dist, uint32_t* out_row,
+									   uint32_t* out_count, uint64_t* out_allowed) {
+	RX_CHECK(query_corr, RXGPU_ERR_PARAMS, "rxgpu_hnsw_search_knn_sq8_filtered: null argument");
+	return hnsw_filtered_entry(h, query_codes, query_corr, query_norm_coef, nq, k, ef, allowed_words, n_words, out_dist, out_row, out_count, out_allowed);
 }
 
 /* ------------------------------------------------------------------------------------------------ SearchRange */

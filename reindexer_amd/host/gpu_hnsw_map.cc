@@ -989,6 +989,98 @@ SearchResultQueue GpuHnswMap::SearchKnn(const float* queryDataRaw, std::optional
 	return result;
 }
 
+// `WHERE cond AND KNN(...)` on the graph: SearchKnn as the reference would run it had MarkDelete (hnswalg.h:1303-1339) been applied to every
+// point whose label is not in `allowed` — one device call (rxgpu_hnsw_search_knn_filtered: the kernels read the allowed-rows bitmap where
+// they read the delete mark, runLayer0Step :871-963).  Labels the Map does not hold are ignored, duplicates are harmless.
+// A float Map with at most ef allowed live nodes does not walk the graph: top_candidates could never fill, so layer0ShouldStopBeforePop
+// (:860-869) would never fire and the walk would visit every node reachable — the exact scan over the allowed rows of the same device
+// index (rxgpu_search_knn_subset) reads at most ef rows instead and returns the exact k nearest of them, ties at the k-th place by
+// internal row.  (The threshold is derived, not measured.)  A quantised Map always walks: its distances are the codes'.
+SearchResultQueue GpuHnswMap::SearchKnnFiltered(const float* queryDataRaw, std::optional<float> queryDataNorm, size_t k, size_t ef, const labeltype* allowed,
+												size_t nAllowed) const {
+	SearchResultQueue result;
+	if (k == 0 || nAllowed == 0) return result;
+	if (sh_) {   // every shard's own filtered search with its part of the labels; the k smallest by (dist, label) of what they return
+		if (shCount(false) == 0) return result;
+		shSyncAll();
+		std::vector<std::vector<labeltype>> parts(sh_->maps.size());
+		for (size_t i = 0; i < nAllowed; ++i) {
+			const auto it = sh_->shardOf.find(allowed[i]);
+			if (it != sh_->shardOf.end()) parts[it->second].push_back(allowed[i]);
+		}
+		std::vector<std::pair<float, labeltype>> all;
+		for (size_t s = 0; s < parts.size(); ++s) {
+			if (parts[s].empty() || !sh_->maps[s]->graph_.Count()) continue;
+			SearchResultQueue part = sh_->maps[s]->SearchKnnFiltered(queryDataRaw, queryDataNorm, k, ef, parts[s].data(), parts[s].size());
+			for (; !part.empty(); part.pop()) all.emplace_back(part.top().first, part.top().second);
+		}
+		std::sort(all.begin(), all.end());
+		if (all.size() > k) all.resize(k);
+		ReserveQueue(result, all.size());
+		for (const auto& e : all) result.emplace(e.first, e.second);
+		return result;
+	}
+	const size_t n = graph_.Count();
+	if (n == 0) return result;
+	syncDevice();
+	k = std::min(k, n);
+	const size_t efEff = ef ? ef : std::max<size_t>(1, k * 3 / 2);   // hnswalg.h:1995
+	std::vector<uint32_t> words((n + 31) / 32, 0u);
+	std::vector<uint32_t> rows;   // allowed live nodes, as far as the exact scan could still take them
+	size_t live = 0;
+	for (size_t i = 0; i < nAllowed; ++i) {
+		if (!graph_.HasLabelSync(allowed[i])) continue;
+		const tableint id = graph_.InternalId(allowed[i]);
+		if (id >= n) continue;
+		const uint32_t bit = 1u << (id & 31);
+		if (words[id >> 5] & bit) continue;
+		words[id >> 5] |= bit;
+		if (graph_.IsDeleted(id)) continue;
+		if (++live <= efEff) rows.push_back(uint32_t(id));
+	}
+	if (live == 0) return result;
+	std::vector<float> dist(k);
+	std::vector<uint32_t> row(k);
+	uint32_t count = 0;
+	if (!quantized_ && live <= efEff) {
+		std::sort(rows.begin(), rows.end());
+		const uint32_t kk = uint32_t(std::min(k, rows.size()));
+		if (rxgpu_search_knn_subset(dev_, queryDataRaw, 1, kk, rows.data(), rows.size(), dist.data(), row.data(), &count) != RXGPU_OK) throwDevice("SearchKnnFiltered");
+		filteredExact_.fetch_add(1, std::memory_order_relaxed);
+	} else if (quantized_) {
+		float normCoef = 1.f;
+		std::vector<uint8_t> qcodes;
+		const float qcorr = quantizeQuery(queryDataRaw, queryDataNorm, qcodes, normCoef);
+		if (rxgpu_hnsw_search_knn_sq8_filtered(dev_, qcodes.data(), &qcorr, &normCoef, 1, uint32_t(k), uint32_t(ef), words.data(), words.size(), dist.data(), row.data(),
+											   &count, nullptr) != RXGPU_OK) {
+			throwDevice("SearchKnnFiltered");
+		}
+		filteredGraph_.fetch_add(1, std::memory_order_relaxed);
+	} else {
+		if (rxgpu_hnsw_search_knn_filtered(dev_, queryDataRaw, 1, uint32_t(k), uint32_t(ef), words.data(), words.size(), dist.data(), row.data(), &count, nullptr) !=
+			RXGPU_OK) {
+			throwDevice("SearchKnnFiltered");
+		}
+		filteredGraph_.fetch_add(1, std::memory_order_relaxed);
+	}
+	ReserveQueue(result, count);
+	for (uint32_t i = 0; i < count; ++i) result.emplace(dist[i], graph_.Label(row[i]));
+	return result;
+}
+
+void GpuHnswMap::ReadFilteredStats(uint64_t& graphSearches, uint64_t& exactScans) const noexcept {
+	graphSearches = filteredGraph_.exchange(0);
+	exactScans = filteredExact_.exchange(0);
+	if (sh_) {
+		for (const auto& m : sh_->maps) {
+			uint64_t g = 0, e = 0;
+			m->ReadFilteredStats(g, e);
+			graphSearches += g;
+			exactScans += e;
+		}
+	}
+}
+
 size_t GpuHnswMap::DeviceCodedRows() const noexcept {
 	size_t n = deviceCodedRows_.load();
 	if (sh_) {

@@ -130,6 +130,15 @@ public:
 
 	SearchResultQueue SearchKnn(const float* queryDataRaw, std::optional<float> queryDataNorm, size_t k, size_t ef = 0) const;
 	SearchResultQueue SearchRange(const float* queryDataRaw, std::optional<float> queryDataNorm, float radius, size_t ef) const;
+	// Pre-filtered SearchKnn (`WHERE cond AND KNN(...)`): what SearchKnn returns with every point whose label is not in `allowed` hidden the
+	// way MarkDelete hides one — one device call (rxgpu_hnsw_search_knn_filtered; _sq8 for a quantised Map).  Labels the Map does not hold
+	// are ignored, duplicates are harmless.  A float Map with at most ef allowed live nodes (ef after the k * 3 / 2 default) takes the exact
+	// scan over those rows instead (rxgpu_search_knn_subset: the graph walk could not stop before it had visited every node).  Over a
+	// device list every shard answers for its labels and the k smallest by (dist, label) are returned.
+	SearchResultQueue SearchKnnFiltered(const float* queryDataRaw, std::optional<float> queryDataNorm, size_t k, size_t ef, const labeltype* allowed,
+										size_t nAllowed) const;
+	// filtered calls that walked the graph / took the exact scan since the last read (over a device list: summed over the shards)
+	void ReadFilteredStats(uint64_t& graphSearches, uint64_t& exactScans) const noexcept;
 
 	// Streaming (batched) KNN, hnswalg.h:1865-1975.  The whole session must run under the caller's read lock, like the reference's.
 	StreamingSearchSession BeginStreamingSearch(const float* queryDataRaw, std::optional<float> queryDataNorm, StreamingSearchOptions opts) const;
@@ -250,6 +259,7 @@ private:
 	mutable unsigned coLeaders_ = 0;
 	mutable size_t coBatches_ = 0;
 	mutable std::atomic<size_t> coPosted_{0};
+	mutable std::atomic<uint64_t> filteredGraph_{0}, filteredExact_{0};
 	bool ownsDev_ = true;                 // false: a shard (the device index belongs to the sharded handle) or the Map over a device list itself
 	std::unique_ptr<ShardedState> sh_;    // non-null: the Map over a device list
 };

@@ -771,6 +771,18 @@ long rxhost_hnsw_search_knn_norm(void* h, const float* q, int hasNorm, float nor
 	});
 	return n;
 }
+long rxhost_hnsw_search_knn_filtered(void* h, const float* q, int hasNorm, float norm, size_t k, size_t ef, const uint64_t* allowed, size_t nAllowed,
+									 float* outDist, uint64_t* outLabel) {
+	long n = -1;
+	guarded([&] {
+		std::vector<labeltype> labels(allowed, allowed + nAllowed);
+		auto res = static_cast<const GpuHnswMap*>(h)->SearchKnnFiltered(q, hasNorm ? std::optional<float>(norm) : std::nullopt, k, ef, labels.data(), labels.size());
+		n = long(drain(res, outDist, outLabel, k));
+	});
+	return n;
+}
+// out2: filtered calls that walked the graph, filtered calls that took the exact scan — since the last read
+void rxhost_hnsw_filtered_stats(void* h, uint64_t* out2) { static_cast<const GpuHnswMap*>(h)->ReadFilteredStats(out2[0], out2[1]); }
 // Sq8Quantize / Sq8Params (sq8_quantizer.h) for the CPU parity tests against Quantizer::Quantize
 float rxhost_sq8_quantize(int metric, float minQ, float maxQ, size_t dim, const float* from, float scale, uint8_t* to, float* params3) {
 	const Sq8Params p = Sq8Params::FromRange(minQ, maxQ, dim);

@@ -849,6 +849,30 @@ class GpuHnswMap:
             _raise()
         return od[:n].copy(), ol[:n].copy()
 
+    def search_knn_filtered(self, q, k, ef, allowed_labels, norm=None):
+        """SearchKnnFiltered: SearchKnn with every point whose label is not in allowed_labels hidden the way a deleted one is, in one device
+        call; unknown labels are ignored.  (dist, label), worst first like search_knn."""
+        L = lib()
+        L.rxhost_hnsw_search_knn_filtered.restype = _l
+        L.rxhost_hnsw_search_knn_filtered.argtypes = [_vp, _vp, _i, _f, _sz, _sz, _vp, _sz, _vp, _vp]
+        q = _f32(q)
+        labels = np.ascontiguousarray(allowed_labels, np.uint64).reshape(-1)
+        od, ol = np.empty(max(k, 1), np.float32), np.empty(max(k, 1), np.uint64)
+        n = L.rxhost_hnsw_search_knn_filtered(self.h, q.ctypes.data, int(norm is not None), 0.0 if norm is None else float(norm), k, ef,
+                                              labels.ctypes.data if labels.size else None, labels.size, od.ctypes.data, ol.ctypes.data)
+        if n < 0:
+            _raise()
+        return od[:n].copy(), ol[:n].copy()
+
+    def filtered_stats(self):
+        """(filtered calls that walked the graph, filtered calls that took the exact scan) since the last read."""
+        L = lib()
+        L.rxhost_hnsw_filtered_stats.restype = None
+        L.rxhost_hnsw_filtered_stats.argtypes = [_vp, _vp]
+        v = (C.c_uint64 * 2)()
+        L.rxhost_hnsw_filtered_stats(self.h, C.addressof(v))
+        return int(v[0]), int(v[1])
+
     def stream(self, q, ef=0, norm=None):
         """BeginStreamingSearch: session with .next(batch) -> (dist, label, exhausted) (worst first) and .close().  norm: the query's
         norm as HnswIndexBase::search passes it (needed by a quantised cosine graph)."""
