@@ -101,11 +101,11 @@ def build_cpp_tests(force: bool = False) -> list[Path]:
         if force or _stale(out, [src, CSRC / "ft_packed_decode.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
-    # the launch policy of an HNSW search compiled for the host (CPU check of the rules the C-ABI follows)
+    # the launch policy of an HNSW search and its re-run ladder compiled for the host (CPU check of the rules the C-ABI follows)
     src = tdir / "hnsw_launch_plan_cpu.cc"
     if src.exists():
         out = tdir / "libhnsw_launch_plan_cpu.so"
-        if force or _stale(out, [src, CSRC / "hnsw_launch_plan.h"]):
+        if force or _stale(out, [src, CSRC / "hnsw_launch_plan.h", CSRC / "hnsw_rerun_plan.h"]):
             _run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", f"-I{CSRC}", src, "-o", out])
         outs.append(out)
     # which kernel an HNSW search gets compiled for the host (CPU check of the rules the launchers and the kernels' LDS layout follow)

@@ -1,4 +1,4 @@
-// The launch policy of an HNSW search (rxgpu_hnsw_capi.hip: hnsw_search_impl) as a pure function of the call's shape and the RXGPU_HNSW_*
+// The launch policy of an HNSW search (rxgpu_hnsw_search.hip: hnsw_search_impl) as a pure function of the call's shape and the RXGPU_HNSW_*
 // hooks: what the executor stages, zeroes, splits and launches follows from the plan alone.  No HIP in here — the file compiles for the host
 // on its own (tests/cpp/hnsw_launch_plan_cpu.cc, tests/test_hnsw_launch_plan.py).
 #pragma once
@@ -18,6 +18,9 @@ constexpr int kHnswLdsCandEf = 1024;    // largest ef whose candidate heap is tr
 constexpr int kHnswCandLds = 2048;      // candidate-heap capacity in LDS
 constexpr int kHnswSortedMaxEf = 256;            // largest ef the sorted-list search holds in registers (4 entries a lane)
 constexpr int kHnswSortedMaxEfDel = 224;         // ... for a graph with deleted nodes: 32 entries of room for the deleted candidates in reach
+// what a search leaves in its out_count instead of a count when the host has to run it again (hnsw_rerun_plan.h)
+constexpr uint32_t kHnswOverflow = 0xFFFFFFFFu;
+constexpr uint32_t kHnswTie = 0xFFFFFFFEu;        // sorted-list search met equal keys: re-run on the heap kernel
 
 // The A/B and test hooks of the HNSW search (RXGPU_HNSW_*), read in ONE pass over the environment per call — a dozen getenv() lookups each
 // walked the whole environment, on the path of every single-query SearchKnn.  (Still the process environment: tests flip the hooks between

@@ -171,8 +171,6 @@ struct GemmBf16Params {
 };
 
 constexpr int kHnswMaxNeighbors = 128;  // 2*M <= 128
-constexpr uint32_t kHnswOverflow = 0xFFFFFFFFu;
-constexpr uint32_t kHnswTie = 0xFFFFFFFEu;        // sorted-list search met equal keys: re-run on the heap kernel
 
 struct HnswParams {
 	const float* rows;

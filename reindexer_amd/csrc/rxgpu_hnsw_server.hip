@@ -186,7 +186,7 @@ static int server_launch(rxgpu_index* h, HnswServerState* st) {
 	p.spec = st->spec ? 1u : 0u;
 	p.nbl = st->nbl ? 1u : 0u;
 	p.queries = reinterpret_cast<const float*>(st->dev_view + st->o_query);
-	if (st->sq8) {   // (as fill_sq8_params, rxgpu_hnsw_capi.hip; the uploads of the code table make this kernel leave first)
+	if (st->sq8) {   // (as fill_sq8_params, rxgpu_hnsw_internal.h; the uploads of the code table make this kernel leave first)
 		p.codes = h->d_codes;
 		p.corr = h->d_corr;
 		p.alpha2 = h->sq8_alpha2;

@@ -244,3 +244,52 @@ def test_graphs_with_deleted_nodes_on_the_sorted_list(rxgpu, oracle, monkeypatch
                     assert np.array_equal(gl, wl) and np.array_equal(bits(gd), bits(wd)), (metric, phase, qi, k, ef)
     monkeypatch.delenv("RXGPU_HNSW_SORTED")
     m.close()
+
+
+def mixed_rows_and_queries(seed, n=4000, d=32, grid_bases=400, nq=64):
+    """Gaussian rows beside rows on a small integer grid, every grid row four times (as in test_equal_distances_are_rerun_on_the_heaps); half
+    of the queries of either kind: searches among the grid rows meet equal keys, those among the Gaussian rows (almost) never."""
+    rng = np.random.default_rng(seed)
+    base = rng.integers(-3, 4, size=(grid_bases, d)).astype(np.float32)
+    base[np.all(base == 0, axis=1)] = 1.0
+    rows = np.concatenate([np.repeat(base, 4, axis=0), rng.standard_normal((n - 4 * grid_bases, d)).astype(np.float32)])
+    rows = np.ascontiguousarray(rows[rng.permutation(n)])
+    on_grid = rng.integers(-3, 4, size=(nq - nq // 2, d)).astype(np.float32)
+    on_grid[::2] = np.repeat(base, 4, axis=0)[rng.integers(4 * grid_bases, size=on_grid[::2].shape[0])]   # every other one IS a grid row: four rows at distance 0
+    queries = np.concatenate([rng.standard_normal((nq // 2, d)).astype(np.float32), on_grid])
+    return rows, np.ascontiguousarray(queries[rng.permutation(nq)])
+
+
+def test_mixed_batch_walks_the_rerun_rungs_in_one_call(rxgpu, oracle, monkeypatch):
+    """One batch that holds clean, tie and overflowing searches together, so that the ids of the re-run ladder (hnsw_rerun_plan.h) matter: the
+    tie queries come back to the host (RXGPU_HNSW_RESTART_CAND=0), their re-run overflows its 4-entry heap (RXGPU_HNSW_LDS_CAND_CAP=4, which
+    also skips the rung with the largest LDS heap), the first global tier overflows its 8 entries (RXGPU_HNSW_GCAND_CAP=8) and the tier of one
+    entry per node answers — while the other queries of the batch keep what the first pass gave them.  Every query must equal the restated
+    engine; the counter shows that some, not all, of the batch took the ladder."""
+    from oracle.pyoracle import oracle_hnsw_search_knn
+    n, d, nq, k, ef = 4000, 32, 64, 10, 64
+    # 3600 of the 4000 rows on the grid: ties that matter are rare among fewer (this seed and split: 10 of the 64 queries come back as ties)
+    rows, queries = mixed_rows_and_queries(174, n, d, grid_bases=900, nq=nq)
+    m, rows, labels = build(0, n, d, M=8, efc=60, rows=rows)
+    g = m.export_graph()
+    g["vectors"] = rows
+    wants = [oracle_hnsw_search_knn(oracle, g, q, k, ef) for q in queries]
+    monkeypatch.setenv("RXGPU_HNSW_RESTART_CAND", "0")
+    monkeypatch.setenv("RXGPU_HNSW_LDS_CAND_CAP", "4")
+    monkeypatch.setenv("RXGPU_HNSW_GCAND_CAP", "8")
+    with rxgpu.VectorIndex(0, d, n) as ix:
+        ix.upload_rows(0, rows)
+        ix.hnsw_attach_graph(g)
+        ix.hnsw_read_tie_reruns()
+        ix.hnsw_read_lds_reruns()
+        dist, row, cnt = ix.hnsw_search_knn(queries, k, ef)
+        ties, lds = ix.hnsw_read_tie_reruns(), ix.hnsw_read_lds_reruns()
+    print("tie re-runs of the batch:", ties, "re-runs with the largest LDS heap:", lds)
+    for qi, (wd, wl) in enumerate(wants):
+        c = int(cnt[qi])
+        assert c == wd.size, (qi, c, wd.size)
+        a, b = as_sorted_pairs(dist[qi, :c], g["labels"][row[qi, :c]]), as_sorted_pairs(wd, wl)
+        assert np.array_equal(a[1], b[1]) and np.array_equal(bits(a[0]), bits(b[0])), qi
+    assert 0 < ties < nq, ties
+    assert lds == 0   # that rung is skipped, and a batch of 64 has no helper workgroups
+    m.close()

@@ -31,6 +31,8 @@ def lib():
     L = C.CDLL(str(LIB))
     L.hnsw_plan_cpu.restype = None
     L.hnsw_plan_cpu.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_void_p]
+    L.hnsw_plan_filtered_cpu.restype = None
+    L.hnsw_plan_filtered_cpu.argtypes = [C.c_uint64, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_void_p]
     L.hnsw_knobs_names_a_kernel.restype = C.c_int
     L.hnsw_plan_constants.argtypes = [C.c_void_p]
     return L
@@ -50,9 +52,12 @@ class Plan:
             setattr(self, name, int(v))
 
 
-def plan(L, n=M1, nq=1, dim=768, k=10, ef=128, bare=True, sq8=False, to_host=True, avail=0):
+def plan(L, n=M1, nq=1, dim=768, k=10, ef=128, bare=True, sq8=False, to_host=True, avail=0, filtered=None):
     out = np.full(len(FIELDS) + 1, 0xDEAD, np.uint64)
-    L.hnsw_plan_cpu(n, dim, int(bare), nq, k, ef, int(sq8), int(to_host), avail, out.ctypes.data)
+    if filtered is None:
+        L.hnsw_plan_cpu(n, dim, int(bare), nq, k, ef, int(sq8), int(to_host), avail, out.ctypes.data)
+    else:   # the entry point that names the argument
+        L.hnsw_plan_filtered_cpu(n, dim, int(bare), nq, k, ef, int(sq8), int(to_host), avail, int(filtered), out.ctypes.data)
     assert out[-1] == 0xDEAD   # the shim wrote exactly the fields named here
     return Plan(out[:-1])
 
@@ -141,6 +146,32 @@ def test_big_ef_goes_to_the_tiers(lib):
     assert (p.tier_cap0, p.tier_cap1) == (65536, 1000001)
     assert not plan(lib, ef=1024).big_ef
     assert plan(lib, n=1000, k=10, ef=100).tier_cap0 == 1001   # a small graph: one tier
+
+
+def test_filtered_plan_differs_in_the_helpers_only(lib, monkeypatch):
+    # a call under an allowed-rows bitmap plans as the same call on a graph with deleted nodes (bare = false), minus the helper workgroups:
+    # the filtered family has none.  Only helper_wanted differs — and, at the one shape where the plan shrinks the restart area BECAUSE helpers
+    # run beside the batch (ef <= 128, a bitset of 2^17 words or more: 10M rows), the restart area, which keeps its 600 entries.
+    shapes = [dict(), dict(nq=64), dict(nq=2047), dict(nq=2048), dict(nq=16384), dict(n=M10, nq=16384, avail=200 * GIB), dict(n=M10, nq=16384, ef=129),
+              dict(nq=20000), dict(sq8=True, nq=4096), dict(ef=224, nq=4096), dict(ef=225, nq=4096), dict(ef=1025, nq=16384), dict(to_host=False, nq=4096)]
+    shrunk = 0
+    for shape in shapes:
+        plain, filt = plan(lib, bare=False, **shape), plan(lib, bare=False, filtered=True, **shape)
+        assert vars(plan(lib, bare=False, filtered=False, **shape)) == vars(plain), shape
+        differ = {f for f in FIELDS if getattr(plain, f) != getattr(filt, f)}
+        assert not filt.helper_wanted, shape
+        if plain.helper_wanted and plain.sorted_restart_cap == 256:
+            shrunk += 1
+            assert shape.get("n") == M10 and shape.get("ef", 128) <= 128
+            assert differ == {"helper_wanted", "sorted_restart_cap"} and filt.sorted_restart_cap == 600, shape
+        else:
+            assert differ == ({"helper_wanted"} if plain.helper_wanted else set()), shape
+        # all of it at once: the plan of the same call with the helpers switched off
+        monkeypatch.setenv("RXGPU_HNSW_HELPER", "0")
+        assert vars(plan(lib, bare=False, **shape)) == vars(filt), shape
+        monkeypatch.delenv("RXGPU_HNSW_HELPER")
+    assert shrunk == 1
+    assert plan(lib, bare=False, nq=16384).helper_wanted and not plan(lib, bare=False, nq=2047).helper_wanted   # (both sides of the rule are among the shapes)
 
 
 def test_hook_visited(lib, monkeypatch):
