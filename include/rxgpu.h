@@ -587,6 +587,46 @@ int rxgpu_hnsw_stream_begin(rxgpu_index* h, const float* query, uint32_t ef, rxg
 int rxgpu_hnsw_stream_begin_sq8(rxgpu_index* h, const uint8_t* query_codes, float query_corr, float query_norm_coef, uint32_t ef, rxgpu_hnsw_stream** out);
 int rxgpu_hnsw_stream_continue(rxgpu_hnsw_stream* s, uint32_t batch, float* out_dist, uint32_t* out_row, uint32_t* out_count, int32_t* exhausted);
 void rxgpu_hnsw_stream_end(rxgpu_hnsw_stream* s);
+/* `WHERE cond AND KNN(...)` over a session: the loop of StreamingKnnIndexIterator::Next (cpp_src/core/nsselecter/
+ * knn_streaming_index_iterator.cc:36-110) for a filter that is a bitmap, in ONE device call (two launches at most) instead of a launch, two
+ * synchronisations and three copies per Continue:
+ *     calls = presented = accepted = 0;  batch = first_batch
+ *     repeat:  B = continue(batch);  calls += 1;  presented += |B|;  accepted += rows of B whose bit is set
+ *              stop if accepted >= needed or B.exhausted or calls >= max_calls
+ *              batch = StreamingKnnEstimator::EstimateBatchSize(accepted, presented, needed)     (clamped to 100 .. 800)
+ * allowed_words: one bit per internal row, bit (row & 31) of word row >> 5 (the rxgpu_search_knn_bitmap layout), n_words >=
+ * ceil(count / 32) or RXGPU_ERR_PARAMS; bits at and above the node count are ignored; NULL = every row is allowed.  max_calls == 0 -> 1000
+ * (kMaxContinueCalls).  needed == 0 or first_batch == 0: RXGPU_OK, nothing runs.
+ * Out: the accepted (dist, row) pairs of every call, calls in order, the rows of a call in the order rxgpu_hnsw_stream_continue delivers
+ * them; per call c its batch, the rows it delivered and out_call_end[c] = accepted rows through call c.  The cut at the needed-th row in
+ * (dist, label) order is the caller's.  cap < rxgpu_hnsw_stream_collect_bound(count, needed, first_batch) = min(count, needed - 1 +
+ * max(first_batch, 800)) or calls_cap < rxgpu_hnsw_stream_collect_calls_bound(...) = min(max_calls, count + 1): RXGPU_ERR_PARAMS — the room
+ * is checked before anything runs, never found short at run time.  An empty graph: exhausted, 0 calls.  A graph that changed under the
+ * session: RXGPU_ERR_LOGIC.  *out_launches (may be NULL): kernel launches the call took — 2 when the session's heaps outgrew LDS on the way.
+ * out_pos (may be NULL): per accepted row its position in its call's batch, 0 = delivered first (the call's worst) — with out_call_emitted it
+ * tells how many rows a consumer that walks the calls best first has been presented when it reaches a given accepted row.
+ * Afterwards the session is in the state behind its last Continue and takes further continue / collect calls. */
+int rxgpu_hnsw_stream_collect(rxgpu_hnsw_stream* s, const uint32_t* allowed_words, uint64_t n_words, uint32_t needed, uint32_t first_batch, uint32_t max_calls,
+							  float* out_dist, uint32_t* out_row, uint64_t cap, uint32_t* out_call_batch, uint32_t* out_call_emitted, uint32_t* out_call_end,
+							  uint32_t calls_cap, uint32_t* out_calls, uint64_t* out_presented, uint64_t* out_accepted, int32_t* out_exhausted,
+							  uint32_t* out_launches, uint32_t* out_pos);
+/* rxgpu_hnsw_collect_knn / _sq8: rxgpu_hnsw_stream_begin(_sq8) + rxgpu_hnsw_stream_collect + rxgpu_hnsw_stream_end for one query in ONE call on a
+ * search context leased from the index: the heaps, the visited set, the bitmap and the outputs live in context buffers that grow once and are
+ * reused, so a call in steady state allocates nothing (a session's Begin makes six allocations); the descent and the collection are one
+ * launch, a handover to the global heaps is the second.  Arguments and results as above (ef as for _begin); the results equal begin ->
+ * collect -> end.  A sharded handle: RXGPU_ERR_LOGIC.  Thread-safe like the other searches (a context per call in flight). */
+int rxgpu_hnsw_collect_knn(rxgpu_index* h, const float* query, uint32_t ef, const uint32_t* allowed_words, uint64_t n_words, uint32_t needed, uint32_t first_batch,
+						   uint32_t max_calls, float* out_dist, uint32_t* out_row, uint64_t cap, uint32_t* out_call_batch, uint32_t* out_call_emitted,
+						   uint32_t* out_call_end, uint32_t calls_cap, uint32_t* out_calls, uint64_t* out_presented, uint64_t* out_accepted, int32_t* out_exhausted,
+						   uint32_t* out_launches, uint32_t* out_pos);
+int rxgpu_hnsw_collect_knn_sq8(rxgpu_index* h, const uint8_t* query_codes, float query_corr, float query_norm_coef, uint32_t ef, const uint32_t* allowed_words,
+							   uint64_t n_words, uint32_t needed, uint32_t first_batch, uint32_t max_calls, float* out_dist, uint32_t* out_row, uint64_t cap,
+							   uint32_t* out_call_batch, uint32_t* out_call_emitted, uint32_t* out_call_end, uint32_t calls_cap, uint32_t* out_calls,
+							   uint64_t* out_presented, uint64_t* out_accepted, int32_t* out_exhausted, uint32_t* out_launches, uint32_t* out_pos);
+/* the rule's pieces (csrc/hnsw_stream_collect_plan.h), for callers that run the loop themselves or size the buffers */
+uint32_t rxgpu_hnsw_stream_collect_batch(uint64_t accepted, uint64_t presented, uint64_t needed);
+uint64_t rxgpu_hnsw_stream_collect_bound(uint64_t count, uint32_t needed, uint32_t first_batch);
+uint64_t rxgpu_hnsw_stream_collect_calls_bound(uint64_t count, uint32_t needed, uint32_t first_batch, uint32_t max_calls);
 
 /* ---------------------------------------------------------------------------------------------------------
  * ft_fast BM25 score accumulation (ft::Merger<..>::mergeSimple, cpp_src/core/ft/ft_fast/mergerimpl.h:194-250)

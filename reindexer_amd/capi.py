@@ -124,6 +124,15 @@ _SIGNATURES = {
     "rxgpu_hnsw_stream_begin": (_i, [_vp, _vp, _u32, C.POINTER(_vp)]),
     "rxgpu_hnsw_stream_continue": (_i, [_vp, _u32, _vp, _vp, C.POINTER(_u32), C.POINTER(_i)]),
     "rxgpu_hnsw_stream_end": (None, [_vp]),
+    "rxgpu_hnsw_stream_collect": (_i, [_vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(_u64),
+                                       C.POINTER(_u64), C.POINTER(C.c_int32), C.POINTER(_u32), _vp]),
+    "rxgpu_hnsw_collect_knn": (_i, [_vp, _vp, _u32, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(_u64),
+                                    C.POINTER(_u64), C.POINTER(C.c_int32), C.POINTER(_u32), _vp]),
+    "rxgpu_hnsw_collect_knn_sq8": (_i, [_vp, _vp, _f, _f, _u32, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _u32, C.POINTER(_u32),
+                                        C.POINTER(_u64), C.POINTER(_u64), C.POINTER(C.c_int32), C.POINTER(_u32), _vp]),
+    "rxgpu_hnsw_stream_collect_batch": (_u32, [_u64, _u64, _u64]),
+    "rxgpu_hnsw_stream_collect_bound": (_u64, [_u64, _u32, _u32]),
+    "rxgpu_hnsw_stream_collect_calls_bound": (_u64, [_u64, _u32, _u32, _u32]),
     "rxgpu_ft_create": (_i, [_u32, _i, C.POINTER(_vp)]),
     "rxgpu_ft_create_sharded": (_i, [_u32, _u32, _vp, C.POINTER(_vp)]),
     "rxgpu_ft_shard_count": (_u32, [_vp]),
@@ -274,6 +283,68 @@ def scan_tier_subset(n_ids: int, dim: int, nq: int = 1, kk: int = 10, shadow_ava
 
 def _f32c(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def _collect_call(fn, head, n, allowed_words, needed, first_batch, max_calls, cap, calls_cap, n_words):
+    """the argument tail rxgpu_hnsw_stream_collect and rxgpu_hnsw_collect_knn(_sq8) share, and their results as a dict"""
+    L = lib()
+    words = None if allowed_words is None else np.ascontiguousarray(allowed_words, np.uint32).reshape(-1)
+    if cap is None:
+        cap = int(L.rxgpu_hnsw_stream_collect_bound(n, needed, first_batch))
+    if calls_cap is None:
+        calls_cap = int(L.rxgpu_hnsw_stream_collect_calls_bound(n, needed, first_batch, max_calls))
+    if n_words is None:
+        n_words = 0 if words is None else words.size
+    od, orow, opos = np.empty(max(cap, 1), np.float32), np.empty(max(cap, 1), np.uint32), np.empty(max(cap, 1), np.uint32)
+    cb, ce, cend = (np.zeros(max(calls_cap, 1), np.uint32) for _ in range(3))
+    calls, launches, ex = _u32(0), _u32(0), C.c_int32(0)
+    presented, accepted = _u64(0), _u64(0)
+    _check(fn(*head, None if words is None else words.ctypes.data, n_words, needed, first_batch, max_calls, od.ctypes.data, orow.ctypes.data, cap,
+              cb.ctypes.data, ce.ctypes.data, cend.ctypes.data, calls_cap, C.byref(calls), C.byref(presented), C.byref(accepted), C.byref(ex),
+              C.byref(launches), opos.ctypes.data))
+    nc, na = int(calls.value), int(accepted.value)
+    return dict(dist=od[:na].copy(), row=orow[:na].copy(), pos=opos[:na].copy(), calls=np.stack([cb[:nc], ce[:nc], cend[:nc]], axis=1),
+                presented=int(presented.value), accepted=na, exhausted=bool(ex.value), launches=int(launches.value))
+
+
+class HnswStream:
+    """A streaming KNN session over an attached HNSW graph (rxgpu_hnsw_stream_begin / _begin_sq8 / _continue / _collect / _end)."""
+
+    def __init__(self, ix, query, ef: int = 0, sq8=None):
+        self._ix, self._n = ix, int(ix.count)
+        self._s = _vp()
+        if sq8 is None:
+            self._q = _f32c(query).reshape(ix.dim)
+            _check(lib().rxgpu_hnsw_stream_begin(ix._h, self._q.ctypes.data, ef, C.byref(self._s)))
+        else:
+            self._q = np.ascontiguousarray(query, np.uint8).reshape(ix.dim)
+            _check(lib().rxgpu_hnsw_stream_begin_sq8(ix._h, self._q.ctypes.data, sq8[0], sq8[1], ef, C.byref(self._s)))
+
+    def next(self, batch: int):
+        """rxgpu_hnsw_stream_continue: (dist, row, exhausted), worst first."""
+        cap = max(1, min(batch, self._n))
+        od, orow = np.empty(cap, np.float32), np.empty(cap, np.uint32)
+        cnt, ex = _u32(0), C.c_int(0)
+        _check(lib().rxgpu_hnsw_stream_continue(self._s, batch, od.ctypes.data, orow.ctypes.data, C.byref(cnt), C.byref(ex)))
+        return od[:cnt.value].copy(), orow[:cnt.value].copy(), bool(ex.value)
+
+    def collect(self, allowed_words, needed: int, first_batch: int, max_calls: int = 1000, cap=None, calls_cap=None, n_words=None):
+        """rxgpu_hnsw_stream_collect: the iterator's loop under an allowed-rows bitmap (None: every row) in one device call.  Returns a dict:
+        dist / row / pos (the accepted rows of every call, in delivery order, and their positions in their calls' batches), calls ([n][3]:
+        batch, emitted, running count of accepted rows), presented, accepted, exhausted, launches.  cap / calls_cap / n_words default to what
+        the call requires."""
+        return _collect_call(lib().rxgpu_hnsw_stream_collect, (self._s,), self._n, allowed_words, needed, first_batch, max_calls, cap, calls_cap, n_words)
+
+    def close(self):
+        if self._s:
+            lib().rxgpu_hnsw_stream_end(self._s)
+            self._s = _vp()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class VectorIndex:
@@ -642,6 +713,26 @@ class VectorIndex:
         _check(lib().rxgpu_hnsw_search_knn_sq8_filtered(self._h, qc.ctypes.data, qcorr.ctypes.data, qnorm.ctypes.data, nq, k, ef, words.ctypes.data,
                                                         words.size, dist.ctypes.data, row.ctypes.data, cnt.ctypes.data, C.byref(n_allowed)))
         return dist[:, :k], row[:, :k], cnt, int(n_allowed.value)
+
+    def hnsw_stream(self, query, ef: int = 0):
+        """rxgpu_hnsw_stream_begin: a streaming KNN session (HnswStream) with .next(batch), .collect(...) and .close()."""
+        return HnswStream(self, query, ef)
+
+    def hnsw_stream_sq8(self, qcodes, qcorr: float, qnorm: float, ef: int = 0):
+        """rxgpu_hnsw_stream_begin_sq8: the same session over the attached SQ8 codes."""
+        return HnswStream(self, qcodes, ef, sq8=(float(qcorr), float(qnorm)))
+
+    def hnsw_collect_knn(self, query, ef: int, allowed_words, needed: int, first_batch: int, max_calls: int = 1000, cap=None, calls_cap=None, n_words=None):
+        """rxgpu_hnsw_collect_knn: begin + collect + end for one query in one call on a leased search context; the dict of HnswStream.collect."""
+        q = _f32c(query).reshape(self.dim)
+        return _collect_call(lib().rxgpu_hnsw_collect_knn, (self._h, q.ctypes.data, ef), int(self.count), allowed_words, needed, first_batch, max_calls, cap,
+                             calls_cap, n_words)
+
+    def hnsw_collect_knn_sq8(self, qcodes, qcorr: float, qnorm: float, ef: int, allowed_words, needed: int, first_batch: int, max_calls: int = 1000):
+        """rxgpu_hnsw_collect_knn_sq8: the same over the attached SQ8 codes."""
+        qc = np.ascontiguousarray(qcodes, np.uint8).reshape(self.dim)
+        return _collect_call(lib().rxgpu_hnsw_collect_knn_sq8, (self._h, qc.ctypes.data, float(qcorr), float(qnorm), ef), int(self.count), allowed_words, needed,
+                             first_batch, max_calls, None, None, None)
 
     def hnsw_search_knn_posted(self, query, k: int, ef: int = 0):
         """One query through the index's resident search kernel (rxgpu_hnsw_search_knn_posted): (dist, row, count, served)."""

@@ -292,6 +292,25 @@ struct HnswStreamState {
 	float lower;             // lowerBound
 	uint32_t top_sel, ext_sel;
 	uint32_t status, out_count, exhausted;
+	// a collection under an allowed-rows bitmap (hnsw_stream_collect.hip): the loop of csrc/hnsw_stream_collect_plan.h as the launch left it
+	uint32_t calls, presented, accepted;   // Continue calls finished, rows they delivered, rows of those that passed the bitmap
+	uint32_t batch;                        // the batch of the call that runs next (in_call: of the one that was running)
+	uint32_t in_call;                      // 1 = the launch stopped inside a call (kStreamNeedGlobal): the resume skips that call's mergeExtras
+};
+// What a collection adds to its session (hnsw_stream_collect_kernel).  Accepted rows are appended to out_dist / out_row call by call in the
+// order the call delivers them; per call c the batch asked, the rows delivered and the running count of accepted rows.
+constexpr int kCollectFresh = 0, kCollectResume = 1, kCollectBegin = 2;
+struct HnswStreamCollect {
+	const uint32_t* allowed;   // one bit per node (the rxgpu_search_knn_bitmap layout), null = every row
+	uint32_t needed, first_batch, max_calls;
+	float* out_dist;           // [cap]
+	uint32_t* out_row;
+	uint32_t* out_pos;         // [cap] the row's position in its call's batch (0 = delivered first = the call's worst)
+	uint32_t cap;
+	uint32_t* call_batch;      // [calls_cap]
+	uint32_t* call_emitted;
+	uint32_t* call_end;
+	uint32_t calls_cap;
 };
 struct HnswStream {
 	const float* query;      // [dim], normalised by the host for cosine

@@ -171,6 +171,9 @@ void launch_hnsw_sq8_quantize(int metric, const float* rows, uint32_t stride, ui
 							  float delta, uint8_t* codes, float* corr, hipStream_t s);
 struct HnswStream;
 void launch_hnsw_stream(int metric, const HnswParams& p, const HnswStream& s, uint32_t batch, int mode, bool lds, hipStream_t st);
+// a whole collection under an allowed-rows bitmap in one launch (hnsw_stream_collect.hip); mode: kCollectFresh / kCollectResume / kCollectBegin
+struct HnswStreamCollect;
+void launch_hnsw_stream_collect(int metric, const HnswParams& p, const HnswStream& s, const HnswStreamCollect& c, int mode, bool lds, hipStream_t st);
 struct HnswRange;
 void launch_hnsw_range(int metric, const HnswParams& p, const HnswRange& r, hipStream_t s);
 

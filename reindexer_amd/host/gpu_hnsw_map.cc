@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../csrc/hnsw_build_plan.h"
+#include "../csrc/hnsw_stream_collect_plan.h"
 #include "rxgpu.h"
 
 namespace rxgpu::host {
@@ -989,6 +990,24 @@ SearchResultQueue GpuHnswMap::SearchKnn(const float* queryDataRaw, std::optional
 	return result;
 }
 
+namespace {
+// A set of labels as the allowed-rows bitmap over the n internal rows of a graph (bit (id & 31) of word id >> 5): labels the graph does
+// not hold are ignored, onNew(id) runs once per row.  SearchKnnFiltered and CollectStreaming share it.
+template <typename F>
+void AllowedBitmap(const HnswGraph& graph, const labeltype* allowed, size_t nAllowed, size_t n, std::vector<uint32_t>& words, F&& onNew) {
+	words.assign((n + 31) / 32, 0u);
+	for (size_t i = 0; i < nAllowed; ++i) {
+		if (!graph.HasLabelSync(allowed[i])) continue;
+		const tableint id = graph.InternalId(allowed[i]);
+		if (id >= n) continue;
+		const uint32_t bit = 1u << (id & 31);
+		if (words[id >> 5] & bit) continue;
+		words[id >> 5] |= bit;
+		onNew(id);
+	}
+}
+}  // namespace
+
 // `WHERE cond AND KNN(...)` on the graph: SearchKnn as the reference would run it had MarkDelete (hnswalg.h:1303-1339) been applied to every
 // point whose label is not in `allowed` — one device call (rxgpu_hnsw_search_knn_filtered: the kernels read the allowed-rows bitmap where
 // they read the delete mark, runLayer0Step :871-963).  Labels the Map does not hold are ignored, duplicates are harmless.
@@ -1025,19 +1044,13 @@ SearchResultQueue GpuHnswMap::SearchKnnFiltered(const float* queryDataRaw, std::
 	syncDevice();
 	k = std::min(k, n);
 	const size_t efEff = ef ? ef : std::max<size_t>(1, k * 3 / 2);   // hnswalg.h:1995
-	std::vector<uint32_t> words((n + 31) / 32, 0u);
+	std::vector<uint32_t> words;
 	std::vector<uint32_t> rows;   // allowed live nodes, as far as the exact scan could still take them
 	size_t live = 0;
-	for (size_t i = 0; i < nAllowed; ++i) {
-		if (!graph_.HasLabelSync(allowed[i])) continue;
-		const tableint id = graph_.InternalId(allowed[i]);
-		if (id >= n) continue;
-		const uint32_t bit = 1u << (id & 31);
-		if (words[id >> 5] & bit) continue;
-		words[id >> 5] |= bit;
-		if (graph_.IsDeleted(id)) continue;
+	AllowedBitmap(graph_, allowed, nAllowed, n, words, [&](tableint id) {
+		if (graph_.IsDeleted(id)) return;
 		if (++live <= efEff) rows.push_back(uint32_t(id));
-	}
+	});
 	if (live == 0) return result;
 	std::vector<float> dist(k);
 	std::vector<uint32_t> row(k);
@@ -1218,6 +1231,145 @@ StreamingBatch GpuHnswMap::ContinueStreamingSearch(StreamingSearchSession& sessi
 	for (uint32_t i = 0; i < count; ++i) batch.results.emplace(dist[i], graph_.Label(row[i]));   // emitStreamingBatch: (dist, ExternalLabel)
 	batch.exhausted = exhausted != 0;
 	return batch;
+}
+
+// The loop of StreamingKnnIndexIterator::Next (knn_streaming_index_iterator.cc:36-110) under a set of labels — the rule is
+// csrc/hnsw_stream_collect_plan.h.  Single device: rxgpu_hnsw_stream_collect runs it next to the heaps; RXGPU_HNSW_COLLECT=host and a Map
+// over a device list run the same plan functions over ContinueStreamingSearch.
+GpuHnswMap::StreamingCollection GpuHnswMap::CollectStreaming(StreamingSearchSession& session, const labeltype* allowed, size_t nAllowed, size_t needed,
+															  size_t firstBatch, size_t maxCalls) const {
+	StreamingCollection out;
+	if (session.graph_ != this || (!session.impl_ && !session.sharded_)) {   // a foreign session is reported exhausted (hnswalg.h:1953-1956)
+		out.exhausted = true;
+		return out;
+	}
+	if (needed == 0 || firstBatch == 0) return out;
+	if (maxCalls == 0) maxCalls = rxgpu::kCollectMaxCalls;
+	if (collectOnHost()) return collectHostLoop(session, allowed, nAllowed, needed, firstBatch, maxCalls);
+	rxgpu_hnsw_stream* impl = session.impl_;
+	return collectDevice(allowed, nAllowed, needed, firstBatch, maxCalls, "CollectStreaming", [impl](const CollectArgs& a) {
+		return rxgpu_hnsw_stream_collect(impl, a.words, a.nWords, a.needed, a.firstBatch, a.maxCalls, a.dist, a.row, a.cap, a.callBatch, a.callEmitted, a.callEnd,
+										 a.callsCap, a.calls, a.presented, a.accepted, a.exhausted, a.launches, a.pos);
+	});
+}
+
+bool GpuHnswMap::collectOnHost() const {
+	const char* mode = std::getenv("RXGPU_HNSW_COLLECT");
+	return sh_ || (mode && std::string(mode) == "host");
+}
+
+// the plan functions over ContinueStreamingSearch: what a caller without the device call runs, and what a Map over a device list always runs
+GpuHnswMap::StreamingCollection GpuHnswMap::collectHostLoop(StreamingSearchSession& session, const labeltype* allowed, size_t nAllowed, size_t needed,
+															 size_t firstBatch, size_t maxCalls) const {
+	StreamingCollection out;
+	if (CurrentElementCount() == 0) {   // as the device call: an empty graph is exhausted with no call made
+		out.exhausted = true;
+		return out;
+	}
+	std::vector<labeltype> sorted(allowed, allowed + nAllowed);
+	std::sort(sorted.begin(), sorted.end());
+	std::vector<size_t> seen;   // per result: rows presented to a consumer that walks the calls best first when it reaches it
+	std::vector<std::pair<float, labeltype>> got;
+	size_t batch = firstBatch;
+	for (;;) {
+		StreamingBatch b = ContinueStreamingSearch(session, batch);
+		StreamingCollection::Call call{uint32_t(batch), uint32_t(b.results.size()), 0};
+		got.clear();
+		for (; !b.results.empty(); b.results.pop()) got.emplace_back(b.results.top().first, b.results.top().second);
+		std::reverse(got.begin(), got.end());   // the queue pops worst first under (dist, label)
+		for (size_t i = 0; i < got.size(); ++i) {
+			if (!std::binary_search(sorted.begin(), sorted.end(), got[i].second)) continue;
+			out.results.push_back(got[i]);
+			seen.push_back(out.presented + i + 1);
+			++call.accepted;
+		}
+		out.presented += call.emitted;
+		out.accepted += call.accepted;
+		out.calls.push_back(call);
+		out.exhausted = b.exhausted;
+		if (rxgpu::collect_stop(out.accepted, needed, b.exhausted, out.calls.size(), maxCalls)) break;
+		batch = rxgpu::collect_batch(out.accepted, out.presented, needed);
+	}
+	out.presentedAtCut = out.results.size() >= needed ? seen[needed - 1] : out.presented;
+	if (out.results.size() > needed) out.results.resize(needed);
+	return out;
+}
+
+GpuHnswMap::StreamingCollection GpuHnswMap::collectDevice(const labeltype* allowed, size_t nAllowed, size_t needed, size_t firstBatch, size_t maxCalls,
+														   const char* what, const std::function<int(const CollectArgs&)>& call) const {
+	StreamingCollection out;
+	const size_t n = graph_.Count();
+	std::vector<uint32_t> words;
+	AllowedBitmap(graph_, allowed, nAllowed, n, words, [](tableint) {});
+	CollectArgs a{};
+	a.needed = uint32_t(std::min<size_t>(needed, 0xFFFFFFFFu)), a.firstBatch = uint32_t(std::min<size_t>(firstBatch, 0xFFFFFFFFu));
+	a.maxCalls = uint32_t(std::min<size_t>(maxCalls, 0xFFFFFFFFu));
+	a.cap = std::max<uint64_t>(1, rxgpu_hnsw_stream_collect_bound(n, a.needed, a.firstBatch));
+	a.callsCap = uint32_t(std::max<uint64_t>(1, rxgpu_hnsw_stream_collect_calls_bound(n, a.needed, a.firstBatch, a.maxCalls)));
+	std::vector<float> dist(a.cap);
+	std::vector<uint32_t> row(a.cap), pos(a.cap), callBatch(a.callsCap), callEmitted(a.callsCap), callEnd(a.callsCap);
+	uint32_t calls = 0, launches = 0;
+	uint64_t presented = 0, accepted = 0;
+	int32_t exhausted = 0;
+	a.words = words.data(), a.nWords = words.size();
+	a.dist = dist.data(), a.row = row.data(), a.pos = pos.data();
+	a.callBatch = callBatch.data(), a.callEmitted = callEmitted.data(), a.callEnd = callEnd.data();
+	a.calls = &calls, a.presented = &presented, a.accepted = &accepted, a.exhausted = &exhausted, a.launches = &launches;
+	if (call(a) != RXGPU_OK) throwDevice(what);
+	struct Hit {
+		float dist;
+		labeltype label;
+		size_t seen;
+	};
+	std::vector<Hit> hits;
+	hits.reserve(accepted);
+	uint32_t from = 0;
+	size_t before = 0;
+	for (uint32_t c = 0; c < calls; ++c) {
+		out.calls.push_back(StreamingCollection::Call{callBatch[c], callEmitted[c], callEnd[c] - from});
+		// a call delivers worst first: the row at position p is the (emitted - p)-th a best-first consumer is presented
+		for (uint32_t i = from; i < callEnd[c]; ++i) hits.push_back(Hit{dist[i], graph_.Label(row[i]), before + callEmitted[c] - pos[i]});
+		std::sort(hits.begin() + long(from), hits.end(), [](const Hit& x, const Hit& y) { return x.dist != y.dist ? x.dist < y.dist : x.label < y.label; });
+		from = callEnd[c];
+		before += callEmitted[c];
+	}
+	out.presentedAtCut = hits.size() >= needed ? hits[needed - 1].seen : size_t(presented);
+	if (hits.size() > needed) hits.resize(needed);
+	out.results.reserve(hits.size());
+	for (const Hit& h : hits) out.results.emplace_back(h.dist, h.label);
+	out.presented = presented;
+	out.accepted = accepted;
+	out.exhausted = exhausted != 0;
+	out.launches = launches;
+	return out;
+}
+
+// Single device: rxgpu_hnsw_collect_knn / _sq8 — Begin and the collection in one call on a leased search context, nothing allocated in steady
+// state.  Under RXGPU_HNSW_COLLECT=host and over a device list: BeginStreamingSearch + the host loop.
+GpuHnswMap::StreamingCollection GpuHnswMap::SearchKnnStreamed(const float* queryDataRaw, std::optional<float> queryDataNorm, size_t needed, size_t ef,
+															   const labeltype* allowed, size_t nAllowed) const {
+	const size_t firstBatch = ef ? ef : 100;   // the iterator's first batch is its ef (kDefaultStreamingEf for 0)
+	if (collectOnHost()) {
+		StreamingSearchSession session = BeginStreamingSearch(queryDataRaw, queryDataNorm, StreamingSearchOptions{ef});
+		return CollectStreaming(session, allowed, nAllowed, needed, firstBatch);
+	}
+	if (needed == 0) return StreamingCollection{};
+	syncDevice();
+	rxgpu_index* dev = dev_;
+	const uint32_t ef32 = uint32_t(ef);
+	if (quantized_) {
+		float normCoef = 1.f;
+		std::vector<uint8_t> qcodes;
+		const float qcorr = quantizeQuery(queryDataRaw, queryDataNorm, qcodes, normCoef);
+		return collectDevice(allowed, nAllowed, needed, firstBatch, rxgpu::kCollectMaxCalls, "SearchKnnStreamed", [&](const CollectArgs& a) {
+			return rxgpu_hnsw_collect_knn_sq8(dev, qcodes.data(), qcorr, normCoef, ef32, a.words, a.nWords, a.needed, a.firstBatch, a.maxCalls, a.dist, a.row, a.cap,
+											  a.callBatch, a.callEmitted, a.callEnd, a.callsCap, a.calls, a.presented, a.accepted, a.exhausted, a.launches, a.pos);
+		});
+	}
+	return collectDevice(allowed, nAllowed, needed, firstBatch, rxgpu::kCollectMaxCalls, "SearchKnnStreamed", [&](const CollectArgs& a) {
+		return rxgpu_hnsw_collect_knn(dev, queryDataRaw, ef32, a.words, a.nWords, a.needed, a.firstBatch, a.maxCalls, a.dist, a.row, a.cap, a.callBatch,
+									  a.callEmitted, a.callEnd, a.callsCap, a.calls, a.presented, a.accepted, a.exhausted, a.launches, a.pos);
+	});
 }
 
 // hnswalg.h:2015-2070: ef-search, then the closure over level-0 links while dist < radius — both on the device (rxgpu_hnsw_search_range:

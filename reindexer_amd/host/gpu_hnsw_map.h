@@ -10,6 +10,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -143,6 +144,31 @@ public:
 	// Streaming (batched) KNN, hnswalg.h:1865-1975.  The whole session must run under the caller's read lock, like the reference's.
 	StreamingSearchSession BeginStreamingSearch(const float* queryDataRaw, std::optional<float> queryDataNorm, StreamingSearchOptions opts) const;
 	StreamingBatch ContinueStreamingSearch(StreamingSearchSession& session, size_t batchSize) const;
+	// `WHERE cond AND KNN(...)` over a session: the loop of StreamingKnnIndexIterator::Next (knn_streaming_index_iterator.cc:36-110) for a
+	// filter that is a set of labels — Continue with firstBatch, then with StreamingKnnEstimator::EstimateBatchSize, until `needed` delivered
+	// rows passed the filter, the session is exhausted or maxCalls calls ran (the rule: csrc/hnsw_stream_collect_plan.h).  On a single-device
+	// Map the whole loop is one device call (rxgpu_hnsw_stream_collect); RXGPU_HNSW_COLLECT=host (read per call), and a Map over a device
+	// list always, run the same rule over ContinueStreamingSearch.  Labels the Map does not hold are ignored, duplicates are harmless.
+	struct StreamingCollection {
+		std::vector<std::pair<float, labeltype>> results;   // best first: each call's accepted rows ascending by (dist, label), calls in order, cut at `needed`
+		struct Call {
+			uint32_t batch, emitted, accepted;              // the batch asked, the rows delivered, those of them that passed
+		};
+		std::vector<Call> calls;
+		size_t presented = 0, accepted = 0;                 // over all calls (accepted: before the cut)
+		// rows a consumer that walks the calls in order, each best first, has been presented when it reaches the needed-th accepted row — the
+		// iterator's presented_ at the cut; = presented when fewer than `needed` rows passed.  (Equal distances inside a call: the device call
+		// knows the order the heap delivered them in, the host loop the order by label.)
+		size_t presentedAtCut = 0;
+		bool exhausted = false;
+		unsigned launches = 0;                              // kernel launches of the device call (0: the host loop ran)
+	};
+	StreamingCollection CollectStreaming(StreamingSearchSession& session, const labeltype* allowed, size_t nAllowed, size_t needed, size_t firstBatch,
+										 size_t maxCalls = 1000) const;
+	// Begin + CollectStreaming (firstBatch = ef, as the iterator starts) + the session's end for one query — on a single-device Map one device
+	// call on a leased search context (rxgpu_hnsw_collect_knn / _sq8: nothing allocated in steady state, the descent and the collection one launch)
+	StreamingCollection SearchKnnStreamed(const float* queryDataRaw, std::optional<float> queryDataNorm, size_t needed, size_t ef, const labeltype* allowed,
+										  size_t nAllowed) const;
 
 	// Query coalescing, as in GpuBruteforceMap: one-shot searches that arrive while the device is busy and ask for the same (k, ef) share
 	// one launch of the batched search kernel (a wavefront per query) instead of one single-wavefront launch each.
@@ -161,7 +187,7 @@ public:
 	// device (rxgpu_hnsw_search_knn_sq8) and returns what HierarchicalNSWImpl<uint8_t> returns on the same graph, bit for bit.  The range
 	// [minQ, maxQ] is what QuantizingParams derives from its sample (quantization_params.h:48-63); the caller supplies it (in-tree:
 	// QuantizingParams over the Map's rows).  Points added later are quantised with the same parameters at the next sync
-	// (addPoint, hnswalg.h:1480-1495).  Streaming and range searches of a quantised Map are not implemented: they throw.
+	// (addPoint, hnswalg.h:1480-1495).  Streaming sessions and range searches of a quantised Map run over the codes too.
 	void Quantize(float minQ, float maxQ);
 	// HierarchicalNSW::Quantize(config) + SwitchMapOnQuantized() (hnsw.h:61-62, hnsw.cc:131-137, Impl::get :108-114) as HnswIndexBase drives them
 	// (hnsw_index.cc:532-551): Quantize derives the parameters from a sample of the stored rows exactly as QuantizingParams does
@@ -185,6 +211,25 @@ public:
 	}
 
 private:
+	struct CollectArgs {   // the argument tail rxgpu_hnsw_stream_collect and rxgpu_hnsw_collect_knn(_sq8) share
+		const uint32_t* words;
+		uint64_t nWords;
+		uint32_t needed, firstBatch, maxCalls;
+		float* dist;
+		uint32_t *row, *pos;
+		uint64_t cap;
+		uint32_t *callBatch, *callEmitted, *callEnd;
+		uint32_t callsCap;
+		uint32_t* calls;
+		uint64_t *presented, *accepted;
+		int32_t* exhausted;
+		uint32_t* launches;
+	};
+	bool collectOnHost() const;
+	StreamingCollection collectHostLoop(StreamingSearchSession& session, const labeltype* allowed, size_t nAllowed, size_t needed, size_t firstBatch,
+										size_t maxCalls) const;
+	StreamingCollection collectDevice(const labeltype* allowed, size_t nAllowed, size_t needed, size_t firstBatch, size_t maxCalls, const char* what,
+									  const std::function<int(const CollectArgs&)>& call) const;
 	void syncDevice() const;
 	void syncLocked() const;            // under syncMtx_; mirrors the LINKED part of the graph
 	void flushPending() const;          // links the pending tail (steps 1 - 7 of the batch rule)

@@ -848,6 +848,54 @@ long rxhost_hnsw_stream_continue(void* h, void* session, size_t batch, float* ou
 	return n;
 }
 void rxhost_hnsw_stream_end(void* session) { delete static_cast<StreamingSearchSession*>(session); }
+namespace {
+// results best first into outDist / outLabel (room for `needed`), per call (batch, emitted, accepted) into outCalls3 (room for callsCap calls),
+// out5 (six words): calls, presented, accepted, exhausted, launches, presented at the cut.  Returns the number of results.
+static long drainCollection(const GpuHnswMap::StreamingCollection& c, size_t needed, float* outDist, uint64_t* outLabel, uint32_t* outCalls3, size_t callsCap,
+					 uint64_t* out5) {
+	const size_t n = std::min(c.results.size(), needed);
+	for (size_t i = 0; i < n; ++i) {
+		outDist[i] = c.results[i].first;
+		outLabel[i] = c.results[i].second;
+	}
+	for (size_t i = 0; i < c.calls.size() && i < callsCap; ++i) {
+		outCalls3[3 * i] = c.calls[i].batch;
+		outCalls3[3 * i + 1] = c.calls[i].emitted;
+		outCalls3[3 * i + 2] = c.calls[i].accepted;
+	}
+	out5[0] = c.calls.size();
+	out5[1] = c.presented;
+	out5[2] = c.accepted;
+	out5[3] = c.exhausted ? 1 : 0;
+	out5[4] = c.launches;
+	out5[5] = c.presentedAtCut;
+	return long(n);
+}
+}  // namespace
+// GpuHnswMap::CollectStreaming: the iterator's loop under a set of labels, one device call on a single-device Map.  -1 on error.
+long rxhost_hnsw_stream_collect(void* h, void* session, const uint64_t* allowed, size_t nAllowed, size_t needed, size_t firstBatch, size_t maxCalls,
+								float* outDist, uint64_t* outLabel, uint32_t* outCalls3, size_t callsCap, uint64_t* out5) {
+	long n = -1;
+	guarded([&] {
+		std::vector<labeltype> labels(allowed, allowed + nAllowed);
+		const auto c = static_cast<const GpuHnswMap*>(h)->CollectStreaming(*static_cast<StreamingSearchSession*>(session), labels.data(), labels.size(), needed,
+																			firstBatch, maxCalls);
+		n = drainCollection(c, needed, outDist, outLabel, outCalls3, callsCap, out5);
+	});
+	return n;
+}
+// GpuHnswMap::SearchKnnStreamed: Begin + collect + end for one query
+long rxhost_hnsw_search_knn_streamed(void* h, const float* q, int hasNorm, float norm, size_t needed, size_t ef, const uint64_t* allowed, size_t nAllowed,
+									 float* outDist, uint64_t* outLabel, uint32_t* outCalls3, size_t callsCap, uint64_t* out5) {
+	long n = -1;
+	guarded([&] {
+		std::vector<labeltype> labels(allowed, allowed + nAllowed);
+		const auto c = static_cast<const GpuHnswMap*>(h)->SearchKnnStreamed(q, hasNorm ? std::optional<float>(norm) : std::nullopt, needed, ef, labels.data(),
+																			 labels.size());
+		n = drainCollection(c, needed, outDist, outLabel, outCalls3, callsCap, out5);
+	});
+	return n;
+}
 long rxhost_hnsw_search_range(void* h, const float* q, float radius, size_t ef, float* outDist, uint64_t* outLabel, size_t cap) {
 	long n = -1;
 	guarded([&] {

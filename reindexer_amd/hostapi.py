@@ -417,6 +417,12 @@ class HnswGraph:
         return vec, inv
 
 
+def _collection(od, ol, oc, o5, n):
+    calls = int(o5[0])
+    return dict(dist=od[:n].copy(), labels=ol[:n].copy(), calls=oc[:min(calls, oc.shape[0])].copy(), n_calls=calls, presented=int(o5[1]),
+                accepted=int(o5[2]), exhausted=bool(o5[3]), launches=int(o5[4]), presented_at_cut=int(o5[5]))
+
+
 class _HnswStream:
     def __init__(self, owner, q, ef, norm=None):
         L = lib()
@@ -443,6 +449,23 @@ class _HnswStream:
         if n < 0:
             _raise()
         return od[:n].copy(), ol[:n].copy(), bool(ex.value)
+
+    def collect(self, allowed_labels, needed, first_batch, max_calls=1000):
+        """CollectStreaming: the loop of StreamingKnnIndexIterator::Next under a set of labels (csrc/hnsw_stream_collect_plan.h) — one device
+        call on a single-device Map, the same rule over next() under RXGPU_HNSW_COLLECT=host or over a device list.  Returns a dict:
+        dist / labels (best first, cut at needed), calls ([n][3]: batch, emitted, accepted), presented, presented_at_cut, accepted, exhausted, launches."""
+        L = lib()
+        L.rxhost_hnsw_stream_collect.restype = _l
+        L.rxhost_hnsw_stream_collect.argtypes = [_vp, _vp, _vp, _sz, _sz, _sz, _sz, _vp, _vp, _vp, _sz, _vp]
+        labels = np.ascontiguousarray(allowed_labels, np.uint64).reshape(-1)
+        calls_cap = max(1, min(max_calls or 1000, int(self.owner.count) + 1))
+        od, ol = np.empty(max(needed, 1), np.float32), np.empty(max(needed, 1), np.uint64)
+        oc, o5 = np.zeros((calls_cap, 3), np.uint32), np.zeros(6, np.uint64)
+        n = L.rxhost_hnsw_stream_collect(self.owner.h, self.s, labels.ctypes.data if labels.size else None, labels.size, needed, first_batch, max_calls,
+                                         od.ctypes.data, ol.ctypes.data, oc.ctypes.data, calls_cap, o5.ctypes.data)
+        if n < 0:
+            _raise()
+        return _collection(od, ol, oc, o5, n)
 
     def close(self):
         if getattr(self, "s", None):
@@ -877,6 +900,24 @@ class GpuHnswMap:
         """BeginStreamingSearch: session with .next(batch) -> (dist, label, exhausted) (worst first) and .close().  norm: the query's
         norm as HnswIndexBase::search passes it (needed by a quantised cosine graph)."""
         return _HnswStream(self, _f32(q), ef, norm)
+
+    def search_knn_streamed(self, q, needed, ef, allowed_labels, norm=None):
+        """SearchKnnStreamed: BeginStreamingSearch + collect (first batch = ef) + the session's end for one query; the dict of
+        _HnswStream.collect."""
+        L = lib()
+        L.rxhost_hnsw_search_knn_streamed.restype = _l
+        L.rxhost_hnsw_search_knn_streamed.argtypes = [_vp, _vp, _i, _f, _sz, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp]
+        q = _f32(q)
+        labels = np.ascontiguousarray(allowed_labels, np.uint64).reshape(-1)
+        calls_cap = max(1, min(1000, int(self.count) + 1))
+        od, ol = np.empty(max(needed, 1), np.float32), np.empty(max(needed, 1), np.uint64)
+        oc, o5 = np.zeros((calls_cap, 3), np.uint32), np.zeros(6, np.uint64)
+        n = L.rxhost_hnsw_search_knn_streamed(self.h, q.ctypes.data, int(norm is not None), 0.0 if norm is None else float(norm), needed, ef,
+                                              labels.ctypes.data if labels.size else None, labels.size, od.ctypes.data, ol.ctypes.data, oc.ctypes.data,
+                                              calls_cap, o5.ctypes.data)
+        if n < 0:
+            _raise()
+        return _collection(od, ol, oc, o5, n)
 
     def knn_stream(self, key, ef=0):
         """Index-level streaming (HnswIndexBase<Map>::beginStreaming / continueStreaming): raw key in; .next(batch) -> (row ids,
